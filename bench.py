@@ -36,8 +36,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# one hardware queue per in-flight trace kernel; read by the HIP runtime when it initialises (before torch does that)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "20")
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -58,6 +56,7 @@ FLAG_ANIMATE = 1
 PORT_TAKEN_RC = 98             # exit code of a rank whose rendezvous port was already in use (EADDRINUSE): self_launch retries with another port
 # set by launchers that start one process per rank themselves (Open MPI, MPICH / PMI, Slurm): bench.py must not spawn N more ranks under them
 FOREIGN_LAUNCHER_VARS = ("OMPI_COMM_WORLD_SIZE", "PMI_SIZE", "PMIX_RANK", "SLURM_NTASKS", "SLURM_PROCID")
+DUMP_MAX_PIXELS = 1 << 21      # --dump-outputs: larger images are written as this many pixels chosen with a fixed seed (48 MB with their indices)
 
 
 def cpu_model():
@@ -144,6 +143,22 @@ def image_parity(image, rays_total, width, height, spp, frames, max_frames=64, m
                parity_seconds=time.perf_counter() - t0,
                parity_note="final image + ray total of this run (frames 0..%d, zeroed tile) vs oracle/tpt_oracle.c, PER_PIXEL seeds, bytes equal" % (frames - 1))
     return out
+
+
+def dump_outputs(out_dir, image, rays):
+    """--dump-outputs: what the caller of the timed path holds after its last step -- the accumulated image tile (float32, H x W x 4)
+    and the rays of the timed steps (float64) -- as out_dir/<name>.npy, so that two builds can be compared output for output.  An
+    image of more than DUMP_MAX_PIXELS pixels is written as a fixed, seeded sample of its pixels (image.npy: N x 4) and their flat
+    indices (image_pixel_index.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.ascontiguousarray(image.detach().cpu().numpy(), np.float32)
+    h, w = img.shape[:2]
+    if h * w > DUMP_MAX_PIXELS:
+        idx = np.sort(np.random.default_rng(0).choice(h * w, DUMP_MAX_PIXELS, replace=False))
+        img = img.reshape(h * w, -1)[idx]
+        np.save(os.path.join(out_dir, "image_pixel_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "image.npy"), img)
+    np.save(os.path.join(out_dir, "rays.npy"), np.array([rays], np.float64))
 
 
 def drain_lookahead(api):
@@ -443,6 +458,9 @@ def main():
     ap.add_argument("--parity-samples", type=float, default=1.6e8,
                     help="... and at most this many camera samples in total (frames x width x height x spp): bounds the oracle leg to ~10 s "
                          "of the host's cores -- 41 frames of configs[1], ONE frame of configs[2] (--workload c3 --prime 0 --warmup 0 --steps 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the image the last step left in the tile (float32) and the rays of the timed steps "
+                         "(float64) as DIR/<name>.npy; the same arguments give the same inputs in every run")
     ap.add_argument("--prime", type=int, default=-1,
                     help="untimed frames rendered BEFORE the warm-up so that the frame pipeline (buffers of all slots, the library's "
                          "estimate of how deep this caller pipelines) is in its steady state when warm-up and timing start; "
@@ -613,6 +631,8 @@ def main():
         rays_all_frames = rays_end
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, image, rays_total)
         info = api.launch_info()
         k_ms = kernel_ms / args.steps                      # average duration of one trace launch (this rank's rows),
         #                                                    what a rocprofv3 kernel trace reports per dispatch; with

@@ -66,4 +66,6 @@ REDEF="DO_MITSUBA_COMPARE 1" build libtpt_ref_mitsuba -O2 -ffp-contract=off -D__
 REDEF="DO_ANIMATE_SMOOTHING 0.5f" build libtpt_ref_smooth05 -O2 -ffp-contract=off -D__EMSCRIPTEN__ -D__EMSCRIPTEN_PTHREADS__
 # the scalar path with the reference's GPU seed formula: pins the product's default seed mode to reference-compiled code
 PERPIXEL=1 build libtpt_ref_perpixel -O2 -ffp-contract=off -D__EMSCRIPTEN__ -D__EMSCRIPTEN_PTHREADS__
-echo "built $OUT/libtpt_ref.so $OUT/libtpt_ref_scalar.so $OUT/libtpt_ref_fast.so + Config.h variants (nols, mitsuba, smooth05) + libtpt_ref_perpixel.so"
+# examples/headless_host.cpp compiled against the reference's own Test.h (nothing of include/ on the path): tests/test_abi.py links it
+g++ -O1 -std=c++11 -DUSE_REFERENCE_HEADER -I"$S" -c "$HERE/../examples/headless_host.cpp" -o "$OUT/headless_host_refheader.o"
+echo "built $OUT/libtpt_ref.so $OUT/libtpt_ref_scalar.so $OUT/libtpt_ref_fast.so + Config.h variants (nols, mitsuba, smooth05) + libtpt_ref_perpixel.so + headless_host_refheader.o"

@@ -1,8 +1,7 @@
-"""Child process of tests/test_gpu_parity.py::test_grouped_kernel_is_exact_in_a_time_sliced_process: starts HIP with 32 hardware queues
-(the variable is read when the runtime starts, so this cannot happen inside the suite's own process), opens 16 extra streams -- more
-queues than the device runs side by side, so the device's scheduler time-slices them -- and renders frames 0-2 of the
-4096-sphere scene `sets` times, three in flight.  Prints one JSON line: how many sets differ from the committed oracle hashes.
-    python tests/c5_timeslice_child.py <sets> <hit-spheres variant>"""
+"""Child process of tests/test_gpu_parity.py::test_grouped_kernel_is_exact_beside_16_extra_streams: opens 16 extra streams beside the
+library's own, on the hardware queues the process was started with, and renders frames 0-2 of the 4096-sphere scene `sets` times,
+three in flight.  Prints one JSON line: how many sets differ from the committed oracle hashes.
+    python tests/c5_extra_streams_child.py <sets> <hit-spheres variant>"""
 import json
 import os
 import sys
@@ -10,7 +9,6 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-os.environ["GPU_MAX_HW_QUEUES"] = "32"
 if len(sys.argv) > 2 and sys.argv[2] == "4":  # the groups' bounds on the matrix cores: in the hooks build of the library only
     os.environ["TPT_LIB"] = os.path.join(ROOT, "toypathtracer_amd", "lib", "libtoypathtracer_hip_hooks.so")
 import torch  # noqa: E402

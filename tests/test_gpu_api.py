@@ -96,14 +96,13 @@ def test_display_conversion_matches_reference_formula(tpt_defaults, tmp_path):
 
 _LATE_HOST = r'''
 import json, os, sys, time
-os.environ.pop("GPU_MAX_HW_QUEUES", None)
 import torch
-torch.zeros(1, device="cuda").sum().item()          # the host initialises HIP FIRST: the runtime starts with its default queues
+torch.zeros(1, device="cuda").sum().item()          # the host initialises HIP FIRST: the runtime starts with the queues it was given
 cap = sys.argv[1]
 if cap != "auto":
     os.environ["TPT_OVERLAP_CAP"] = cap
 sys.path.insert(0, sys.argv[2])
-from toypathtracer_amd import api                    # (sets GPU_MAX_HW_QUEUES=20 -- too late for this process)
+from toypathtracer_amd import api
 api.InitializeTest()
 w, h = 1280, 720
 tile = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda")
@@ -123,9 +122,9 @@ api.ShutdownTest()
 
 def test_host_that_initialised_hip_first_still_gets_a_working_pipeline(tmp_path):
     """GPU_MAX_HW_QUEUES is read when the HIP runtime starts; a host (or torch) that touched HIP before this library was
-    loaded keeps the default of 4 hardware queues, on which 16 frames in flight run slower than 2.  tptInitialize measures
-    how many streams really run side by side and clamps the frame pipeline: the automatic choice must be within 10 % of
-    the best forced limit."""
+    loaded keeps the few hardware queues it started with, on which 16 frames in flight run slower than 2.  tptInitialize
+    measures how many streams really run side by side and clamps the frame pipeline: the automatic choice must be within
+    10 % of the best forced limit."""
     import json
     import sys
     script = tmp_path / "late_host.py"
@@ -141,13 +140,21 @@ def test_host_that_initialised_hip_first_still_gets_a_working_pipeline(tmp_path)
     assert auto["rate"] >= 0.9 * best, res
 
 
+def queue_cap(info):
+    """frames in flight the measured hardware queues carry (tpt_host.cpp, probeHardwareQueues): all 16 with a queue per trace stream"""
+    q = info["hw_queues"]
+    return 16 if q >= 16 else q - 3 if q >= 8 else 2
+
+
 def test_pipeline_info_with_queues_set_early(tpt_defaults):
-    """In the test process GPU_MAX_HW_QUEUES=20 was exported before HIP started (api.load_library): all trace streams run
-    side by side, the full pipeline is used, and the per-slot buffers are allocated once per frame shape."""
+    """The frame pipeline is as deep as the hardware queues the process started with carry -- with a queue per trace stream all
+    of them run side by side and the full pipeline is used -- and the per-slot buffers are allocated once per frame shape."""
     import torch
     tpt = tpt_defaults
     info = tpt.pipeline_info()
-    assert info["hw_queues"] == 16 and info["overlap_effective"] == 16, info
+    q = info["hw_queues"]
+    assert 1 <= q <= 16, info
+    assert info["overlap_effective"] == queue_cap(info), info
     w, h = 320, 200
     tile = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda")
     for f in range(0, 4):  # (a streaming caller with frames this small gets several frames per launch from its third call on:
@@ -486,9 +493,10 @@ def test_loopback_rank0_of_n_matches_its_rows(tpt_defaults, oracle, n):
     from common import oracle_frames
     tpt = tpt_defaults
     w, h, frames, stripe = 200, 120, 20, 8
+    cap = queue_cap(tpt.pipeline_info())
     tpt.comm_init_loopback(n, stripe)
     try:
-        assert tpt.pipeline_info()["overlap_effective"] == (16 if n <= 2 else 8)
+        assert tpt.pipeline_info()["overlap_effective"] == min(16 if n <= 2 else 8, cap)
         img = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda")
         for f in range(frames):
             tpt.UpdateTest(0.0, f, w, h, FLAG_PROGRESSIVE)
@@ -497,7 +505,7 @@ def test_loopback_rank0_of_n_matches_its_rows(tpt_defaults, oracle, n):
         got = img.cpu().numpy()
     finally:
         tpt.comm_destroy()
-    assert tpt.pipeline_info()["overlap_effective"] == 16
+    assert tpt.pipeline_info()["overlap_effective"] == cap
     _, bo, _ = oracle_frames(oracle, w, h, 4, frames, seed_mode=SEED_PER_PIXEL)
     want = np.frombuffer(bo.tobytes(), np.float32).reshape(h, w, 4)
     mine = (np.arange(h) // stripe) % n == 0
@@ -607,7 +615,8 @@ def test_synchronous_device_caller_gets_lookahead_and_the_same_bits(tpt_defaults
         assert tile.cpu().numpy().tobytes() == bo.tobytes(), synchronous
         hits = tpt.lookahead_hits() - hits0
         if synchronous:  # (a streaming caller normally gets none; a host hiccup may make it look synchronous for a moment -- harmless)
-            assert hits >= frames - 4, hits
+            # frames traced ahead leave one slot spare (traceAhead): a pipeline clamped to 2 by few hardware queues has none to give
+            assert hits >= frames - 4 if tpt.pipeline_info()["overlap_effective"] > 2 else hits == 0, hits
     # a change of configuration in the middle drops what was traced ahead
     tile = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda")
     for f in range(6):

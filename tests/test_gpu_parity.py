@@ -659,19 +659,17 @@ def test_config5_with_the_bounds_on_the_matrix_cores_in_the_hooks_build(tpt_hook
     tpt.set_camera(None)
 
 
-def test_grouped_kernel_is_exact_in_a_time_sliced_process():
-    """Rounds 5-6: a process that holds more hardware queues than the device runs side by side is time-sliced, and the
-    grouped kernel with its groups' bounds ON THE MATRIX CORES then came back with 1-4 wrong pixels in 8-80 % of the renders, depending
-    on the build.  Round 6 localised it -- the masks the matrix cores deliver are right; a per-lane gather of a group's members behind
-    them now and then delivers wrong data to a wave that has executed that path, never to one that has not -- and made the two-level
-    packed VALU filter the default for grouped scenes.  The condition cannot be created inside this process (the HIP runtime reads
-    GPU_MAX_HW_QUEUES when it starts), so a child process starts HIP with 32 queues, opens 16 extra streams and renders frames 0-2 of
-    configs[4] 70 times, three in flight: every one of the 210 renders must equal the oracle's committed hash."""
+def test_grouped_kernel_is_exact_beside_16_extra_streams():
+    """Rounds 5-6: in a time-sliced process the grouped kernel with its groups' bounds ON THE MATRIX CORES came back
+    with 1-4 wrong pixels in 8-80 % of the renders -- a per-lane gather of a group's members behind them now and then delivered wrong
+    data -- and the two-level packed VALU filter became the default for grouped scenes.  A child process opens 16 extra streams
+    beside the library's own on the hardware queues it was started with and renders frames 0-2 of configs[4] 70 times, three in
+    flight: every one of the 210 renders must equal the oracle's committed hash."""
     import json
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
-    out = subprocess.run([sys.executable, os.path.join(here, "c5_timeslice_child.py"), "70", "0"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    out = subprocess.run([sys.executable, os.path.join(here, "c5_extra_streams_child.py"), "70", "0"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert out.returncode == 0, out.stderr.decode()[-3000:]
     res = json.loads(out.stdout.decode().strip().splitlines()[-1])
     assert res["scene_info"] == dict(spheres=4096, groups=512, bounds_on_matrix_cores=False), res

@@ -2,7 +2,6 @@
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "20")
 import torch
 from toypathtracer_amd import api
 api.InitializeTest()

@@ -221,8 +221,8 @@ int requireInit()
 }
 
 // How many of the trace streams does the runtime really run side by side?  ROCm maps streams onto GPU_MAX_HW_QUEUES
-// hardware queues (default 4) and reads that variable when the runtime starts -- a host that touched HIP before loading
-// this library keeps its 4, whatever tptInitialize puts into the environment, and streams that share a queue serialise
+// hardware queues (default 4) and reads that variable when the runtime starts -- the host decides it, this library never
+// sets it -- and streams that share a queue serialise
 // (3 frames in flight on 4 queues were SLOWER than 2).  So measure instead of assuming: one wave spinning 2 ms on each
 // trace stream; 16 concurrent ones take ~2 ms, 4 queues take 4 rounds.  The frame pipeline is then clamped to what the
 // queues can carry (tptGetPipelineInfo reports both numbers).
@@ -305,15 +305,6 @@ const char* tptGetDeviceName(void) { return g.deviceName.c_str(); }
 int tptInitialize(void)
 {
     if (g.inited) return 0;
-    // Frame pipelining wants one hardware queue per in-flight trace kernel; the ROCm runtime exposes 4 by default and
-    // maps further streams onto them round-robin (3 streams then run slower than 2).  Only effective if the HIP
-    // runtime has not been initialised yet by the host application; harmless otherwise.
-    // 20, not more: this library's 18 streams, the null stream and one of the host's each get their own, and the process
-    // stays below what the device runs side by side.  A process that holds MORE queues than that (measured on MI355X /
-    // ROCm 7.2: 20 and 22 fine, 24 and up not) is time-sliced by the device's scheduler -- running waves are switched out
-    // and back in -- which halves the frame rate (round 4).  A PERFORMANCE hint only: nothing the library computes depends on
-    // it (rounds 5-6: the one kernel path that was not safe under time-slicing is no longer taken by default).
-    setenv("GPU_MAX_HW_QUEUES", TPT_DEFAULT_HW_QUEUES, 0);
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count <= 0)
