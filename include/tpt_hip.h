@@ -136,6 +136,20 @@ TPT_API int tptDrawDevice(float time, int frameCount, int screenWidth, int scree
  * per batch instead of once per frame -- what bounds small frames and tiles of a sharded frame.  Path-queue kernel only
  * (the default); frames up to 8192 x 8192; kFlagAnimate is refused (the scene changes every frame). */
 TPT_API int tptDrawDeviceBatch(float time, int firstFrame, int nFrames, int screenWidth, int screenHeight, float* deviceTile, unsigned testFlags);
+/* nViews (1..32) cameras of the scene as of the last tptUpdate, traced by ONE launch.  views: nViews x 9 floats
+ * {lookFrom xyz, lookAt xyz, vfovDegrees, aperture, focusDist} -- tptSetCamera's arguments; aspect = w / h, vup (0,1,0),
+ * aperture forced to 0 in Mitsuba-compare mode, as tptUpdate does.  deviceTiles: nViews consecutive device tiles of h*w*4
+ * floats, each blended exactly like tptDrawDevice blends its tile (frameCount, testFlags).  deviceViewRays: NULL or nViews
+ * int64 in device memory, OVERWRITTEN with this call's rays per view; the context's counter (tptRayCounterRead) advances
+ * by their sum.  Asynchronous on the context's stream.
+ * View v is bit-identical to tptSetCamera(views[v]...), tptUpdate(time, frameCount, w, h, testFlags), tptDrawDevice(..., tile v, ...)
+ * on a tile holding the same previous contents, with the same ray count; every view uses the seeds of frameCount.  The context's
+ * own camera is not changed; frames traced ahead and stream-batch planes are dropped (the call does not continue a sequence).
+ * Refused (non-zero, tptGetLastError, no tile written): nViews outside 1..32, views or deviceTiles NULL, no tptUpdate at this size,
+ * w or h over 8192, colour planes over 4096 MiB, row-serial seeds, the forward fold, a kernel variant other than the path-queue
+ * kernel, row sharding or a communicator, a tile mirror. */
+TPT_API int tptDrawDeviceViews(float time, int frameCount, int screenWidth, int screenHeight, int nViews, const float* views,
+                               float* deviceTiles, int64_t* deviceViewRays, unsigned testFlags);
 /* Frame pipelining of the asynchronous path: the trace kernels of up to `frames` consecutive tptDrawDevice
  * calls may be in flight at once (each on its own internal stream, writing its own per-frame colour
  * buffer); the progressive blend into the tile (Test.cpp:293-295) is a separate, ordered kernel on the

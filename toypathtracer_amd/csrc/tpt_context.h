@@ -59,6 +59,7 @@ struct Context {
     PackedScene packed;
     bool sceneDirty = true; // host arrays changed since last pack
     bool updated = false;   // tptUpdate ran at least once
+    int updatedW = 0, updatedH = 0; // ... at this size (the aspect of g.cam; tptDrawDeviceViews builds its cameras for it)
 
     // device scene: a ring of scene sets, so that an animated scene (kFlagAnimate re-packs every frame,
     // Test.cpp:304-308,321-339) is uploaded asynchronously while earlier frames still read the older sets.
@@ -195,6 +196,18 @@ struct Context {
         unsigned long long key = 0;
         int syncStreak = 0, seqStreak = 0;
     } devCaller;
+    // tptDrawDeviceViews: per frame slot, the views' cameras (device table the views kernel stages in LDS, pinned host staging) and
+    // their ray counters.  Per slot, because up to kMaxSlots launches are in flight: the table of one call must not be overwritten
+    // while an earlier launch still reads it (the upload is stream-ordered behind the slot's previous blend, like its colour buffer).
+    struct ViewSlot {
+        CameraPOD* dev = nullptr;       // [kMaxBatch] cameras
+        unsigned long long* rays = nullptr; // [kMaxBatch] rays of each view
+        CameraPOD* stage = nullptr;     // pinned [kMaxBatch]
+        hipEvent_t evUploaded = nullptr;
+        bool copyEnqueued = false;
+    } views[kMaxSlots];
+    char* dViews = nullptr;             // one allocation behind every slot's dev + rays (made by the first views call)
+    CameraPOD* hViewsStage = nullptr;   // pinned, behind every slot's stage
     long long aheadHits = 0;            // frames that were found traced ahead when their call arrived (tptGetLookaheadHits)
     unsigned long long* dRaysAhead = nullptr; // [kMaxSlots] per-slot ray counters of frames traced ahead of their call (both synchronous paths)
     unsigned long long configEpoch = 1;       // bumped by every call that changes what a frame looks like
@@ -318,7 +331,8 @@ int requireInit();
 int drainPipeline();
 int effectiveOverlap();
 // tpt_host_pipeline.cpp
-int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long long* frameRays, TraceTicket& T, int batch = 1, int rayStride = 0);
+int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long long* frameRays, TraceTicket& T, int batch = 1, int rayStride = 0,
+                 const CameraPOD* viewCams = nullptr);
 int enqueueResolve(const TraceTicket& T, float* deviceTile, const unsigned long long* frameRays);
 int syncAllStreams();
 int launchTailHelpers();

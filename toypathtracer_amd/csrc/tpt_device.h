@@ -53,6 +53,9 @@ struct KernelArgs {
     int helperPct;                   // a helper workgroup joins only while at least this % of the pool is unclaimed
     int ldsGroupPairs;               // grouped scenes, path-queue kernel, the two-level bounds filter: > 0 pair records of the groups' bounds staged in
                                      // LDS (whole super-groups), 0 = read them from global memory (too many for the LDS area), < 0 = flat filter over all groups
+    // Several views in one launch (tptDrawDeviceViews): batchFrames cameras, one per frame of the batch, in device memory; the launch
+    // takes tptTraceViewsKernel, which stages them in LDS and seeds every view with fc.frame.  Null for every other launch.
+    const CameraPOD* viewCams = nullptr;
 };
 
 } // namespace tpt

@@ -432,8 +432,16 @@ int tptShutdown(void)
     if (g.evOrder) { (void)hipEventDestroy(g.evOrder); g.evOrder = nullptr; }
     (void)hipStreamDestroy(g.ownStream);
     g.ownStream = g.stream = nullptr;
+    for (int k = 0; k < Context::kMaxSlots; ++k) {
+        if (g.views[k].evUploaded) (void)hipEventDestroy(g.views[k].evUploaded);
+        g.views[k] = Context::ViewSlot();
+    }
+    (void)hipFree(g.dViews); g.dViews = nullptr;
+    if (g.hViewsStage) (void)hipHostFree(g.hViewsStage);
+    g.hViewsStage = nullptr;
     g.inited = false;
     g.updated = false;
+    g.updatedW = g.updatedH = 0;
     g.occCache.clear();
     g.mirror = nullptr; g.mirrorCounter = nullptr;
     if (g.hostStream2) { (void)hipStreamSynchronize(g.hostStream2); (void)hipStreamDestroy(g.hostStream2); g.hostStream2 = nullptr; }
@@ -651,6 +659,8 @@ int tptUpdate(float time, int frameCount, int screenWidth, int screenHeight, uns
     if (g.config & CFG_MITSUBA_COMPARE) cs.aperture = 0.0f; // Test.cpp:312-313
     g.cam = makeCamera(cs, float(screenWidth) / float(screenHeight)); // Test.cpp:341
     g.updated = true;
+    g.updatedW = screenWidth;
+    g.updatedH = screenHeight;
     return 0;
 }
 

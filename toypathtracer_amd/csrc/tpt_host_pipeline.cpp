@@ -403,10 +403,37 @@ int enqueueChunkOrder(FramePlan& P, hipStream_t ts)
     return 0;
 }
 
+// tptDrawDeviceViews: the per-slot camera tables and view ray counters (Context::ViewSlot), allocated by the first views call (a
+// context that never draws views never holds them).
+int ensureViewSlots()
+{
+    if (g.dViews) return 0;
+    const size_t camBytes = sizeof(CameraPOD) * kMaxBatch, perSlot = camBytes + sizeof(unsigned long long) * kMaxBatch;
+    static_assert((sizeof(CameraPOD) * kMaxBatch) % 16 == 0, "the ray counters behind a slot's cameras stay aligned");
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dViews), perSlot * Context::kMaxSlots));
+    if (hipHostMalloc(reinterpret_cast<void**>(&g.hViewsStage), camBytes * Context::kMaxSlots, 0) != hipSuccess) {
+        (void)hipFree(g.dViews);
+        g.dViews = nullptr;
+        g.hViewsStage = nullptr;
+        return hipFail(hipErrorOutOfMemory, "tptDrawDeviceViews: pinned camera staging");
+    }
+    for (int k = 0; k < Context::kMaxSlots; ++k) {
+        Context::ViewSlot& V = g.views[k];
+        V.dev = reinterpret_cast<CameraPOD*>(g.dViews + perSlot * k);
+        V.rays = reinterpret_cast<unsigned long long*>(g.dViews + perSlot * k + camBytes);
+        V.stage = g.hViewsStage + (size_t)kMaxBatch * k;
+        V.copyEnqueued = false;
+        if (!V.evUploaded) HIPCHK(hipEventCreateWithFlags(&V.evUploaded, kOrderingEvent));
+    }
+    return 0;
+}
 
 // First half of a frame: plan, buffers, trace kernel on the slot's stream.  `frameRays`: where the kernel adds its ray
 // count (the context's counter, or a per-slot one for frames that are traced ahead of their DrawTest call).
-int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long long* frameRays, TraceTicket& T, int batch, int rayStride)
+// `viewCams` (tptDrawDeviceViews): the batch's frames are `batch` views of frame frameCount, one camera each (host memory, copied to
+// the slot's table on the frame's stream); the views kernel traces them.
+int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long long* frameRays, TraceTicket& T, int batch, int rayStride,
+                 const CameraPOD* viewCams)
 {
     if (g.sceneDirty || (g.curSet < 0 && g.pendingSet < 0)) { // tptSetScene after the last tptUpdate
         int rc = stageScene();
@@ -461,8 +488,17 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
         ~SeqGuard() { if (!launched) g.frameSeq--; }
     } seqGuard;
 
-    int rc = chooseKernel(P);
-    if (rc) return rc;
+    int rc = 0;
+    a.viewCams = nullptr;
+    if (viewCams) {
+        if ((rc = ensureViewSlots())) return rc;
+        a.viewCams = g.views[P.slot].dev; // (before chooseKernel: the views kernel's LDS differs)
+        frameRays = g.views[P.slot].rays;  // every view counts its own rays (the blends add them to the running total)
+        rayStride = 1;
+    }
+    if ((rc = chooseKernel(P))) return rc;
+    if (viewCams && !P.queued)
+        return refuse("tptDrawDeviceViews: needs the path-queue kernel (per-pixel seeds, recursive fold, two-phase HitSpheres, at most 2047 spp)");
     // a batch is traced by the path-queue kernel (per-pixel seeds) or, in the reference's own seed mode, by the lane-refill
     // kernel: one lane per (frame, row) -- rows AND frames are independent RNG streams there (Test.cpp:280)
     if (batch > 1 && (!(P.queued || P.rowSerial) || w > 8192 || h > 8192 || (long long)a.nLocalRows * w * batch > (1ll << 30)))
@@ -500,9 +536,19 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
         HIPCHK(hipStreamWaitEvent(ts, g.evResolve[slot], 0)); // colour buffer free again
     }
     if ((rc = enqueueSceneUpload(ts))) return rc; // behind the wait above: nobody reads the set being replaced any more
+    if (viewCams) {
+        // the views' cameras, behind the same wait: the slot's previous launch has read its table; the previous copy out of the
+        // slot's pinned staging (an earlier views call on this slot) has left the host before the staging is overwritten
+        Context::ViewSlot& V = g.views[slot];
+        if (V.copyEnqueued) HIPCHK(hipEventSynchronize(V.evUploaded));
+        memcpy(V.stage, viewCams, sizeof(CameraPOD) * (size_t)batch);
+        HIPCHK(hipMemcpyAsync(V.dev, V.stage, sizeof(CameraPOD) * (size_t)batch, hipMemcpyHostToDevice, ts));
+        HIPCHK(hipEventRecord(V.evUploaded, ts));
+        V.copyEnqueued = true;
+    }
     if ((rc = enqueueChunkOrder(P, ts))) return rc;
     if (frameRays && frameRays != g.dRays) HIPCHK(hipMemsetAsync(frameRays, 0, sizeof(unsigned long long) * (size_t)(rayStride > 0 ? batch : 1), ts));
-    const bool helpable = P.queued && pipelined && batch == 1 && !P.rowSerial; // (single frames of the path-queue kernel)
+    const bool helpable = P.queued && pipelined && batch == 1 && !P.rowSerial && !viewCams; // (single frames of the path-queue kernel)
     a.helperBase = 0;
     a.helperPct = 0;
     a.gen = 0u;
@@ -678,6 +724,63 @@ int tptDrawDeviceBatch(float time, int firstFrame, int nFrames, int w, int h, fl
         TraceTicket T;
         if ((rc = enqueueTrace(firstFrame + f, w, h, testFlags, nullptr, T, n))) return rc;
         if ((rc = enqueueResolve(T, deviceTile, nullptr))) return rc;
+    }
+    return 0;
+}
+
+// nViews cameras of the scene as of the last tptUpdate, traced by ONE launch (the frames of a batch, a camera each, the seeds of
+// frameCount for all), each view blended into its own tile: the same bits and ray counts as nViews tptSetCamera / tptUpdate /
+// tptDrawDevice sequences.  Not a continuation of anything: frames traced ahead and stream-batch planes are dropped, the caller's
+// camera and the bookkeeping of later tptDrawDevice calls are left as they were.
+int tptDrawDeviceViews(float time, int frameCount, int w, int h, int nViews, const float* views, float* deviceTiles, int64_t* deviceViewRays,
+                       unsigned testFlags)
+{
+    (void)time; // (the scene state is that of the last tptUpdate, as for tptDrawDevice)
+    if (int rc_ = flushShardDeferred()) return rc_; // (see tptDrawDevice)
+    if (requireInit()) return -1;
+    if (nViews < 1 || nViews > kMaxBatch) return fail("tptDrawDeviceViews: nViews must be 1.." + std::to_string(kMaxBatch));
+    if (!views || !deviceTiles || w <= 0 || h <= 0) return fail("tptDrawDeviceViews: bad arguments (views, deviceTiles, size)");
+    if (!g.updated || w != g.updatedW || h != g.updatedH) return fail("tptDrawDeviceViews: call tptUpdate (UpdateTest) at this size first");
+    if (w > 8192 || h > 8192) return fail("tptDrawDeviceViews: frames of at most 8192 x 8192");
+    if ((size_t)h * (size_t)w * sizeof(f4) * (size_t)nViews > (4ull << 30))
+        return refuse("tptDrawDeviceViews: " + std::to_string(((size_t)h * w * sizeof(f4) * nViews) >> 20) + " MiB of view colour per launch: over the 4096 MiB limit, use fewer views");
+    if (g.seedMode == SEED_ROW_SERIAL) return fail("tptDrawDeviceViews: needs per-pixel seeds (tptSetSeedMode(1)); row-serial views are not supported");
+    if (g.foldMode != FOLD_RECURSIVE) return fail("tptDrawDeviceViews: needs the recursive fold (tptSetFoldMode(0))");
+    if (g.persist != 3 || g.hs != HS_TWO_PHASE) return fail("tptDrawDeviceViews: needs the path-queue kernel (tptSetKernelVariant(0, 3, ..))");
+    if (g.numParts > 1 || g.shard.active) return fail("tptDrawDeviceViews: not with row sharding or a communicator (sharded views are not supported)");
+    if (g.mirror) return fail("tptDrawDeviceViews: not with a tile mirror (tptSetTileMirror)");
+    // the cameras exactly as tptSetCamera + tptUpdate at this size would build them (Test.cpp:309-319, 341)
+    CameraPOD cams[kMaxBatch];
+    for (int v = 0; v < nViews; ++v) {
+        const float* p = views + 9 * v;
+        CameraSetup cs = defaultCameraSetup(); // (vup (0, 1, 0))
+        for (int i = 0; i < 3; ++i) {
+            cs.lookFrom[i] = p[i];
+            cs.lookAt[i] = p[3 + i];
+        }
+        cs.vfov = p[6];
+        cs.aperture = (g.config & CFG_MITSUBA_COMPARE) ? 0.0f : p[7]; // Test.cpp:312-313
+        cs.focusDist = p[8];
+        cams[v] = makeCamera(cs, float(w) / float(h));
+    }
+    int rc = discardLookahead();
+    if (rc) return rc;
+    // one launch: the views are the frames of a batch (colour planes nPixels apart in the slot's buffer, a ray counter each)
+    TraceTicket T;
+    if ((rc = enqueueTrace(frameCount, w, h, testFlags, nullptr, T, nViews, 1, cams))) return rc;
+    if (!T.valid) return 0;
+    // the blends, in view order on the context's stream, each into its own tile with the frame's lerp factor; blend v also adds view
+    // v's rays to the running total.  The per-view counts go to the caller first: the slot's counters are free again once its last
+    // blend has run (the next launch on this slot waits for that).
+    const Context::ViewSlot& V = g.views[T.slot];
+    if (T.pipelined) HIPCHK(hipStreamWaitEvent(g.stream, g.evTrace[T.slot], 0));
+    if (deviceViewRays) HIPCHK(hipMemcpyAsync(deviceViewRays, V.rays, sizeof(unsigned long long) * (size_t)nViews, hipMemcpyDeviceToDevice, g.stream));
+    for (int v = 0; v < nViews; ++v)
+        HIPCHK(tptLaunchResolve(deviceTiles + (size_t)v * (size_t)T.nPixels * 4, T.colour + (size_t)v * (size_t)T.nPixels, T.nPixels, T.lerpFac,
+                                nullptr, g.dRays, nullptr, V.rays + v, g.stream));
+    if (T.pipelined) {
+        HIPCHK(hipEventRecord(g.evResolve[T.slot], g.stream));
+        g.resolveRecorded[T.slot] = true;
     }
     return 0;
 }

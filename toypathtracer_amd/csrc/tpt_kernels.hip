@@ -477,6 +477,12 @@ static_assert(TPT_GROUP_DEAL_ENTRIES >= TPT_GROUP_DEAL_CAP, "the flat variants' 
 // 256-B margin per workgroup: chooseKernel); 960 measured no slower than 1024 (profiles/r03/r03_run10.log)
 #define TPT_Q_PATHS (TPT_MATRIX_FILTER ? 952 : TPT_Q_P)
 #endif
+// Several views in one launch (tptTraceViewsKernel): the views' cameras sit in LDS (32 x 88 B), and the instantiation owns 44 paths
+// fewer than its single-view twin to make room for them (44 x 64 B of path records = 32 x 88 B): the LDS a launch takes stays what it
+// was, so the default scene keeps two workgroups per CU and the matrix-core filter (chooseKernel drops both when it does not fit).
+#define TPT_Q_VIEWS_MAX 32
+#define TPT_Q_VIEW_CAM_BYTES (TPT_Q_VIEWS_MAX * 88)
+#define TPT_Q_VIEW_PATHS ((TPT_Q_VIEW_CAM_BYTES + TPT_Q_NF4 * 16 - 1) / (TPT_Q_NF4 * 16))
 #ifndef TPT_Q_PATHS_GROUPED
 // ... and of the instantiation for GROUPED scenes (no scene staging, no matrix-filter table): 608.  The LDS the smaller pool frees holds
 // the entry areas of the three-stage dealing (640 entries per wave) and the groups' bounding spheres (pair records, 144 B per super-group
@@ -1149,7 +1155,9 @@ __device__ __forceinline__ int hitSpheresGroupedDeal(const SceneView& sv, bool g
 #endif
 // BATCH: the launch traces a.batchFrames consecutive frames (tptDrawDeviceBatch).  A compile-time switch: the frame index
 // a path carries costs the single-frame kernel two more spilled registers if it is a run-time one.
-template <bool LDS_SCENE, bool BATCH>
+// VIEWS (with BATCH; tptDrawDeviceViews): frame j of the batch is VIEW j of one frame -- camera a.viewCams[j] (staged in LDS), the
+// seed of frame fc.frame for every view.  Its own kernel (tptTraceViewsKernel) for the same reason.
+template <bool LDS_SCENE, bool BATCH, bool VIEWS = false>
 __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1157,20 +1165,23 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     // registers): path records, rings, control block, frame constants; then the scene arrays, whose sizes the launch decides
     // (kernels that stage the scene keep {centre, r^2} of up to 64 spheres -- every scene the matrix filter serves -- at offset
     //  0: phase 2 then addresses a sphere with sphere index x 16 and an immediate, like the path records)
-    constexpr int kPaths = LDS_SCENE ? TPT_Q_PATHS : TPT_Q_PATHS_GROUPED; // paths this workgroup owns
+    static_assert(BATCH || !VIEWS, "views are frames of a batched launch");
+    constexpr int kPaths = (LDS_SCENE ? TPT_Q_PATHS : TPT_Q_PATHS_GROUPED) - (VIEWS ? TPT_Q_VIEW_PATHS : 0); // paths this workgroup owns
     constexpr int kOffSt = LDS_SCENE ? TPT_Q_SPH_FIXED : 0;
     constexpr int kOffQ = kOffSt + TPT_Q_NF4 * kPaths * 16;
     constexpr int kOffCtl = kOffQ + Q_COUNT * TPT_Q_P * 2;
     constexpr int kOffDeal = kOffCtl + (((int)sizeof(QueueCtl) + 63) & ~63);
     constexpr int kDealBytes = (!LDS_SCENE && TPT_GROUP_DEAL) ? TPT_Q_WAVES * TPT_GROUP_DEAL_WAVE_BYTES : 0; // pair lists of the grouped traversal
     constexpr int kOffFc = kOffDeal + kDealBytes;
-    constexpr int kOffScene = kOffFc + (((int)sizeof(FrameConsts) + 15) & ~15);
+    constexpr int kOffCams = kOffFc + (((int)sizeof(FrameConsts) + 15) & ~15);
+    constexpr int kOffScene = kOffCams + (VIEWS ? TPT_Q_VIEW_CAM_BYTES : 0);
     f4* st = reinterpret_cast<f4*>(smem + kOffSt);
     LdsRing q = (LdsRing)(smem + kOffQ);
     QueueCtl* ctl = reinterpret_cast<QueueCtl*>(smem + kOffCtl);
     // the frame constants the camera code reads (22 camera floats, 1/w, 1/h): in LDS, read where a sample starts, instead of
     // ~30 SGPRs held (and spilled) across the whole loop
     FrameConsts* ldsFc = reinterpret_cast<FrameConsts*>(smem + kOffFc);
+    CameraPOD* ldsCams = reinterpret_cast<CameraPOD*>(smem + kOffCams); // (VIEWS: the cameras of the batch's views)
     const int nPad = a.scene.nPairs * 2;
     const bool sphFixed = LDS_SCENE && nPad * 16 <= TPT_Q_SPH_FIXED;
     f4* ldsSphFixed = reinterpret_cast<f4*>(smem);
@@ -1241,6 +1252,9 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
 #endif
 #endif
     for (int i = tid; i < (int)(sizeof(FrameConsts) / 4); i += TPT_Q_T) reinterpret_cast<uint32_t*>(ldsFc)[i] = reinterpret_cast<const uint32_t*>(&a.fc)[i];
+    if (VIEWS)
+        for (int i = tid; i < a.batchFrames * (int)(sizeof(CameraPOD) / 4); i += TPT_Q_T)
+            reinterpret_cast<uint32_t*>(ldsCams)[i] = reinterpret_cast<const uint32_t*>(a.viewCams)[i];
     // every path starts in the FREE queue; all other queues empty (sentinel everywhere)
     for (int i = tid; i < Q_COUNT * TPT_Q_P; i += TPT_Q_T) q[i] = (unsigned short)(i < kPaths ? i : 0xFFFF);
     if (tid < 8) {
@@ -1433,12 +1447,15 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                 if (lane == 0) atomicSub(&ctl->poolTotal, (unsigned)take);
             }
             if (got) {
-                rng = pixelSeed(fc.seedMode, px, py, fc.frame + (BATCH ? laneFrame : 0));
+                rng = pixelSeed(fc.seedMode, px, py, fc.frame + ((BATCH && !VIEWS) ? laneFrame : 0));
                 // colour sum = 0; the pixel: x | y << 16, or in a batched launch x | y << 13 | frame << 26
                 const uint32_t where = BATCH ? ((uint32_t)px | ((uint32_t)py << 13) | ((uint32_t)laneFrame << 26))
                                              : ((uint32_t)px | ((uint32_t)py << 16));
                 colSum[p] = mk4(0.0f, 0.0f, 0.0f, u2f(where));
-                qCamera(*ldsFc, px, py, rng, ro, rd);
+                if (VIEWS)
+                    qCameraView(ldsCams[laneFrame], *ldsFc, px, py, rng, ro, rd);
+                else
+                    qCamera(*ldsFc, px, py, rng, ro, rd);
                 ray = true;
             } else if (mine) {
                 toFree = true; // no pixel left for this path
@@ -1463,7 +1480,10 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                 sample++;
                 if (sample < fc.spp) {
                     colSum[p] = mk4(col.x, col.y, col.z, c3.w);
-                    qCamera(*ldsFc, px, py, rng, ro, rd);
+                    if (VIEWS)
+                        qCameraView(ldsCams[f2u(c3.w) >> 26], *ldsFc, px, py, rng, ro, rd);
+                    else
+                        qCamera(*ldsFc, px, py, rng, ro, rd);
                     depth = 0;
                     doMatE = true;
                     ray = true;
@@ -1697,6 +1717,20 @@ __global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute
 tptTraceQueueKernel<false, true>(const KernelArgs a)
 {
     traceQueueBody<false, true>(a);
+}
+// Several views of one frame per launch (tptDrawDeviceViews): the batched kernel with a camera per frame of the batch.  A kernel of
+// its own, not a third template argument of tptTraceQueueKernel: the queue kernels keep their names and their code.
+template <bool LDS_SCENE>
+__global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute__((amdgpu_num_vgpr(TPT_Q_MAX_VGPR)))
+tptTraceViewsKernel(const KernelArgs a)
+{
+    traceQueueBody<LDS_SCENE, true, true>(a);
+}
+template <>
+__global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute__((amdgpu_num_vgpr(TPT_Q_MAX_VGPR_GROUPED)))
+tptTraceViewsKernel<false>(const KernelArgs a)
+{
+    traceQueueBody<false, true, true>(a);
 }
 
 #if defined(TPT_TEST_HOOKS)
@@ -1965,14 +1999,18 @@ constexpr size_t kQueueLdsFixedPart = (size_t)TPT_Q_NF4 * TPT_Q_PATHS * 16 + (si
                                       ((sizeof(tpt::FrameConsts) + 15) & ~(size_t)15);
 constexpr size_t kDefaultSceneLds = TPT_Q_SPH_FIXED + ((46 * 4 + 15) & ~15) + 46 * 48 + 2 * 32 + (TPT_MATRIX_FILTER ? TPT_MXH_TABLE_DWORDS * 4 + 64 : 0);
 static_assert(2 * (kQueueLdsFixedPart + kDefaultSceneLds + 256) <= 160 * 1024, "the default scene no longer fits two path-queue workgroups per CU: shrink TPT_Q_PATHS");
+static_assert(TPT_Q_VIEW_CAM_BYTES <= TPT_Q_NF4 * TPT_Q_VIEW_PATHS * 16, "the views' cameras take no more LDS than the path records they replace");
+static_assert(sizeof(tpt::CameraPOD) == 88 && sizeof(tpt::CameraPOD) % 4 == 0, "cameras are staged in LDS as 22 words");
 }
 size_t tptQueueLdsBytes(const KernelArgs& a, bool ldsScene)
 {
     const int nPad = a.scene.nPairs * 2;
+    const bool views = a.viewCams != nullptr; // (tptTraceViewsKernel: the cameras in LDS, TPT_Q_VIEW_PATHS path records fewer)
     size_t bytes = 0;
     if (ldsScene) bytes += TPT_Q_SPH_FIXED + ((size_t)nPad * 16 <= TPT_Q_SPH_FIXED ? 0 : (size_t)nPad * 16) + (((size_t)nPad * 4 + 15) & ~(size_t)15) + (size_t)a.scene.nSpheres * 48;
     bytes += (size_t)a.scene.nLights * 32;
     bytes += (size_t)TPT_Q_NF4 * (ldsScene ? TPT_Q_PATHS : TPT_Q_PATHS_GROUPED) * 16 + (size_t)Q_COUNT * TPT_Q_P * 2 + ((sizeof(QueueCtl) + 63) & ~(size_t)63) + ((sizeof(FrameConsts) + 15) & ~(size_t)15);
+    if (views) bytes += (size_t)TPT_Q_VIEW_CAM_BYTES - (size_t)TPT_Q_NF4 * TPT_Q_VIEW_PATHS * 16;
     if (!ldsScene && TPT_GROUP_DEAL) bytes += (size_t)TPT_Q_WAVES * TPT_GROUP_DEAL_WAVE_BYTES;
     if (!ldsScene && a.ldsGroupPairs > 0) bytes += 16 + (size_t)(a.ldsGroupPairs / (TPT_SUPER / 2)) * TPT_GPAIR_LDS_STRIDE * 4; // the groups' bounds for the second filter level (tptQueueGroupPairsInLds), padded stride
 #if TPT_MATRIX_FILTER
@@ -1989,8 +2027,23 @@ static hipError_t launchTraceQueue(const KernelArgs& a, int blocks, size_t lds, 
     hipLaunchKernelGGL(k, dim3(blocks), dim3(TPT_Q_T), lds, stream, a);
     return hipSuccess;
 }
+template <bool LDS_SCENE>
+static hipError_t launchTraceViews(const KernelArgs& a, int blocks, size_t lds, hipStream_t stream)
+{
+    auto k = tptTraceViewsKernel<LDS_SCENE>;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(TPT_Q_T), lds, stream, a);
+    return hipSuccess;
+}
 hipError_t tptLaunchTraceQueue(const KernelArgs& a, bool ldsScene, int blocks, size_t lds, hipStream_t stream)
 {
+    if (a.viewCams) { // (tptDrawDeviceViews: 1 .. TPT_Q_VIEWS_MAX views, the frames of the batch)
+        if (a.batchFrames < 1 || a.batchFrames > TPT_Q_VIEWS_MAX) return hipErrorInvalidValue;
+        hipError_t e = ldsScene ? launchTraceViews<true>(a, blocks, lds, stream) : launchTraceViews<false>(a, blocks, lds, stream);
+        if (e != hipSuccess) return e;
+        return hipGetLastError();
+    }
     const bool batch = a.batchFrames > 1;
     hipError_t e = ldsScene ? (batch ? launchTraceQueue<true, true>(a, blocks, lds, stream) : launchTraceQueue<true, false>(a, blocks, lds, stream))
                             : (batch ? launchTraceQueue<false, true>(a, blocks, lds, stream) : launchTraceQueue<false, false>(a, blocks, lds, stream));

@@ -1134,6 +1134,14 @@ TPT_HD void qCamera(const FrameConsts& fc, int x, int y, uint32_t& rng, f3& o, f
     const float v = ((float)y + rnd01(rng)) * fc.invHeight;
     cameraGetRay(fc.cam, u, v, rng, o, d);
 }
+// the same for a view of tptDrawDeviceViews: its own camera, the frame's 1/w and 1/h
+TPT_HD void qCameraView(const CameraPOD& cam, const FrameConsts& fc, int x, int y, uint32_t& rng, f3& o, f3& d)
+{
+    TPT_STAT(ST_CAMERA);
+    const float u = ((float)x + rnd01(rng)) * fc.invWidth;
+    const float v = ((float)y + rnd01(rng)) * fc.invHeight;
+    cameraGetRay(cam, u, v, rng, o, d);
+}
 // what a path that ends contributes before the fold: sky (Test.cpp:226-231) or the un-zeroed emission of the sphere it
 // stopped on (depth cap / failed scatter / unknown material, Test.cpp:207,218-221,187-191)
 TPT_HD f3 qEndTerm(const SceneView& sv, const FrameConsts& fc, f3 dir, int id)
