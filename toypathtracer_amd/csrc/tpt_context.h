@@ -3,7 +3,8 @@
 //
 //   tpt_host.cpp           context, initialisation, scene staging, the setters, UpdateTest, the reference's C++ symbols
 //   tpt_host_pipeline.cpp  one frame: plan, buffers, trace launch, ordered blend; tail helpers; tptDrawDevice / tptDrawDeviceBatch
-//   tpt_host_draw.cpp      DrawTest on a host backbuffer: look-ahead, row-serial batches, banded copies; display conversion
+//   tpt_host_draw.cpp      the queue of launches traced ahead of their call (LaunchQueue); DrawTest on a host backbuffer: banded
+//                          copies; display conversion
 //   tpt_host_shard.cpp     multi-GPU inside the library: RCCL (dlopen), tptDrawSharded, tptShardedFinish
 //   tpt_host_hooks.cpp     unit-test / profiling entry points (include/tpt_test_hooks.h; the second build only)
 #pragma once
@@ -38,6 +39,55 @@ struct TraceTicket {
     const f4* colour = nullptr;
     int batch = 1;           // frames traced by the launch; their colour planes lie nPixels apart
     tptLerpTable lerp = {};  // batch > 1: each frame's lerp factor
+    TraceTicket plane(int j) const // frame j of the launch, as a ticket of its own (a single-frame launch: plane 0 is itself)
+    {
+        TraceTicket t = *this;
+        t.colour = colour + (size_t)j * (size_t)nPixels;
+        if (batch > 1) t.lerpFac = lerp.v[j];
+        t.batch = 1;
+        return t;
+    }
+};
+
+// Are a caller's calls consecutive frames of one (w, h, flags, configuration)?  n: how many in a row (0: not a continuation).
+struct Streak {
+    int frame = 0, w = 0, h = 0, n = 0;
+    unsigned flags = 0;
+    unsigned long long key = 0;
+    int next(int frame_, int w_, int h_, unsigned flags_, unsigned long long key_)
+    {
+        n = frame_ == frame + 1 && w_ == w && h_ == h && flags_ == flags && key_ == key ? n + 1 : 0;
+        frame = frame_; w = w_; h = h_; flags = flags_; key = key_;
+        return n;
+    }
+};
+
+// A launch traced ahead of the calls that will blend its frames, one frame per call, in frame order.  Its kind says who serves it:
+//   AHEAD       a single frame traced ahead (tptSetHostLookahead): tptDraw and tptDrawDevice;
+//   ROW_SERIAL  a batch in the reference's own seed mode (one launch of rows x frames lanes): tptDraw only;
+//   STREAM      a batch of small frames for a streaming caller (tptSetStreamBatching): tptDrawDevice only (and tptDrawSharded through it).
+struct PendingLaunch {
+    enum Kind { AHEAD, ROW_SERIAL, STREAM } kind = AHEAD;
+    TraceTicket T;                      // T.batch frames: firstFrame, firstFrame + 1, ...
+    int firstFrame = 0, next = 0;       // frame firstFrame + next is served next
+    int w = 0, h = 0;                   // what the launch was traced for ...
+    unsigned flags = 0;
+    unsigned long long key = 0;         // ... and Context::configEpoch at the time: everything else a trace depends on
+    unsigned long long* rays = nullptr; // per-frame ray counters: rays[j] for frame firstFrame + j
+};
+// The pending launches, oldest first (tpt_host_draw.cpp).  All of one kind: push refuses another kind, so a caller discards first.
+// At most three AHEAD frames, two ROW_SERIAL batches (the one being served and the one after it) or one STREAM batch.  A launch's
+// colour planes sit in frame slots that reserveSlotBuffers may neither shrink nor grow while the queue is not empty.
+struct LaunchQueue {
+    static const int kCap = 4;
+    PendingLaunch e[kCap];
+    int n = 0;
+    bool empty() const { return n == 0; }
+    bool holds(PendingLaunch::Kind kind) const { return n > 0 && e[0].kind == kind; }
+    bool frontMatches(PendingLaunch::Kind kind, int frame, int w, int h, unsigned flags, unsigned long long key) const;
+    void serveFront(bool wasOpen, TraceTicket& T, const unsigned long long*& rays);
+    int push(const PendingLaunch& L);
+    int discard();
 };
 
 struct Context {
@@ -105,7 +155,6 @@ struct Context {
     int gridDiv = 0;                            // env TPT_GRID_DIV: launch resident/gridDiv workgroups per frame; 0 = adaptive
     unsigned long long oldestPending = 0;       // adaptive grid: oldest frame whose trace kernel may still be running
     int streamDepth = 1, prevInFlight = -1;     // adaptive grid: deepest pipeline the caller has built / in flight at the previous enqueue
-    int framesSinceIdle = 0;                    // adaptive grid: frames enqueued since one found the pipeline empty
     int depthOverride = 0;                      // > 0: frames that share the machine, known to the caller of enqueueTrace (tptDraw)
     int ldsStackLevels = 6;                     // recursive fold, lane-refill kernel: bounce-stack levels kept in LDS
 
@@ -117,7 +166,7 @@ struct Context {
     long long lastTotal = 0;
 
     f4* dStack[kMaxSlots] = {};         // recursive fold: global bounce stacks / spill levels (one per trace stream: the first kMaxOverlap entries)
-    size_t stackCap = 0, colourCap = 0, pathCap = 0; // bytes per slot; all reserved slots have the same capacities
+    size_t stackCap = 0, colourCap = 0; // bytes per slot; all reserved slots have the same capacities
     int slotsReserved = 0;              // slots [0, slotsReserved) hold buffers of those capacities
     int smallStreak = 0;                // consecutive launches that needed a quarter of the reserved colour slot or less (reserveSlotBuffers)
     int slotReservations = 0;           // how often the slot buffers were (re-)allocated (tptGetPipelineInfo)
@@ -129,10 +178,8 @@ struct Context {
     int costOrder = 1;                // expensive tiles first (lane-refill kernel)
     hipEvent_t evOrder = nullptr;     // the last sort of an order table (recorded on the stream that ran it)
     hipStream_t orderStream = nullptr;
-    bool orderDone = true;
     unsigned long long orderSeq = 0;
     int lastOrderTable = 0;
-    f4* dPath[kMaxSlots] = {};          // (unused since the path record moved into LDS; kept for the size bookkeeping)
     float* dFrame = nullptr; // device tile behind the host-pointer DrawTest
     // ---- host-pointer path (tptDraw / DrawTest)
     hipStream_t hostStream2 = nullptr;  // second stream of the banded upload / blend / download (full-duplex PCIe)
@@ -141,60 +188,22 @@ struct Context {
     const float* tileSrc = nullptr;     // which host buffer (and size) the device tile g.dFrame currently mirrors
     int tileW = 0, tileH = 0;
     int lookahead = 2;                  // tptSetHostLookahead: frames traced ahead of the caller's next DrawTest
-    struct Ahead {                      // a frame traced ahead: what it was traced for, where its result sits
-        int frameCount, w, h;
-        unsigned flags;
-        unsigned long long configKey;   // everything else a trace depends on (see hostConfigKey)
-        int raySlot;
-        bool used;
-    };
-    Ahead ahead[4];
-    TraceTicket aheadTicket[4];
-    // The same in the reference's own seed mode (one RNG stream per row, Test.cpp:280): a frame alone offers `rows` lanes of
-    // work, so the frames ahead are traced as ONE batched launch (rows x frames lanes, tptDrawDeviceBatch's kernel path) with a
-    // ray counter per frame, and served one by one; [0] is being served, [1] is the batch after it, launched when [0] starts.
-    struct RowSerialBatch {
-        bool used = false;
-        int firstFrame = 0, n = 0, next = 0, w = 0, h = 0;
-        unsigned flags = 0;
-        unsigned long long key = 0;
-        TraceTicket T;
-        int counterBase = 0;
-    } rsb[2];
-    struct HostCaller { // tptDraw: are the calls consecutive frames of one configuration?  (gates the row-serial batches)
-        int frame = 0, w = 0, h = 0, streak = 0;
-        unsigned flags = 0;
-        unsigned long long key = 0;
+    LaunchQueue pending;                // launches traced ahead of the calls that will blend their frames
+    struct HostCaller {                 // tptDraw: are the calls consecutive frames of one configuration?  (gates the row-serial batches)
+        Streak seq;
         // a configuration whose batched launch was refused (frame too large for a batch, not enough device memory): served frame
         // by frame from then on instead of failing (or retrying the reservation) on every call
         int refusedW = 0, refusedH = 0;
         unsigned long long refusedKey = 0;
     } hostCaller;
-    unsigned long long* dRaysBatch = nullptr; // [2][kMaxBatch] per-frame ray counters of those two batches
-    // Streaming callers of tptDrawDevice / tptDrawSharded with SMALL frames (tiles of a sharded frame, 640x360): a launch cannot
-    // be shorter than its longest pixel's sequential samples, so frame by frame such callers are bound by launch latency, not
-    // by arithmetic.  When the calls are consecutive frames of one static configuration, the next call's frames are traced in
-    // the SAME launch (2-8 frames, tptDrawDeviceBatch's kernel path, a ray counter per frame) and each later call only blends
-    // its own plane -- every frame is still delivered, in order, with its own ray count.  A wrong guess costs GPU time only.
-    struct StreamBatch {
-        bool used = false;
-        int firstFrame = 0, n = 0, next = 0, w = 0, h = 0;
-        unsigned flags = 0;
-        unsigned long long key = 0;
-        TraceTicket T;
-        int counterBase = 0;
-    } sbatch;
     static const int kStreamBatchMax = 8, kStreamRing = 64;
-    unsigned long long* dRaysStream = nullptr; // [kStreamRing][kStreamBatchMax]
-    unsigned long long streamBatches = 0;       // batches launched (ring index)
+    unsigned long long streamBatches = 0;       // stream batches launched (index into their ring of ray counters)
     int streamBatch = 1;                        // on by default since round 4; tptSetStreamBatching(0) / env TPT_STREAM_BATCH=0 turn it off
     // tptDrawDevice: is the caller synchronous (the previous frame's blend has completed by the time the next call arrives)
     // and are its calls consecutive frames of one configuration?  Then the next frames are traced ahead for it too.
     struct DeviceCaller {
-        int lastSlot = -1, frame = 0, w = 0, h = 0;
-        unsigned flags = 0;
-        unsigned long long key = 0;
-        int syncStreak = 0, seqStreak = 0;
+        int lastSlot = -1, syncStreak = 0;
+        Streak seq;
     } devCaller;
     // tptDrawDeviceViews: per frame slot, the views' cameras (device table the views kernel stages in LDS, pinned host staging) and
     // their ray counters.  Per slot, because up to kMaxSlots launches are in flight: the table of one call must not be overwritten
@@ -209,7 +218,9 @@ struct Context {
     char* dViews = nullptr;             // one allocation behind every slot's dev + rays (made by the first views call)
     CameraPOD* hViewsStage = nullptr;   // pinned, behind every slot's stage
     long long aheadHits = 0;            // frames that were found traced ahead when their call arrived (tptGetLookaheadHits)
-    unsigned long long* dRaysAhead = nullptr; // [kMaxSlots] per-slot ray counters of frames traced ahead of their call (both synchronous paths)
+    // per-frame ray counters of the pending launches, one allocation: [kMaxSlots] AHEAD frames (indexed by the frame's sequence number
+    // at enqueue), [2][kMaxBatch] ROW_SERIAL batches (two banks, alternating), [kStreamRing][kStreamBatchMax] STREAM batches (a ring)
+    unsigned long long *dRaysAhead = nullptr, *dRaysBatch = nullptr, *dRaysStream = nullptr;
     unsigned long long configEpoch = 1;       // bumped by every call that changes what a frame looks like
 
     // ---- multi-GPU inside the library (one process per GPU, RCCL): tptCommInit .. tptDrawSharded
@@ -285,6 +296,13 @@ struct Context {
 
 extern Context g;
 
+// Launches made inside the scope share the machine with d frames (this one and the ones traced ahead), not with a deep device-path
+// pipeline (sizeGrid).
+struct DepthScope {
+    explicit DepthScope(int d) { g.depthOverride = d; }
+    ~DepthScope() { g.depthOverride = 0; }
+};
+
 // Events that order work between the streams of this context (trace -> resolve -> next use of a colour buffer, scene
 // upload -> trace, order-table sort -> trace).  Plain events: hipEventDisableSystemFence was measured (no gain: the
 // fences are not what bounds small frames) and dropped again -- a dependency between kernels on different streams is
@@ -336,10 +354,8 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
 int enqueueResolve(const TraceTicket& T, float* deviceTile, const unsigned long long* frameRays);
 int syncAllStreams();
 int launchTailHelpers();
-// tpt_host_draw.cpp
-int discardLookahead();
 int flushShardDeferred(); // tpt_host_shard.cpp: issue the sharded frames tptDrawSharded has accepted but deferred (none: nothing happens)
-int takeAhead(TraceTicket& T, int& raySlot);
+// tpt_host_draw.cpp (and LaunchQueue)
 int traceAhead(int frameCount, int w, int h, unsigned testFlags, unsigned long long key, int want);
 
 } // namespace tpth

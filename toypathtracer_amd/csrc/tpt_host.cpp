@@ -276,7 +276,7 @@ int createTraceStreams()
 int drainPipeline()
 {
     if (g.inited) {
-        if (discardLookahead()) return -2;
+        if (g.pending.discard()) return -2;
         HIPCHK(hipStreamSynchronize(g.stream));
         for (int k = 0; k < Context::kMaxOverlap; ++k)
             if (g.traceStream[k]) HIPCHK(hipStreamSynchronize(g.traceStream[k]));
@@ -332,7 +332,6 @@ int tptInitialize(void)
     HIPCHK(hipStreamCreateWithFlags(&g.ownStream, hipStreamDefault));
     g.stream = g.ownStream;
     HIPCHK(hipEventCreateWithFlags(&g.evOrder, kOrderingEvent));
-    g.orderDone = true;
     HIPCHK(hipEventCreate(&g.ev0));
     HIPCHK(hipEventCreate(&g.ev1));
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dWork), 64 * Context::kMaxSlots));
@@ -353,16 +352,13 @@ int tptInitialize(void)
     HIPCHK(hipStreamCreateWithFlags(&g.hostStream2, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&g.evBand, kOrderingEvent));
     HIPCHK(hipEventCreateWithFlags(&g.evBandEnd, kOrderingEvent));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dRaysAhead), sizeof(unsigned long long) * Context::kMaxSlots));
-    HIPCHK(hipMemsetAsync(g.dRaysAhead, 0, sizeof(unsigned long long) * Context::kMaxSlots, g.stream));
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dRaysStream), sizeof(unsigned long long) * Context::kStreamRing * Context::kStreamBatchMax));
-    HIPCHK(hipMemsetAsync(g.dRaysStream, 0, sizeof(unsigned long long) * Context::kStreamRing * Context::kStreamBatchMax, g.stream));
-    g.sbatch.used = false;
+    const size_t pendingRays = sizeof(unsigned long long) * (Context::kMaxSlots + 2 * kMaxBatch + Context::kStreamRing * Context::kStreamBatchMax);
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dRaysAhead), pendingRays));
+    HIPCHK(hipMemsetAsync(g.dRaysAhead, 0, pendingRays, g.stream));
+    g.dRaysBatch = g.dRaysAhead + Context::kMaxSlots;
+    g.dRaysStream = g.dRaysBatch + 2 * kMaxBatch;
+    g.pending.n = 0;
     if (const char* esb = getenv("TPT_STREAM_BATCH")) g.streamBatch = atoi(esb) != 0; // (default on)
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dRaysBatch), sizeof(unsigned long long) * 2 * kMaxBatch));
-    HIPCHK(hipMemsetAsync(g.dRaysBatch, 0, sizeof(unsigned long long) * 2 * kMaxBatch, g.stream));
-    g.rsb[0].used = g.rsb[1].used = false;
-    for (int k = 0; k < 4; ++k) g.ahead[k].used = false;
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dRaysOwn), 64));
     HIPCHK(hipMemsetAsync(g.dRaysOwn, 0, 64, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
@@ -390,7 +386,7 @@ int tptInitialize(void)
 int tptShutdown(void)
 {
     if (!g.inited) return 0;
-    (void)discardLookahead();
+    (void)g.pending.discard();
     (void)tptCommDestroy();
     (void)hipStreamSynchronize(g.stream);
     (void)hipDeviceSynchronize();
@@ -424,10 +420,9 @@ int tptShutdown(void)
         if (g.evResolve[k]) (void)hipEventDestroy(g.evResolve[k]);
         (void)hipFree(g.dColour[k]);
         (void)hipFree(g.dStack[k]); g.dStack[k] = nullptr;
-        (void)hipFree(g.dPath[k]); g.dPath[k] = nullptr;
         g.evTrace[k] = nullptr; g.evResolve[k] = nullptr; g.dColour[k] = nullptr;
     }
-    g.stackCap = g.colourCap = g.pathCap = 0; g.slotsReserved = 0; g.slotReservations = 0;
+    g.stackCap = g.colourCap = 0; g.slotsReserved = 0; g.slotReservations = 0;
     (void)hipEventDestroy(g.ev0); (void)hipEventDestroy(g.ev1);
     if (g.evOrder) { (void)hipEventDestroy(g.evOrder); g.evOrder = nullptr; }
     (void)hipStreamDestroy(g.ownStream);
@@ -448,16 +443,12 @@ int tptShutdown(void)
     if (g.evBand) { (void)hipEventDestroy(g.evBand); g.evBand = nullptr; }
     if (g.evBandEnd) { (void)hipEventDestroy(g.evBandEnd); g.evBandEnd = nullptr; }
     g.tileSrc = nullptr; g.tileW = g.tileH = 0;
-    for (int k = 0; k < 4; ++k) g.ahead[k].used = false;
-    (void)hipFree(g.dRaysAhead); g.dRaysAhead = nullptr;
-    (void)hipFree(g.dRaysBatch); g.dRaysBatch = nullptr;
-    (void)hipFree(g.dRaysStream); g.dRaysStream = nullptr;
-    g.sbatch.used = false;
-    g.rsb[0].used = g.rsb[1].used = false;
-    g.orderDone = true; g.orderStream = nullptr; g.oldestPending = 0; g.frameSeq = 0;
+    g.pending.n = 0;
+    (void)hipFree(g.dRaysAhead); g.dRaysAhead = g.dRaysBatch = g.dRaysStream = nullptr;
+    g.orderStream = nullptr; g.oldestPending = 0; g.frameSeq = 0;
     g.streamDepth = 1; g.prevInFlight = -1;
     g.hostCaller = Context::HostCaller(); g.devCaller = Context::DeviceCaller(); // (a refusal or a streak remembered for a configuration
-    g.smallStreak = 0; g.framesSinceIdle = 0; g.configEpoch = 1;                 //  does not survive re-initialisation)
+    g.smallStreak = 0; g.configEpoch = 1;                                        //  does not survive re-initialisation)
     return 0;
 }
 
@@ -465,7 +456,7 @@ int tptSetStream(void* hipStream)
 {
     if (int rc_ = flushShardDeferred()) return rc_;
     if (requireInit()) return -1;
-    if (discardLookahead()) return -2;
+    if (g.pending.discard()) return -2;
     HIPCHK(hipStreamSynchronize(g.stream));
     g.stream = hipStream ? reinterpret_cast<hipStream_t>(hipStream) : g.ownStream;
     return 0;

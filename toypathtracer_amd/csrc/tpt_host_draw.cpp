@@ -1,4 +1,5 @@
-// tpt_host_draw.cpp -- DrawTest on the caller's HOST backbuffer (Test.cpp:344-367, synchronous): look-ahead, row-serial batches, banded copies; the display conversion
+// tpt_host_draw.cpp -- the launches traced ahead of their call (LaunchQueue); DrawTest on the caller's HOST backbuffer (Test.cpp:344-367,
+// synchronous): look-ahead, row-serial batches, banded copies; the display conversion
 // (one of the host runtime's translation units: tpt_context.h lists them)
 #include "tpt_context.h"
 
@@ -7,29 +8,40 @@ using namespace tpth;
 
 namespace tpth {
 
-// The frames traced ahead belong to a DrawTest sequence that did not continue as predicted (or the device path is about
-// to be used): let them finish and forget them.  Their colour buffers were never blended into anything.
-int discardLookahead()
+bool LaunchQueue::frontMatches(PendingLaunch::Kind kind, int frame, int w, int h, unsigned flags, unsigned long long key) const
 {
-    g.sbatch.used = false; // (an open stream batch needs no wait: its unserved planes are simply never blended)
-    bool any = g.rsb[0].used || g.rsb[1].used;
-    for (int k = 0; k < 4; ++k) any = any || g.ahead[k].used;
-    if (!any) return 0;
-    for (int k = 0; k < Context::kMaxOverlap; ++k) HIPCHK(hipStreamSynchronize(g.traceStream[k]));
-    for (int k = 0; k < 4; ++k) g.ahead[k].used = false;
-    g.rsb[0].used = g.rsb[1].used = false;
-    g.sbatch.used = false;
+    const PendingLaunch& F = e[0];
+    return holds(kind) && frame == F.firstFrame + F.next && F.w == w && F.h == h && F.flags == flags && F.key == key;
+}
+
+// The front launch's next frame becomes the caller's: its plane of the launch and its ray counter.  wasOpen: the launch was pending
+// when the call arrived (not pushed by it); its AHEAD and ROW_SERIAL frames then count as look-ahead hits.
+void LaunchQueue::serveFront(bool wasOpen, TraceTicket& T, const unsigned long long*& rays)
+{
+    PendingLaunch& F = e[0];
+    if (wasOpen && F.kind != PendingLaunch::STREAM) g.aheadHits++;
+    T = F.T.plane(F.next);
+    rays = F.rays + F.next;
+    if (++F.next < F.T.batch) return;
+    for (int k = 0; k + 1 < n; ++k) e[k] = e[k + 1]; // used up: the launch after it moves to the front
+    --n;
+}
+
+int LaunchQueue::push(const PendingLaunch& L)
+{
+    if (n == kCap || (n > 0 && !holds(L.kind))) return fail("internal: launch queue full or of another kind");
+    e[n++] = L;
     return 0;
 }
 
-// The frame at the head of the look-ahead queue becomes the caller's frame.
-int takeAhead(TraceTicket& T, int& raySlot)
+// The launches traced ahead belong to a sequence that did not continue as predicted (or another path is about to be used): let
+// them finish and forget them.  Their colour planes were never blended into anything.  (An open STREAM batch needs no wait: its
+// unserved planes are simply never blended.)
+int LaunchQueue::discard()
 {
-    g.aheadHits++;
-    T = g.aheadTicket[0];
-    raySlot = g.ahead[0].raySlot;
-    for (int k = 0; k + 1 < 4; ++k) { g.ahead[k] = g.ahead[k + 1]; g.aheadTicket[k] = g.aheadTicket[k + 1]; }
-    g.ahead[3].used = false;
+    if (n > 0 && !holds(PendingLaunch::STREAM))
+        for (int k = 0; k < Context::kMaxOverlap; ++k) HIPCHK(hipStreamSynchronize(g.traceStream[k]));
+    n = 0;
     return 0;
 }
 
@@ -38,27 +50,23 @@ int takeAhead(TraceTicket& T, int& raySlot)
 // frame alone on the GPU is bound by its longest paths (one frame in flight: 1.0 ms, three: 0.55 ms per frame).
 int traceAhead(int frameCount, int w, int h, unsigned testFlags, unsigned long long key, int want)
 {
-    int have = 0;
-    while (have < 4 && g.ahead[have].used) ++have;
-    int nextFrame = have ? g.ahead[have - 1].frameCount + 1 : frameCount + 1;
+    LaunchQueue& Q = g.pending;
+    int nextFrame = Q.n ? Q.e[Q.n - 1].firstFrame + 1 : frameCount + 1;
     // every frame traced but not yet blended holds a slot (its colour buffer): this one plus the ones ahead must leave one
     // slot spare, whatever the hardware-queue probe clamped the pipeline to
     const int nSlots = effectiveOverlap();
     const int maxAhead = want < nSlots - 2 ? want : nSlots - 2;
-    while (have < maxAhead) {
-        Context::Ahead& A = g.ahead[have];
-        A.frameCount = nextFrame; A.w = w; A.h = h; A.flags = testFlags; A.configKey = key;
-        A.raySlot = (int)(g.frameSeq % (unsigned long long)Context::kMaxSlots);
-        int rc = enqueueTrace(nextFrame, w, h, testFlags, g.dRaysAhead + A.raySlot, g.aheadTicket[have]);
+    while (Q.n < maxAhead) {
+        PendingLaunch A; // (an AHEAD launch: the default kind)
+        A.firstFrame = nextFrame++; A.w = w; A.h = h; A.flags = testFlags; A.key = key;
+        A.rays = g.dRaysAhead + g.frameSeq % (unsigned long long)Context::kMaxSlots;
+        int rc = enqueueTrace(A.firstFrame, w, h, testFlags, A.rays, A.T);
         if (rc) return rc;
-        A.used = g.aheadTicket[have].valid;
-        if (!A.used) break;
-        ++have;
-        ++nextFrame;
+        if (!A.T.valid) break;
+        if ((rc = Q.push(A))) return rc;
     }
     return 0;
 }
-
 
 } // namespace tpth
 
@@ -74,7 +82,7 @@ int tptSetHostBufferMode(int hostBufferOnlyWrittenByDrawTest)
 int tptSetStreamBatching(int enable)
 {
     if (requireInit()) return -1;
-    int rc = discardLookahead();
+    int rc = g.pending.discard();
     if (rc) return rc;
     g.streamBatch = enable ? 1 : 0;
     return 0;
@@ -84,7 +92,7 @@ int tptSetHostLookahead(int frames)
 {
     if (frames < 0 || frames > 3) return fail("tptSetHostLookahead: 0..3");
     if (g.inited) {
-        int rc = discardLookahead();
+        int rc = g.pending.discard();
         if (rc) return rc;
     }
     g.lookahead = frames;
@@ -102,7 +110,7 @@ int tptDraw(float time, int frameCount, int w, int h, float* backbuffer, int* ou
     const size_t rowBytes = (size_t)w * 4 * sizeof(float);
     const size_t need = rowBytes * (size_t)(rows > 0 ? rows : 1);
     if (need > g.frameCap) {
-        int rc = discardLookahead();
+        int rc = g.pending.discard();
         if (rc) return rc;
         HIPCHK(hipStreamSynchronize(g.stream));
         if (g.dFrame) HIPCHK(hipFree(g.dFrame));
@@ -120,17 +128,13 @@ int tptDraw(float time, int frameCount, int w, int h, float* backbuffer, int* ou
     const bool stable = !g.sceneDirty && g.pendingSet < 0 && !(testFlags & TPT_FLAG_ANIMATE);
 
     // ---- 1. this frame's trace: traced ahead by an earlier call, or now
-    struct DepthScope { // launches made from here share the machine with the frames traced ahead, not with a deep device-path pipeline
-        explicit DepthScope(int d) { g.depthOverride = d; }
-        ~DepthScope() { g.depthOverride = 0; }
-    } depthScope(pipelined && stable ? 1 + (g.lookahead < 3 ? g.lookahead : 3) : 1);
+    DepthScope depthScope(pipelined && stable ? 1 + (g.lookahead < 3 ? g.lookahead : 3) : 1);
+    LaunchQueue& Q = g.pending;
     TraceTicket T;
-    int raySlot = -1;
     const unsigned long long* rayPtr = nullptr;
     bool servedFromBatch = false;
     Context::HostCaller& HC = g.hostCaller;
-    HC.streak = (frameCount == HC.frame + 1 && w == HC.w && h == HC.h && testFlags == HC.flags && key == HC.key) ? HC.streak + 1 : 0;
-    HC.frame = frameCount; HC.w = w; HC.h = h; HC.flags = testFlags; HC.key = key;
+    const int streak = HC.seq.next(frameCount, w, h, testFlags, key);
     const bool batchRefused = HC.refusedKey == key && HC.refusedW == w && HC.refusedH == h;
     if (g.seedMode == SEED_ROW_SERIAL && stable && pipelined && !sharded && g.lookahead > 0 && rows > 0 && !g.mirror && !batchRefused) {
         // ---- 1r. the reference's own seed mode: a frame alone is `rows` lanes of work, so the frames AHEAD are traced as one
@@ -139,78 +143,51 @@ int tptDraw(float time, int frameCount, int w, int h, float* backbuffer, int* ou
         //          configuration (a one-shot DrawTest, or a host that jumps about, takes the plain path below).  A batch the pipeline
         //          refuses (frame wider than 8192, over 4 GiB of colour planes, not enough device memory) is retried at half the size, down to 2 frames; if nothing fits
         //          the configuration is served frame by frame: DrawTest never fails because of the look-ahead.
-        auto matches = [&](const Context::RowSerialBatch& B) {
-            return B.used && B.w == w && B.h == h && B.flags == testFlags && B.key == key && frameCount == B.firstFrame + B.next;
-        };
-        auto launch = [&](int which, int firstFrame) -> int {
-            Context::RowSerialBatch& B = g.rsb[which];
-            B.used = false;
-            // (two banks of per-frame counters; the batch being served keeps its bank when it moves from [1] to [0])
-            const int bank = (which == 1 && g.rsb[0].used && g.rsb[0].counterBase == 0) ? kMaxBatch : 0;
+        auto launch = [&](int firstFrame) -> int { // the first batch (empty queue) or the one behind the batch being served
+            const PendingLaunch* F = Q.empty() ? nullptr : &Q.e[0];
+            PendingLaunch B;
+            B.kind = PendingLaunch::ROW_SERIAL;
+            B.firstFrame = firstFrame; B.w = w; B.h = h; B.flags = testFlags; B.key = key;
+            B.rays = g.dRaysBatch + (F && F->rays == g.dRaysBatch ? kMaxBatch : 0); // (two banks of counters: the other one than F's)
             // the batch behind one that is being served starts at THAT batch's size: a larger one would have to grow the colour
             // slots the first still reads (refused now) after draining the pipeline to find that out
-            const int nMax = (which == 1 && g.rsb[0].used) ? g.rsb[0].n : kMaxBatch;
-            for (int n = nMax; n >= 2; n /= 2) {
+            for (int n = F ? F->T.batch : kMaxBatch; n >= 2; n /= 2) {
                 if (w > 8192 || h > 8192 || (long long)rows * w * n > (1ll << 30) || (unsigned long long)rows * w * 16ull * n > (4ull << 30)) continue;
-                B.firstFrame = firstFrame; B.n = n; B.next = 0; B.w = w; B.h = h; B.flags = testFlags; B.key = key;
-                B.counterBase = bank;
-                const int rc = enqueueTrace(firstFrame, w, h, testFlags, g.dRaysBatch + B.counterBase, B.T, B.n, 1);
-                if (rc == 0) {
-                    B.used = B.T.valid;
-                    return 0;
-                }
+                const int rc = enqueueTrace(firstFrame, w, h, testFlags, B.rays, B.T, n, 1);
+                if (rc == 0) return B.T.valid ? Q.push(B) : 0;
                 if (rc != kRefused) return rc; // a real failure (HIP error, no scene): not something a smaller batch cures
             }
-            if (which == 0) { HC.refusedKey = key; HC.refusedW = w; HC.refusedH = h; } // nothing fits: frame by frame from here on
+            if (!F) { HC.refusedKey = key; HC.refusedW = w; HC.refusedH = h; } // nothing fits: frame by frame from here on
             return 0;
         };
-        if (matches(g.rsb[0])) {
-            g.aheadHits++;
-        } else {
-            if (g.rsb[0].used || g.rsb[1].used) {
-                int rc = discardLookahead();
-                if (rc) return rc;
-            }
-            if (HC.streak >= 2) {
-                int rc = discardLookahead();
-                if (rc) return rc;
-                if ((rc = launch(0, frameCount))) return rc;
-            }
+        const bool open = Q.frontMatches(PendingLaunch::ROW_SERIAL, frameCount, w, h, testFlags, key);
+        if (!open && (streak >= 2 || Q.holds(PendingLaunch::ROW_SERIAL))) {
+            int rc = Q.discard();
+            if (rc) return rc;
+            if (streak >= 2 && (rc = launch(frameCount))) return rc;
         }
-        Context::RowSerialBatch& B = g.rsb[0];
-        if (B.used) {
+        if (Q.holds(PendingLaunch::ROW_SERIAL)) { // (matched, or launched just now)
             // (the batch after this one is launched at once: holding it back until the first hit -- the batch above only completes
             //  when its slowest row has, 60-90 ms -- serialises the batches and costs the sequential caller 2.7x: 1.6 instead of
             //  4.3 Gray/s, profiles/r04/r04_evidence.log; the caller has shown three consecutive frames by now)
-            if (!g.rsb[1].used && !(HC.refusedKey == key && HC.refusedW == w && HC.refusedH == h)) {
-                int rc = launch(1, B.firstFrame + B.n);
+            if (Q.n == 1) {
+                int rc = launch(Q.e[0].firstFrame + Q.e[0].T.batch);
                 if (rc) return rc;
             }
-            const int j = B.next;
-            T = B.T;
-            T.colour = B.T.colour + (size_t)j * (size_t)B.T.nPixels;
-            T.lerpFac = B.T.lerp.v[j];
-            T.batch = 1;
-            rayPtr = g.dRaysBatch + B.counterBase + j;
+            Q.serveFront(open, T, rayPtr);
             servedFromBatch = true;
-            if (++B.next == B.n) { // the batch is used up with this frame: the one after it becomes current
-                g.rsb[0] = g.rsb[1];
-                g.rsb[0].counterBase = g.rsb[1].counterBase;
-                g.rsb[1].used = false;
-            }
         }
     }
-    Context::Ahead& front = g.ahead[0];
     if (servedFromBatch) {
         // (nothing more to trace)
-    } else if (front.used && front.frameCount == frameCount && front.w == w && front.h == h && front.flags == testFlags && front.configKey == key && stable) {
-        int rc = takeAhead(T, raySlot);
-        if (rc) return rc;
+    } else if (stable && Q.frontMatches(PendingLaunch::AHEAD, frameCount, w, h, testFlags, key)) {
+        Q.serveFront(true, T, rayPtr);
     } else {
-        int rc = discardLookahead();
+        int rc = Q.discard();
         if (rc) return rc;
-        raySlot = (int)(g.frameSeq % (unsigned long long)Context::kMaxSlots);
-        if ((rc = enqueueTrace(frameCount, w, h, testFlags, g.dRaysAhead + raySlot, T))) return rc;
+        unsigned long long* rays = g.dRaysAhead + g.frameSeq % (unsigned long long)Context::kMaxSlots;
+        if ((rc = enqueueTrace(frameCount, w, h, testFlags, rays, T))) return rc;
+        rayPtr = T.valid ? rays : nullptr;
     }
     // ---- 2. trace the next frames ahead (a wrong guess costs GPU time only)
     // (in the reference's own seed mode the batches above ARE the look-ahead: single frames traced ahead would be 60-90 ms of
@@ -220,7 +197,6 @@ int tptDraw(float time, int frameCount, int w, int h, float* backbuffer, int* ou
         int rc = traceAhead(frameCount, w, h, testFlags, key, g.lookahead);
         if (rc) return rc;
     }
-    if (!servedFromBatch) rayPtr = T.valid ? g.dRaysAhead + raySlot : nullptr;
     // ---- 3. the previous image: the host buffer is the source of truth (previous frame's RGB, caller-owned alpha) unless
     //         the caller has promised that only DrawTest writes it (tptSetHostBufferMode): then the device tile is, and the
     //         upload happens once per buffer.  Then blend and download.

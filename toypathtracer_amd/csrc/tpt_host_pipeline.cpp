@@ -14,35 +14,33 @@ struct FramePlan {
     size_t lds = 0;
     int occ = 0, threadsPerBlock = 0, blocks = 0;
     int nOverlap = 1;           // launches that may run side by side (trace streams in use)
-    int nSlots = 1, slot = 0;   // frames that may be enqueued ahead / this frame's slot (colour, stack, path buffers, events)
+    int nSlots = 1, slot = 0;   // frames that may be enqueued ahead / this frame's slot (colour, stack buffers, events)
     int batch = 1;              // frames traced by this launch (tptDrawDeviceBatch)
 };
 
-// Per-slot device buffers (frame colour, bounce stacks, path colour sums) are allocated for ALL slots of the pipeline at
+// Per-slot device buffers (frame colour, bounce stacks) are allocated for ALL slots of the pipeline at
 // once, sized for the largest grid this kernel can ever be launched with at this frame shape -- never on the per-frame
 // path: a lazily grown slot drained the whole pipeline (two stream syncs + hipFree/hipMalloc) on every first use, and with
 // fewer warm-up frames than slots those drains landed inside the caller's timed region (round-1 driver bench: 17 instead
 // of 35 Gray/s).  A re-allocation happens only when the frame shape / kernel variant / overlap asks for MORE than any
 // earlier frame did; it synchronises everything once.
 int syncAllStreams();
-int reserveSlotBuffers(int nSlots, size_t colourBytes, size_t stackBytes, size_t pathBytes)
-{ // (stack / path buffers are used while the kernel runs only: indexed by stream, allocated for the first kMaxOverlap slots)
+int reserveSlotBuffers(int nSlots, size_t colourBytes, size_t stackBytes)
+{ // (stack buffers are used while the kernel runs only: indexed by stream, allocated for the first kMaxOverlap slots)
     // Memory that a large batched frame pinned is given back when the caller returns to frames a quarter of that size and more
     // than 1 GiB of colour slots is held (one drain, like a growth); anything smaller stays (no churn between similar shapes).
     // ... and only after 8 launches in a row were that small: a caller that alternates large batches with a small tail chunk
     // (33..40 frames through tptDrawDeviceBatch: 32 + 1..8) must not free and re-allocate gigabytes on every call.
     const bool small = colourBytes * 4 <= g.colourCap && g.colourCap * (size_t)g.slotsReserved > (1ull << 30);
     g.smallStreak = small ? g.smallStreak + 1 : 0;
-    // ... and never while a frame that was traced ahead (look-ahead, a row-serial or stream batch being served) still waits
-    // for its blend: its ticket points into the very buffers a shrink frees.
-    bool ticketsOut = g.rsb[0].used || g.rsb[1].used || g.sbatch.used;
-    for (int k = 0; k < 4; ++k) ticketsOut = ticketsOut || g.ahead[k].used;
-    const bool shrink = small && g.smallStreak >= 8 && !ticketsOut;
+    // ... and never while a launch traced ahead of its call (g.pending) still waits for its blends: its ticket points into the very
+    // buffers a shrink frees.
+    const bool shrink = small && g.smallStreak >= 8 && g.pending.empty();
     if (shrink) g.smallStreak = 0;
-    if (!shrink && nSlots <= g.slotsReserved && colourBytes <= g.colourCap && stackBytes <= g.stackCap && pathBytes <= g.pathCap) return 0;
+    if (!shrink && nSlots <= g.slotsReserved && colourBytes <= g.colourCap && stackBytes <= g.stackCap) return 0;
     // ... nor may the slots GROW under such a frame: growth frees and re-allocates every colour slot (found by the round-4 advisor:
     // the second row-serial batch asking for more than the first had got).  The caller retries with less or drops its look-ahead.
-    if (ticketsOut && colourBytes > g.colourCap)
+    if (!g.pending.empty() && colourBytes > g.colourCap)
         return refuse("frame buffers: the colour slots are held by frames traced ahead of their call; a larger launch has to wait for them");
     int rc = syncAllStreams();
     if (rc) return rc;
@@ -53,8 +51,7 @@ int reserveSlotBuffers(int nSlots, size_t colourBytes, size_t stackBytes, size_t
         }
         g.colourCap = 0;
     }
-    const size_t cb = colourBytes > g.colourCap ? colourBytes : g.colourCap, sb = stackBytes > g.stackCap ? stackBytes : g.stackCap,
-                 pb = pathBytes > g.pathCap ? pathBytes : g.pathCap;
+    const size_t cb = colourBytes > g.colourCap ? colourBytes : g.colourCap, sb = stackBytes > g.stackCap ? stackBytes : g.stackCap;
     const int n = nSlots > g.slotsReserved ? nSlots : g.slotsReserved;
     {
         // refuse BEFORE anything is freed when the device cannot hold the request (a failed hipMalloc half-way would leave the
@@ -97,16 +94,14 @@ int reserveSlotBuffers(int nSlots, size_t colourBytes, size_t stackBytes, size_t
             (void)hipFree(g.dStack[k]); g.dStack[k] = nullptr;
         }
         (void)hipGetLastError();
-        g.colourCap = g.stackCap = g.pathCap = 0; g.slotsReserved = 0;
-        // ... and no ticket may keep pointing into a buffer that is gone (frames traced ahead, an open stream batch, the row-serial
-        // batches): drop them all -- a later takeAhead / batch serve would blend from freed memory, and every later enqueueTrace
-        // would be refused with "colour slots are held by frames traced ahead".  (Everything was drained before the buffers grew.)
-        g.rsb[0].used = g.rsb[1].used = false;
-        for (int k = 0; k < 4; ++k) g.ahead[k].used = false;
-        g.sbatch.used = false;
+        g.colourCap = g.stackCap = 0; g.slotsReserved = 0;
+        // ... and no pending launch may keep pointing into a buffer that is gone: a later serve would blend from freed memory, and
+        // every later enqueueTrace would be refused with "colour slots are held by frames traced ahead".  (Everything was drained
+        // before the buffers grew: nothing to wait for.)
+        g.pending.n = 0;
         return rc;
     }
-    g.colourCap = cb; g.stackCap = sb; g.pathCap = pb; g.slotsReserved = n;
+    g.colourCap = cb; g.stackCap = sb; g.slotsReserved = n;
     g.slotReservations++;
     return 0;
 }
@@ -216,7 +211,6 @@ void sizeGrid(FramePlan& P)
         // when two consecutive frames find the pipeline empty: that is a caller who synchronises every frame
         // (the reference's DrawTest contract) and gets the whole machine.
         const int inFlight = framesInFlight(P.nSlots);
-        g.framesSinceIdle = inFlight == 0 ? 0 : g.framesSinceIdle + 1;
         if (inFlight == 0 && g.prevInFlight == 0) g.streamDepth = 1;
         if (inFlight + 1 > g.streamDepth) g.streamDepth = inFlight + 1;
         g.prevInFlight = inFlight;
@@ -248,7 +242,7 @@ int maxGridBlocks(const FramePlan& P)
     return m < 1 ? 1 : m;
 }
 
-// Per-slot buffers of this frame: colour, bounce-stack spill / per-path stacks, path colour sums.
+// Per-slot buffers of this frame: colour, bounce-stack spill / per-path stacks.
 int ensureFrameBuffers(FramePlan& P, int w)
 {
     KernelArgs& a = P.a;
@@ -257,8 +251,7 @@ int ensureFrameBuffers(FramePlan& P, int w)
     const bool needStack = g.foldMode == FOLD_RECURSIVE && a.ldsStackLevels < TPT_MAX_DEPTH;
     const size_t maxColumns = (size_t)maxBlocks * (size_t)(P.queued ? tptQueuePathsPerBlock() : P.threadsPerBlock);
     const size_t stackBytes = needStack ? maxColumns * (size_t)(TPT_MAX_DEPTH - a.ldsStackLevels) * sizeof(f4) : 0;
-    const size_t pathBytes = 0; // (the path-queue kernel's per-path colour sums moved into LDS)
-    int rc = reserveSlotBuffers(P.nSlots, (size_t)a.nLocalRows * w * sizeof(f4) * (size_t)P.batch, stackBytes, pathBytes);
+    int rc = reserveSlotBuffers(P.nSlots, (size_t)a.nLocalRows * w * sizeof(f4) * (size_t)P.batch, stackBytes);
     if (rc) return rc;
     a.frameColour = g.dColour[slot];
     a.work = g.dWork + 16 * slot;
@@ -372,7 +365,6 @@ int prepareChunkOrder(FramePlan& P)
         HIPCHK(hipStreamSynchronize(g.stream));
         g.chunkCount = a.numChunks;
         g.orderSeq = 0;
-        g.orderDone = true;
     }
     a.chunkCost = g.dChunkCost;
     return 0;
@@ -391,7 +383,6 @@ int enqueueChunkOrder(FramePlan& P, hipStream_t ts)
             HIPCHK(tptLaunchChunkOrder(g.dChunkCost, g.dChunkSnap[P.slot % P.nOverlap], g.dChunkOrder[fresh], P.a.numChunks, ts));
             HIPCHK(hipEventRecord(g.evOrder, ts));
             g.orderStream = ts;
-            g.orderDone = false;
             g.lastOrderTable = fresh;
         } else if (g.orderStream && g.orderStream != ts) {
             // the most recent table may still be being written by another stream's sort kernel
@@ -634,74 +625,66 @@ int tptDrawDevice(float time, int frameCount, int w, int h, float* deviceTile, u
         (void)hipGetLastError();
     }
     D.syncStreak = prevDone ? D.syncStreak + 1 : 0;
-    D.seqStreak = (frameCount == D.frame + 1 && w == D.w && h == D.h && testFlags == D.flags && key == D.key) ? D.seqStreak + 1 : 0;
-    D.frame = frameCount; D.w = w; D.h = h; D.flags = testFlags; D.key = key;
-    const bool lookAhead = pipelined && stable && !g.mirror && g.lookahead > 0 && D.syncStreak >= 2 && D.seqStreak >= 2;
+    const int seqStreak = D.seq.next(frameCount, w, h, testFlags, key);
+    const bool lookAhead = pipelined && stable && !g.mirror && g.lookahead > 0 && D.syncStreak >= 2 && seqStreak >= 2;
 
+    LaunchQueue& Q = g.pending;
     TraceTicket T;
+    const unsigned long long* rays = nullptr;
     int rc;
-    const Context::Ahead& front = g.ahead[0];
-    const bool hit = front.used && front.frameCount == frameCount && front.w == w && front.h == h && front.flags == testFlags &&
-                     front.configKey == key && stable && !g.mirror;
+    const bool hit = stable && !g.mirror && Q.frontMatches(PendingLaunch::AHEAD, frameCount, w, h, testFlags, key);
     if (!hit && !lookAhead) {
-        // ---- a streaming caller with small frames: served from / starting a stream batch (see Context::StreamBatch)
-        Context::StreamBatch& SB = g.sbatch;
-        if (SB.used && SB.w == w && SB.h == h && SB.flags == testFlags && SB.key == key && stable && frameCount == SB.firstFrame + SB.next) {
-            const int j = SB.next++;
-            T = SB.T;
-            T.colour = SB.T.colour + (size_t)j * (size_t)SB.T.nPixels;
-            T.lerpFac = SB.T.lerp.v[j];
-            T.batch = 1;
-            if (SB.next == SB.n) SB.used = false;
-            rc = enqueueResolve(T, deviceTile, g.dRaysStream + SB.counterBase + j);
-            D.lastSlot = T.slot;
-            return rc;
+        // ---- a streaming caller.  With SMALL frames (tiles of a sharded frame, 640x360) a launch cannot be shorter than its longest
+        //      pixel's sequential samples, so frame by frame such a caller is bound by launch latency, not by arithmetic.  When the
+        //      calls are consecutive frames of one static configuration, the next calls' frames are traced in the SAME launch (a
+        //      STREAM batch of 2-8 frames, tptDrawDeviceBatch's kernel path, a ray counter per frame) and each later call only blends
+        //      its own plane -- every frame is still delivered, in order, with its own ray count.  A wrong guess costs GPU time only.
+        //      (No !g.mirror here: the sharded path mirrors its tile.)
+        if (stable && Q.frontMatches(PendingLaunch::STREAM, frameCount, w, h, testFlags, key)) {
+            Q.serveFront(true, T, rays);
+        } else {
+            if ((rc = Q.discard())) return rc; // (also closes a stream batch that did not continue as guessed)
+            int nBatch = 1;
+            if (g.streamBatch && pipelined && stable && seqStreak >= 2 && g.persist == 3 && g.seedMode == SEED_PER_PIXEL && g.foldMode == FOLD_RECURSIVE &&
+                g.hs == HS_TWO_PHASE && w <= 8192 && h <= 8192 && g.spp <= 2047) {
+                // how many frames make a launch long enough to amortise its fixed cost: 1 at 1280x720x4 (3.7 M samples), 2 / 4 / 8 for
+                // halves / quarters / eighths of that (profiles/r03/r03_run19.log: where several frames per launch pay)
+                const long long samples = (long long)localRows(h) * w * g.spp;
+                nBatch = samples >= 2400000 ? 1 : samples >= 1200000 ? 2 : samples >= 600000 ? 4 : Context::kStreamBatchMax;
+                if (samples <= 0) nBatch = 1;
+            }
+            if (nBatch > 1) {
+                PendingLaunch S;
+                S.kind = PendingLaunch::STREAM;
+                S.firstFrame = frameCount; S.w = w; S.h = h; S.flags = testFlags; S.key = key;
+                S.rays = g.dRaysStream + (g.streamBatches++ % (unsigned long long)Context::kStreamRing) * Context::kStreamBatchMax;
+                if ((rc = enqueueTrace(frameCount, w, h, testFlags, S.rays, S.T, nBatch, 1))) return rc;
+                if (S.T.valid) {
+                    if ((rc = Q.push(S))) return rc;
+                    Q.serveFront(false, T, rays);
+                }
+            } else if ((rc = enqueueTrace(frameCount, w, h, testFlags, nullptr, T))) {
+                return rc; // (the plain path: the kernel adds its rays to the running total itself)
+            }
         }
-        if ((rc = discardLookahead())) return rc; // (also closes a stream batch that did not continue as guessed)
-        int nBatch = 1;
-        if (g.streamBatch && pipelined && stable && D.seqStreak >= 2 && g.persist == 3 && g.seedMode == SEED_PER_PIXEL && g.foldMode == FOLD_RECURSIVE &&
-            g.hs == HS_TWO_PHASE && w <= 8192 && h <= 8192 && g.spp <= 2047) {
-            // how many frames make a launch long enough to amortise its fixed cost: 1 at 1280x720x4 (3.7 M samples), 2 / 4 / 8 for
-            // halves / quarters / eighths of that (profiles/r03/r03_run19.log: where several frames per launch pay)
-            const long long samples = (long long)localRows(h) * w * g.spp;
-            nBatch = samples >= 2400000 ? 1 : samples >= 1200000 ? 2 : samples >= 600000 ? 4 : Context::kStreamBatchMax;
-            if (samples <= 0) nBatch = 1;
-        }
-        if (nBatch > 1) {
-            SB.firstFrame = frameCount; SB.n = nBatch; SB.next = 1; SB.w = w; SB.h = h; SB.flags = testFlags; SB.key = key;
-            SB.counterBase = (int)(g.streamBatches++ % (unsigned long long)Context::kStreamRing) * Context::kStreamBatchMax;
-            if ((rc = enqueueTrace(frameCount, w, h, testFlags, g.dRaysStream + SB.counterBase, SB.T, nBatch, 1))) return rc;
-            SB.used = SB.T.valid;
-            T = SB.T;
-            T.lerpFac = SB.T.lerp.v[0];
-            T.batch = 1;
-            rc = enqueueResolve(T, deviceTile, T.valid ? g.dRaysStream + SB.counterBase : nullptr);
-            if (T.valid) D.lastSlot = T.slot;
-            return rc;
-        }
-        // the plain path: trace + blend, the kernel adds its rays to the running total itself
-        if ((rc = enqueueTrace(frameCount, w, h, testFlags, nullptr, T))) return rc;
-        rc = enqueueResolve(T, deviceTile, nullptr);
+        rc = enqueueResolve(T, deviceTile, rays);
         if (T.valid) D.lastSlot = T.slot;
         return rc;
     }
     // one frame more than the host-pointer path looks ahead: there the PCIe copies fill the caller's time (2 ahead: 0.88 ms
     // per frame, 3: 0.92), here nothing does (2: 0.598 ms, 3: 0.561; profiles/r02/r02_run50.log)
     const int devAhead = g.lookahead + 1 < 3 ? g.lookahead + 1 : 3;
-    struct DepthScope { // launches made from here share the machine with the frames traced ahead, not with a deep pipeline
-        explicit DepthScope(int d) { g.depthOverride = d; }
-        ~DepthScope() { g.depthOverride = 0; }
-    } depthScope(1 + devAhead);
-    int raySlot = -1;
+    DepthScope depthScope(1 + devAhead);
     if (hit) {
-        if ((rc = takeAhead(T, raySlot))) return rc;
+        Q.serveFront(true, T, rays);
     } else {
-        if ((rc = discardLookahead())) return rc;
-        raySlot = (int)(g.frameSeq % (unsigned long long)Context::kMaxSlots);
-        if ((rc = enqueueTrace(frameCount, w, h, testFlags, g.dRaysAhead + raySlot, T))) return rc;
+        if ((rc = Q.discard())) return rc;
+        unsigned long long* own = g.dRaysAhead + g.frameSeq % (unsigned long long)Context::kMaxSlots;
+        if ((rc = enqueueTrace(frameCount, w, h, testFlags, own, T))) return rc;
+        rays = T.valid ? own : nullptr;
     }
     if (lookAhead && T.valid && (rc = traceAhead(frameCount, w, h, testFlags, key, devAhead))) return rc;
-    rc = enqueueResolve(T, deviceTile, T.valid ? g.dRaysAhead + raySlot : nullptr);
+    rc = enqueueResolve(T, deviceTile, rays);
     if (T.valid) D.lastSlot = T.slot;
     return rc;
 }
@@ -717,7 +700,7 @@ int tptDrawDeviceBatch(float time, int firstFrame, int nFrames, int w, int h, fl
     if (!deviceTile || w <= 0 || h <= 0 || nFrames < 1) return fail("tptDrawDeviceBatch: bad arguments");
     if (nFrames > 1 && (testFlags & TPT_FLAG_ANIMATE))
         return fail("tptDrawDeviceBatch: an animated scene changes every frame (Test.cpp:304-308): one tptUpdate + tptDrawDevice per frame");
-    int rc = discardLookahead();
+    int rc = g.pending.discard();
     if (rc) return rc;
     for (int f = 0; f < nFrames; f += kMaxBatch) {
         const int n = nFrames - f < kMaxBatch ? nFrames - f : kMaxBatch;
@@ -763,7 +746,7 @@ int tptDrawDeviceViews(float time, int frameCount, int w, int h, int nViews, con
         cs.focusDist = p[8];
         cams[v] = makeCamera(cs, float(w) / float(h));
     }
-    int rc = discardLookahead();
+    int rc = g.pending.discard();
     if (rc) return rc;
     // one launch: the views are the frames of a batch (colour planes nPixels apart in the slot's buffer, a ray counter each)
     TraceTicket T;
@@ -807,7 +790,7 @@ int tptSetRayCounter(void* deviceU64)
 {
     if (int rc_ = flushShardDeferred()) return rc_;
     if (requireInit()) return -1;
-    if (discardLookahead()) return -2;
+    if (g.pending.discard()) return -2;
     HIPCHK(hipStreamSynchronize(g.stream));
     g.dRays = deviceU64 ? static_cast<unsigned long long*>(deviceU64) : g.dRaysOwn;
     int64_t total = 0;

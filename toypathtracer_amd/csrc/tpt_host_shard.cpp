@@ -165,7 +165,7 @@ int tptCommDestroy(void)
     Context::Shard& S = g.shard;
     if (!S.active) return 0;
     S.pendCount = 0; // (frames accepted but never waited for are dropped with the communicator: the collective needs every rank)
-    (void)discardLookahead();
+    (void)g.pending.discard();
     if (g.stream) (void)hipStreamSynchronize(g.stream);
     (void)releaseShardBuffers();
     (void)tptSetTileMirror(nullptr, nullptr);
