@@ -168,7 +168,11 @@ TPT_API int tptSetFrameOverlap(int frames);
  * the frames of the next 1-7 calls in the SAME launch (2 / 4 / 8 frames per launch for halves / quarters / eighths of 1280x720x4)
  * and every later call only blends its own colour plane: each frame is still delivered, in order, with its own ray count (the
  * counter and the mirrored snapshot are exact per frame), bit-identical to one launch per frame.  A call that does not continue
- * the sequence (other frame number, size, flags, scene, ...) drops the unserved planes: GPU time only. */
+ * the sequence (other frame number, size, flags, scene, ...) drops the unserved planes: GPU time only.
+ * Larger frames are batched too when the pipeline is shallow (few hardware queues: two launches in flight at 4 queues): enough frames
+ * per launch that the launches in flight carry what 16 did, 2 then 4 then 8 at 1280x720x4 as the stream goes on; with the full
+ * 16-deep pipeline they keep one frame per launch.  tptSynchronize and tptRayCounterRead drop an open batch's unserved planes, so a
+ * frame traced before the caller waited is never served after it; the next call starts a stream afresh. */
 TPT_API int tptSetStreamBatching(int enable);
 /* Display conversion of a device-resident FULL image (w*h float4, row 0 = bottom) into w*h RGBA8 in device memory,
  * top row first: the reference's own conversion for its C++ path, Cpp/Emscripten/main.cpp:63-79

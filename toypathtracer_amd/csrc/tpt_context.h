@@ -16,6 +16,7 @@
 #include "tpt_device.h"
 #include "tpt_scene.h"
 #include "tpt_shard.h"
+#include "tpt_stream_batch.h"
 #include <hip/hip_runtime.h>
 #include <thread>
 #include <rccl/rccl.h> // types and prototypes only: the library is dlopen()ed when tptCommInit is called
@@ -65,7 +66,8 @@ struct Streak {
 // A launch traced ahead of the calls that will blend its frames, one frame per call, in frame order.  Its kind says who serves it:
 //   AHEAD       a single frame traced ahead (tptSetHostLookahead): tptDraw and tptDrawDevice;
 //   ROW_SERIAL  a batch in the reference's own seed mode (one launch of rows x frames lanes): tptDraw only;
-//   STREAM      a batch of small frames for a streaming caller (tptSetStreamBatching): tptDrawDevice only (and tptDrawSharded through it).
+//   STREAM      a batch of frames for a streaming caller (tptSetStreamBatching, tpt_stream_batch.h): tptDrawDevice only (and tptDrawSharded
+//               through it); dropped when the caller waits (closeStream).
 struct PendingLaunch {
     enum Kind { AHEAD, ROW_SERIAL, STREAM } kind = AHEAD;
     TraceTicket T;                      // T.batch frames: firstFrame, firstFrame + 1, ...
@@ -88,6 +90,7 @@ struct LaunchQueue {
     void serveFront(bool wasOpen, TraceTicket& T, const unsigned long long*& rays);
     int push(const PendingLaunch& L);
     int discard();
+    void closeStream();
 };
 
 struct Context {
@@ -198,6 +201,7 @@ struct Context {
     } hostCaller;
     static const int kStreamBatchMax = 8, kStreamRing = 64;
     unsigned long long streamBatches = 0;       // stream batches launched (index into their ring of ray counters)
+    int streamRun = 0, streamNext = -1;         // stream batches launched back to back before the newest / the frame that continues it (-1: none)
     int streamBatch = 1;                        // on by default since round 4; tptSetStreamBatching(0) / env TPT_STREAM_BATCH=0 turn it off
     // tptDrawDevice: is the caller synchronous (the previous frame's blend has completed by the time the next call arrives)
     // and are its calls consecutive frames of one configuration?  Then the next frames are traced ahead for it too.

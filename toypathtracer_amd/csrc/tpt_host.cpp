@@ -229,9 +229,7 @@ int requireInit()
 int probeHardwareQueues()
 {
     auto clampCap = [] {
-        // the ordered resolve chain, the scene uploads and the caller's own streams need queues too: with fewer than
-        // ~3 queues per 2 trace streams to spare, two frames in flight is the best there is
-        g.overlapCap = g.hwQueues >= Context::kMaxOverlap ? Context::kMaxOverlap : (g.hwQueues >= 8 ? g.hwQueues - 3 : 2);
+        g.overlapCap = queueOverlapCap(g.hwQueues, Context::kMaxOverlap); // (tpt_stream_batch.h)
         if (const char* e = getenv("TPT_OVERLAP_CAP")) g.overlapCap = atoi(e) < 1 ? 1 : (atoi(e) > Context::kMaxOverlap ? Context::kMaxOverlap : atoi(e));
     };
     // env TPT_HW_QUEUES=n: the host knows how many hardware queues this process has (GPU_MAX_HW_QUEUES as the runtime read it):

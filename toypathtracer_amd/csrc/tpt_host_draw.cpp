@@ -45,6 +45,15 @@ int LaunchQueue::discard()
     return 0;
 }
 
+// The caller waits (tptSynchronize, tptRayCounterRead): an open STREAM batch is dropped, so that no frame traced before the wait is
+// served after it, and the next call starts a stream afresh.  No wait and no ray lost: a STREAM frame's rays are folded in when it is
+// served.  AHEAD and ROW_SERIAL launches stay (a synchronous caller's look-ahead).
+void LaunchQueue::closeStream()
+{
+    if (holds(PendingLaunch::STREAM)) n = 0;
+    g.streamNext = -1;
+}
+
 // Trace the frames after `frameCount` ahead of the caller, up to tptSetHostLookahead of them: the reference's hosts call
 // DrawTest(f), DrawTest(f + 1), ... with nothing else changing (TestWin.cpp:313-316, Renderer.mm:225, main.cpp:59-60); a
 // frame alone on the GPU is bound by its longest paths (one frame in flight: 1.0 ms, three: 0.55 ms per frame).

@@ -643,29 +643,37 @@ int tptDrawDevice(float time, int frameCount, int w, int h, float* deviceTile, u
         if (stable && Q.frontMatches(PendingLaunch::STREAM, frameCount, w, h, testFlags, key)) {
             Q.serveFront(true, T, rays);
         } else {
+            // (a batch used up by the previous call, continued by this one: the stream goes on, and its batches may grow)
+            const bool continues = Q.empty() && seqStreak >= 2 && frameCount == g.streamNext;
             if ((rc = Q.discard())) return rc; // (also closes a stream batch that did not continue as guessed)
+            g.streamNext = -1;
             int nBatch = 1;
             if (g.streamBatch && pipelined && stable && seqStreak >= 2 && g.persist == 3 && g.seedMode == SEED_PER_PIXEL && g.foldMode == FOLD_RECURSIVE &&
                 g.hs == HS_TWO_PHASE && w <= 8192 && h <= 8192 && g.spp <= 2047) {
-                // how many frames make a launch long enough to amortise its fixed cost: 1 at 1280x720x4 (3.7 M samples), 2 / 4 / 8 for
-                // halves / quarters / eighths of that (profiles/r03/r03_run19.log: where several frames per launch pay)
-                const long long samples = (long long)localRows(h) * w * g.spp;
-                nBatch = samples >= 2400000 ? 1 : samples >= 1200000 ? 2 : samples >= 600000 ? 4 : Context::kStreamBatchMax;
-                if (samples <= 0) nBatch = 1;
+                // how many frames make a launch long enough to amortise its fixed cost at this pipeline depth (tpt_stream_batch.h)
+                g.streamRun = continues ? g.streamRun + 1 : 0;
+                nBatch = streamBatchFrames((long long)localRows(h) * w * g.spp, effectiveOverlap(), Context::kMaxOverlap, g.streamRun,
+                                           (long long)localRows(h) * w * (long long)sizeof(f4), Context::kStreamBatchMax);
             }
             if (nBatch > 1) {
                 PendingLaunch S;
                 S.kind = PendingLaunch::STREAM;
                 S.firstFrame = frameCount; S.w = w; S.h = h; S.flags = testFlags; S.key = key;
-                S.rays = g.dRaysStream + (g.streamBatches++ % (unsigned long long)Context::kStreamRing) * Context::kStreamBatchMax;
-                if ((rc = enqueueTrace(frameCount, w, h, testFlags, S.rays, S.T, nBatch, 1))) return rc;
-                if (S.T.valid) {
+                S.rays = g.dRaysStream + (g.streamBatches % (unsigned long long)Context::kStreamRing) * Context::kStreamBatchMax;
+                rc = enqueueTrace(frameCount, w, h, testFlags, S.rays, S.T, nBatch, 1);
+                if (rc == kRefused && localRows(h) * (long long)w * g.spp >= kStreamLaunchSamples) {
+                    nBatch = 1; // (a large frame's batch the device has no memory for: this frame alone, as without batching)
+                } else if (rc) {
+                    return rc;
+                } else if (S.T.valid) {
+                    g.streamBatches++;
+                    g.streamNext = frameCount + nBatch;
                     if ((rc = Q.push(S))) return rc;
                     Q.serveFront(false, T, rays);
                 }
-            } else if ((rc = enqueueTrace(frameCount, w, h, testFlags, nullptr, T))) {
-                return rc; // (the plain path: the kernel adds its rays to the running total itself)
             }
+            if (nBatch == 1 && (rc = enqueueTrace(frameCount, w, h, testFlags, nullptr, T)))
+                return rc; // (the plain path: the kernel adds its rays to the running total itself)
         }
         rc = enqueueResolve(T, deviceTile, rays);
         if (T.valid) D.lastSlot = T.slot;
@@ -772,6 +780,7 @@ int tptRayCounterRead(int64_t* outTotalRays)
 {
     if (int rc_ = flushShardDeferred()) return rc_;
     if (requireInit()) return -1;
+    g.pending.closeStream(); // (the caller waits: tpt_host_draw.cpp)
     unsigned long long v = 0;
     HIPCHK(hipMemcpyAsync(&v, g.dRays, sizeof(v), hipMemcpyDeviceToHost, g.stream));
     HIPCHK(hipStreamSynchronize(g.stream));
@@ -804,6 +813,7 @@ int tptSynchronize(void)
 {
     if (int rc_ = flushShardDeferred()) return rc_;
     if (requireInit()) return -1;
+    g.pending.closeStream();
     if (int rc = launchTailHelpers()) return rc;
     HIPCHK(hipStreamSynchronize(g.stream));
     return 0;
