@@ -134,8 +134,28 @@ TPT_API int tptDrawDevice(float time, int frameCount, int screenWidth, int scree
  * kernel launch and blended into the tile in frame order by one more.  Bit-identical to nFrames tptDrawDevice calls; a
  * launch's fixed costs (pool ramp-up and drain, no launch shorter than its longest pixel, queue latencies) are paid once
  * per batch instead of once per frame -- what bounds small frames and tiles of a sharded frame.  Path-queue kernel only
- * (the default); frames up to 8192 x 8192; kFlagAnimate is refused (the scene changes every frame). */
+ * (the default); frames up to 8192 x 8192; kFlagAnimate is refused (the scene changes every frame: tptDrawDeviceAnimation). */
 TPT_API int tptDrawDeviceBatch(float time, int firstFrame, int nFrames, int screenWidth, int screenHeight, float* deviceTile, unsigned testFlags);
+/* Frames of an ANIMATED scene at times the caller knows (a clip at a fixed frame rate, a video export, a dataset), up to 32 per
+ * launch.  Frame j (0 <= j < nFrames) is bit-identical to tptUpdate(times[j], firstFrame + j, w, h, testFlags) followed by
+ * tptDrawDevice(times[j], firstFrame + j, w, h, deviceTile, testFlags), with the same ray count: seeds, lerp factor (with
+ * animateSmoothing), light list and all.  deviceTile ends as that sequence leaves it.  deviceFrameImages: NULL or nFrames consecutive
+ * device tiles of h*w*4 floats; tile j receives the tile as it stands right after frame j is blended (what a host reading the tile
+ * after each DrawTest sees).  deviceFrameRays: NULL or nFrames int64 in device memory, OVERWRITTEN with each frame's rays; the
+ * context's counter advances by their sum.  Asynchronous on the context's stream.
+ * Afterwards the context is where the sequence leaves it: spheres 1 and 8 at times[nFrames - 1] (tptGetSceneDesc), that frame's scene
+ * staged (a tptDrawDevice without tptUpdate draws what it draws after the sequence), the camera of tptUpdate; frames traced ahead and
+ * stream-batch planes are dropped first.  Without kFlagAnimate, or with 8 spheres or fewer, nothing moves: the frames are those of
+ * tptDrawDeviceBatch(times[0], firstFrame, nFrames, ...), plus the optional outputs.
+ * One launch per 32 frames with per-pixel seeds, the recursive fold and the path-queue kernel (the defaults), on scenes under 256
+ * spheres (any size when nothing moves); row-serial seeds, the forward fold and other kernel variants -- animated or not -- and
+ * animated scenes of 256 spheres and more take one launch per frame, with the same bits.  A non-finite time affects its own frame only.
+ * Refused (non-zero, tptGetLastError, no tile or ray count written, the context untouched): nFrames < 1, times or deviceTile NULL,
+ * no tptUpdate at this size, w or h over 8192, colour planes over 4096 MiB per launch, row sharding or a communicator, a tile mirror.
+ * A failure after the first launch was enqueued (a HIP error; a scene tptDrawDevice would refuse too) returns non-zero with the
+ * earlier launches' frames enqueued and the context where the sequence stood at the failing launch's last frame. */
+TPT_API int tptDrawDeviceAnimation(int firstFrame, int nFrames, const float* times, int screenWidth, int screenHeight,
+                                   float* deviceTile, float* deviceFrameImages, int64_t* deviceFrameRays, unsigned testFlags);
 /* nViews (1..32) cameras of the scene as of the last tptUpdate, traced by ONE launch.  views: nViews x 9 floats
  * {lookFrom xyz, lookAt xyz, vfovDegrees, aperture, focusDist} -- tptSetCamera's arguments; aspect = w / h, vup (0,1,0),
  * aperture forced to 0 in Mitsuba-compare mode, as tptUpdate does.  deviceTiles: nViews consecutive device tiles of h*w*4

@@ -17,6 +17,7 @@
 #include "tpt_scene.h"
 #include "tpt_shard.h"
 #include "tpt_stream_batch.h"
+#include "tpt_animation.h"
 #include <hip/hip_runtime.h>
 #include <thread>
 #include <rccl/rccl.h> // types and prototypes only: the library is dlopen()ed when tptCommInit is called
@@ -209,11 +210,12 @@ struct Context {
         int lastSlot = -1, syncStreak = 0;
         Streak seq;
     } devCaller;
-    // tptDrawDeviceViews: per frame slot, the views' cameras (device table the views kernel stages in LDS, pinned host staging) and
-    // their ray counters.  Per slot, because up to kMaxSlots launches are in flight: the table of one call must not be overwritten
-    // while an earlier launch still reads it (the upload is stream-ordered behind the slot's previous blend, like its colour buffer).
+    // tptDrawDeviceViews / tptDrawDeviceAnimation: per frame slot, the launch's BatchTable (device table the kernel stages in LDS, pinned
+    // host staging) and its frames' ray counters.  Per slot, because up to kMaxSlots launches are in flight: the table of one call must
+    // not be overwritten while an earlier launch still reads it (the upload is stream-ordered behind the slot's previous blend, like its
+    // colour buffer).  The moving centres of an animation batch (2 x 16 B per frame) take the room of its first 12 cameras.
     struct ViewSlot {
-        CameraPOD* dev = nullptr;       // [kMaxBatch] cameras
+        CameraPOD* dev = nullptr;       // [kMaxBatch] cameras (or [kMaxBatch][2] centres)
         unsigned long long* rays = nullptr; // [kMaxBatch] rays of each view
         CameraPOD* stage = nullptr;     // pinned [kMaxBatch]
         hipEvent_t evUploaded = nullptr;
@@ -353,8 +355,15 @@ int requireInit();
 int drainPipeline();
 int effectiveOverlap();
 // tpt_host_pipeline.cpp
+// What differs between the frames of one launch besides their seeds (tptDrawDeviceViews, tptDrawDeviceAnimation).  The table is copied
+// to the slot's device table on the frame's stream, and every frame counts its rays into the slot's counters (Context::ViewSlot).  With
+// neither table the launch is the plain (batched) kernel with those per-frame counters.
+struct BatchTable {
+    const CameraPOD* cams = nullptr; // [batch] cameras, every frame with the seeds of frameCount: tptTraceViewsKernel
+    const f4* centres = nullptr;     // [batch][2] {x, y, z, -} of spheres 1 and 8 (Test.cpp:304-308): tptTraceAnimationKernel
+};
 int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long long* frameRays, TraceTicket& T, int batch = 1, int rayStride = 0,
-                 const CameraPOD* viewCams = nullptr);
+                 const BatchTable* table = nullptr);
 int enqueueResolve(const TraceTicket& T, float* deviceTile, const unsigned long long* frameRays);
 int syncAllStreams();
 int launchTailHelpers();

@@ -56,6 +56,10 @@ struct KernelArgs {
     // Several views in one launch (tptDrawDeviceViews): batchFrames cameras, one per frame of the batch, in device memory; the launch
     // takes tptTraceViewsKernel, which stages them in LDS and seeds every view with fc.frame.  Null for every other launch.
     const CameraPOD* viewCams = nullptr;
+    // Frames of an animated scene in one launch (tptDrawDeviceAnimation): batchFrames x {sphere 1, sphere 8} centres {x, y, z, -}, one
+    // pair per frame of the batch, in device memory; the launch takes tptTraceAnimationKernel, which stages them in LDS and reads the
+    // path's frame's centres wherever the exact data of sphere 1 or 8 is used.  Null for every other launch.
+    const f4* moveCentres = nullptr;
 };
 
 } // namespace tpt

@@ -636,8 +636,8 @@ int tptUpdate(float time, int frameCount, int screenWidth, int screenHeight, uns
     if (g.shard.pendCount > 0 && (screenWidth != g.shard.pendW || screenHeight != g.shard.pendH || (testFlags & TPT_FLAG_ANIMATE)))
         if (int rc_ = flushShardDeferred()) return rc_;
     if ((testFlags & TPT_FLAG_ANIMATE) && g.spheres.size() > 8) { // Test.cpp:304-308
-        g.spheres[1].cy = cosf(time) + 1.0f;
-        g.spheres[8].cz = sinf(time) * 0.3f;
+        g.spheres[1].cy = animatedY1(time);
+        g.spheres[8].cz = animatedZ8(time);
         g.sceneDirty = true;
     }
     if (g.sceneDirty || (g.curSet < 0 && g.pendingSet < 0)) {

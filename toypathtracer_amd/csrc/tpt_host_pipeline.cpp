@@ -421,11 +421,14 @@ int ensureViewSlots()
 
 // First half of a frame: plan, buffers, trace kernel on the slot's stream.  `frameRays`: where the kernel adds its ray
 // count (the context's counter, or a per-slot one for frames that are traced ahead of their DrawTest call).
-// `viewCams` (tptDrawDeviceViews): the batch's frames are `batch` views of frame frameCount, one camera each (host memory, copied to
-// the slot's table on the frame's stream); the views kernel traces them.
+// `table` (tptDrawDeviceViews, tptDrawDeviceAnimation): what differs between the batch's frames (host memory, copied to the slot's
+// table on the frame's stream) -- cameras: `batch` views of frame frameCount, traced by the views kernel; centres: `batch` frames of an
+// animated scene, traced by the animation kernel; neither: the plain kernel.  Every frame counts its rays into the slot's counters.
 int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long long* frameRays, TraceTicket& T, int batch, int rayStride,
-                 const CameraPOD* viewCams)
+                 const BatchTable* table)
 {
+    const CameraPOD* viewCams = table ? table->cams : nullptr;
+    const f4* centres = table ? table->centres : nullptr;
     if (g.sceneDirty || (g.curSet < 0 && g.pendingSet < 0)) { // tptSetScene after the last tptUpdate
         int rc = stageScene();
         if (rc) return rc;
@@ -481,15 +484,20 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
 
     int rc = 0;
     a.viewCams = nullptr;
-    if (viewCams) {
+    a.moveCentres = nullptr;
+    if (table) {
         if ((rc = ensureViewSlots())) return rc;
-        a.viewCams = g.views[P.slot].dev; // (before chooseKernel: the views kernel's LDS differs)
-        frameRays = g.views[P.slot].rays;  // every view counts its own rays (the blends add them to the running total)
+        // (before chooseKernel: the views and animation kernels' LDS differs)
+        if (viewCams) a.viewCams = g.views[P.slot].dev;
+        if (centres) a.moveCentres = reinterpret_cast<const f4*>(g.views[P.slot].dev);
+        frameRays = g.views[P.slot].rays; // every frame counts its own rays (the blends add them to the running total)
         rayStride = 1;
     }
     if ((rc = chooseKernel(P))) return rc;
     if (viewCams && !P.queued)
         return refuse("tptDrawDeviceViews: needs the path-queue kernel (per-pixel seeds, recursive fold, two-phase HitSpheres, at most 2047 spp)");
+    if (centres && (!P.queued || a.scene.nGroups > 0))
+        return refuse("tptDrawDeviceAnimation: one launch per batch needs the path-queue kernel and a flat scene");
     // a batch is traced by the path-queue kernel (per-pixel seeds) or, in the reference's own seed mode, by the lane-refill
     // kernel: one lane per (frame, row) -- rows AND frames are independent RNG streams there (Test.cpp:280)
     if (batch > 1 && (!(P.queued || P.rowSerial) || w > 8192 || h > 8192 || (long long)a.nLocalRows * w * batch > (1ll << 30)))
@@ -527,19 +535,21 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
         HIPCHK(hipStreamWaitEvent(ts, g.evResolve[slot], 0)); // colour buffer free again
     }
     if ((rc = enqueueSceneUpload(ts))) return rc; // behind the wait above: nobody reads the set being replaced any more
-    if (viewCams) {
-        // the views' cameras, behind the same wait: the slot's previous launch has read its table; the previous copy out of the
-        // slot's pinned staging (an earlier views call on this slot) has left the host before the staging is overwritten
+    if (viewCams || centres) {
+        // the launch's table, behind the same wait: the slot's previous launch has read its table; the previous copy out of the
+        // slot's pinned staging (an earlier call on this slot) has left the host before the staging is overwritten
+        static_assert(2 * sizeof(f4) * kMaxBatch <= sizeof(CameraPOD) * kMaxBatch, "a batch's moving centres fit the slot's camera table");
         Context::ViewSlot& V = g.views[slot];
+        const size_t bytes = viewCams ? sizeof(CameraPOD) * (size_t)batch : 2 * sizeof(f4) * (size_t)batch;
         if (V.copyEnqueued) HIPCHK(hipEventSynchronize(V.evUploaded));
-        memcpy(V.stage, viewCams, sizeof(CameraPOD) * (size_t)batch);
-        HIPCHK(hipMemcpyAsync(V.dev, V.stage, sizeof(CameraPOD) * (size_t)batch, hipMemcpyHostToDevice, ts));
+        memcpy(V.stage, viewCams ? static_cast<const void*>(viewCams) : static_cast<const void*>(centres), bytes);
+        HIPCHK(hipMemcpyAsync(V.dev, V.stage, bytes, hipMemcpyHostToDevice, ts));
         HIPCHK(hipEventRecord(V.evUploaded, ts));
         V.copyEnqueued = true;
     }
     if ((rc = enqueueChunkOrder(P, ts))) return rc;
     if (frameRays && frameRays != g.dRays) HIPCHK(hipMemsetAsync(frameRays, 0, sizeof(unsigned long long) * (size_t)(rayStride > 0 ? batch : 1), ts));
-    const bool helpable = P.queued && pipelined && batch == 1 && !P.rowSerial && !viewCams; // (single frames of the path-queue kernel)
+    const bool helpable = P.queued && pipelined && batch == 1 && !P.rowSerial && !table; // (single frames of the path-queue kernel)
     a.helperBase = 0;
     a.helperPct = 0;
     a.gen = 0u;
@@ -758,7 +768,9 @@ int tptDrawDeviceViews(float time, int frameCount, int w, int h, int nViews, con
     if (rc) return rc;
     // one launch: the views are the frames of a batch (colour planes nPixels apart in the slot's buffer, a ray counter each)
     TraceTicket T;
-    if ((rc = enqueueTrace(frameCount, w, h, testFlags, nullptr, T, nViews, 1, cams))) return rc;
+    BatchTable table;
+    table.cams = cams;
+    if ((rc = enqueueTrace(frameCount, w, h, testFlags, nullptr, T, nViews, 1, &table))) return rc;
     if (!T.valid) return 0;
     // the blends, in view order on the context's stream, each into its own tile with the frame's lerp factor; blend v also adds view
     // v's rays to the running total.  The per-view counts go to the caller first: the slot's counters are free again once its last
@@ -772,6 +784,80 @@ int tptDrawDeviceViews(float time, int frameCount, int w, int h, int nViews, con
     if (T.pipelined) {
         HIPCHK(hipEventRecord(g.evResolve[T.slot], g.stream));
         g.resolveRecorded[T.slot] = true;
+    }
+    return 0;
+}
+
+// nFrames frames of the scene as tptUpdate(times[j], firstFrame + j, ...) animates it, each followed by tptDrawDevice: the same bits,
+// the same ray counts.  Up to kMaxBatch frames per launch (tptTraceAnimationKernel: each frame's centres of the two moving spheres in
+// a table and tested for every ray; on a static scene the batched kernel), blended in
+// frame order one frame at a time, each blend also writing the tile as it stands to the frame's image.  Configurations the batched
+// kernels do not serve take one launch per frame.  Like tptDrawDeviceViews, not a continuation of anything: frames traced ahead and
+// stream-batch planes are dropped; unlike it, the context is left as the sequence leaves it (spheres, staged scene, camera).
+int tptDrawDeviceAnimation(int firstFrame, int nFrames, const float* times, int w, int h, float* deviceTile, float* deviceFrameImages,
+                           int64_t* deviceFrameRays, unsigned testFlags)
+{
+    if (int rc_ = flushShardDeferred()) return rc_; // (see tptDrawDevice)
+    if (requireInit()) return -1;
+    if (nFrames < 1) return fail("tptDrawDeviceAnimation: nFrames must be at least 1");
+    if (!times || !deviceTile || w <= 0 || h <= 0) return fail("tptDrawDeviceAnimation: bad arguments (times, deviceTile, size)");
+    if (!g.updated || w != g.updatedW || h != g.updatedH) return fail("tptDrawDeviceAnimation: call tptUpdate (UpdateTest) at this size first");
+    if (w > 8192 || h > 8192) return fail("tptDrawDeviceAnimation: frames of at most 8192 x 8192");
+    // (the tptUpdate guard, Test.cpp:304: a scene of 8 spheres or fewer does not move)
+    const bool animate = (testFlags & TPT_FLAG_ANIMATE) && g.spheres.size() > 8;
+    // one launch per kMaxBatch frames on the path-queue kernel; the animation kernel also wants a flat scene (its exact tests are
+    // those of the flat filters); everything else: one launch per frame, the kernels of tptDrawDevice
+    const bool pathQueue = g.persist == 3 && g.hs == HS_TWO_PHASE && g.seedMode == SEED_PER_PIXEL && g.foldMode == FOLD_RECURSIVE && g.spp <= 2047;
+    const int perLaunch = pathQueue && (!animate || g.spheres.size() < TPT_GROUP_MIN_SPHERES) ? kMaxBatch : 1;
+    const size_t colour = (size_t)h * (size_t)w * sizeof(f4) * (size_t)(nFrames < perLaunch ? nFrames : perLaunch);
+    if (colour > (4ull << 30))
+        return refuse("tptDrawDeviceAnimation: " + std::to_string(colour >> 20) + " MiB of frame colour per launch: over the 4096 MiB limit");
+    if (g.numParts > 1 || g.shard.active) return fail("tptDrawDeviceAnimation: not with row sharding or a communicator (sharded animation is not supported)");
+    if (g.mirror) return fail("tptDrawDeviceAnimation: not with a tile mirror (tptSetTileMirror)");
+    int rc = g.pending.discard();
+    if (rc) return rc;
+    // the camera as every tptUpdate of the sequence builds it (Test.cpp:309-313, 341)
+    CameraSetup cs = g.camSetup;
+    if (g.config & CFG_MITSUBA_COMPARE) cs.aperture = 0.0f;
+    g.cam = makeCamera(cs, float(w) / float(h));
+    for (int f = 0; f < nFrames; f += perLaunch) {
+        const int n = nFrames - f < perLaunch ? nFrames - f : perLaunch;
+        BatchTable table;
+        f4 centres[2 * kMaxBatch];
+        if (animate) {
+            // each frame's centres of spheres 1 and 8 exactly as tptUpdate moves them (a non-finite time touches its own frame only); the
+            // context's spheres end at the batch's last time
+            const SpherePOD s1 = g.spheres[1], s8 = g.spheres[8];
+            for (int j = 0; j < n; ++j) {
+                const float t = times[f + j];
+                centres[2 * j] = f4{s1.cx, animatedY1(t), s1.cz, 0.0f};
+                centres[2 * j + 1] = f4{s8.cx, s8.cy, animatedZ8(t), 0.0f};
+            }
+            g.spheres[1].cy = centres[2 * (n - 1)].y;
+            g.spheres[8].cz = centres[2 * (n - 1) + 1].z;
+            // the staged scene is the batch's last frame: exact for the spheres that do not move, and the animation kernel reads spheres
+            // 1 and 8 from the table and tests them for every ray (tpt_trace.h, movedSphere)
+            if (perLaunch > 1) table.centres = centres;
+            if ((rc = stageScene())) return rc;
+        }
+        TraceTicket T;
+        if ((rc = enqueueTrace(firstFrame + f, w, h, testFlags, nullptr, T, n, 1, &table))) return rc;
+        if (!T.valid) continue;
+        // the blends, in frame order on the context's stream: blend j adds frame j's rays to the running total and writes the tile as it
+        // stands to image j.  The per-frame counts go to the caller first (the slot's counters are free once its last blend has run).
+        const Context::ViewSlot& V = g.views[T.slot];
+        if (T.pipelined) HIPCHK(hipStreamWaitEvent(g.stream, g.evTrace[T.slot], 0));
+        if (deviceFrameRays)
+            HIPCHK(hipMemcpyAsync(deviceFrameRays + f, V.rays, sizeof(unsigned long long) * (size_t)n, hipMemcpyDeviceToDevice, g.stream));
+        for (int j = 0; j < n; ++j) {
+            const TraceTicket P = T.plane(j);
+            float* image = deviceFrameImages ? deviceFrameImages + (size_t)(f + j) * (size_t)T.nPixels * 4 : nullptr;
+            HIPCHK(tptLaunchResolve(deviceTile, P.colour, T.nPixels, P.lerpFac, image, g.dRays, nullptr, V.rays + j, g.stream));
+        }
+        if (T.pipelined) {
+            HIPCHK(hipEventRecord(g.evResolve[T.slot], g.stream));
+            g.resolveRecorded[T.slot] = true;
+        }
     }
     return 0;
 }

@@ -483,6 +483,10 @@ static_assert(TPT_GROUP_DEAL_ENTRIES >= TPT_GROUP_DEAL_CAP, "the flat variants' 
 #define TPT_Q_VIEWS_MAX 32
 #define TPT_Q_VIEW_CAM_BYTES (TPT_Q_VIEWS_MAX * 88)
 #define TPT_Q_VIEW_PATHS ((TPT_Q_VIEW_CAM_BYTES + TPT_Q_NF4 * 16 - 1) / (TPT_Q_NF4 * 16))
+// Frames of an animated scene in one launch (tptTraceAnimationKernel): each frame's centres of spheres 1 and 8 sit in LDS (32 x 2 x 16 B),
+// in the place of 16 path records (16 x 64 B): the same LDS per launch as the single-frame twin, as for the views.
+#define TPT_Q_ANIM_TABLE_BYTES (TPT_Q_VIEWS_MAX * 2 * 16)
+#define TPT_Q_ANIM_PATHS ((TPT_Q_ANIM_TABLE_BYTES + TPT_Q_NF4 * 16 - 1) / (TPT_Q_NF4 * 16))
 #ifndef TPT_Q_PATHS_GROUPED
 // ... and of the instantiation for GROUPED scenes (no scene staging, no matrix-filter table): 608.  The LDS the smaller pool frees holds
 // the entry areas of the three-stage dealing (640 entries per wave) and the groups' bounding spheres (pair records, 144 B per super-group
@@ -1157,7 +1161,10 @@ __device__ __forceinline__ int hitSpheresGroupedDeal(const SceneView& sv, bool g
 // a path carries costs the single-frame kernel two more spilled registers if it is a run-time one.
 // VIEWS (with BATCH; tptDrawDeviceViews): frame j of the batch is VIEW j of one frame -- camera a.viewCams[j] (staged in LDS), the
 // seed of frame fc.frame for every view.  Its own kernel (tptTraceViewsKernel) for the same reason.
-template <bool LDS_SCENE, bool BATCH, bool VIEWS = false>
+// MOVING (with BATCH; tptDrawDeviceAnimation): frame j of the batch is a frame of an animated scene -- spheres 1 and 8 at the centres
+// a.moveCentres[2 j], [2 j + 1] (staged in LDS) in phase 2, the hit normal and the light loop, and candidates of every ray whatever the
+// filter says (tpt_trace.h, movedSphere).  Flat scenes only.  Its own kernel (tptTraceAnimationKernel) for the same reason.
+template <bool LDS_SCENE, bool BATCH, bool VIEWS = false, bool MOVING = false>
 __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1166,7 +1173,9 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     // (kernels that stage the scene keep {centre, r^2} of up to 64 spheres -- every scene the matrix filter serves -- at offset
     //  0: phase 2 then addresses a sphere with sphere index x 16 and an immediate, like the path records)
     static_assert(BATCH || !VIEWS, "views are frames of a batched launch");
-    constexpr int kPaths = (LDS_SCENE ? TPT_Q_PATHS : TPT_Q_PATHS_GROUPED) - (VIEWS ? TPT_Q_VIEW_PATHS : 0); // paths this workgroup owns
+    static_assert((BATCH || !MOVING) && !(VIEWS && MOVING), "animation frames are frames of a batched launch of their own");
+    constexpr int kPaths = (LDS_SCENE ? TPT_Q_PATHS : TPT_Q_PATHS_GROUPED) - (VIEWS ? TPT_Q_VIEW_PATHS : 0) -
+                           (MOVING ? TPT_Q_ANIM_PATHS : 0); // paths this workgroup owns
     constexpr int kOffSt = LDS_SCENE ? TPT_Q_SPH_FIXED : 0;
     constexpr int kOffQ = kOffSt + TPT_Q_NF4 * kPaths * 16;
     constexpr int kOffCtl = kOffQ + Q_COUNT * TPT_Q_P * 2;
@@ -1174,7 +1183,8 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     constexpr int kDealBytes = (!LDS_SCENE && TPT_GROUP_DEAL) ? TPT_Q_WAVES * TPT_GROUP_DEAL_WAVE_BYTES : 0; // pair lists of the grouped traversal
     constexpr int kOffFc = kOffDeal + kDealBytes;
     constexpr int kOffCams = kOffFc + (((int)sizeof(FrameConsts) + 15) & ~15);
-    constexpr int kOffScene = kOffCams + (VIEWS ? TPT_Q_VIEW_CAM_BYTES : 0);
+    constexpr int kOffMoved = kOffCams + (VIEWS ? TPT_Q_VIEW_CAM_BYTES : 0);
+    constexpr int kOffScene = kOffMoved + (MOVING ? TPT_Q_ANIM_TABLE_BYTES : 0);
     f4* st = reinterpret_cast<f4*>(smem + kOffSt);
     LdsRing q = (LdsRing)(smem + kOffQ);
     QueueCtl* ctl = reinterpret_cast<QueueCtl*>(smem + kOffCtl);
@@ -1182,6 +1192,8 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     // ~30 SGPRs held (and spilled) across the whole loop
     FrameConsts* ldsFc = reinterpret_cast<FrameConsts*>(smem + kOffFc);
     CameraPOD* ldsCams = reinterpret_cast<CameraPOD*>(smem + kOffCams); // (VIEWS: the cameras of the batch's views)
+    f4* ldsMoved = reinterpret_cast<f4*>(smem + kOffMoved);              // (MOVING: the centres of spheres 1 and 8, two per frame)
+    const LdsMovedPtr movedLds = (LdsMovedPtr)ldsMoved;                  // (... as the readers take them)
     const int nPad = a.scene.nPairs * 2;
     const bool sphFixed = LDS_SCENE && nPad * 16 <= TPT_Q_SPH_FIXED;
     f4* ldsSphFixed = reinterpret_cast<f4*>(smem);
@@ -1255,6 +1267,8 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     if (VIEWS)
         for (int i = tid; i < a.batchFrames * (int)(sizeof(CameraPOD) / 4); i += TPT_Q_T)
             reinterpret_cast<uint32_t*>(ldsCams)[i] = reinterpret_cast<const uint32_t*>(a.viewCams)[i];
+    if (MOVING)
+        for (int i = tid; i < a.batchFrames * 2; i += TPT_Q_T) ldsMoved[i] = a.moveCentres[i];
     // every path starts in the FREE queue; all other queues empty (sentinel everywhere)
     for (int i = tid; i < Q_COUNT * TPT_Q_P; i += TPT_Q_T) q[i] = (unsigned short)(i < kPaths ? i : 0xFFFF);
     if (tid < 8) {
@@ -1277,7 +1291,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
 #if TPT_GROUP_DEAL
     LdsList dealList = (LdsList)(smem + kOffDeal + (tid >> 6) * TPT_GROUP_DEAL_WAVE_BYTES);
     unsigned* dealCount = reinterpret_cast<unsigned*>(smem + kOffDeal + (tid >> 6) * TPT_GROUP_DEAL_WAVE_BYTES + TPT_GROUP_DEAL_ENTRIES * 4);
-    const bool groupDeal = !LDS_SCENE && sv.nGroups > 0 && sv.nGroups <= 65536; // (16 bits of group index, 20 of member slot, in a list entry)
+    const bool groupDeal = !MOVING && !LDS_SCENE && sv.nGroups > 0 && sv.nGroups <= 65536; // (16 bits of group index, 20 of member slot, in a list entry)
 #endif
     f4* colSum = st + 2 * kPaths;                        // plane 2: per-path colour sums + pixel coordinates
     int chunkNext = 0, chunkEnd = 0; // this wave's private pixel pool
@@ -1384,7 +1398,9 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
         QLambert lam;
         lam.sdir = lam.nl = lam.albedo = lam.lightE = mk3(0, 0, 0);
         lam.cosAMax = 0.0f;
+        int movedAt = 0; // MOVING: where the centres of this path's frame start in ldsMoved (2 x its frame of the batch)
         if (pick != Q_FREE && mine) {
+            if (MOVING) movedAt = 2 * (int)(f2u(colSum[p].w) >> 26);
             const f4 r0 = st[0 * kPaths + p], r1 = st[1 * kPaths + p];
             ro = mk3(r0.x, r0.y, r0.z);
             rng = f2u(r0.w);
@@ -1452,6 +1468,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                 const uint32_t where = BATCH ? ((uint32_t)px | ((uint32_t)py << 13) | ((uint32_t)laneFrame << 26))
                                              : ((uint32_t)px | ((uint32_t)py << 16));
                 colSum[p] = mk4(0.0f, 0.0f, 0.0f, u2f(where));
+                if (MOVING) movedAt = 2 * laneFrame;
                 if (VIEWS)
                     qCameraView(ldsCams[laneFrame], *ldsFc, px, py, rng, ro, rd);
                 else
@@ -1496,7 +1513,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
         } else if (pick == Q_DIEL) {
             if (mine) {
                 f3 e;
-                rd = qDielectric(sv, fc, ro, rd, recId, doMatE, rng, e);
+                rd = qDielectric<MOVING>(sv, fc, ro, rd, recId, doMatE, rng, e, movedLds + movedAt);
                 qStackPush(stack, depth, e, -1);
                 depth++;
                 doMatE = true; // Test.cpp:214
@@ -1505,7 +1522,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
         } else if (pick == Q_METAL) {
             if (mine) {
                 f3 e, nd;
-                if (qMetal(sv, fc, ro, rd, recId, doMatE, rng, e, nd)) {
+                if (qMetal<MOVING>(sv, fc, ro, rd, recId, doMatE, rng, e, nd, movedLds + movedAt)) {
                     qStackPush(stack, depth, e, recId);
                     depth++;
                     doMatE = true;
@@ -1517,7 +1534,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
             }
         } else { // Q_LAMBERT
             if (mine) {
-                qLambertBegin(sv, ro, rd, recId, rng, lam);
+                qLambertBegin<MOVING>(sv, ro, rd, recId, rng, lam, movedLds + movedAt);
                 ray = true;
             }
         }
@@ -1553,7 +1570,10 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                     l1 = sv.lights[j * 2 + 1];
                     lightId = (int)f2u(l1.w);
                     go = ray && lightId != recId; // Test.cpp:100: not the sphere itself
-                    if (go) d2 = qLightRay(sv.lights[j * 2], ro, rng, lam.cosAMax, (sv.flags & SCENE_LIGHT_R2_DIV_SAFE) != 0);
+                    if (go) {
+                        const f4 l0 = MOVING ? movedSphere(sv.lights[j * 2], lightId, movedLds + movedAt) : sv.lights[j * 2];
+                        d2 = qLightRay(l0, ro, rng, lam.cosAMax, (sv.flags & SCENE_LIGHT_R2_DIV_SAFE) != 0);
+                    }
                 }
 #if TPT_MATRIX_FILTER
                 // phase 1 of HitSpheres for the whole wave on the matrix cores: every lane takes part (this loop is wave-uniform);
@@ -1579,9 +1599,12 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
 #endif
 #if TPT_MATRIX_FILTER
                     if (LDS_SCENE && useMatrix)
-                        id = hitSpheresCandidates(svM, cand, ro, d2, TPT_MIN_T, TPT_MAX_T, t);
+                        id = hitSpheresCandidates<MOVING>(svM, cand, ro, d2, TPT_MIN_T, TPT_MAX_T, t, movedLds + movedAt);
                     else
 #endif
+                    if (MOVING) // (a flat scene: what hitSpheres runs for it, with the frame's centres)
+                        id = hitSpheresTwoPhase<true>(sv, ro, d2, TPT_MIN_T, TPT_MAX_T, t, movedLds + movedAt);
+                    else
                         id = hitSpheres<LDS_SCENE ? HS_TWO_PHASE : HS_TWO_PHASE_GROUPS>(sv, ro, d2, TPT_MIN_T, TPT_MAX_T, t);
                     if (BATCH) iterRays++; else myRays++;
                     if (shadow) {
@@ -1731,6 +1754,20 @@ __global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute
 tptTraceViewsKernel<false>(const KernelArgs a)
 {
     traceQueueBody<false, true, true>(a);
+}
+// Frames of an animated scene per launch (tptDrawDeviceAnimation): the batched kernel with spheres 1 and 8 where each frame has them.
+// A kernel of its own for the same reason; <false>: flat scenes whose arrays stay in global memory (grouped scenes take one launch per frame).
+template <bool LDS_SCENE>
+__global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute__((amdgpu_num_vgpr(TPT_Q_MAX_VGPR)))
+tptTraceAnimationKernel(const KernelArgs a)
+{
+    traceQueueBody<LDS_SCENE, true, false, true>(a);
+}
+template <>
+__global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute__((amdgpu_num_vgpr(TPT_Q_MAX_VGPR_GROUPED)))
+tptTraceAnimationKernel<false>(const KernelArgs a)
+{
+    traceQueueBody<false, true, false, true>(a);
 }
 
 #if defined(TPT_TEST_HOOKS)
@@ -2001,16 +2038,19 @@ constexpr size_t kDefaultSceneLds = TPT_Q_SPH_FIXED + ((46 * 4 + 15) & ~15) + 46
 static_assert(2 * (kQueueLdsFixedPart + kDefaultSceneLds + 256) <= 160 * 1024, "the default scene no longer fits two path-queue workgroups per CU: shrink TPT_Q_PATHS");
 static_assert(TPT_Q_VIEW_CAM_BYTES <= TPT_Q_NF4 * TPT_Q_VIEW_PATHS * 16, "the views' cameras take no more LDS than the path records they replace");
 static_assert(sizeof(tpt::CameraPOD) == 88 && sizeof(tpt::CameraPOD) % 4 == 0, "cameras are staged in LDS as 22 words");
+static_assert(TPT_Q_ANIM_TABLE_BYTES == TPT_Q_NF4 * TPT_Q_ANIM_PATHS * 16, "the moving centres take exactly the LDS of the path records they replace");
 }
 size_t tptQueueLdsBytes(const KernelArgs& a, bool ldsScene)
 {
     const int nPad = a.scene.nPairs * 2;
     const bool views = a.viewCams != nullptr; // (tptTraceViewsKernel: the cameras in LDS, TPT_Q_VIEW_PATHS path records fewer)
+    const bool moving = a.moveCentres != nullptr; // (tptTraceAnimationKernel: the centres in LDS, TPT_Q_ANIM_PATHS path records fewer)
     size_t bytes = 0;
     if (ldsScene) bytes += TPT_Q_SPH_FIXED + ((size_t)nPad * 16 <= TPT_Q_SPH_FIXED ? 0 : (size_t)nPad * 16) + (((size_t)nPad * 4 + 15) & ~(size_t)15) + (size_t)a.scene.nSpheres * 48;
     bytes += (size_t)a.scene.nLights * 32;
     bytes += (size_t)TPT_Q_NF4 * (ldsScene ? TPT_Q_PATHS : TPT_Q_PATHS_GROUPED) * 16 + (size_t)Q_COUNT * TPT_Q_P * 2 + ((sizeof(QueueCtl) + 63) & ~(size_t)63) + ((sizeof(FrameConsts) + 15) & ~(size_t)15);
     if (views) bytes += (size_t)TPT_Q_VIEW_CAM_BYTES - (size_t)TPT_Q_NF4 * TPT_Q_VIEW_PATHS * 16;
+    if (moving) bytes += (size_t)TPT_Q_ANIM_TABLE_BYTES - (size_t)TPT_Q_NF4 * TPT_Q_ANIM_PATHS * 16;
     if (!ldsScene && TPT_GROUP_DEAL) bytes += (size_t)TPT_Q_WAVES * TPT_GROUP_DEAL_WAVE_BYTES;
     if (!ldsScene && a.ldsGroupPairs > 0) bytes += 16 + (size_t)(a.ldsGroupPairs / (TPT_SUPER / 2)) * TPT_GPAIR_LDS_STRIDE * 4; // the groups' bounds for the second filter level (tptQueueGroupPairsInLds), padded stride
 #if TPT_MATRIX_FILTER
@@ -2036,11 +2076,26 @@ static hipError_t launchTraceViews(const KernelArgs& a, int blocks, size_t lds, 
     hipLaunchKernelGGL(k, dim3(blocks), dim3(TPT_Q_T), lds, stream, a);
     return hipSuccess;
 }
+template <bool LDS_SCENE>
+static hipError_t launchTraceAnimation(const KernelArgs& a, int blocks, size_t lds, hipStream_t stream)
+{
+    auto k = tptTraceAnimationKernel<LDS_SCENE>;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(TPT_Q_T), lds, stream, a);
+    return hipSuccess;
+}
 hipError_t tptLaunchTraceQueue(const KernelArgs& a, bool ldsScene, int blocks, size_t lds, hipStream_t stream)
 {
     if (a.viewCams) { // (tptDrawDeviceViews: 1 .. TPT_Q_VIEWS_MAX views, the frames of the batch)
         if (a.batchFrames < 1 || a.batchFrames > TPT_Q_VIEWS_MAX) return hipErrorInvalidValue;
         hipError_t e = ldsScene ? launchTraceViews<true>(a, blocks, lds, stream) : launchTraceViews<false>(a, blocks, lds, stream);
+        if (e != hipSuccess) return e;
+        return hipGetLastError();
+    }
+    if (a.moveCentres) { // (tptDrawDeviceAnimation: 1 .. TPT_Q_VIEWS_MAX frames of the batch, a flat scene)
+        if (a.batchFrames < 1 || a.batchFrames > TPT_Q_VIEWS_MAX || a.scene.nGroups > 0) return hipErrorInvalidValue;
+        hipError_t e = ldsScene ? launchTraceAnimation<true>(a, blocks, lds, stream) : launchTraceAnimation<false>(a, blocks, lds, stream);
         if (e != hipSuccess) return e;
         return hipGetLastError();
     }

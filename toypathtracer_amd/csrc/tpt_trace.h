@@ -170,6 +170,31 @@ TPT_HD void testSphere(f4 s, int i, f3 o, f3 d, float tMin, float& hitT, int& id
     }
 }
 
+// tptDrawDeviceAnimation (tptTraceAnimationKernel): spheres 1 and 8 move every frame (Test.cpp:304-308).  `moved` points at the centres
+// {x, y, z, -} of both in the path's frame; s.w (r^2, or a light's radius) stays the scene's own.  Called where the exact data of a
+// sphere is read -- phase 2, the hit normal, the light loop.  The filter's data is the scene's and holds for the spheres that do not
+// move; spheres 1 and 8 are made candidates of every ray (TPT_MOVED_CANDIDATES), so phase 1 can drop nothing a frame's exact test
+// accepts, whatever the motion: every filter bit depends on its own sphere only, and phase 2 gives the same nearest hit for any
+// superset of the spheres the exact test accepts (index order, strict t < hitT -- what the reference's loop over all spheres does).
+// (`moved` is an LDS address explicitly: with a generic pointer LLVM merges the two loads into one FLAT load from either address)
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef const f4 __attribute__((address_space(3))) * LdsMovedPtr;
+#else
+typedef const f4* LdsMovedPtr;
+#endif
+// spheres 1 and 8 in a candidate mask of the first 64 spheres (sphere i at bit 63 - i: phase1Chunk's first chunk, phase1MatrixH)
+#define TPT_MOVED_CANDIDATES ((1ull << 62) | (1ull << 55))
+TPT_HD f4 movedSphere(f4 s, int id, LdsMovedPtr moved)
+{
+    if (id == 1 || id == 8) {
+        const f4 c = moved[id == 8 ? 1 : 0];
+        s.x = c.x;
+        s.y = c.y;
+        s.z = c.z;
+    }
+    return s;
+}
+
 TPT_HD int hitSpheresSimple(const SceneView& sv, f3 o, f3 d, float tMin, float tMax, float& outT)
 {
     float hitT = tMax;
@@ -313,7 +338,9 @@ __shared__ unsigned long long g_hsLds[4]; // per-workgroup sums, flushed to g_tp
 #define TPT_HS_TRIP() do { } while (0)
 #define TPT_HS_ADD(a, b, c) do { } while (0)
 #endif
-TPT_HD int hitSpheresTwoPhase(const SceneView& sv, f3 o, f3 d, float tMin, float tMax, float& outT)
+// MOVED: tptTraceAnimationKernel (movedSphere)
+template <bool MOVED = false>
+TPT_HD int hitSpheresTwoPhase(const SceneView& sv, f3 o, f3 d, float tMin, float tMax, float& outT, LdsMovedPtr moved = nullptr)
 {
     float hitT = tMax;
     int id = -1;
@@ -327,6 +354,7 @@ TPT_HD int hitSpheresTwoPhase(const SceneView& sv, f3 o, f3 d, float tMin, float
         (void)hsTrips_;
         TPT_HS_STAMP(t0_);
         uint64_t cand = phase1Chunk(pairPtr(sv.pairs + (size_t)pb * 8), cnt, ox, oy, oz, dx, dy, dz);
+        if (MOVED && pb == 0) cand |= TPT_MOVED_CANDIDATES; // (a scene that animates has more than 8 spheres)
         TPT_HS_STAMP(t1_);
         while (cand) {
             int k = __builtin_clzll(cand);
@@ -334,7 +362,7 @@ TPT_HD int hitSpheresTwoPhase(const SceneView& sv, f3 o, f3 d, float tMin, float
             int i = pb * 2 + k;
             TPT_STAT(ST_PHASE2);
             TPT_HS_TRIP();
-            testSphere(sv.sph4[i], i, o, d, tMin, hitT, id);
+            testSphere(MOVED ? movedSphere(sv.sph4[i], i, moved) : sv.sph4[i], i, o, d, tMin, hitT, id);
         }
         TPT_HS_STAMP(t2_);
         TPT_HS_ADD(t0_, t1_, t2_);
@@ -606,19 +634,21 @@ __device__ __forceinline__ uint64_t phase1MatrixH(const uint32_t* ldsA, int R1, 
 }
 #endif
 // phase 2 over a candidate mask (sphere p at bit 63 - p): the reference's arithmetic, ascending index
-TPT_HD int hitSpheresCandidates(const SceneView& sv, uint64_t cand, f3 o, f3 d, float tMin, float tMax, float& outT)
+template <bool MOVED = false> // (tptTraceAnimationKernel: movedSphere)
+TPT_HD int hitSpheresCandidates(const SceneView& sv, uint64_t cand, f3 o, f3 d, float tMin, float tMax, float& outT, LdsMovedPtr moved = nullptr)
 {
     float hitT = tMax;
     int id = -1;
     unsigned hsTrips_ = 0;
     (void)hsTrips_;
+    if (MOVED) cand |= TPT_MOVED_CANDIDATES;
     TPT_HS_STAMP(t1_);
     while (cand) {
         const int i = __builtin_clzll(cand);
         cand &= ~(0x8000000000000000ull >> i);
         TPT_STAT(ST_PHASE2);
         TPT_HS_TRIP();
-        testSphere(sv.sph4[i], i, o, d, tMin, hitT, id);
+        testSphere(MOVED ? movedSphere(sv.sph4[i], i, moved) : sv.sph4[i], i, o, d, tMin, hitT, id);
     }
     TPT_HS_STAMP(t2_);
     TPT_HS_ADD(t1_, t1_, t2_);
@@ -1120,10 +1150,11 @@ TPT_HD void qStackPush(const QStack& s, int level, f3 e, int attId)
     else
         s.spill[(level - 1) * s.stride] = v;
 }
-// hit normal, Maths.cpp:196-197
-TPT_HD f3 qNormal(const SceneView& sv, int id, f3 pos)
+// hit normal, Maths.cpp:196-197 (MOVED: tptTraceAnimationKernel, movedSphere)
+template <bool MOVED = false>
+TPT_HD f3 qNormal(const SceneView& sv, int id, f3 pos, LdsMovedPtr moved = nullptr)
 {
-    const f4 s = sv.sph4[id];
+    const f4 s = MOVED ? movedSphere(sv.sph4[id], id, moved) : sv.sph4[id];
     return (pos - mk3(s.x, s.y, s.z)) * sv.invR[id];
 }
 // camera ray of the next sample of pixel (x, y), Test.cpp:286-288
@@ -1186,11 +1217,12 @@ TPT_HD f3 qFold(const SceneView& sv, f3 term, int depth, const QStack& s)
     return c;
 }
 // Dielectric, Test.cpp:151-186: always scatters.  e = what this level adds (matE + lightE, lightE = 0), attenuation (1,1,1).
-TPT_HD f3 qDielectric(const SceneView& sv, const FrameConsts& fc, f3 pos, f3 rdir, int id, bool doMatE, uint32_t& rng, f3& e)
+template <bool MOVED = false>
+TPT_HD f3 qDielectric(const SceneView& sv, const FrameConsts& fc, f3 pos, f3 rdir, int id, bool doMatE, uint32_t& rng, f3& e, LdsMovedPtr moved = nullptr)
 {
     TPT_STAT(ST_DIELECTRIC);
     (void)fc;
-    const f3 normal = qNormal(sv, id, pos);
+    const f3 normal = qNormal<MOVED>(sv, id, pos, moved);
     const f4 m1 = sv.mats[id * 3 + 1];
     const f4 m2 = sv.mats[id * 3 + 2]; // {ri, 1.0f / ri, r0^2}: the division of Test.cpp:168 and schlick's r0 (Maths.h:329-330) depend on the material only
     const float ri = m2.x;
@@ -1216,10 +1248,12 @@ TPT_HD f3 qDielectric(const SceneView& sv, const FrameConsts& fc, f3 pos, f3 rdi
     return normalize(pick);
 }
 // Metal, Test.cpp:137-150: false = the scattered ray points into the surface (the path ends with the sphere's emission).
-TPT_HD bool qMetal(const SceneView& sv, const FrameConsts& fc, f3 pos, f3 rdir, int id, bool doMatE, uint32_t& rng, f3& e, f3& newDir)
+template <bool MOVED = false>
+TPT_HD bool qMetal(const SceneView& sv, const FrameConsts& fc, f3 pos, f3 rdir, int id, bool doMatE, uint32_t& rng, f3& e, f3& newDir,
+                   LdsMovedPtr moved = nullptr)
 {
     TPT_STAT(ST_METAL);
-    const f3 normal = qNormal(sv, id, pos);
+    const f3 normal = qNormal<MOVED>(sv, id, pos, moved);
     const f4 m1 = sv.mats[id * 3 + 1];
     const f3 refl = reflect(rdir, normal);
     const float roughness = (fc.config & CFG_MITSUBA_COMPARE) ? 0.0f : m1.w; // Test.cpp:143-145 (the samples are drawn either way)
@@ -1235,10 +1269,11 @@ struct QLambert {
     f3 sdir, nl, albedo, lightE;
     float cosAMax;
 };
-TPT_HD void qLambertBegin(const SceneView& sv, f3 pos, f3 rdir, int id, uint32_t& rng, QLambert& q)
+template <bool MOVED = false>
+TPT_HD void qLambertBegin(const SceneView& sv, f3 pos, f3 rdir, int id, uint32_t& rng, QLambert& q, LdsMovedPtr moved = nullptr)
 {
     TPT_STAT(ST_LAMBERT);
-    const f3 normal = qNormal(sv, id, pos);
+    const f3 normal = qNormal<MOVED>(sv, id, pos, moved);
     const f4 m0 = sv.mats[id * 3];
     const f3 target = pos + normal + randomUnitVector(rng);
     q.sdir = normalize(target - pos);
