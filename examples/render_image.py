@@ -1,6 +1,9 @@
 """Render the built-in scene on the GPU and write it as TGA (the reference's Cs/Program.cs:33-59 format) and PNG.
 
-    python examples/render_image.py [width height frames]
+    python examples/render_image.py [--aov] [width height frames [out_dir]]
+
+--aov: the last frame is drawn with tptDrawDeviceAov, and its first-hit planes are written too: albedo.png (the albedo) and
+normal.png (0.5 + 0.5 n) -- the guide images a denoiser takes beside the colour.
 """
 import os
 import struct
@@ -28,24 +31,45 @@ def write_png(path, rgba):
                 chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
 
 
+def to_rgba8(rgb):
+    """[h, w, 3] floats in [0, 1] -> [h, w, 4] uint8, opaque"""
+    h, w = rgb.shape[:2]
+    out = np.full((h, w, 4), 255, np.uint8)
+    out[..., :3] = np.clip(rgb * 255.0 + 0.5, 0, 255).astype(np.uint8)
+    return out
+
+
 def main():
-    w = int(sys.argv[1]) if len(sys.argv) > 1 else 1280
-    h = int(sys.argv[2]) if len(sys.argv) > 2 else 720
-    frames = int(sys.argv[3]) if len(sys.argv) > 3 else 64
-    out_dir = sys.argv[4] if len(sys.argv) > 4 else "."
+    aov = "--aov" in sys.argv[1:]
+    args = [a for a in sys.argv[1:] if a != "--aov"]
+    w = int(args[0]) if len(args) > 0 else 1280
+    h = int(args[1]) if len(args) > 1 else 720
+    frames = int(args[2]) if len(args) > 2 else 64
+    out_dir = args[3] if len(args) > 3 else "."
     api.InitializeTest()
     tile = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda")
     rgba = torch.zeros((h, w, 4), dtype=torch.uint8, device="cuda")
+    albedo = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda") if aov else None
+    normal_depth = torch.zeros_like(albedo) if aov else None
     r0 = api.ray_counter_read()
     for f in range(frames):
         api.UpdateTest(0.0, f, w, h, api.kFlagProgressive)
-        api.draw_device(0.0, f, w, h, tile.data_ptr(), api.kFlagProgressive)
+        if aov and f == frames - 1:
+            api.draw_device_aov(0.0, f, w, h, tile.data_ptr(), api.kFlagProgressive, albedo_ptr=albedo.data_ptr(),
+                                normal_depth_ptr=normal_depth.data_ptr())
+        else:
+            api.draw_device(0.0, f, w, h, tile.data_ptr(), api.kFlagProgressive)
     api.display_rgba8(tile.data_ptr(), w, h, rgba.data_ptr())
     rays = api.ray_counter_read() - r0
     img = rgba.cpu().numpy()
     api.write_tga(os.path.join(out_dir, "output.tga"), img)
     write_png(os.path.join(out_dir, "output.png"), img)
     print("%dx%d, %d frames x 4 spp, %d rays -> output.tga / output.png" % (w, h, frames, rays))
+    if aov:
+        # (the planes of the last frame: means over its samples; a pixel no sample hit is 0 in both)
+        write_png(os.path.join(out_dir, "albedo.png"), to_rgba8(albedo.cpu().numpy()[..., :3]))
+        write_png(os.path.join(out_dir, "normal.png"), to_rgba8(0.5 + 0.5 * normal_depth.cpu().numpy()[..., :3]))
+        print("first-hit planes of frame %d -> albedo.png / normal.png" % (frames - 1))
     api.ShutdownTest()
 
 

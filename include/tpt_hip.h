@@ -156,6 +156,21 @@ TPT_API int tptDrawDeviceBatch(float time, int firstFrame, int nFrames, int scre
  * earlier launches' frames enqueued and the context where the sequence stood at the failing launch's last frame. */
 TPT_API int tptDrawDeviceAnimation(int firstFrame, int nFrames, const float* times, int screenWidth, int screenHeight,
                                    float* deviceTile, float* deviceFrameImages, int64_t* deviceFrameRays, unsigned testFlags);
+/* One frame with the first-hit planes a denoiser takes as guides.  deviceTile is blended exactly as tptDrawDevice(time, frameCount,
+ * w, h, deviceTile, testFlags) blends it, with the same ray count.  deviceAlbedo / deviceNormalDepth: device buffers of h*w*4 floats,
+ * row-major like the tile, either may be NULL (not both); OVERWRITTEN (never blended: the progressive flag applies to the colour only).
+ * For every sample s of pixel (x, y), r_s is the sample's camera ray (its jitter and lens draws from the pixel's RNG stream as the
+ * trace reaches them) and h_s = HitWorld(r_s) its nearest hit (ties to the lowest sphere index).  On a hit: albedo a_s = the material's
+ * albedo, normal n_s = (pos - centre) * invRadius, depth d_s = t, coverage c_s = 1; on a miss all four are 0.  Then
+ *   albedo[px]      = {sum a_s, sum c_s} * (1.0f / spp)      normalDepth[px] = {sum n_s, sum d_s} * (1.0f / spp)
+ * float sums from +0 in sample order.  The scene is that of the last tptUpdate.  Asynchronous on the context's stream: work enqueued
+ * there before the call finishes before the planes are written, work enqueued after it sees them.  Frames traced ahead and
+ * stream-batch planes are dropped (the call does not continue a sequence); the camera and the scene are unchanged.
+ * Refused (non-zero, tptGetLastError, no tile or plane written): deviceTile NULL or both planes NULL, no tptUpdate at this size, w or h
+ * over 8192, row-serial seeds, the forward fold, a kernel variant other than the path-queue kernel, spp over 2047, row sharding or a
+ * communicator, a tile mirror. */
+TPT_API int tptDrawDeviceAov(float time, int frameCount, int screenWidth, int screenHeight, float* deviceTile,
+                             float* deviceAlbedo, float* deviceNormalDepth, unsigned testFlags);
 /* nViews (1..32) cameras of the scene as of the last tptUpdate, traced by ONE launch.  views: nViews x 9 floats
  * {lookFrom xyz, lookAt xyz, vfovDegrees, aperture, focusDist} -- tptSetCamera's arguments; aspect = w / h, vup (0,1,0),
  * aperture forced to 0 in Mitsuba-compare mode, as tptUpdate does.  deviceTiles: nViews consecutive device tiles of h*w*4

@@ -223,6 +223,12 @@ struct Context {
     } views[kMaxSlots];
     char* dViews = nullptr;             // one allocation behind every slot's dev + rays (made by the first views call)
     CameraPOD* hViewsStage = nullptr;   // pinned, behind every slot's stage
+    // tptDrawDeviceAov: the per-path first-hit sums (KernelArgs::aovSums, 2 x f4 per path column of the largest grid seen), made by the
+    // first AOV call.  One buffer serves every AOV launch: each waits for the context stream (evAov), and the context stream waits for
+    // each, so two of them never run at the same time.
+    f4* dAovSums = nullptr;
+    size_t aovSumsBytes = 0;
+    hipEvent_t evAov = nullptr;         // recorded on the context stream by an AOV call; its trace stream waits for it
     long long aheadHits = 0;            // frames that were found traced ahead when their call arrived (tptGetLookaheadHits)
     // per-frame ray counters of the pending launches, one allocation: [kMaxSlots] AHEAD frames (indexed by the frame's sequence number
     // at enqueue), [2][kMaxBatch] ROW_SERIAL batches (two banks, alternating), [kStreamRing][kStreamBatchMax] STREAM batches (a ring)
@@ -362,8 +368,14 @@ struct BatchTable {
     const CameraPOD* cams = nullptr; // [batch] cameras, every frame with the seeds of frameCount: tptTraceViewsKernel
     const f4* centres = nullptr;     // [batch][2] {x, y, z, -} of spheres 1 and 8 (Test.cpp:304-308): tptTraceAnimationKernel
 };
+// The caller's first-hit planes of a single frame (tptDrawDeviceAov): device [h][w] f4 each, either may be null (not both); the launch
+// is tptTraceAovKernel, ordered behind everything enqueued on the context stream so far.
+struct AovPlanes {
+    f4* albedo = nullptr;
+    f4* normalDepth = nullptr;
+};
 int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long long* frameRays, TraceTicket& T, int batch = 1, int rayStride = 0,
-                 const BatchTable* table = nullptr);
+                 const BatchTable* table = nullptr, const AovPlanes* aov = nullptr);
 int enqueueResolve(const TraceTicket& T, float* deviceTile, const unsigned long long* frameRays);
 int syncAllStreams();
 int launchTailHelpers();

@@ -60,6 +60,13 @@ struct KernelArgs {
     // pair per frame of the batch, in device memory; the launch takes tptTraceAnimationKernel, which stages them in LDS and reads the
     // path's frame's centres wherever the exact data of sphere 1 or 8 is used.  Null for every other launch.
     const f4* moveCentres = nullptr;
+    // A single frame with its first-hit planes (tptDrawDeviceAov): per path two f4 of sums {albedo, coverage} {normal, t}, at
+    // aovSums[2 x column], the column numbered like the bounce stack's (workgroup + helperBase, then path); the launch takes
+    // tptTraceAovKernel, which stores the means into aovAlbedo / aovNormalDepth ([nLocalRows][width] f4 each; either may be null).
+    // aovSums is null for every other launch.
+    f4* aovSums = nullptr;
+    f4* aovAlbedo = nullptr;
+    f4* aovNormalDepth = nullptr;
 };
 
 } // namespace tpt

@@ -430,6 +430,9 @@ int tptShutdown(void)
         g.views[k] = Context::ViewSlot();
     }
     (void)hipFree(g.dViews); g.dViews = nullptr;
+    (void)hipFree(g.dAovSums); g.dAovSums = nullptr;
+    g.aovSumsBytes = 0;
+    if (g.evAov) { (void)hipEventDestroy(g.evAov); g.evAov = nullptr; }
     if (g.hViewsStage) (void)hipHostFree(g.hViewsStage);
     g.hViewsStage = nullptr;
     g.inited = false;

@@ -419,13 +419,31 @@ int ensureViewSlots()
     return 0;
 }
 
+// tptDrawDeviceAov: the per-path sums (Context::dAovSums) for the largest grid this frame shape can take, and the ordering event;
+// made by the first AOV call, grown (after a drain) when a later one asks for more.
+int ensureAovSums(const FramePlan& P)
+{
+    if (!g.evAov) HIPCHK(hipEventCreateWithFlags(&g.evAov, kOrderingEvent));
+    const size_t need = 2 * sizeof(f4) * (size_t)maxGridBlocks(P) * (size_t)tptQueuePathsPerBlock();
+    if (need <= g.aovSumsBytes) return 0;
+    int rc = syncAllStreams(); // (an earlier AOV launch may still be reading the old buffer)
+    if (rc) return rc;
+    (void)hipFree(g.dAovSums);
+    g.dAovSums = nullptr;
+    g.aovSumsBytes = 0;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dAovSums), need));
+    g.aovSumsBytes = need;
+    return 0;
+}
+
 // First half of a frame: plan, buffers, trace kernel on the slot's stream.  `frameRays`: where the kernel adds its ray
 // count (the context's counter, or a per-slot one for frames that are traced ahead of their DrawTest call).
 // `table` (tptDrawDeviceViews, tptDrawDeviceAnimation): what differs between the batch's frames (host memory, copied to the slot's
 // table on the frame's stream) -- cameras: `batch` views of frame frameCount, traced by the views kernel; centres: `batch` frames of an
 // animated scene, traced by the animation kernel; neither: the plain kernel.  Every frame counts its rays into the slot's counters.
+// `aov` (tptDrawDeviceAov, a single frame): the caller's first-hit planes, written by the AOV kernel behind the context stream.
 int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long long* frameRays, TraceTicket& T, int batch, int rayStride,
-                 const BatchTable* table)
+                 const BatchTable* table, const AovPlanes* aov)
 {
     const CameraPOD* viewCams = table ? table->cams : nullptr;
     const f4* centres = table ? table->centres : nullptr;
@@ -498,12 +516,21 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
         return refuse("tptDrawDeviceViews: needs the path-queue kernel (per-pixel seeds, recursive fold, two-phase HitSpheres, at most 2047 spp)");
     if (centres && (!P.queued || a.scene.nGroups > 0))
         return refuse("tptDrawDeviceAnimation: one launch per batch needs the path-queue kernel and a flat scene");
+    if (aov && (!P.queued || batch != 1 || table))
+        return refuse("tptDrawDeviceAov: needs the path-queue kernel (per-pixel seeds, recursive fold, two-phase HitSpheres, at most 2047 spp)");
     // a batch is traced by the path-queue kernel (per-pixel seeds) or, in the reference's own seed mode, by the lane-refill
     // kernel: one lane per (frame, row) -- rows AND frames are independent RNG streams there (Test.cpp:280)
     if (batch > 1 && (!(P.queued || P.rowSerial) || w > 8192 || h > 8192 || (long long)a.nLocalRows * w * batch > (1ll << 30)))
         return refuse("tptDrawDeviceBatch: needs the path-queue kernel (per-pixel seeds, recursive fold, two-phase HitSpheres) or row-serial seeds, and a frame of at most 8192 x 8192 (2^30 pixels per batch)");
     sizeGrid(P);
     if ((rc = ensureFrameBuffers(P, w))) return rc;
+    a.aovSums = a.aovAlbedo = a.aovNormalDepth = nullptr;
+    if (aov) {
+        if ((rc = ensureAovSums(P))) return rc;
+        a.aovSums = g.dAovSums;
+        a.aovAlbedo = aov->albedo;
+        a.aovNormalDepth = aov->normalDepth;
+    }
     if (frameRays) a.rayCounter = frameRays;
     a.rayCounterStride = rayStride; // (batched row-serial launch for the host path: one counter per frame of the batch)
     if ((rc = prepareChunkOrder(P))) return rc;
@@ -535,6 +562,12 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
         HIPCHK(hipStreamWaitEvent(ts, g.evResolve[slot], 0)); // colour buffer free again
     }
     if ((rc = enqueueSceneUpload(ts))) return rc; // behind the wait above: nobody reads the set being replaced any more
+    if (aov && ts != g.stream) {
+        // the caller's planes: written after everything enqueued on the context stream before this call (its blend, like the tile's,
+        // follows the launch there); this also keeps the AOV launches, and their one buffer of sums, one after the other
+        HIPCHK(hipEventRecord(g.evAov, g.stream));
+        HIPCHK(hipStreamWaitEvent(ts, g.evAov, 0));
+    }
     if (viewCams || centres) {
         // the launch's table, behind the same wait: the slot's previous launch has read its table; the previous copy out of the
         // slot's pinned staging (an earlier call on this slot) has left the host before the staging is overwritten
@@ -549,7 +582,7 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
     }
     if ((rc = enqueueChunkOrder(P, ts))) return rc;
     if (frameRays && frameRays != g.dRays) HIPCHK(hipMemsetAsync(frameRays, 0, sizeof(unsigned long long) * (size_t)(rayStride > 0 ? batch : 1), ts));
-    const bool helpable = P.queued && pipelined && batch == 1 && !P.rowSerial && !table; // (single frames of the path-queue kernel)
+    const bool helpable = P.queued && pipelined && batch == 1 && !P.rowSerial && !table && !aov; // (single frames of the path-queue kernel)
     a.helperBase = 0;
     a.helperPct = 0;
     a.gen = 0u;
@@ -860,6 +893,35 @@ int tptDrawDeviceAnimation(int firstFrame, int nFrames, const float* times, int 
         }
     }
     return 0;
+}
+
+// One frame blended into the tile exactly as tptDrawDevice blends it (same bits, same ray count), plus the first-hit planes of its
+// samples: albedo and coverage, normal and t, averaged over the samples (tptTraceAovKernel).  The planes are overwritten, not blended, and
+// are ordered on the context stream like the tile.  Like tptDrawDeviceViews, not a continuation of anything: frames traced ahead and
+// stream-batch planes are dropped; the camera and the scene are left as they were.
+int tptDrawDeviceAov(float time, int frameCount, int w, int h, float* deviceTile, float* deviceAlbedo, float* deviceNormalDepth, unsigned testFlags)
+{
+    (void)time; // (the scene state is that of the last tptUpdate, as for tptDrawDevice)
+    if (int rc_ = flushShardDeferred()) return rc_; // (see tptDrawDevice)
+    if (requireInit()) return -1;
+    if (!deviceTile || (!deviceAlbedo && !deviceNormalDepth) || w <= 0 || h <= 0)
+        return fail("tptDrawDeviceAov: bad arguments (deviceTile, at least one of deviceAlbedo / deviceNormalDepth, size)");
+    if (!g.updated || w != g.updatedW || h != g.updatedH) return fail("tptDrawDeviceAov: call tptUpdate (UpdateTest) at this size first");
+    if (w > 8192 || h > 8192) return fail("tptDrawDeviceAov: frames of at most 8192 x 8192");
+    if (g.seedMode == SEED_ROW_SERIAL) return fail("tptDrawDeviceAov: needs per-pixel seeds (tptSetSeedMode(1)); row-serial planes are not supported");
+    if (g.foldMode != FOLD_RECURSIVE) return fail("tptDrawDeviceAov: needs the recursive fold (tptSetFoldMode(0))");
+    if (g.persist != 3 || g.hs != HS_TWO_PHASE) return fail("tptDrawDeviceAov: needs the path-queue kernel (tptSetKernelVariant(0, 3, ..))");
+    if (g.spp > 2047) return fail("tptDrawDeviceAov: at most 2047 samples per pixel (the path-queue kernel)");
+    if (g.numParts > 1 || g.shard.active) return fail("tptDrawDeviceAov: not with row sharding or a communicator (sharded planes are not supported)");
+    if (g.mirror) return fail("tptDrawDeviceAov: not with a tile mirror (tptSetTileMirror)");
+    int rc = g.pending.discard();
+    if (rc) return rc;
+    TraceTicket T;
+    AovPlanes aov;
+    aov.albedo = reinterpret_cast<f4*>(deviceAlbedo);
+    aov.normalDepth = reinterpret_cast<f4*>(deviceNormalDepth);
+    if ((rc = enqueueTrace(frameCount, w, h, testFlags, nullptr, T, 1, 0, nullptr, &aov))) return rc;
+    return enqueueResolve(T, deviceTile, nullptr); // (the kernel added its rays to the running total itself, as tptDrawDevice's plain path)
 }
 
 int tptRayCounterRead(int64_t* outTotalRays)

@@ -1164,7 +1164,10 @@ __device__ __forceinline__ int hitSpheresGroupedDeal(const SceneView& sv, bool g
 // MOVING (with BATCH; tptDrawDeviceAnimation): frame j of the batch is a frame of an animated scene -- spheres 1 and 8 at the centres
 // a.moveCentres[2 j], [2 j + 1] (staged in LDS) in phase 2, the hit normal and the light loop, and candidates of every ray whatever the
 // filter says (tpt_trace.h, movedSphere).  Flat scenes only.  Its own kernel (tptTraceAnimationKernel) for the same reason.
-template <bool LDS_SCENE, bool BATCH, bool VIEWS = false, bool MOVING = false>
+// AOV (single frames; tptDrawDeviceAov): every sample's first hit -- albedo, coverage, normal, t -- is summed in the path's two f4 of
+// a.aovSums (global memory, a column per path like the bounce stack's spill levels) and the means are stored beside the pixel's colour
+// into a.aovAlbedo / a.aovNormalDepth.  Its own kernel (tptTraceAovKernel) for the same reason.
+template <bool LDS_SCENE, bool BATCH, bool VIEWS = false, bool MOVING = false, bool AOV = false>
 __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1174,6 +1177,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     //  0: phase 2 then addresses a sphere with sphere index x 16 and an immediate, like the path records)
     static_assert(BATCH || !VIEWS, "views are frames of a batched launch");
     static_assert((BATCH || !MOVING) && !(VIEWS && MOVING), "animation frames are frames of a batched launch of their own");
+    static_assert(!AOV || !BATCH, "first-hit planes are made by single-frame launches");
     constexpr int kPaths = (LDS_SCENE ? TPT_Q_PATHS : TPT_Q_PATHS_GROUPED) - (VIEWS ? TPT_Q_VIEW_PATHS : 0) -
                            (MOVING ? TPT_Q_ANIM_PATHS : 0); // paths this workgroup owns
     constexpr int kOffSt = LDS_SCENE ? TPT_Q_SPH_FIXED : 0;
@@ -1395,6 +1399,9 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
         stack.l0 = (LdsF4Ptr)(st + 3 * kPaths + p); // level 0 in the path record
         stack.spill = a.stackBuf + ((size_t)(blockIdx.x + (unsigned)a.helperBase) * TPT_Q_PATHS + p);
         stack.stride = a.stackStride;
+        // AOV: this path's sums {albedo, coverage} {normal, t} over the first hits of its pixel's samples so far (the address is made
+        // where it is used, not held across the iteration)
+        auto aovSum = [&]() { return a.aovSums + 2 * ((size_t)(blockIdx.x + (unsigned)a.helperBase) * TPT_Q_PATHS + p); };
         QLambert lam;
         lam.sdir = lam.nl = lam.albedo = lam.lightE = mk3(0, 0, 0);
         lam.cosAMax = 0.0f;
@@ -1468,6 +1475,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                 const uint32_t where = BATCH ? ((uint32_t)px | ((uint32_t)py << 13) | ((uint32_t)laneFrame << 26))
                                              : ((uint32_t)px | ((uint32_t)py << 16));
                 colSum[p] = mk4(0.0f, 0.0f, 0.0f, u2f(where));
+                if (AOV) aovSum()[0] = aovSum()[1] = mk4(0.0f, 0.0f, 0.0f, 0.0f);
                 if (MOVING) movedAt = 2 * laneFrame;
                 if (VIEWS)
                     qCameraView(ldsCams[laneFrame], *ldsFc, px, py, rng, ro, rd);
@@ -1507,6 +1515,12 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                 } else {
                     const f3 out = col * fc.invSpp; // Test.cpp:291
                     a.frameColour[plane + globalRowToLocal(a, py) * fc.width + px] = mk4(out.x, out.y, out.z, 0.0f); // one 16-B store per pixel
+                    if (AOV) { // the means of the first-hit sums, in the form of Test.cpp:291; one 16-B store per plane (either may be absent)
+                        const size_t at = (size_t)globalRowToLocal(a, py) * fc.width + px;
+                        const f4 s0 = aovSum()[0], s1 = aovSum()[1];
+                        if (a.aovAlbedo) a.aovAlbedo[at] = mk4(s0.x * fc.invSpp, s0.y * fc.invSpp, s0.z * fc.invSpp, s0.w * fc.invSpp);
+                        if (a.aovNormalDepth) a.aovNormalDepth[at] = mk4(s1.x * fc.invSpp, s1.y * fc.invSpp, s1.z * fc.invSpp, s1.w * fc.invSpp);
+                    }
                     toFree = true;
                 }
             }
@@ -1623,6 +1637,16 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                     cls = type == MAT_LAMBERT ? Q_LAMBERT : type == MAT_METAL ? Q_METAL : type == MAT_DIELECTRIC ? Q_DIEL : Q_END;
                 }
                 if (hitId >= 0) ro = ro + rd * hitT; // the hit position (Maths.cpp:195), all the class code needs of {orig, t}
+                if (AOV && depth == 0 && hitId >= 0) {
+                    // a camera ray's nearest hit (every bounce ray has depth >= 1 here): add the sample's albedo, coverage, normal (the
+                    // class code's qNormal, Maths.cpp:196-197) and t.  A miss adds zeros: nothing to do.
+                    const f3 nrm = qNormal(sv, hitId, ro);
+                    const f4 m0 = sv.mats[hitId * 3];
+                    f4* sum = aovSum();
+                    const f4 s0 = sum[0], s1 = sum[1];
+                    sum[0] = mk4(s0.x + m0.x, s0.y + m0.y, s0.z + m0.z, s0.w + 1.0f);
+                    sum[1] = mk4(s1.x + nrm.x, s1.y + nrm.y, s1.z + nrm.z, s1.w + hitT);
+                }
                 recId = hitId;
             }
         } else if (ray) {
@@ -1768,6 +1792,20 @@ __global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute
 tptTraceAnimationKernel<false>(const KernelArgs a)
 {
     traceQueueBody<false, true, false, true>(a);
+}
+// A single frame with its first-hit planes (tptDrawDeviceAov): the single-frame kernel plus the per-path sums.  A kernel of its own for
+// the same reason; <false>: grouped scenes and flat scenes whose arrays stay in global memory.
+template <bool LDS_SCENE>
+__global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute__((amdgpu_num_vgpr(TPT_Q_MAX_VGPR)))
+tptTraceAovKernel(const KernelArgs a)
+{
+    traceQueueBody<LDS_SCENE, false, false, false, true>(a);
+}
+template <>
+__global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute__((amdgpu_num_vgpr(TPT_Q_MAX_VGPR_GROUPED)))
+tptTraceAovKernel<false>(const KernelArgs a)
+{
+    traceQueueBody<false, false, false, false, true>(a);
 }
 
 #if defined(TPT_TEST_HOOKS)
@@ -2045,6 +2083,7 @@ size_t tptQueueLdsBytes(const KernelArgs& a, bool ldsScene)
     const int nPad = a.scene.nPairs * 2;
     const bool views = a.viewCams != nullptr; // (tptTraceViewsKernel: the cameras in LDS, TPT_Q_VIEW_PATHS path records fewer)
     const bool moving = a.moveCentres != nullptr; // (tptTraceAnimationKernel: the centres in LDS, TPT_Q_ANIM_PATHS path records fewer)
+    // (tptTraceAovKernel, a.aovSums: the LDS of its single-frame twin -- its sums live in global memory)
     size_t bytes = 0;
     if (ldsScene) bytes += TPT_Q_SPH_FIXED + ((size_t)nPad * 16 <= TPT_Q_SPH_FIXED ? 0 : (size_t)nPad * 16) + (((size_t)nPad * 4 + 15) & ~(size_t)15) + (size_t)a.scene.nSpheres * 48;
     bytes += (size_t)a.scene.nLights * 32;
@@ -2085,11 +2124,26 @@ static hipError_t launchTraceAnimation(const KernelArgs& a, int blocks, size_t l
     hipLaunchKernelGGL(k, dim3(blocks), dim3(TPT_Q_T), lds, stream, a);
     return hipSuccess;
 }
+template <bool LDS_SCENE>
+static hipError_t launchTraceAov(const KernelArgs& a, int blocks, size_t lds, hipStream_t stream)
+{
+    auto k = tptTraceAovKernel<LDS_SCENE>;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(TPT_Q_T), lds, stream, a);
+    return hipSuccess;
+}
 hipError_t tptLaunchTraceQueue(const KernelArgs& a, bool ldsScene, int blocks, size_t lds, hipStream_t stream)
 {
     if (a.viewCams) { // (tptDrawDeviceViews: 1 .. TPT_Q_VIEWS_MAX views, the frames of the batch)
         if (a.batchFrames < 1 || a.batchFrames > TPT_Q_VIEWS_MAX) return hipErrorInvalidValue;
         hipError_t e = ldsScene ? launchTraceViews<true>(a, blocks, lds, stream) : launchTraceViews<false>(a, blocks, lds, stream);
+        if (e != hipSuccess) return e;
+        return hipGetLastError();
+    }
+    if (a.aovSums) { // (tptDrawDeviceAov: a single frame)
+        if (a.batchFrames != 1 || a.viewCams || a.moveCentres) return hipErrorInvalidValue;
+        hipError_t e = ldsScene ? launchTraceAov<true>(a, blocks, lds, stream) : launchTraceAov<false>(a, blocks, lds, stream);
         if (e != hipSuccess) return e;
         return hipGetLastError();
     }
