@@ -1,9 +1,10 @@
 """Render the built-in scene on the GPU and write it as TGA (the reference's Cs/Program.cs:33-59 format) and PNG.
 
-    python examples/render_image.py [--aov] [width height frames [out_dir]]
+    python examples/render_image.py [--aov] [--denoise] [width height frames [out_dir]]
 
 --aov: the last frame is drawn with tptDrawDeviceAov, and its first-hit planes are written too: albedo.png (the albedo) and
 normal.png (0.5 + 0.5 n) -- the guide images a denoiser takes beside the colour.
+--denoise: implies --aov, and also writes denoised.png: the final tile through tptDenoiseDevice, guided by those planes (api defaults).
 """
 import os
 import struct
@@ -40,8 +41,9 @@ def to_rgba8(rgb):
 
 
 def main():
-    aov = "--aov" in sys.argv[1:]
-    args = [a for a in sys.argv[1:] if a != "--aov"]
+    denoise = "--denoise" in sys.argv[1:]
+    aov = denoise or "--aov" in sys.argv[1:]
+    args = [a for a in sys.argv[1:] if a not in ("--aov", "--denoise")]
     w = int(args[0]) if len(args) > 0 else 1280
     h = int(args[1]) if len(args) > 1 else 720
     frames = int(args[2]) if len(args) > 2 else 64
@@ -70,6 +72,12 @@ def main():
         write_png(os.path.join(out_dir, "albedo.png"), to_rgba8(albedo.cpu().numpy()[..., :3]))
         write_png(os.path.join(out_dir, "normal.png"), to_rgba8(0.5 + 0.5 * normal_depth.cpu().numpy()[..., :3]))
         print("first-hit planes of frame %d -> albedo.png / normal.png" % (frames - 1))
+    if denoise:
+        out = torch.empty_like(tile)
+        api.denoise_device(w, h, tile.data_ptr(), out.data_ptr(), albedo_ptr=albedo.data_ptr(), normal_depth_ptr=normal_depth.data_ptr())
+        api.display_rgba8(out.data_ptr(), w, h, rgba.data_ptr())
+        write_png(os.path.join(out_dir, "denoised.png"), rgba.cpu().numpy())
+        print("the tile through tptDenoiseDevice (%s) -> denoised.png" % ", ".join("%s %g" % kv for kv in api.DENOISE_DEFAULTS.items()))
     api.ShutdownTest()
 
 

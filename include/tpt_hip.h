@@ -171,6 +171,26 @@ TPT_API int tptDrawDeviceAnimation(int firstFrame, int nFrames, const float* tim
  * communicator, a tile mirror. */
 TPT_API int tptDrawDeviceAov(float time, int frameCount, int screenWidth, int screenHeight, float* deviceTile,
                              float* deviceAlbedo, float* deviceNormalDepth, unsigned testFlags);
+/* An edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010) of a tile, guided by the planes of tptDrawDeviceAov.  All five
+ * buffers are device buffers of h*w*4 floats, row-major like the tile; deviceAlbedo and deviceNormalDepth may be NULL.  Binary32, in
+ * the order written, no FMA, correctly rounded division, sums from +0:
+ *   hk = {1/16, 1/4, 3/8, 1/4, 1/16};  ic0 = sigmaColour > 0 ? 1 / sigmaColour^2 : 0  (in, id likewise)
+ *   cur_0 = DEMODULATE ? (albedo.c > 0 ? colour.c / albedo.c : colour.c) : colour           (per channel r, g, b)
+ *   iteration i (0 .. iterations-1), step s = 1 << i, ic = ic0 * 4^i; for each pixel p, the 5 x 5 taps q = p + (k - 2) s (ky outer)
+ *   that lie inside the image (no clamping):
+ *     den = 1 + ((dr*dr + dg*dg) + db*db) * ic          (d = cur_i[q] - cur_i[p])
+ *     with normalDepth: den *= 1 + ((dnx*dnx + dny*dny) + dnz*dnz) * in;  den *= 1 + (dd*dd) * id    (dd = nd[q].w - nd[p].w)
+ *     w = (hk[ky] * hk[kx]) / den;  cur_{i+1}[p].rgb = sum(w cur_i[q].rgb) / sum(w)
+ *   out.rgb = DEMODULATE ? (albedo.c > 0 ? cur_N.c * albedo.c : cur_N.c) : cur_N;  out.a = colour.a
+ * Asynchronous on the context's stream (ordered like tptDisplayRGBA8); needs tptInitialize only; leaves every other state alone
+ * (frames traced ahead and stream batches are kept).  The inputs are never written.  Refused (non-zero, tptGetLastError, nothing
+ * enqueued, deviceOut untouched): no context; w or h outside 1..8192; deviceColour or deviceOut NULL; deviceOut overlapping an input;
+ * iterations outside 1..8; a sigma negative, NaN, infinite, inside (0, 1e-6) or above 1e6; sigmaNormal or sigmaDepth non-zero without
+ * deviceNormalDepth; TPT_DENOISE_DEMODULATE without deviceAlbedo; an unknown flag bit. */
+enum { TPT_DENOISE_DEMODULATE = 1 << 0 };
+TPT_API int tptDenoiseDevice(int screenWidth, int screenHeight, const float* deviceColour, const float* deviceAlbedo,
+                             const float* deviceNormalDepth, float* deviceOut, int iterations, float sigmaColour,
+                             float sigmaNormal, float sigmaDepth, unsigned denoiseFlags);
 /* nViews (1..32) cameras of the scene as of the last tptUpdate, traced by ONE launch.  views: nViews x 9 floats
  * {lookFrom xyz, lookAt xyz, vfovDegrees, aperture, focusDist} -- tptSetCamera's arguments; aspect = w / h, vup (0,1,0),
  * aperture forced to 0 in Mitsuba-compare mode, as tptUpdate does.  deviceTiles: nViews consecutive device tiles of h*w*4

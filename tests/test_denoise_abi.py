@@ -1,0 +1,211 @@
+"""tptDenoiseDevice without a GPU: the declaration, the binding and the export of the entry point; the binding's argument checks; the
+gfx950 code of the a-trous kernels in the shipped library; and every refusal of the ABI, driven through the host runtime compiled
+against tests/hostemu (a refused call returns before anything is enqueued, so no kernel is emulated)."""
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import pytest
+
+from oracle_lib import ROOT
+
+LLVM = "/opt/rocm/lib/llvm/bin"
+BUNDLER = os.path.join(LLVM, "clang-offload-bundler")
+OBJDUMP = os.path.join(LLVM, "llvm-objdump")
+READELF = os.path.join(LLVM, "llvm-readelf")
+TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
+DENOISE = "_ZN3tpt16tptDenoiseKernelILb%dELb%dELb%dEEEvPKNS_2f4ES3_S3_PS1_iiifffi"  # <FIRST, LAST, GUIDE>
+HAVE_TOOLS = all(os.path.exists(p) for p in (BUNDLER, OBJDUMP, READELF)) and shutil.which("objcopy") is not None
+
+
+def test_header_declares_the_entry_point():
+    text = open(os.path.join(ROOT, "include", "tpt_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    decl = re.search(r"TPT_API\s+int\s+tptDenoiseDevice\s*\(([^)]*)\)\s*;", text)
+    assert decl, "tptDenoiseDevice is not declared in include/tpt_hip.h"
+    params = [" ".join(p.split()) for p in decl.group(1).split(",")]
+    assert params == ["int screenWidth", "int screenHeight", "const float* deviceColour", "const float* deviceAlbedo",
+                      "const float* deviceNormalDepth", "float* deviceOut", "int iterations", "float sigmaColour", "float sigmaNormal",
+                      "float sigmaDepth", "unsigned denoiseFlags"], params
+    assert re.search(r"enum\s*\{\s*TPT_DENOISE_DEMODULATE\s*=\s*1\s*<<\s*0\s*\}\s*;", text)
+
+
+def test_binding_and_export():
+    from toypathtracer_amd import api
+    assert "tptDenoiseDevice" in api.C_ABI_SYMBOLS
+    assert callable(api.denoise_device) and api.DENOISE_DEMODULATE == 1
+    lib = api.load_library()
+    assert hasattr(lib, "tptDenoiseDevice")
+    out = subprocess.check_output(["nm", "-D", "--defined-only", api.library_path()]).decode()
+    assert re.search(r"\bT tptDenoiseDevice\b", out)
+
+
+@pytest.mark.parametrize("args", [
+    dict(w=0), dict(h=-3), dict(w=8.0), dict(h=True), dict(iterations=0), dict(iterations=2.0), dict(iterations=True),
+    dict(colour=0), dict(colour=None), dict(colour=1.5), dict(out=None), dict(out=0), dict(out="x"),
+    dict(albedo=-16), dict(albedo=2.0), dict(nd="x"), dict(nd=True),
+    dict(sigma_colour=-1.0), dict(sigma_normal=float("nan")), dict(sigma_depth=float("inf")), dict(sigma_colour="1"),
+    dict(albedo=None, demodulate=True),
+], ids=lambda a: ",".join("%s=%r" % kv for kv in a.items()))
+def test_binding_checks_arguments_before_the_library(monkeypatch, args):
+    """every bad argument raises ValueError in Python: the library is never reached (load_library would fail the test)"""
+    from toypathtracer_amd import api
+
+    def no_library():
+        raise AssertionError("the library was called")
+
+    monkeypatch.setattr(api, "load_library", no_library)
+    a = dict(w=16, h=8, colour=4096, out=8192, albedo=16384, nd=32768, iterations=5, sigma_colour=1.0, sigma_normal=0.2,
+             sigma_depth=0.5, demodulate=None)
+    a.update(args)
+    with pytest.raises(ValueError):
+        api.denoise_device(a["w"], a["h"], a["colour"], a["out"], albedo_ptr=a["albedo"], normal_depth_ptr=a["nd"],
+                           iterations=a["iterations"], sigma_colour=a["sigma_colour"], sigma_normal=a["sigma_normal"],
+                           sigma_depth=a["sigma_depth"], demodulate=a["demodulate"])
+
+
+def test_binding_passes_what_it_means(monkeypatch):
+    """demodulate=None follows the albedo plane; the sigmas of a guide that is not given go to the library as 0"""
+    from toypathtracer_amd import api
+    calls = []
+
+    class Lib:
+        def tptDenoiseDevice(self, *a):
+            calls.append(a)
+            return 0
+
+    monkeypatch.setattr(api, "load_library", lambda: Lib())
+    api.denoise_device(16, 8, 4096, 8192, albedo_ptr=16384, normal_depth_ptr=32768, iterations=3, sigma_colour=0.5)
+    api.denoise_device(16, 8, 4096, 8192, iterations=1)
+    api.denoise_device(16, 8, 4096, 8192, albedo_ptr=16384, demodulate=False)
+    (a0, a1, a2) = calls
+    assert a0[6] == 3 and a0[7] == 0.5 and a0[8] > 0 and a0[9] > 0 and a0[10] == 1
+    assert a1[3] is None and a1[4] is None and a1[8] == 0.0 and a1[9] == 0.0 and a1[10] == 0
+    assert a2[3] is not None and a2[10] == 0
+
+
+@pytest.fixture(scope="module")
+def code_object(tmp_path_factory):
+    if not HAVE_TOOLS:
+        pytest.skip("ROCm LLVM tools not installed")
+    from toypathtracer_amd import api
+    d = tmp_path_factory.mktemp("isa_denoise")
+    fat, co = str(d / "fat.bin"), str(d / "kernels.co")
+    subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", api.library_path(), fat])
+    subprocess.check_call([BUNDLER, "--unbundle", "--type=o", "--targets=" + TARGET, "--input=" + fat, "--output=" + co])
+    dis = subprocess.check_output([OBJDUMP, "-d", co]).decode()
+    notes = subprocess.check_output([READELF, "--notes", co]).decode()
+    bodies = {}
+    for m in re.finditer(r"^[0-9a-f]+ <(\w+)>:\n(.*?)(?=^[0-9a-f]+ <\w+>:|\Z)", dis, flags=re.S | re.M):
+        bodies[m.group(1)] = [ln.split("//")[0].split() for ln in m.group(2).splitlines() if ln.startswith("\t")]
+    meta = {}
+    for blk in re.split(r"\n\s+- (?=\.agpr_count)", notes)[1:]:
+        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
+        meta[name] = {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*$", blk, flags=re.M)}
+    return bodies, meta
+
+
+def count(body, pattern):
+    rx = re.compile(pattern)
+    return sum(1 for ins in body if ins and rx.match(ins[0]))
+
+
+@pytest.mark.parametrize("first,last,guide", [(f, l, g) for f in (1, 0) for l in (1, 0) for g in (1, 0)],
+                         ids=lambda v: str(v))
+def test_denoise_kernels_in_the_code_object(code_object, first, last, guide):
+    bodies, meta = code_object
+    name = DENOISE % (first, last, guide)
+    assert name in meta and name in bodies, "the a-trous kernel is missing from the shipped code object"
+    assert "Test" not in name
+    body, m = bodies[name], meta[name]
+    assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0, m
+    assert count(body, r"scratch_") == 0
+    assert count(body, r"flat_") == 0, "a FLAT instruction: a global pointer lost its address space"
+    assert m["group_segment_fixed_size"] == 0 and m["agpr_count"] == 0
+    assert m["max_flat_workgroup_size"] == 256 and m["wavefront_size"] == 64
+    # 25 taps, each one coalesced load of the colour's rgb (+ the albedo when the first iteration demodulates, + the guide's 16 B)
+    assert count(body, r"global_load_dwordx[34]") >= 25 * (1 + guide)
+    assert count(body, r"global_store_dwordx4") == 1
+    # the weights' division: the 6-instruction form (v_rcp_f32) on every tap, hipcc's expansion only behind its range check
+    assert count(body, r"v_rcp_f32") >= 25
+
+
+def test_no_kernel_name_contains_test(code_object):
+    bodies, meta = code_object
+    names = [n for n in meta if "Denoise" in n]
+    assert len(names) == 8 and not [n for n in names if "Test" in n], names
+
+
+REFUSALS = r'''
+import ctypes as C, sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+from toypathtracer_amd import api as tpt
+lib = tpt.load_library()
+lib.tptDenoiseDevice.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float,
+                                 C.c_float, C.c_uint]
+w, h = 16, 8
+col = np.full((h, w, 4), 0.5, np.float32)
+alb = np.full((h, w, 4), 0.25, np.float32)
+nd = np.full((h, w, 4), 3.0, np.float32)
+out = np.full((h, w, 4), np.nan, np.float32)
+big = np.zeros((2 * h, w, 4), np.float32)  # (room for an output that overlaps the tail of an input)
+def call(ww=w, hh=h, c=col, a=alb, n=nd, o=out, it=3, sc=1.0, sn=0.2, sd=0.5, fl=1):
+    ptr = lambda x: None if x is None else (x if isinstance(x, int) else x.ctypes.data)
+    return lib.tptDenoiseDevice(ww, hh, ptr(c), ptr(a), ptr(n), ptr(o), it, sc, sn, sd, fl)
+def refused(what, expect="tptDenoiseDevice", **kw):
+    rc = call(**kw)
+    msg = lib.tptGetLastError().decode()
+    assert rc != 0 and expect in msg, (what, rc, msg)
+    print("refused:", what, "--", msg)
+refused("no context", expect="not initialised")
+tpt.InitializeTest()
+for ww, hh in ((0, h), (w, 0), (-1, h), (8193, 1), (1, 8193)):
+    refused("size %dx%d" % (ww, hh), ww=ww, hh=hh)
+refused("colour NULL", c=None)
+refused("out NULL", o=None)
+refused("out is the colour", o=col)
+refused("out is the albedo", o=alb)
+refused("out is the normal/depth plane", o=nd)
+refused("out overlaps the colour's tail", c=big, o=big.ctypes.data + 16 * (w * h - 1))
+refused("colour overlaps out's tail", c=big.ctypes.data + 16 * (w * h - 1), o=big, a=None, n=None, sn=0.0, sd=0.0, fl=0)
+for it in (0, -1, 9):
+    refused("iterations %d" % it, it=it)
+for name in ("sc", "sn", "sd"):
+    for v in (-1.0, -1e-7, float("nan"), float("inf"), float("-inf"), 1e-7, 5e-7, 1.000001e6, 1e30):
+        refused("%s = %r" % (name, v), **{name: v})
+refused("sigmaNormal without the plane", n=None, sd=0.0)
+refused("sigmaDepth without the plane", n=None, sn=0.0)
+refused("demodulate without albedo", a=None)
+for fl in (2, 4, 0x80000000, 3):
+    refused("flags %#x" % fl, fl=fl)
+launches = C.CDLL(tpt.library_path()).hostemuDenoiseLaunches
+assert launches() == 0, "a refused call reached the launcher"
+# accepted at the edges: each reaches the launcher (tests/hostemu_denoise.cpp counts them and runs nothing, so out stays NaN)
+for kw in (dict(ww=8192, hh=1, c=np.zeros((1, 8192, 4), np.float32), o=np.zeros((1, 8192, 4), np.float32), a=None, n=None, sn=0.0, sd=0.0, fl=0),
+           dict(it=1), dict(it=8), dict(sc=0.0, sn=0.0, sd=0.0), dict(sc=1e-6, sn=1e6, sd=1e-6), dict(a=None, fl=0), dict(n=None, sn=0.0, sd=0.0),
+           dict(sc=-0.0)):
+    assert call(**kw) == 0, (kw, lib.tptGetLastError().decode())
+    print("accepted:", sorted(kw))
+assert launches() == 8
+tpt.synchronize()
+assert np.isnan(out).all(), "a refused call wrote deviceOut"
+assert (col == 0.5).all() and (alb == 0.25).all() and (nd == 3.0).all()
+tpt.ShutdownTest()
+print("ok")
+'''
+
+
+def test_refusals_through_the_host_runtime(tmp_path):
+    from test_host_logic import build
+    # (the host runtime with the counting launcher of tests/hostemu_denoise.cpp beside the emulated kernels)
+    lib = build("libtpt_hostemu_denoise.so", [os.path.join(ROOT, "tests", "hostemu_denoise.cpp")])
+    env = dict(os.environ, TPT_LIB=lib, HOSTEMU_POLICY="lazy")
+    env.pop("TPT_LIB_DIR", None)
+    p = subprocess.run([sys.executable, "-c", REFUSALS, ROOT], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+    out = p.stdout.decode()
+    assert p.returncode == 0 and out.rstrip().endswith("ok"), out[-3000:]
+    assert out.count("refused:") == 1 + 5 + 2 + 3 + 2 + 3 + 27 + 3 + 4, out
+    assert out.count("accepted:") == 8, out

@@ -39,7 +39,7 @@ C_ABI_SYMBOLS = [
     "tptSetSamplesPerPixel", "tptSetConfig", "tptSetSeedMode", "tptSetFoldMode", "tptSetScene", "tptSetCamera", "tptSetStream",
     "tptSetRowShard", "tptLocalRowCount", "tptLocalRowToGlobal", "tptDrawDevice", "tptRayCounterRead", "tptSetRayCounter", "tptSetFrameOverlap", "tptDisplayRGBA8", "tptKernelTimingBegin", "tptKernelTimingEnd",
     "tptSynchronize", "tptTimerBegin", "tptTimerEnd", "tptSetKernelVariant",
-    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
+    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
 ]
 # include/tpt_test_hooks.h: exported by the second build (libtoypathtracer_hip_hooks.so) only
 HOOK_SYMBOLS = ["tptTestMath", "tptTestMathExhaustive", "tptTestHitSpheres", "tptTestMatrixFilter", "tptTestGroupFilter", "tptTestSetDealCapacities", "tptDebugStats", "tptDebugChunkOrder"]
@@ -78,7 +78,7 @@ def _bind(path, hooks):
         "tptSetRayCounter": [p], "tptSetTileMirror": [p, p], "tptSetFrameOverlap": [i], "tptDisplayRGBA8": [p, i, i, p], "tptKernelTimingBegin": [i],
         "tptKernelTimingEnd": [C.POINTER(f), C.POINTER(i)],
         "tptSynchronize": [], "tptTimerBegin": [], "tptTimerEnd": [C.POINTER(f)], "tptSetKernelVariant": [i, i, i],
-        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
+        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
     }
     if hooks:
         sigs.update({"tptDebugStats": [p, i], "tptDebugChunkOrder": [p, p, i], "tptTestMath": [i, p, p, p, i], "tptTestMathExhaustive": [i, u, u, p, p],
@@ -444,6 +444,39 @@ def draw_device_aov(time, frame, w, h, tile_ptr, flags, albedo_ptr=None, normal_
         raise ValueError("albedo_ptr, normal_depth_ptr: at least one plane is required")
     _chk(load_library().tptDrawDeviceAov(time, frame, w, h, C.c_void_p(tile_ptr), C.c_void_p(albedo_ptr) if albedo_ptr else None,
                                          C.c_void_p(normal_depth_ptr) if normal_depth_ptr else None, flags), "tptDrawDeviceAov")
+
+
+DENOISE_DEMODULATE = 1  # include/tpt_hip.h: TPT_DENOISE_DEMODULATE
+# denoise_device's defaults, chosen by tools/denoise_rate.py's sweep
+DENOISE_DEFAULTS = dict(iterations=5, sigma_colour=32.0, sigma_normal=0.03, sigma_depth=0.5)
+
+
+def denoise_device(w, h, colour_ptr, out_ptr, albedo_ptr=None, normal_depth_ptr=None, iterations=DENOISE_DEFAULTS["iterations"],
+                   sigma_colour=DENOISE_DEFAULTS["sigma_colour"], sigma_normal=DENOISE_DEFAULTS["sigma_normal"],
+                   sigma_depth=DENOISE_DEFAULTS["sigma_depth"], demodulate=None):
+    """tptDenoiseDevice: the edge-avoiding a-trous filter of the tile at colour_ptr into out_ptr (device buffers of h*w*4 floats), guided
+    by draw_device_aov's planes (None = not given).  A guide's sigma is ignored (passed as 0) when its plane is not given; demodulate=None
+    means "on if an albedo plane is given".  The default sigmas are DESIGN.md's measured choice.  Ordered on the context's stream."""
+    for name, v in (("w", w), ("h", h), ("iterations", iterations)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v <= 0:
+            raise ValueError("%s: a positive int expected, got %r" % (name, v))
+    for name, v in (("colour_ptr", colour_ptr), ("out_ptr", out_ptr), ("albedo_ptr", albedo_ptr), ("normal_depth_ptr", normal_depth_ptr)):
+        if v is not None and (not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 0):
+            raise ValueError("%s: a device pointer (int) or None expected, got %r" % (name, v))
+    if not colour_ptr or not out_ptr:
+        raise ValueError("colour_ptr, out_ptr: device buffers are required")
+    for name, v in (("sigma_colour", sigma_colour), ("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth)):
+        if not isinstance(v, (int, float, np.integer, np.floating)) or isinstance(v, bool) or not v >= 0 or v == float("inf"):
+            raise ValueError("%s: a finite float >= 0 expected, got %r" % (name, v))
+    if demodulate is None:
+        demodulate = bool(albedo_ptr)
+    if demodulate and not albedo_ptr:
+        raise ValueError("demodulate: needs albedo_ptr")
+    if not normal_depth_ptr:
+        sigma_normal = sigma_depth = 0.0
+    _chk(load_library().tptDenoiseDevice(w, h, C.c_void_p(colour_ptr), C.c_void_p(albedo_ptr) if albedo_ptr else None,
+                                         C.c_void_p(normal_depth_ptr) if normal_depth_ptr else None, C.c_void_p(out_ptr), iterations,
+                                         sigma_colour, sigma_normal, sigma_depth, DENOISE_DEMODULATE if demodulate else 0), "tptDenoiseDevice")
 
 
 def sharded_finish():

@@ -229,6 +229,11 @@ struct Context {
     f4* dAovSums = nullptr;
     size_t aovSumsBytes = 0;
     hipEvent_t evAov = nullptr;         // recorded on the context stream by an AOV call; its trace stream waits for it
+    // tptDenoiseDevice: the plane the a-trous iterations ping-pong through beside the caller's output ([h][w] f4 of the largest frame
+    // denoised so far), made by the first call that iterates more than once, grown when a later one needs more, freed by tptShutdown.
+    // Only the context stream uses it, so stream order alone keeps one call's iterations from another's.
+    f4* dDenoise = nullptr;
+    size_t denoiseBytes = 0;
     long long aheadHits = 0;            // frames that were found traced ahead when their call arrived (tptGetLookaheadHits)
     // per-frame ray counters of the pending launches, one allocation: [kMaxSlots] AHEAD frames (indexed by the frame's sequence number
     // at enqueue), [2][kMaxBatch] ROW_SERIAL batches (two banks, alternating), [kStreamRing][kStreamBatchMax] STREAM batches (a ring)

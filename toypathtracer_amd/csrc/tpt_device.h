@@ -82,6 +82,13 @@ int tptQueueMatrixFilter();
 int tptQueueGroupMatrixBounds(); // 1: this build carries the groups' bounds on the matrix cores (hooks build only)
 int tptQueueThreadsPerBlock();
 hipError_t tptLaunchDisplay(const float* tile, unsigned char* rgba, int width, int height, hipStream_t stream);
+// tptDenoiseDevice: `iterations` launches of the a-trous kernel, ping-ponging between out and scratch (both [h][w] f4, neither
+// overlapping an input) so that the last one writes out; albedo / normalDepth may be null (ic, in, id: the first iteration's
+// inverse squared sigmas).  Weak: the host runtime is also linked against the CPU suite's emulated kernels, which have no
+// a-trous kernel; tptDenoiseDevice fails there instead of the library failing to load.
+__attribute__((weak)) hipError_t tptLaunchDenoise(const float* colour, const float* albedo, const float* normalDepth, float* out,
+                                                  float* scratch, int width, int height, int iterations, float ic, float in, float id,
+                                                  bool demodulate, hipStream_t stream);
 hipError_t tptLaunchAssemble(const float* gathered, float* image, int width, int height, int stripeRows, int nRanks, int padRows, hipStream_t stream);
 hipError_t tptLaunchQueueProbe(unsigned long long ticks, hipStream_t stream);
 hipError_t tptLaunchChunkOrder(const unsigned* cost, unsigned* snap, unsigned* order, int numChunks, hipStream_t stream);

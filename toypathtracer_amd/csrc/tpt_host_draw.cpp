@@ -288,4 +288,44 @@ int tptDisplayRGBA8(const float* deviceTile, int w, int h, unsigned char* device
     return 0;
 }
 
+// The a-trous denoiser (include/tpt_hip.h states the filter): a post-process on the context stream like the display conversion above.
+// It touches no trace state -- frames traced ahead, stream batches, scene and camera stay as they are -- only the context's scratch
+// plane, which the iterations ping-pong through beside deviceOut.
+int tptDenoiseDevice(int w, int h, const float* deviceColour, const float* deviceAlbedo, const float* deviceNormalDepth, float* deviceOut,
+                     int iterations, float sigmaColour, float sigmaNormal, float sigmaDepth, unsigned denoiseFlags)
+{
+    if (requireInit()) return -1;
+    if (w < 1 || w > 8192 || h < 1 || h > 8192) return fail("tptDenoiseDevice: w and h must lie in 1..8192");
+    if (!deviceColour || !deviceOut) return fail("tptDenoiseDevice: deviceColour and deviceOut are required");
+    const uintptr_t bytes = (uintptr_t)w * (uintptr_t)h * 16u;
+    const uintptr_t o = reinterpret_cast<uintptr_t>(deviceOut);
+    for (const float* in : {deviceColour, deviceAlbedo, deviceNormalDepth}) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(in);
+        if (in && o < a + bytes && a < o + bytes) return fail("tptDenoiseDevice: deviceOut overlaps an input");
+    }
+    if (iterations < 1 || iterations > 8) return fail("tptDenoiseDevice: iterations must lie in 1..8");
+    for (float s : {sigmaColour, sigmaNormal, sigmaDepth}) // (NaN fails both comparisons)
+        if (!(s == 0.0f || (s >= 1e-6f && s <= 1e6f)))
+            return fail("tptDenoiseDevice: every sigma must be 0 or lie in [1e-6, 1e6]");
+    if ((sigmaNormal != 0.0f || sigmaDepth != 0.0f) && !deviceNormalDepth)
+        return fail("tptDenoiseDevice: sigmaNormal and sigmaDepth need deviceNormalDepth");
+    if (denoiseFlags & ~(unsigned)TPT_DENOISE_DEMODULATE) return fail("tptDenoiseDevice: unknown flag bits");
+    const bool demodulate = (denoiseFlags & TPT_DENOISE_DEMODULATE) != 0;
+    if (demodulate && !deviceAlbedo) return fail("tptDenoiseDevice: TPT_DENOISE_DEMODULATE needs deviceAlbedo");
+    if (!tptLaunchDenoise) return fail("tptDenoiseDevice: this build has no a-trous kernel");
+    if (iterations > 1 && bytes > g.denoiseBytes) {
+        // (an earlier call's iterations may still be reading the plane being replaced; only the context stream uses it)
+        HIPCHK(hipStreamSynchronize(g.stream));
+        (void)hipFree(g.dDenoise);
+        g.dDenoise = nullptr;
+        g.denoiseBytes = 0;
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dDenoise), bytes));
+        g.denoiseBytes = bytes;
+    }
+    auto inv2 = [](float s) { return s > 0.0f ? 1.0f / (s * s) : 0.0f; };
+    HIPCHK(tptLaunchDenoise(deviceColour, deviceAlbedo, deviceNormalDepth, deviceOut, reinterpret_cast<float*>(g.dDenoise), w, h,
+                            iterations, inv2(sigmaColour), inv2(sigmaNormal), inv2(sigmaDepth), demodulate, g.stream));
+    return 0;
+}
+
 } // extern "C"

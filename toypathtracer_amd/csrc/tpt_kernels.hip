@@ -219,6 +219,78 @@ __global__ void __launch_bounds__(256) tptDisplayKernel(const f4* __restrict__ t
     rgba[i] = to8(c.x) | (to8(c.y) << 8) | (to8(c.z) << 16) | 0xff000000u;
 }
 
+// One iteration of tptDenoiseDevice's edge-avoiding a-trous filter (include/tpt_hip.h states it; tests/denoise_checker.c restates it):
+// step `step`, inverse squared sigmas ic (already x 4^i), in, id.  One lane per pixel, a wave along 64 pixels of a row, so every tap
+// is one 1-KiB coalesced load of 16 B per lane; the centre's colour and guides stay in registers.  FIRST reads the caller's colour
+// (demodulated per tap when `demod`), the others the previous iteration's plane; LAST stores into the caller's plane (remodulated when
+// `demod`), with the colour's alpha, which every plane in between carries in .w.  GUIDE: a normal / depth plane is given.  Taps
+// outside the image are skipped; the weight's division is tdivSafeNum (its numerator, a product of two B3-spline taps, is in
+// [2^-8, 2^-2]; its range check covers the denominator), the quotients of the demodulation and the normalisation plain IEEE ones.
+template <bool FIRST, bool LAST, bool GUIDE>
+__global__ void __launch_bounds__(256) tptDenoiseKernel(const f4* __restrict__ src, const f4* __restrict__ albedo, const f4* __restrict__ nd,
+                                                        f4* __restrict__ dst, int width, int height, int step, float ic, float in, float id,
+                                                        int demod)
+{
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x >= width || y >= height) return;
+    constexpr float hk[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+    auto tap = [&](size_t q) -> f4 {
+        f4 c = src[q];
+        if (FIRST && demod) { // demod(c, a) = a > 0 ? c / a : c
+            const f4 a = albedo[q];
+            c.x = a.x > 0.0f ? c.x / a.x : c.x;
+            c.y = a.y > 0.0f ? c.y / a.y : c.y;
+            c.z = a.z > 0.0f ? c.z / a.z : c.z;
+        }
+        return c;
+    };
+    const size_t p = (size_t)y * width + x;
+    const f4 cp = tap(p);
+    f4 np;
+    if (GUIDE) np = nd[p];
+    float sumW = 0.0f, sumR = 0.0f, sumG = 0.0f, sumB = 0.0f;
+#pragma unroll
+    for (int ky = 0; ky < 5; ++ky) {
+        const int qy = y + (ky - 2) * step;
+        if (qy < 0 || qy >= height) continue;
+#pragma unroll
+        for (int kx = 0; kx < 5; ++kx) {
+            const int qx = x + (kx - 2) * step;
+            if (qx < 0 || qx >= width) continue;
+            const size_t q = (size_t)qy * width + qx;
+            const f4 cq = tap(q);
+            const float dr = cq.x - cp.x, dg = cq.y - cp.y, db = cq.z - cp.z;
+            const float dc = (dr * dr + dg * dg) + db * db;
+            float den = 1.0f + dc * ic;
+            if (GUIDE) {
+                const f4 nq = nd[q];
+                const float dx = nq.x - np.x, dy = nq.y - np.y, dz = nq.z - np.z;
+                const float dn = (dx * dx + dy * dy) + dz * dz;
+                den = den * (1.0f + dn * in);
+                const float dd = nq.w - np.w;
+                den = den * (1.0f + (dd * dd) * id);
+            }
+            const float w = tdivSafeNum(hk[ky] * hk[kx], den);
+            sumW += w;
+            sumR += w * cq.x;
+            sumG += w * cq.y;
+            sumB += w * cq.z;
+        }
+    }
+    f4 o;
+    o.x = sumR / sumW;
+    o.y = sumG / sumW;
+    o.z = sumB / sumW;
+    o.w = cp.w; // (the colour's alpha: demodulation leaves it alone)
+    if (LAST && demod) { // remod(f, a) = a > 0 ? f * a : f
+        const f4 a = albedo[p];
+        o.x = a.x > 0.0f ? o.x * a.x : o.x;
+        o.y = a.y > 0.0f ? o.y * a.y : o.y;
+        o.z = a.z > 0.0f ? o.z * a.z : o.z;
+    }
+    dst[p] = o;
+}
+
 template <int HS, int FOLD, bool LDS_SCENE>
 // 112 VGPRs x 4 waves/SIMD leaves 64 registers per SIMD lane for the resolve kernel's waves (see tptTraceQueueKernel;
 // amdgpu_num_vgpr counts half of the unified file on gfx90a+, so 56 means 112)
@@ -2189,6 +2261,37 @@ hipError_t tptLaunchDisplay(const float* tile, unsigned char* rgba, int width, i
     hipLaunchKernelGGL(tptDisplayKernel, dim3((width * height + 255) / 256), dim3(256), 0, stream, reinterpret_cast<const f4*>(tile),
                        reinterpret_cast<uint32_t*>(rgba), width, height);
     return hipGetLastError();
+}
+
+template <bool GUIDE>
+static void launchDenoiseIteration(bool first, bool last, dim3 grid, hipStream_t stream, const f4* src, const f4* albedo, const f4* nd,
+                                   f4* dst, int width, int height, int step, float ic, float in, float id, int demod)
+{
+    auto k = first ? (last ? tptDenoiseKernel<true, true, GUIDE> : tptDenoiseKernel<true, false, GUIDE>)
+                   : (last ? tptDenoiseKernel<false, true, GUIDE> : tptDenoiseKernel<false, false, GUIDE>);
+    hipLaunchKernelGGL(k, grid, dim3(64, 4), 0, stream, src, albedo, nd, dst, width, height, step, ic, in, id, demod);
+}
+hipError_t tptLaunchDenoise(const float* colour, const float* albedo, const float* normalDepth, float* out, float* scratch, int width,
+                            int height, int iterations, float ic, float in, float id, bool demodulate, hipStream_t stream)
+{
+    const dim3 grid((unsigned)(width + 63) / 64, (unsigned)(height + 3) / 4);
+    const f4* src = reinterpret_cast<const f4*>(colour);
+    for (int i = 0; i < iterations; ++i) {
+        // (the parity that makes the last iteration write `out`)
+        f4* dst = reinterpret_cast<f4*>(((iterations - 1 - i) & 1) ? scratch : out);
+        const float scale = (float)(1u << (2 * i)); // 4^i: ic0 * 4^i is exact (a power of two; the sigmas are bounded on the host)
+        if (normalDepth)
+            launchDenoiseIteration<true>(i == 0, i == iterations - 1, grid, stream, src, reinterpret_cast<const f4*>(albedo),
+                                         reinterpret_cast<const f4*>(normalDepth), dst, width, height, 1 << i, ic * scale, in, id,
+                                         demodulate ? 1 : 0);
+        else
+            launchDenoiseIteration<false>(i == 0, i == iterations - 1, grid, stream, src, reinterpret_cast<const f4*>(albedo), nullptr,
+                                          dst, width, height, 1 << i, ic * scale, in, id, demodulate ? 1 : 0);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        src = dst;
+    }
+    return hipSuccess;
 }
 
 hipError_t tptLaunchAssemble(const float* gathered, float* image, int width, int height, int stripeRows, int nRanks, int padRows, hipStream_t stream)
