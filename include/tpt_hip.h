@@ -191,6 +191,46 @@ enum { TPT_DENOISE_DEMODULATE = 1 << 0 };
 TPT_API int tptDenoiseDevice(int screenWidth, int screenHeight, const float* deviceColour, const float* deviceAlbedo,
                              const float* deviceNormalDepth, float* deviceOut, int iterations, float sigmaColour,
                              float sigmaNormal, float sigmaDepth, unsigned denoiseFlags);
+/* One frame with the per-pixel luminance moments of its samples, for tptDenoiseDeviceVariance.  deviceTile is blended exactly as
+ * tptDrawDevice blends it, with the same ray count; deviceAlbedo / deviceNormalDepth (either or both may be NULL) are overwritten
+ * byte for byte as tptDrawDeviceAov writes them.  deviceMoments (required): h*w*4 floats, row-major like the tile.  For every sample s
+ * of a pixel, c_s is the colour the trace adds to the pixel's sum and l_s = (0.2126f*c_s.x + 0.7152f*c_s.y) + 0.0722f*c_s.z (binary32,
+ * no FMA); the frame's moments are {sum l_s, sum l_s*l_s, 0} * (1.0f / spp), float sums from +0 in sample order, and they are blended
+ * into deviceMoments.xyz with the tile's own arithmetic (the same lerp factor; .w untouched): a progressive caller holds running
+ * means of l and l^2 over all its samples.  Ordering, state and refusals are tptDrawDeviceAov's (asynchronous on the context stream,
+ * ordered behind earlier work there; frames traced ahead and stream-batch planes dropped; camera and scene unchanged), and also
+ * refused: deviceMoments NULL, or overlapping the tile or a given plane.  A refused call writes nothing. */
+TPT_API int tptDrawDeviceMoments(float time, int frameCount, int screenWidth, int screenHeight, float* deviceTile,
+                                 float* deviceAlbedo, float* deviceNormalDepth, float* deviceMoments, unsigned testFlags);
+/* The spatial filter of SVGF (Schied et al., HPG 2017) in tptDenoiseDevice's rational form: an a-trous filter whose luminance term is
+ * scaled by a per-pixel variance made from tptDrawDeviceMoments' moments and carried through the iterations.  All six buffers are
+ * device buffers of h*w*4 floats; deviceAlbedo and deviceNormalDepth may be NULL.  samples: how many samples the colour and the moments
+ * average (spp * (frameCount + 1) for a static progressive caller, spp for a single frame).  Binary32, in the order written, no FMA,
+ * correctly rounded division, sums from +0 in the order written (ky, jy outer):
+ *   lum(c) = (0.2126f*c.r + 0.7152f*c.g) + 0.0722f*c.b;  hk = {1/16, 1/4, 3/8, 1/4, 1/16};  gk = {1/4, 1/2, 1/4}
+ *   sl2 = sigmaLuminance * sigmaLuminance;  in, id = 1 / sigma^2 (0 for a sigma of 0), as tptDenoiseDevice's
+ *   cur_0 = colour, demodulated as tptDenoiseDevice does under TPT_DENOISE_DEMODULATE
+ *   v_0[p] = (d > 0 ? d : 0) / samples,  d = m.y - m.x*m.x,  m = moments[p]
+ *            with DEMODULATE and la2 = la*la > 0 (la = lum(albedo[p])):  v_0[p] = v_0[p] / la2
+ *   iteration i (0 .. iterations-1), step s = 1 << i; for each pixel p:
+ *     g  = sum of (gk[jy]*gk[jx]) * v_i[q'] over the 3x3 unit-spaced q' = p + (j - 1) inside the image, / sum of those (gk[jy]*gk[jx])
+ *     il = s / (sl2 * g + TPT_DENOISE_VARIANCE_EPS)     (the step: sigma^2 halved per iteration)
+ *     over the 5x5 taps q = p + (k - 2) s inside the image:
+ *       den = 1 + (dl*dl) * il     (dl = lum(cur_i[q]) - lum(cur_i[p]));  with normalDepth den *= the normal and depth factors of
+ *       tptDenoiseDevice (not scaled per iteration);  w = (hk[ky]*hk[kx]) / den
+ *     cur_{i+1}[p].rgb = sum(w cur_i[q].rgb) / sum(w);   v_{i+1}[p] = sum((w*w) v_i[q]) / (sum(w)*sum(w))
+ *   out.rgb = cur_N remodulated under DEMODULATE (as tptDenoiseDevice);  out.a = colour.a
+ * The step in il's numerator makes each iteration twice as strict as the one before; the carried variance alone let 5 iterations blur
+ * a 64-frame image past its own noise.  The guides should describe the same samples as the colour: a progressive
+ * caller averages the albedo and normal / depth planes over its frames as the tile is averaged (one frame's 4-spp planes beside
+ * a 256-sample colour mis-demodulate and mis-guide the edges).  Asynchronous on the context stream; needs
+ * tptInitialize only and leaves every other state alone.  The inputs are never written.  Refused (non-zero, tptGetLastError, nothing
+ * enqueued, deviceOut untouched): tptDenoiseDevice's refusals (sigmaNormal, sigmaDepth, iterations, flags, sizes, overlaps), and
+ * deviceMoments NULL or overlapping deviceOut, samples not finite or below 1, sigmaLuminance not in (0, 1e6]. */
+#define TPT_DENOISE_VARIANCE_EPS 1e-4f
+TPT_API int tptDenoiseDeviceVariance(int screenWidth, int screenHeight, const float* deviceColour, const float* deviceAlbedo,
+                                     const float* deviceNormalDepth, const float* deviceMoments, float samples, float* deviceOut,
+                                     int iterations, float sigmaLuminance, float sigmaNormal, float sigmaDepth, unsigned denoiseFlags);
 /* nViews (1..32) cameras of the scene as of the last tptUpdate, traced by ONE launch.  views: nViews x 9 floats
  * {lookFrom xyz, lookAt xyz, vfovDegrees, aperture, focusDist} -- tptSetCamera's arguments; aspect = w / h, vup (0,1,0),
  * aperture forced to 0 in Mitsuba-compare mode, as tptUpdate does.  deviceTiles: nViews consecutive device tiles of h*w*4

@@ -39,7 +39,7 @@ C_ABI_SYMBOLS = [
     "tptSetSamplesPerPixel", "tptSetConfig", "tptSetSeedMode", "tptSetFoldMode", "tptSetScene", "tptSetCamera", "tptSetStream",
     "tptSetRowShard", "tptLocalRowCount", "tptLocalRowToGlobal", "tptDrawDevice", "tptRayCounterRead", "tptSetRayCounter", "tptSetFrameOverlap", "tptDisplayRGBA8", "tptKernelTimingBegin", "tptKernelTimingEnd",
     "tptSynchronize", "tptTimerBegin", "tptTimerEnd", "tptSetKernelVariant",
-    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
+    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDenoiseDeviceVariance", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
 ]
 # include/tpt_test_hooks.h: exported by the second build (libtoypathtracer_hip_hooks.so) only
 HOOK_SYMBOLS = ["tptTestMath", "tptTestMathExhaustive", "tptTestHitSpheres", "tptTestMatrixFilter", "tptTestGroupFilter", "tptTestSetDealCapacities", "tptDebugStats", "tptDebugChunkOrder"]
@@ -78,7 +78,7 @@ def _bind(path, hooks):
         "tptSetRayCounter": [p], "tptSetTileMirror": [p, p], "tptSetFrameOverlap": [i], "tptDisplayRGBA8": [p, i, i, p], "tptKernelTimingBegin": [i],
         "tptKernelTimingEnd": [C.POINTER(f), C.POINTER(i)],
         "tptSynchronize": [], "tptTimerBegin": [], "tptTimerEnd": [C.POINTER(f)], "tptSetKernelVariant": [i, i, i],
-        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
+        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
     }
     if hooks:
         sigs.update({"tptDebugStats": [p, i], "tptDebugChunkOrder": [p, p, i], "tptTestMath": [i, p, p, p, i], "tptTestMathExhaustive": [i, u, u, p, p],
@@ -477,6 +477,78 @@ def denoise_device(w, h, colour_ptr, out_ptr, albedo_ptr=None, normal_depth_ptr=
     _chk(load_library().tptDenoiseDevice(w, h, C.c_void_p(colour_ptr), C.c_void_p(albedo_ptr) if albedo_ptr else None,
                                          C.c_void_p(normal_depth_ptr) if normal_depth_ptr else None, C.c_void_p(out_ptr), iterations,
                                          sigma_colour, sigma_normal, sigma_depth, DENOISE_DEMODULATE if demodulate else 0), "tptDenoiseDevice")
+
+
+def draw_device_moments(time, frame, w, h, tile_ptr, moments_ptr, flags, albedo_ptr=None, normal_depth_ptr=None):
+    """draw_device_aov (same tile bits, same ray count, the same planes where given; both may be None) plus the luminance moments of the
+    frame's samples, blended into moments_ptr (a device buffer of h*w*4 floats) with the tile's lerp factor: {mean l, mean l^2, 0} of
+    l = (0.2126 r + 0.7152 g) + 0.0722 b, .w kept.  Ordered on the context's stream like the tile."""
+    for name, v in (("w", w), ("h", h)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v <= 0:
+            raise ValueError("%s: a positive int expected, got %r" % (name, v))
+    for name, v in (("tile_ptr", tile_ptr), ("moments_ptr", moments_ptr), ("albedo_ptr", albedo_ptr), ("normal_depth_ptr", normal_depth_ptr)):
+        if v is not None and (not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 0):
+            raise ValueError("%s: a device pointer (int) or None expected, got %r" % (name, v))
+    if not tile_ptr or not moments_ptr:
+        raise ValueError("tile_ptr, moments_ptr: device buffers are required")
+    _chk(load_library().tptDrawDeviceMoments(time, frame, w, h, C.c_void_p(tile_ptr), C.c_void_p(albedo_ptr) if albedo_ptr else None,
+                                             C.c_void_p(normal_depth_ptr) if normal_depth_ptr else None, C.c_void_p(moments_ptr), flags),
+         "tptDrawDeviceMoments")
+
+
+def moment_samples(spp, frame=None, flags=0):
+    """The `samples` argument of denoise_device_variance: how many samples the colour and the moments average.  A single frame (frame
+    None, or flags without kFlagProgressive): spp.  A static progressive caller after its frame `frame`: spp * (frame + 1).  An animated
+    progressive caller (kFlagAnimate) blends with a smoothed lerp factor, so no count follows from the frame number: it passes its own."""
+    if not isinstance(spp, (int, np.integer)) or isinstance(spp, bool) or spp < 1:
+        raise ValueError("spp: a positive int expected, got %r" % (spp,))
+    if frame is None or not (flags & kFlagProgressive):
+        return float(spp)
+    if flags & kFlagAnimate:
+        raise ValueError("an animated progressive caller's moments average no fixed number of samples: pass samples explicitly")
+    if not isinstance(frame, (int, np.integer)) or isinstance(frame, bool) or frame < 0:
+        raise ValueError("frame: an int >= 0 expected, got %r" % (frame,))
+    return float(spp * (frame + 1))
+
+
+# denoise_device_variance's defaults, chosen by tools/denoise_variance_rate.py's sweep (DESIGN.md 3.7)
+DENOISE_VARIANCE_DEFAULTS = dict(iterations=5, sigma_luminance=4.0, sigma_normal=0.03, sigma_depth=0.5)
+
+
+def denoise_device_variance(w, h, colour_ptr, moments_ptr, samples, out_ptr, albedo_ptr=None, normal_depth_ptr=None,
+                            iterations=DENOISE_VARIANCE_DEFAULTS["iterations"], sigma_luminance=DENOISE_VARIANCE_DEFAULTS["sigma_luminance"],
+                            sigma_normal=DENOISE_VARIANCE_DEFAULTS["sigma_normal"], sigma_depth=DENOISE_VARIANCE_DEFAULTS["sigma_depth"],
+                            demodulate=None):
+    """tptDenoiseDeviceVariance: the variance-guided a-trous filter of the tile at colour_ptr into out_ptr, its luminance term scaled by
+    the per-pixel variance of draw_device_moments' moments (moments_ptr) over `samples` samples (moment_samples).  Guides and demodulate
+    as denoise_device; a progressive caller passes guide planes averaged over its frames like the tile (include/tpt_hip.h).  Ordered on
+    the context's stream."""
+    for name, v in (("w", w), ("h", h), ("iterations", iterations)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v <= 0:
+            raise ValueError("%s: a positive int expected, got %r" % (name, v))
+    for name, v in (("colour_ptr", colour_ptr), ("moments_ptr", moments_ptr), ("out_ptr", out_ptr), ("albedo_ptr", albedo_ptr),
+                    ("normal_depth_ptr", normal_depth_ptr)):
+        if v is not None and (not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 0):
+            raise ValueError("%s: a device pointer (int) or None expected, got %r" % (name, v))
+    if not colour_ptr or not out_ptr or not moments_ptr:
+        raise ValueError("colour_ptr, moments_ptr, out_ptr: device buffers are required")
+    if not isinstance(samples, (int, float, np.integer, np.floating)) or isinstance(samples, bool) or not 1 <= samples < float("inf"):
+        raise ValueError("samples: a finite number >= 1 expected, got %r" % (samples,))
+    if not isinstance(sigma_luminance, (int, float, np.integer, np.floating)) or isinstance(sigma_luminance, bool) or not 0 < sigma_luminance <= 1e6:
+        raise ValueError("sigma_luminance: a float in (0, 1e6] expected, got %r" % (sigma_luminance,))
+    for name, v in (("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth)):
+        if not isinstance(v, (int, float, np.integer, np.floating)) or isinstance(v, bool) or not v >= 0 or v == float("inf"):
+            raise ValueError("%s: a finite float >= 0 expected, got %r" % (name, v))
+    if demodulate is None:
+        demodulate = bool(albedo_ptr)
+    if demodulate and not albedo_ptr:
+        raise ValueError("demodulate: needs albedo_ptr")
+    if not normal_depth_ptr:
+        sigma_normal = sigma_depth = 0.0
+    _chk(load_library().tptDenoiseDeviceVariance(w, h, C.c_void_p(colour_ptr), C.c_void_p(albedo_ptr) if albedo_ptr else None,
+                                                 C.c_void_p(normal_depth_ptr) if normal_depth_ptr else None, C.c_void_p(moments_ptr),
+                                                 samples, C.c_void_p(out_ptr), iterations, sigma_luminance, sigma_normal, sigma_depth,
+                                                 DENOISE_DEMODULATE if demodulate else 0), "tptDenoiseDeviceVariance")
 
 
 def sharded_finish():

@@ -229,6 +229,11 @@ struct Context {
     f4* dAovSums = nullptr;
     size_t aovSumsBytes = 0;
     hipEvent_t evAov = nullptr;         // recorded on the context stream by an AOV call; its trace stream waits for it
+    // tptDrawDeviceMoments: the frame's moments plane (KernelArgs::momentsOut, [nLocalRows][w] f4 of the largest frame seen), written
+    // by the moments kernel and blended into the caller's plane on the context stream; AOV launches run one at a time (evAov), so
+    // one plane serves them all.  Its sums are a third f4 per path column of dAovSums.
+    f4* dMoments = nullptr;
+    size_t momentsBytes = 0;
     // tptDenoiseDevice: the plane the a-trous iterations ping-pong through beside the caller's output ([h][w] f4 of the largest frame
     // denoised so far), made by the first call that iterates more than once, grown when a later one needs more, freed by tptShutdown.
     // Only the context stream uses it, so stream order alone keeps one call's iterations from another's.
@@ -378,6 +383,7 @@ struct BatchTable {
 struct AovPlanes {
     f4* albedo = nullptr;
     f4* normalDepth = nullptr;
+    bool moments = false; // tptDrawDeviceMoments: tptTraceMomentsKernel, into Context::dMoments
 };
 int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long long* frameRays, TraceTicket& T, int batch = 1, int rayStride = 0,
                  const BatchTable* table = nullptr, const AovPlanes* aov = nullptr);

@@ -67,6 +67,9 @@ struct KernelArgs {
     f4* aovSums = nullptr;
     f4* aovAlbedo = nullptr;
     f4* aovNormalDepth = nullptr;
+    // ... and its luminance moments (tptDrawDeviceMoments): a third f4 of sums per path, aovSums[3 x column .. + 2], and the frame's
+    // means {l, l^2, 0, 0} stored into momentsOut ([nLocalRows][width] f4); the launch takes tptTraceMomentsKernel.  Null otherwise.
+    f4* momentsOut = nullptr;
 };
 
 } // namespace tpt
@@ -89,6 +92,13 @@ hipError_t tptLaunchDisplay(const float* tile, unsigned char* rgba, int width, i
 __attribute__((weak)) hipError_t tptLaunchDenoise(const float* colour, const float* albedo, const float* normalDepth, float* out,
                                                   float* scratch, int width, int height, int iterations, float ic, float in, float id,
                                                   bool demodulate, hipStream_t stream);
+// tptDenoiseDeviceVariance: `iterations` launches of the variance-guided a-trous kernel, ping-ponging between out and scratch as
+// tptLaunchDenoise does; albedo / normalDepth may be null (sl2 = sigmaLuminance^2; in, id: the inverse squared guide sigmas).  Weak for
+// the same reason as tptLaunchDenoise.
+__attribute__((weak)) hipError_t tptLaunchDenoiseVariance(const float* colour, const float* albedo, const float* normalDepth,
+                                                          const float* moments, float* out, float* scratch, int width, int height,
+                                                          int iterations, float samples, float sl2, float in, float id, bool demodulate,
+                                                          hipStream_t stream);
 hipError_t tptLaunchAssemble(const float* gathered, float* image, int width, int height, int stripeRows, int nRanks, int padRows, hipStream_t stream);
 hipError_t tptLaunchQueueProbe(unsigned long long ticks, hipStream_t stream);
 hipError_t tptLaunchChunkOrder(const unsigned* cost, unsigned* snap, unsigned* order, int numChunks, hipStream_t stream);

@@ -328,4 +328,49 @@ int tptDenoiseDevice(int w, int h, const float* deviceColour, const float* devic
     return 0;
 }
 
+// The variance-guided a-trous filter (include/tpt_hip.h states it): tptDenoiseDevice's checks, plus the moments plane, the sample
+// count and the luminance sigma; the same scratch plane, which carries the variance in .w between the iterations.
+int tptDenoiseDeviceVariance(int w, int h, const float* deviceColour, const float* deviceAlbedo, const float* deviceNormalDepth,
+                             const float* deviceMoments, float samples, float* deviceOut, int iterations, float sigmaLuminance,
+                             float sigmaNormal, float sigmaDepth, unsigned denoiseFlags)
+{
+    if (requireInit()) return -1;
+    if (w < 1 || w > 8192 || h < 1 || h > 8192) return fail("tptDenoiseDeviceVariance: w and h must lie in 1..8192");
+    if (!deviceColour || !deviceOut) return fail("tptDenoiseDeviceVariance: deviceColour and deviceOut are required");
+    if (!deviceMoments) return fail("tptDenoiseDeviceVariance: deviceMoments is required");
+    const uintptr_t bytes = (uintptr_t)w * (uintptr_t)h * 16u;
+    const uintptr_t o = reinterpret_cast<uintptr_t>(deviceOut);
+    for (const float* in : {deviceColour, deviceAlbedo, deviceNormalDepth, deviceMoments}) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(in);
+        if (in && o < a + bytes && a < o + bytes) return fail("tptDenoiseDeviceVariance: deviceOut overlaps an input");
+    }
+    if (iterations < 1 || iterations > 8) return fail("tptDenoiseDeviceVariance: iterations must lie in 1..8");
+    if (!(samples >= 1.0f && samples <= 3.40282347e38f)) // (NaN and +inf fail)
+        return fail("tptDenoiseDeviceVariance: samples must be finite and at least 1");
+    if (!(sigmaLuminance > 0.0f && sigmaLuminance <= 1e6f)) return fail("tptDenoiseDeviceVariance: sigmaLuminance must lie in (0, 1e6]");
+    for (float s : {sigmaNormal, sigmaDepth}) // (NaN fails both comparisons)
+        if (!(s == 0.0f || (s >= 1e-6f && s <= 1e6f)))
+            return fail("tptDenoiseDeviceVariance: sigmaNormal and sigmaDepth must be 0 or lie in [1e-6, 1e6]");
+    if ((sigmaNormal != 0.0f || sigmaDepth != 0.0f) && !deviceNormalDepth)
+        return fail("tptDenoiseDeviceVariance: sigmaNormal and sigmaDepth need deviceNormalDepth");
+    if (denoiseFlags & ~(unsigned)TPT_DENOISE_DEMODULATE) return fail("tptDenoiseDeviceVariance: unknown flag bits");
+    const bool demodulate = (denoiseFlags & TPT_DENOISE_DEMODULATE) != 0;
+    if (demodulate && !deviceAlbedo) return fail("tptDenoiseDeviceVariance: TPT_DENOISE_DEMODULATE needs deviceAlbedo");
+    if (!tptLaunchDenoiseVariance) return fail("tptDenoiseDeviceVariance: this build has no variance-guided a-trous kernel");
+    if (iterations > 1 && bytes > g.denoiseBytes) {
+        // (an earlier call's iterations may still be reading the plane being replaced; only the context stream uses it)
+        HIPCHK(hipStreamSynchronize(g.stream));
+        (void)hipFree(g.dDenoise);
+        g.dDenoise = nullptr;
+        g.denoiseBytes = 0;
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dDenoise), bytes));
+        g.denoiseBytes = bytes;
+    }
+    auto inv2 = [](float s) { return s > 0.0f ? 1.0f / (s * s) : 0.0f; };
+    HIPCHK(tptLaunchDenoiseVariance(deviceColour, deviceAlbedo, deviceNormalDepth, deviceMoments, deviceOut,
+                                    reinterpret_cast<float*>(g.dDenoise), w, h, iterations, samples, sigmaLuminance * sigmaLuminance,
+                                    inv2(sigmaNormal), inv2(sigmaDepth), demodulate, g.stream));
+    return 0;
+}
+
 } // extern "C"

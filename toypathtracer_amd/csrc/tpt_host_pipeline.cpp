@@ -420,19 +420,29 @@ int ensureViewSlots()
 }
 
 // tptDrawDeviceAov: the per-path sums (Context::dAovSums) for the largest grid this frame shape can take, and the ordering event;
-// made by the first AOV call, grown (after a drain) when a later one asks for more.
-int ensureAovSums(const FramePlan& P)
+// made by the first AOV call, grown (after a drain) when a later one asks for more.  tptDrawDeviceMoments (`momentsBytes` > 0): a
+// third f4 per path, and the frame's moments plane (Context::dMoments) of that many bytes.
+int ensureAovSums(const FramePlan& P, size_t momentsBytes)
 {
     if (!g.evAov) HIPCHK(hipEventCreateWithFlags(&g.evAov, kOrderingEvent));
-    const size_t need = 2 * sizeof(f4) * (size_t)maxGridBlocks(P) * (size_t)tptQueuePathsPerBlock();
-    if (need <= g.aovSumsBytes) return 0;
-    int rc = syncAllStreams(); // (an earlier AOV launch may still be reading the old buffer)
+    const size_t need = (momentsBytes ? 3 : 2) * sizeof(f4) * (size_t)maxGridBlocks(P) * (size_t)tptQueuePathsPerBlock();
+    if (need <= g.aovSumsBytes && momentsBytes <= g.momentsBytes) return 0;
+    int rc = syncAllStreams(); // (an earlier AOV launch, or its blend, may still be reading the old buffers)
     if (rc) return rc;
-    (void)hipFree(g.dAovSums);
-    g.dAovSums = nullptr;
-    g.aovSumsBytes = 0;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dAovSums), need));
-    g.aovSumsBytes = need;
+    if (need > g.aovSumsBytes) {
+        (void)hipFree(g.dAovSums);
+        g.dAovSums = nullptr;
+        g.aovSumsBytes = 0;
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dAovSums), need));
+        g.aovSumsBytes = need;
+    }
+    if (momentsBytes > g.momentsBytes) {
+        (void)hipFree(g.dMoments);
+        g.dMoments = nullptr;
+        g.momentsBytes = 0;
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dMoments), momentsBytes));
+        g.momentsBytes = momentsBytes;
+    }
     return 0;
 }
 
@@ -524,12 +534,13 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
         return refuse("tptDrawDeviceBatch: needs the path-queue kernel (per-pixel seeds, recursive fold, two-phase HitSpheres) or row-serial seeds, and a frame of at most 8192 x 8192 (2^30 pixels per batch)");
     sizeGrid(P);
     if ((rc = ensureFrameBuffers(P, w))) return rc;
-    a.aovSums = a.aovAlbedo = a.aovNormalDepth = nullptr;
+    a.aovSums = a.aovAlbedo = a.aovNormalDepth = a.momentsOut = nullptr;
     if (aov) {
-        if ((rc = ensureAovSums(P))) return rc;
+        if ((rc = ensureAovSums(P, aov->moments ? (size_t)a.nLocalRows * (size_t)w * sizeof(f4) : 0))) return rc;
         a.aovSums = g.dAovSums;
         a.aovAlbedo = aov->albedo;
         a.aovNormalDepth = aov->normalDepth;
+        if (aov->moments) a.momentsOut = g.dMoments;
     }
     if (frameRays) a.rayCounter = frameRays;
     a.rayCounterStride = rayStride; // (batched row-serial launch for the host path: one counter per frame of the batch)
@@ -922,6 +933,46 @@ int tptDrawDeviceAov(float time, int frameCount, int w, int h, float* deviceTile
     aov.normalDepth = reinterpret_cast<f4*>(deviceNormalDepth);
     if ((rc = enqueueTrace(frameCount, w, h, testFlags, nullptr, T, 1, 0, nullptr, &aov))) return rc;
     return enqueueResolve(T, deviceTile, nullptr); // (the kernel added its rays to the running total itself, as tptDrawDevice's plain path)
+}
+
+// tptDrawDeviceAov plus the luminance moments of the frame's samples (tptTraceMomentsKernel into the context's moments plane), blended
+// into deviceMoments by a second resolve launch right behind the tile's, with the tile's lerp factor.  The next moments launch waits
+// for the context stream (evAov) before it overwrites the plane, so one plane serves every call.
+int tptDrawDeviceMoments(float time, int frameCount, int w, int h, float* deviceTile, float* deviceAlbedo, float* deviceNormalDepth,
+                         float* deviceMoments, unsigned testFlags)
+{
+    (void)time; // (the scene state is that of the last tptUpdate, as for tptDrawDevice)
+    if (int rc_ = flushShardDeferred()) return rc_; // (see tptDrawDevice)
+    if (requireInit()) return -1;
+    if (!deviceTile || !deviceMoments || w <= 0 || h <= 0)
+        return fail("tptDrawDeviceMoments: bad arguments (deviceTile, deviceMoments, size)");
+    if (!g.updated || w != g.updatedW || h != g.updatedH) return fail("tptDrawDeviceMoments: call tptUpdate (UpdateTest) at this size first");
+    if (w > 8192 || h > 8192) return fail("tptDrawDeviceMoments: frames of at most 8192 x 8192");
+    const uintptr_t bytes = (uintptr_t)w * (uintptr_t)h * 16u;
+    const uintptr_t m = reinterpret_cast<uintptr_t>(deviceMoments);
+    for (const float* other : {(const float*)deviceTile, (const float*)deviceAlbedo, (const float*)deviceNormalDepth}) {
+        const uintptr_t o = reinterpret_cast<uintptr_t>(other);
+        if (other && m < o + bytes && o < m + bytes) return fail("tptDrawDeviceMoments: deviceMoments overlaps the tile or a plane");
+    }
+    if (g.seedMode == SEED_ROW_SERIAL) return fail("tptDrawDeviceMoments: needs per-pixel seeds (tptSetSeedMode(1)); row-serial moments are not supported");
+    if (g.foldMode != FOLD_RECURSIVE) return fail("tptDrawDeviceMoments: needs the recursive fold (tptSetFoldMode(0))");
+    if (g.persist != 3 || g.hs != HS_TWO_PHASE) return fail("tptDrawDeviceMoments: needs the path-queue kernel (tptSetKernelVariant(0, 3, ..))");
+    if (g.spp > 2047) return fail("tptDrawDeviceMoments: at most 2047 samples per pixel (the path-queue kernel)");
+    if (g.numParts > 1 || g.shard.active) return fail("tptDrawDeviceMoments: not with row sharding or a communicator (sharded moments are not supported)");
+    if (g.mirror) return fail("tptDrawDeviceMoments: not with a tile mirror (tptSetTileMirror)");
+    int rc = g.pending.discard();
+    if (rc) return rc;
+    TraceTicket T;
+    AovPlanes aov;
+    aov.albedo = reinterpret_cast<f4*>(deviceAlbedo);
+    aov.normalDepth = reinterpret_cast<f4*>(deviceNormalDepth);
+    aov.moments = true;
+    if ((rc = enqueueTrace(frameCount, w, h, testFlags, nullptr, T, 1, 0, nullptr, &aov))) return rc;
+    if ((rc = enqueueResolve(T, deviceTile, nullptr))) return rc;
+    if (!T.valid) return 0;
+    // (behind the tile's blend, so behind the trace; .xyz blended, .w kept; no ray count: the tile's blend has taken it)
+    HIPCHK(tptLaunchResolve(deviceMoments, g.dMoments, T.nPixels, T.lerpFac, nullptr, g.dRays, nullptr, nullptr, g.stream));
+    return 0;
 }
 
 int tptRayCounterRead(int64_t* outTotalRays)

@@ -23,6 +23,7 @@
 // its conservative FILTER does -- the discriminant is bilinear in (sphere, ray), so the path-queue kernel evaluates
 // [64 spheres x 32 slots] x [32 slots x 64 rays] with v_mfma_f32_32x32x16_f16 on f16-split operands (tpt_trace.h phase1MatrixH)
 // and runs the reference's exact arithmetic only on what passes.  Everything a branch can depend on stays on the VALU.
+#include "../../include/tpt_hip.h" // (TPT_DENOISE_VARIANCE_EPS)
 #include "tpt_device.h"
 #include "tpt_shard.h"
 
@@ -287,6 +288,113 @@ __global__ void __launch_bounds__(256) tptDenoiseKernel(const f4* __restrict__ s
         o.x = a.x > 0.0f ? o.x * a.x : o.x;
         o.y = a.y > 0.0f ? o.y * a.y : o.y;
         o.z = a.z > 0.0f ? o.z * a.z : o.z;
+    }
+    dst[p] = o;
+}
+
+// One iteration of tptDenoiseDeviceVariance's variance-guided a-trous filter (include/tpt_hip.h states it; tests/variance_checker.c
+// restates it): step `step`.  The layout of tptDenoiseKernel -- one lane per pixel, a wave along 64 pixels of a row -- with the
+// pixel's luminance variance v carried in .w of every plane in between.  FIRST reads the caller's colour (demodulated per tap when
+// `demod`) and makes v_0 from the caller's moments (divided by the albedo's squared luminance when `demod`); the others read the
+// previous iteration's plane, colour and v.  LAST stores the colour (remodulated when `demod`) with the caller's alpha.  GUIDE: a
+// normal / depth plane is given.  Each lane first takes g, the 3x3 binomial blur of v around it, for its luminance weight; taps
+// outside the image are skipped everywhere.  The weight's division is tdivSafeNum (numerator in [2^-8, 2^-2], as in
+// tptDenoiseKernel), every other quotient a plain IEEE one.
+template <bool FIRST, bool LAST, bool GUIDE>
+__global__ void __launch_bounds__(256) tptVarianceAtrousKernel(const f4* __restrict__ src, const f4* __restrict__ colour,
+                                                                const f4* __restrict__ albedo, const f4* __restrict__ nd,
+                                                                const f4* __restrict__ moments, f4* __restrict__ dst, int width, int height,
+                                                                int step, float samples, float sl2, float in, float id, int demod)
+{
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x >= width || y >= height) return;
+    constexpr float hk[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+    constexpr float gk[3] = {0.25f, 0.5f, 0.25f};
+    auto lum = [](float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; };
+    // {colour, v} of pixel q as this iteration sees it
+    auto tap = [&](size_t q) -> f4 {
+        f4 c = src[q];
+        if (FIRST) {
+            const f4 m = moments[q];
+            const float d = m.y - m.x * m.x;
+            c.w = (d > 0.0f ? d : 0.0f) / samples;
+            if (demod) { // demod(c, a) = a > 0 ? c / a : c;  v / lum(a)^2 where that square is > 0
+                const f4 a = albedo[q];
+                c.x = a.x > 0.0f ? c.x / a.x : c.x;
+                c.y = a.y > 0.0f ? c.y / a.y : c.y;
+                c.z = a.z > 0.0f ? c.z / a.z : c.z;
+                const float la = lum(a.x, a.y, a.z);
+                const float la2 = la * la;
+                c.w = la2 > 0.0f ? c.w / la2 : c.w;
+            }
+        }
+        return c;
+    };
+    const size_t p = (size_t)y * width + x;
+    const f4 cp = tap(p);
+    const float lp = lum(cp.x, cp.y, cp.z);
+    f4 np;
+    if (GUIDE) np = nd[p];
+    // g: the unit-spaced 3x3 binomial blur of v around p (its weights are exact dyadics, their sum too)
+    float gv = 0.0f, gw = 0.0f;
+#pragma unroll
+    for (int jy = 0; jy < 3; ++jy) {
+        const int qy = y + jy - 1;
+        if (qy < 0 || qy >= height) continue;
+#pragma unroll
+        for (int jx = 0; jx < 3; ++jx) {
+            const int qx = x + jx - 1;
+            if (qx < 0 || qx >= width) continue;
+            const float k = gk[jy] * gk[jx];
+            const float v = (jy == 1 && jx == 1) ? cp.w : tap((size_t)qy * width + qx).w;
+            gv += k * v;
+            gw += k;
+        }
+    }
+    const float il = (float)step / (sl2 * (gv / gw) + TPT_DENOISE_VARIANCE_EPS); // (the step 2^i: sigma^2 halved per iteration)
+    float sumW = 0.0f, sumR = 0.0f, sumG = 0.0f, sumB = 0.0f, sumV = 0.0f;
+#pragma unroll
+    for (int ky = 0; ky < 5; ++ky) {
+        const int qy = y + (ky - 2) * step;
+        if (qy < 0 || qy >= height) continue;
+#pragma unroll
+        for (int kx = 0; kx < 5; ++kx) {
+            const int qx = x + (kx - 2) * step;
+            if (qx < 0 || qx >= width) continue;
+            const size_t q = (size_t)qy * width + qx;
+            const f4 cq = tap(q);
+            const float dl = lum(cq.x, cq.y, cq.z) - lp;
+            float den = 1.0f + (dl * dl) * il;
+            if (GUIDE) {
+                const f4 nq = nd[q];
+                const float dx = nq.x - np.x, dy = nq.y - np.y, dz = nq.z - np.z;
+                const float dn = (dx * dx + dy * dy) + dz * dz;
+                den = den * (1.0f + dn * in);
+                const float dd = nq.w - np.w;
+                den = den * (1.0f + (dd * dd) * id);
+            }
+            const float w = tdivSafeNum(hk[ky] * hk[kx], den);
+            sumW += w;
+            sumR += w * cq.x;
+            sumG += w * cq.y;
+            sumB += w * cq.z;
+            sumV += (w * w) * cq.w;
+        }
+    }
+    f4 o;
+    o.x = sumR / sumW;
+    o.y = sumG / sumW;
+    o.z = sumB / sumW;
+    if (LAST) {
+        o.w = colour[p].w; // (the caller's alpha)
+        if (demod) { // remod(f, a) = a > 0 ? f * a : f
+            const f4 a = albedo[p];
+            o.x = a.x > 0.0f ? o.x * a.x : o.x;
+            o.y = a.y > 0.0f ? o.y * a.y : o.y;
+            o.z = a.z > 0.0f ? o.z * a.z : o.z;
+        }
+    } else {
+        o.w = sumV / (sumW * sumW);
     }
     dst[p] = o;
 }
@@ -1239,7 +1347,9 @@ __device__ __forceinline__ int hitSpheresGroupedDeal(const SceneView& sv, bool g
 // AOV (single frames; tptDrawDeviceAov): every sample's first hit -- albedo, coverage, normal, t -- is summed in the path's two f4 of
 // a.aovSums (global memory, a column per path like the bounce stack's spill levels) and the means are stored beside the pixel's colour
 // into a.aovAlbedo / a.aovNormalDepth.  Its own kernel (tptTraceAovKernel) for the same reason.
-template <bool LDS_SCENE, bool BATCH, bool VIEWS = false, bool MOVING = false, bool AOV = false>
+// MOMENTS (with AOV; tptDrawDeviceMoments): a third f4 per path in a.aovSums sums every sample's luminance l and l^2, and the means
+// go into a.momentsOut, the frame's moments plane, beside the colour.  Its own kernel (tptTraceMomentsKernel) for the same reason.
+template <bool LDS_SCENE, bool BATCH, bool VIEWS = false, bool MOVING = false, bool AOV = false, bool MOMENTS = false>
 __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1250,6 +1360,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     static_assert(BATCH || !VIEWS, "views are frames of a batched launch");
     static_assert((BATCH || !MOVING) && !(VIEWS && MOVING), "animation frames are frames of a batched launch of their own");
     static_assert(!AOV || !BATCH, "first-hit planes are made by single-frame launches");
+    static_assert(!MOMENTS || AOV, "moments are summed beside the first-hit sums");
     constexpr int kPaths = (LDS_SCENE ? TPT_Q_PATHS : TPT_Q_PATHS_GROUPED) - (VIEWS ? TPT_Q_VIEW_PATHS : 0) -
                            (MOVING ? TPT_Q_ANIM_PATHS : 0); // paths this workgroup owns
     constexpr int kOffSt = LDS_SCENE ? TPT_Q_SPH_FIXED : 0;
@@ -1471,9 +1582,10 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
         stack.l0 = (LdsF4Ptr)(st + 3 * kPaths + p); // level 0 in the path record
         stack.spill = a.stackBuf + ((size_t)(blockIdx.x + (unsigned)a.helperBase) * TPT_Q_PATHS + p);
         stack.stride = a.stackStride;
-        // AOV: this path's sums {albedo, coverage} {normal, t} over the first hits of its pixel's samples so far (the address is made
-        // where it is used, not held across the iteration)
-        auto aovSum = [&]() { return a.aovSums + 2 * ((size_t)(blockIdx.x + (unsigned)a.helperBase) * TPT_Q_PATHS + p); };
+        // AOV: this path's sums {albedo, coverage} {normal, t} over the first hits of its pixel's samples so far, and with MOMENTS
+        // {sum l, sum l^2, 0, 0} over their luminances (the address is made where it is used, not held across the iteration)
+        constexpr int kAovSums = MOMENTS ? 3 : 2;
+        auto aovSum = [&]() { return a.aovSums + kAovSums * ((size_t)(blockIdx.x + (unsigned)a.helperBase) * TPT_Q_PATHS + p); };
         QLambert lam;
         lam.sdir = lam.nl = lam.albedo = lam.lightE = mk3(0, 0, 0);
         lam.cosAMax = 0.0f;
@@ -1548,6 +1660,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                                              : ((uint32_t)px | ((uint32_t)py << 16));
                 colSum[p] = mk4(0.0f, 0.0f, 0.0f, u2f(where));
                 if (AOV) aovSum()[0] = aovSum()[1] = mk4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (MOMENTS) aovSum()[2] = mk4(0.0f, 0.0f, 0.0f, 0.0f);
                 if (MOVING) movedAt = 2 * laneFrame;
                 if (VIEWS)
                     qCameraView(ldsCams[laneFrame], *ldsFc, px, py, rng, ro, rd);
@@ -1574,9 +1687,16 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                     px = (int)(f2u(c3.w) & 0xffffu);
                     py = (int)(f2u(c3.w) >> 16);
                 }
+                [[maybe_unused]] f4 mom; // MOMENTS: the sums with this sample's luminance l (include/tpt_hip.h: binary32, no FMA) and l^2 added
+                if (MOMENTS) {
+                    const float l = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
+                    const f4 m = aovSum()[2];
+                    mom = mk4(m.x + l, m.y + l * l, 0.0f, 0.0f);
+                }
                 sample++;
                 if (sample < fc.spp) {
                     colSum[p] = mk4(col.x, col.y, col.z, c3.w);
+                    if (MOMENTS) aovSum()[2] = mom;
                     if (VIEWS)
                         qCameraView(ldsCams[f2u(c3.w) >> 26], *ldsFc, px, py, rng, ro, rd);
                     else
@@ -1592,6 +1712,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                         const f4 s0 = aovSum()[0], s1 = aovSum()[1];
                         if (a.aovAlbedo) a.aovAlbedo[at] = mk4(s0.x * fc.invSpp, s0.y * fc.invSpp, s0.z * fc.invSpp, s0.w * fc.invSpp);
                         if (a.aovNormalDepth) a.aovNormalDepth[at] = mk4(s1.x * fc.invSpp, s1.y * fc.invSpp, s1.z * fc.invSpp, s1.w * fc.invSpp);
+                        if (MOMENTS) a.momentsOut[at] = mk4(mom.x * fc.invSpp, mom.y * fc.invSpp, 0.0f, 0.0f);
                     }
                     toFree = true;
                 }
@@ -1879,6 +2000,20 @@ tptTraceAovKernel<false>(const KernelArgs a)
 {
     traceQueueBody<false, false, false, false, true>(a);
 }
+// A single frame with its first-hit planes and its luminance moments (tptDrawDeviceMoments): the AOV kernel plus a third f4 of sums
+// per path.  A kernel of its own for the same reason (tests pin the AOV kernel's name); <false> as above.
+template <bool LDS_SCENE>
+__global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute__((amdgpu_num_vgpr(TPT_Q_MAX_VGPR)))
+tptTraceMomentsKernel(const KernelArgs a)
+{
+    traceQueueBody<LDS_SCENE, false, false, false, true, true>(a);
+}
+template <>
+__global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute__((amdgpu_num_vgpr(TPT_Q_MAX_VGPR_GROUPED)))
+tptTraceMomentsKernel<false>(const KernelArgs a)
+{
+    traceQueueBody<false, false, false, false, true, true>(a);
+}
 
 #if defined(TPT_TEST_HOOKS)
 // ---------------------------------------------------------------- unit-test kernels (GPU parity of the math layer)
@@ -2155,7 +2290,7 @@ size_t tptQueueLdsBytes(const KernelArgs& a, bool ldsScene)
     const int nPad = a.scene.nPairs * 2;
     const bool views = a.viewCams != nullptr; // (tptTraceViewsKernel: the cameras in LDS, TPT_Q_VIEW_PATHS path records fewer)
     const bool moving = a.moveCentres != nullptr; // (tptTraceAnimationKernel: the centres in LDS, TPT_Q_ANIM_PATHS path records fewer)
-    // (tptTraceAovKernel, a.aovSums: the LDS of its single-frame twin -- its sums live in global memory)
+    // (tptTraceAovKernel and tptTraceMomentsKernel, a.aovSums: the LDS of their single-frame twin -- their sums live in global memory)
     size_t bytes = 0;
     if (ldsScene) bytes += TPT_Q_SPH_FIXED + ((size_t)nPad * 16 <= TPT_Q_SPH_FIXED ? 0 : (size_t)nPad * 16) + (((size_t)nPad * 4 + 15) & ~(size_t)15) + (size_t)a.scene.nSpheres * 48;
     bytes += (size_t)a.scene.nLights * 32;
@@ -2205,6 +2340,15 @@ static hipError_t launchTraceAov(const KernelArgs& a, int blocks, size_t lds, hi
     hipLaunchKernelGGL(k, dim3(blocks), dim3(TPT_Q_T), lds, stream, a);
     return hipSuccess;
 }
+template <bool LDS_SCENE>
+static hipError_t launchTraceMoments(const KernelArgs& a, int blocks, size_t lds, hipStream_t stream)
+{
+    auto k = tptTraceMomentsKernel<LDS_SCENE>;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k, dim3(blocks), dim3(TPT_Q_T), lds, stream, a);
+    return hipSuccess;
+}
 hipError_t tptLaunchTraceQueue(const KernelArgs& a, bool ldsScene, int blocks, size_t lds, hipStream_t stream)
 {
     if (a.viewCams) { // (tptDrawDeviceViews: 1 .. TPT_Q_VIEWS_MAX views, the frames of the batch)
@@ -2213,9 +2357,10 @@ hipError_t tptLaunchTraceQueue(const KernelArgs& a, bool ldsScene, int blocks, s
         if (e != hipSuccess) return e;
         return hipGetLastError();
     }
-    if (a.aovSums) { // (tptDrawDeviceAov: a single frame)
+    if (a.aovSums) { // (tptDrawDeviceAov, tptDrawDeviceMoments with a.momentsOut: a single frame)
         if (a.batchFrames != 1 || a.viewCams || a.moveCentres) return hipErrorInvalidValue;
-        hipError_t e = ldsScene ? launchTraceAov<true>(a, blocks, lds, stream) : launchTraceAov<false>(a, blocks, lds, stream);
+        hipError_t e = a.momentsOut ? (ldsScene ? launchTraceMoments<true>(a, blocks, lds, stream) : launchTraceMoments<false>(a, blocks, lds, stream))
+                                    : (ldsScene ? launchTraceAov<true>(a, blocks, lds, stream) : launchTraceAov<false>(a, blocks, lds, stream));
         if (e != hipSuccess) return e;
         return hipGetLastError();
     }
@@ -2287,6 +2432,41 @@ hipError_t tptLaunchDenoise(const float* colour, const float* albedo, const floa
         else
             launchDenoiseIteration<false>(i == 0, i == iterations - 1, grid, stream, src, reinterpret_cast<const f4*>(albedo), nullptr,
                                           dst, width, height, 1 << i, ic * scale, in, id, demodulate ? 1 : 0);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        src = dst;
+    }
+    return hipSuccess;
+}
+
+template <bool GUIDE>
+static void launchDenoiseVarianceIteration(bool first, bool last, dim3 grid, hipStream_t stream, const f4* src, const f4* colour,
+                                           const f4* albedo, const f4* nd, const f4* moments, f4* dst, int width, int height, int step,
+                                           float samples, float sl2, float in, float id, int demod)
+{
+    auto k = first ? (last ? tptVarianceAtrousKernel<true, true, GUIDE> : tptVarianceAtrousKernel<true, false, GUIDE>)
+                   : (last ? tptVarianceAtrousKernel<false, true, GUIDE> : tptVarianceAtrousKernel<false, false, GUIDE>);
+    hipLaunchKernelGGL(k, grid, dim3(64, 4), 0, stream, src, colour, albedo, nd, moments, dst, width, height, step, samples, sl2, in, id,
+                       demod);
+}
+hipError_t tptLaunchDenoiseVariance(const float* colour, const float* albedo, const float* normalDepth, const float* moments, float* out,
+                                    float* scratch, int width, int height, int iterations, float samples, float sl2, float in, float id,
+                                    bool demodulate, hipStream_t stream)
+{
+    const dim3 grid((unsigned)(width + 63) / 64, (unsigned)(height + 3) / 4);
+    const f4* c = reinterpret_cast<const f4*>(colour);
+    const f4* src = c;
+    for (int i = 0; i < iterations; ++i) {
+        // (the parity that makes the last iteration write `out`)
+        f4* dst = reinterpret_cast<f4*>(((iterations - 1 - i) & 1) ? scratch : out);
+        if (normalDepth)
+            launchDenoiseVarianceIteration<true>(i == 0, i == iterations - 1, grid, stream, src, c, reinterpret_cast<const f4*>(albedo),
+                                                 reinterpret_cast<const f4*>(normalDepth), reinterpret_cast<const f4*>(moments), dst,
+                                                 width, height, 1 << i, samples, sl2, in, id, demodulate ? 1 : 0);
+        else
+            launchDenoiseVarianceIteration<false>(i == 0, i == iterations - 1, grid, stream, src, c, reinterpret_cast<const f4*>(albedo),
+                                                  nullptr, reinterpret_cast<const f4*>(moments), dst, width, height, 1 << i, samples, sl2,
+                                                  in, id, demodulate ? 1 : 0);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         src = dst;
