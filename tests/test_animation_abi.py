@@ -8,26 +8,20 @@ import math
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from isa_lib import QUEUE, code_object, count, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
 from oracle_lib import ROOT
-from test_views_abi import code_object, count  # noqa: F401  (the module-scoped fixture: the shipped code object, disassembled)
 
 INC = os.path.join(ROOT, "toypathtracer_amd", "csrc")
 SHIM = os.path.join(ROOT, "tests", "animation_filter.cpp")
 ANIM = "_ZN3tpt23tptTraceAnimationKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
-QUEUE = "_ZN3tpt19tptTraceQueueKernelILb%dELb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE, BATCH>
 
 
 def test_header_declares_the_entry_point():
-    text = open(os.path.join(ROOT, "include", "tpt_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    decl = re.search(r"TPT_API\s+int\s+tptDrawDeviceAnimation\s*\(([^)]*)\)\s*;", text)
-    assert decl, "tptDrawDeviceAnimation is not declared in include/tpt_hip.h"
-    params = [" ".join(p.split()) for p in decl.group(1).split(",")]
+    params = header_params("tptDrawDeviceAnimation")
     assert params == ["int firstFrame", "int nFrames", "const float* times", "int screenWidth", "int screenHeight", "float* deviceTile",
                       "float* deviceFrameImages", "int64_t* deviceFrameRays", "unsigned testFlags"], params
 
@@ -171,11 +165,5 @@ print("ok")
 
 
 def test_refusals_through_the_host_runtime():
-    from test_host_logic import build
-    lib = build("libtpt_hostemu.so", [])
-    env = dict(os.environ, TPT_LIB=lib, HOSTEMU_POLICY="lazy")
-    env.pop("TPT_LIB_DIR", None)
-    p = subprocess.run([sys.executable, "-c", REFUSALS, ROOT], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    out = p.stdout.decode()
-    assert p.returncode == 0 and out.rstrip().endswith("ok"), out[-3000:]
+    out = run_refusals(REFUSALS)
     assert out.count("refused:") == 11, out

@@ -2,32 +2,18 @@
 gfx950 code of the AOV kernels in the shipped library against their plain single-frame counterparts (tests/test_isa_contract.py); and
 the refusals, driven through the host runtime compiled against tests/hostemu (a refused call returns before anything is enqueued, so no
 kernel is emulated)."""
-import os
 import re
-import shutil
 import subprocess
-import sys
 
 import pytest
 
-from oracle_lib import ROOT
+from isa_lib import QUEUE, code_object, count, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
 
-LLVM = "/opt/rocm/lib/llvm/bin"
-BUNDLER = os.path.join(LLVM, "clang-offload-bundler")
-OBJDUMP = os.path.join(LLVM, "llvm-objdump")
-READELF = os.path.join(LLVM, "llvm-readelf")
-TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 AOV = "_ZN3tpt17tptTraceAovKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
-QUEUE = "_ZN3tpt19tptTraceQueueKernelILb%dELb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE, BATCH>
-HAVE_TOOLS = all(os.path.exists(p) for p in (BUNDLER, OBJDUMP, READELF)) and shutil.which("objcopy") is not None
 
 
 def test_header_declares_the_entry_point():
-    text = open(os.path.join(ROOT, "include", "tpt_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    decl = re.search(r"TPT_API\s+int\s+tptDrawDeviceAov\s*\(([^)]*)\)\s*;", text)
-    assert decl, "tptDrawDeviceAov is not declared in include/tpt_hip.h"
-    params = [" ".join(p.split()) for p in decl.group(1).split(",")]
+    params = header_params("tptDrawDeviceAov")
     assert params == ["float time", "int frameCount", "int screenWidth", "int screenHeight", "float* deviceTile", "float* deviceAlbedo",
                       "float* deviceNormalDepth", "unsigned testFlags"], params
 
@@ -59,32 +45,6 @@ def test_binding_checks_arguments_before_the_library(monkeypatch, args):
     a.update(args)
     with pytest.raises(ValueError):
         api.draw_device_aov(0.0, 0, a["w"], a["h"], a["tile"], 2, albedo_ptr=a["albedo"], normal_depth_ptr=a["nd"])
-
-
-@pytest.fixture(scope="module")
-def code_object(tmp_path_factory):
-    if not HAVE_TOOLS:
-        pytest.skip("ROCm LLVM tools not installed")
-    from toypathtracer_amd import api
-    d = tmp_path_factory.mktemp("isa_aov")
-    fat, co = str(d / "fat.bin"), str(d / "kernels.co")
-    subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", api.library_path(), fat])
-    subprocess.check_call([BUNDLER, "--unbundle", "--type=o", "--targets=" + TARGET, "--input=" + fat, "--output=" + co])
-    dis = subprocess.check_output([OBJDUMP, "-d", co]).decode()
-    notes = subprocess.check_output([READELF, "--notes", co]).decode()
-    bodies = {}
-    for m in re.finditer(r"^[0-9a-f]+ <(\w+)>:\n(.*?)(?=^[0-9a-f]+ <\w+>:|\Z)", dis, flags=re.S | re.M):
-        bodies[m.group(1)] = [ln.split("//")[0].split() for ln in m.group(2).splitlines() if ln.startswith("\t")]
-    meta = {}
-    for blk in re.split(r"\n\s+- (?=\.agpr_count)", notes)[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        meta[name] = {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*$", blk, flags=re.M)}
-    return bodies, meta
-
-
-def count(body, pattern):
-    rx = re.compile(pattern)
-    return sum(1 for ins in body if ins and rx.match(ins[0]))
 
 
 @pytest.mark.parametrize("lds", [1, 0], ids=["lds-scene", "grouped"])
@@ -159,11 +119,5 @@ print("ok")
 
 
 def test_refusals_through_the_host_runtime(tmp_path):
-    from test_host_logic import build
-    lib = build("libtpt_hostemu.so", [])
-    env = dict(os.environ, TPT_LIB=lib, HOSTEMU_POLICY="lazy")
-    env.pop("TPT_LIB_DIR", None)
-    p = subprocess.run([sys.executable, "-c", REFUSALS, ROOT], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    out = p.stdout.decode()
-    assert p.returncode == 0 and out.rstrip().endswith("ok"), out[-3000:]
+    out = run_refusals(REFUSALS)
     assert out.count("refused:") == 17, out

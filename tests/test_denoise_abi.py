@@ -1,35 +1,22 @@
 """tptDenoiseDevice without a GPU: the declaration, the binding and the export of the entry point; the binding's argument checks; the
 gfx950 code of the a-trous kernels in the shipped library; and every refusal of the ABI, driven through the host runtime compiled
 against tests/hostemu (a refused call returns before anything is enqueued, so no kernel is emulated)."""
-import os
 import re
-import shutil
 import subprocess
-import sys
 
 import pytest
 
-from oracle_lib import ROOT
+from isa_lib import code_object, count, header, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
 
-LLVM = "/opt/rocm/lib/llvm/bin"
-BUNDLER = os.path.join(LLVM, "clang-offload-bundler")
-OBJDUMP = os.path.join(LLVM, "llvm-objdump")
-READELF = os.path.join(LLVM, "llvm-readelf")
-TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 DENOISE = "_ZN3tpt16tptDenoiseKernelILb%dELb%dELb%dEEEvPKNS_2f4ES3_S3_PS1_iiifffi"  # <FIRST, LAST, GUIDE>
-HAVE_TOOLS = all(os.path.exists(p) for p in (BUNDLER, OBJDUMP, READELF)) and shutil.which("objcopy") is not None
 
 
 def test_header_declares_the_entry_point():
-    text = open(os.path.join(ROOT, "include", "tpt_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    decl = re.search(r"TPT_API\s+int\s+tptDenoiseDevice\s*\(([^)]*)\)\s*;", text)
-    assert decl, "tptDenoiseDevice is not declared in include/tpt_hip.h"
-    params = [" ".join(p.split()) for p in decl.group(1).split(",")]
+    params = header_params("tptDenoiseDevice")
     assert params == ["int screenWidth", "int screenHeight", "const float* deviceColour", "const float* deviceAlbedo",
                       "const float* deviceNormalDepth", "float* deviceOut", "int iterations", "float sigmaColour", "float sigmaNormal",
                       "float sigmaDepth", "unsigned denoiseFlags"], params
-    assert re.search(r"enum\s*\{\s*TPT_DENOISE_DEMODULATE\s*=\s*1\s*<<\s*0\s*\}\s*;", text)
+    assert re.search(r"enum\s*\{\s*TPT_DENOISE_DEMODULATE\s*=\s*1\s*<<\s*0\s*\}\s*;", header())
 
 
 def test_binding_and_export():
@@ -84,32 +71,6 @@ def test_binding_passes_what_it_means(monkeypatch):
     assert a0[6] == 3 and a0[7] == 0.5 and a0[8] > 0 and a0[9] > 0 and a0[10] == 1
     assert a1[3] is None and a1[4] is None and a1[8] == 0.0 and a1[9] == 0.0 and a1[10] == 0
     assert a2[3] is not None and a2[10] == 0
-
-
-@pytest.fixture(scope="module")
-def code_object(tmp_path_factory):
-    if not HAVE_TOOLS:
-        pytest.skip("ROCm LLVM tools not installed")
-    from toypathtracer_amd import api
-    d = tmp_path_factory.mktemp("isa_denoise")
-    fat, co = str(d / "fat.bin"), str(d / "kernels.co")
-    subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", api.library_path(), fat])
-    subprocess.check_call([BUNDLER, "--unbundle", "--type=o", "--targets=" + TARGET, "--input=" + fat, "--output=" + co])
-    dis = subprocess.check_output([OBJDUMP, "-d", co]).decode()
-    notes = subprocess.check_output([READELF, "--notes", co]).decode()
-    bodies = {}
-    for m in re.finditer(r"^[0-9a-f]+ <(\w+)>:\n(.*?)(?=^[0-9a-f]+ <\w+>:|\Z)", dis, flags=re.S | re.M):
-        bodies[m.group(1)] = [ln.split("//")[0].split() for ln in m.group(2).splitlines() if ln.startswith("\t")]
-    meta = {}
-    for blk in re.split(r"\n\s+- (?=\.agpr_count)", notes)[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        meta[name] = {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*$", blk, flags=re.M)}
-    return bodies, meta
-
-
-def count(body, pattern):
-    rx = re.compile(pattern)
-    return sum(1 for ins in body if ins and rx.match(ins[0]))
 
 
 @pytest.mark.parametrize("first,last,guide", [(f, l, g) for f in (1, 0) for l in (1, 0) for g in (1, 0)],
@@ -199,13 +160,7 @@ print("ok")
 
 
 def test_refusals_through_the_host_runtime(tmp_path):
-    from test_host_logic import build
     # (the host runtime with the counting launcher of tests/hostemu_denoise.cpp beside the emulated kernels)
-    lib = build("libtpt_hostemu_denoise.so", [os.path.join(ROOT, "tests", "hostemu_denoise.cpp")])
-    env = dict(os.environ, TPT_LIB=lib, HOSTEMU_POLICY="lazy")
-    env.pop("TPT_LIB_DIR", None)
-    p = subprocess.run([sys.executable, "-c", REFUSALS, ROOT], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    out = p.stdout.decode()
-    assert p.returncode == 0 and out.rstrip().endswith("ok"), out[-3000:]
+    out = run_refusals(REFUSALS, "libtpt_hostemu_denoise.so", ["hostemu_denoise.cpp"])
     assert out.count("refused:") == 1 + 5 + 2 + 3 + 2 + 3 + 27 + 3 + 4, out
     assert out.count("accepted:") == 8, out

@@ -10,52 +10,11 @@ a profiling session to find when it was lost:
   * register spills stay where they were measured in round 5 (headline: 2 VGPRs, 12 B of scratch, 33 SGPRs spilled to lanes; grouped: 22 VGPRs, 92 B);
   * the hot path holds no IEEE division expansion beyond the cold fallbacks of the short forms (tpt_math.h).
 """
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-from oracle_lib import ROOT
+from isa_lib import HAVE_TOOLS, QUEUE, code_object, count  # noqa: F401  (code_object: a module fixture)
 
-LLVM = "/opt/rocm/lib/llvm/bin"
-BUNDLER = os.path.join(LLVM, "clang-offload-bundler")
-OBJDUMP = os.path.join(LLVM, "llvm-objdump")
-READELF = os.path.join(LLVM, "llvm-readelf")
-TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
-
-pytestmark = pytest.mark.skipif(not all(os.path.exists(p) for p in (BUNDLER, OBJDUMP, READELF)) or shutil.which("objcopy") is None,
-                                reason="ROCm LLVM tools not installed")
-
-QUEUE = "_ZN3tpt19tptTraceQueueKernelILb%dELb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE, BATCH>
-
-
-@pytest.fixture(scope="module")
-def code_object(tmp_path_factory):
-    from toypathtracer_amd import api
-    d = tmp_path_factory.mktemp("isa")
-    fat, co = str(d / "fat.bin"), str(d / "kernels.co")
-    subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", api.library_path(), fat])
-    targets = subprocess.check_output([BUNDLER, "--list", "--type=o", "--input=" + fat]).decode().split()
-    assert [t for t in targets if t.startswith("hipv4-amdgcn")] == [TARGET], "the library carries gfx950 code only: %r" % targets
-    subprocess.check_call([BUNDLER, "--unbundle", "--type=o", "--targets=" + TARGET, "--input=" + fat, "--output=" + co])
-    dis = subprocess.check_output([OBJDUMP, "-d", co]).decode()
-    notes = subprocess.check_output([READELF, "--notes", co]).decode()
-    bodies = {}
-    for m in re.finditer(r"^[0-9a-f]+ <(\w+)>:\n(.*?)(?=^[0-9a-f]+ <\w+>:|\Z)", dis, flags=re.S | re.M):
-        # one instruction per line: "\t<mnemonic> operands  // address: encoding"
-        bodies[m.group(1)] = [ln.split("//")[0].split() for ln in m.group(2).splitlines() if ln.startswith("\t")]
-    meta = {}
-    for blk in re.split(r"\n\s+- (?=\.agpr_count)", notes)[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        meta[name] = {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*$", blk, flags=re.M)}
-    return bodies, meta
-
-
-def count(body, pattern):
-    rx = re.compile(pattern)
-    return sum(1 for ins in body if ins and rx.match(ins[0]))
+pytestmark = pytest.mark.skipif(not HAVE_TOOLS, reason="ROCm LLVM tools not installed")
 
 
 def test_every_kernel_of_the_library_is_there(code_object):

@@ -3,36 +3,23 @@ checks and moment_samples; the gfx950 code of the new kernels in the shipped lib
 kernel, tests/test_denoise_abi.py's for the filter); and the refusals, driven through the host runtime compiled against tests/hostemu
 (a refused call returns before anything is enqueued; the filter's launcher is tests/hostemu_variance.cpp, which counts and runs
 nothing)."""
-import os
 import re
 import subprocess
-import sys
 
 import pytest
 
-from oracle_lib import ROOT
-from test_aov_abi import AOV, QUEUE, code_object, count  # noqa: F401  (code_object: the shipped code object, a module fixture)
+from isa_lib import QUEUE, code_object, count, header, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
+from test_aov_abi import AOV
 
 MOMENTS = "_ZN3tpt21tptTraceMomentsKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
 VARIANCE = "_ZN3tpt23tptVarianceAtrousKernelILb%dELb%dELb%dEEEvPKNS_2f4ES3_S3_S3_S3_PS1_iiiffffi"  # <FIRST, LAST, GUIDE>
 
 
-def header():
-    text = open(os.path.join(ROOT, "include", "tpt_hip.h")).read()
-    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-
-def params(name):
-    decl = re.search(r"TPT_API\s+int\s+%s\s*\(([^)]*)\)\s*;" % name, header())
-    assert decl, "%s is not declared in include/tpt_hip.h" % name
-    return [" ".join(p.split()) for p in decl.group(1).split(",")]
-
-
 def test_header_declares_the_entry_points():
-    assert params("tptDrawDeviceMoments") == ["float time", "int frameCount", "int screenWidth", "int screenHeight", "float* deviceTile",
+    assert header_params("tptDrawDeviceMoments") == ["float time", "int frameCount", "int screenWidth", "int screenHeight", "float* deviceTile",
                                               "float* deviceAlbedo", "float* deviceNormalDepth", "float* deviceMoments",
                                               "unsigned testFlags"]
-    assert params("tptDenoiseDeviceVariance") == ["int screenWidth", "int screenHeight", "const float* deviceColour",
+    assert header_params("tptDenoiseDeviceVariance") == ["int screenWidth", "int screenHeight", "const float* deviceColour",
                                                   "const float* deviceAlbedo", "const float* deviceNormalDepth",
                                                   "const float* deviceMoments", "float samples", "float* deviceOut", "int iterations",
                                                   "float sigmaLuminance", "float sigmaNormal", "float sigmaDepth", "unsigned denoiseFlags"]
@@ -238,12 +225,6 @@ print("ok")
 
 
 def test_refusals_through_the_host_runtime(tmp_path):
-    from test_host_logic import build
-    lib = build("libtpt_hostemu_variance.so", [os.path.join(ROOT, "tests", "hostemu_variance.cpp")])
-    env = dict(os.environ, TPT_LIB=lib, HOSTEMU_POLICY="lazy")
-    env.pop("TPT_LIB_DIR", None)
-    p = subprocess.run([sys.executable, "-c", REFUSALS, ROOT], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    out = p.stdout.decode()
-    assert p.returncode == 0 and out.rstrip().endswith("ok"), out[-3000:]
+    out = run_refusals(REFUSALS, "libtpt_hostemu_variance.so", ["hostemu_variance.cpp"])
     assert out.count("refused:") == 2 + 9 + 8 + 2 + 6 + 2 + 5 + 6 + 4 + 3, out
     assert out.count("accepted:") == 9, out

@@ -1,31 +1,18 @@
 """tptDrawDeviceViews without a GPU: the declaration, the binding and the export of the entry point; the gfx950 code of the views
 kernels in the shipped library (the contract of the path-queue kernels, tests/test_isa_contract.py); and its refusals, driven through
 the host runtime compiled against tests/hostemu (a refused call returns before anything is enqueued, so no kernel is emulated)."""
-import os
 import re
-import shutil
 import subprocess
-import sys
 
 import pytest
 
-from oracle_lib import ROOT
+from isa_lib import code_object, count, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
 
-LLVM = "/opt/rocm/lib/llvm/bin"
-BUNDLER = os.path.join(LLVM, "clang-offload-bundler")
-OBJDUMP = os.path.join(LLVM, "llvm-objdump")
-READELF = os.path.join(LLVM, "llvm-readelf")
-TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 VIEWS = "_ZN3tpt19tptTraceViewsKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
-HAVE_TOOLS = all(os.path.exists(p) for p in (BUNDLER, OBJDUMP, READELF)) and shutil.which("objcopy") is not None
 
 
 def test_header_declares_the_entry_point():
-    text = open(os.path.join(ROOT, "include", "tpt_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    decl = re.search(r"TPT_API\s+int\s+tptDrawDeviceViews\s*\(([^)]*)\)\s*;", text)
-    assert decl, "tptDrawDeviceViews is not declared in include/tpt_hip.h"
-    params = [" ".join(p.split()) for p in decl.group(1).split(",")]
+    params = header_params("tptDrawDeviceViews")
     assert params == ["float time", "int frameCount", "int screenWidth", "int screenHeight", "int nViews", "const float* views",
                       "float* deviceTiles", "int64_t* deviceViewRays", "unsigned testFlags"], params
 
@@ -44,32 +31,6 @@ def test_views_argument_shape_is_checked_before_the_library():
     from toypathtracer_amd import api
     with pytest.raises(ValueError):
         api.draw_device_views(0.0, 0, 8, 8, [[0.0] * 8], 0, 0)
-
-
-@pytest.fixture(scope="module")
-def code_object(tmp_path_factory):
-    if not HAVE_TOOLS:
-        pytest.skip("ROCm LLVM tools not installed")
-    from toypathtracer_amd import api
-    d = tmp_path_factory.mktemp("isa_views")
-    fat, co = str(d / "fat.bin"), str(d / "kernels.co")
-    subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", api.library_path(), fat])
-    subprocess.check_call([BUNDLER, "--unbundle", "--type=o", "--targets=" + TARGET, "--input=" + fat, "--output=" + co])
-    dis = subprocess.check_output([OBJDUMP, "-d", co]).decode()
-    notes = subprocess.check_output([READELF, "--notes", co]).decode()
-    bodies = {}
-    for m in re.finditer(r"^[0-9a-f]+ <(\w+)>:\n(.*?)(?=^[0-9a-f]+ <\w+>:|\Z)", dis, flags=re.S | re.M):
-        bodies[m.group(1)] = [ln.split("//")[0].split() for ln in m.group(2).splitlines() if ln.startswith("\t")]
-    meta = {}
-    for blk in re.split(r"\n\s+- (?=\.agpr_count)", notes)[1:]:
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        meta[name] = {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*$", blk, flags=re.M)}
-    return bodies, meta
-
-
-def count(body, pattern):
-    rx = re.compile(pattern)
-    return sum(1 for ins in body if ins and rx.match(ins[0]))
 
 
 @pytest.mark.parametrize("lds", [1, 0], ids=["lds-scene", "grouped"])
@@ -140,11 +101,5 @@ print("ok")
 
 
 def test_refusals_through_the_host_runtime(tmp_path):
-    from test_host_logic import build
-    lib = build("libtpt_hostemu.so", [])
-    env = dict(os.environ, TPT_LIB=lib, HOSTEMU_POLICY="lazy")
-    env.pop("TPT_LIB_DIR", None)
-    p = subprocess.run([sys.executable, "-c", REFUSALS, ROOT], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    out = p.stdout.decode()
-    assert p.returncode == 0 and out.rstrip().endswith("ok"), out[-3000:]
+    out = run_refusals(REFUSALS)
     assert out.count("refused:") == 17, out

@@ -428,16 +428,33 @@ def draw_device_animation(times, first_frame, w, h, tile_ptr, flags, frame_image
                                                frame_images_ptr, frame_rays_ptr, flags), "tptDrawDeviceAnimation")
 
 
+def _positive_ints(*named):
+    """(name, value) pairs: ValueError for the first value that is not an int > 0"""
+    for name, v in named:
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v <= 0:
+            raise ValueError("%s: a positive int expected, got %r" % (name, v))
+
+
+def _pointers(*named):
+    """(name, value) pairs: ValueError for the first value that is neither None nor a device pointer (an int >= 0)"""
+    for name, v in named:
+        if v is not None and (not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 0):
+            raise ValueError("%s: a device pointer (int) or None expected, got %r" % (name, v))
+
+
+def _sigmas(*named):
+    """(name, value) pairs: ValueError for the first value that is not a finite number >= 0"""
+    for name, v in named:
+        if not isinstance(v, (int, float, np.integer, np.floating)) or isinstance(v, bool) or not v >= 0 or v == float("inf"):
+            raise ValueError("%s: a finite float >= 0 expected, got %r" % (name, v))
+
+
 def draw_device_aov(time, frame, w, h, tile_ptr, flags, albedo_ptr=None, normal_depth_ptr=None):
     """draw_device on tile_ptr (same bits, same ray count) plus the first-hit planes of the samples: albedo_ptr / normal_depth_ptr, device
     buffers of h*w*4 floats (None = not wanted; at least one), overwritten with {albedo, coverage} / {normal, depth} averaged over the
     samples.  Ordered on the context's stream like the tile."""
-    for name, v in (("w", w), ("h", h)):
-        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v <= 0:
-            raise ValueError("%s: a positive int expected, got %r" % (name, v))
-    for name, v in (("tile_ptr", tile_ptr), ("albedo_ptr", albedo_ptr), ("normal_depth_ptr", normal_depth_ptr)):
-        if v is not None and (not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 0):
-            raise ValueError("%s: a device pointer (int) or None expected, got %r" % (name, v))
+    _positive_ints(("w", w), ("h", h))
+    _pointers(("tile_ptr", tile_ptr), ("albedo_ptr", albedo_ptr), ("normal_depth_ptr", normal_depth_ptr))
     if not tile_ptr:
         raise ValueError("tile_ptr: a device tile is required")
     if not albedo_ptr and not normal_depth_ptr:
@@ -457,17 +474,11 @@ def denoise_device(w, h, colour_ptr, out_ptr, albedo_ptr=None, normal_depth_ptr=
     """tptDenoiseDevice: the edge-avoiding a-trous filter of the tile at colour_ptr into out_ptr (device buffers of h*w*4 floats), guided
     by draw_device_aov's planes (None = not given).  A guide's sigma is ignored (passed as 0) when its plane is not given; demodulate=None
     means "on if an albedo plane is given".  The default sigmas are DESIGN.md's measured choice.  Ordered on the context's stream."""
-    for name, v in (("w", w), ("h", h), ("iterations", iterations)):
-        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v <= 0:
-            raise ValueError("%s: a positive int expected, got %r" % (name, v))
-    for name, v in (("colour_ptr", colour_ptr), ("out_ptr", out_ptr), ("albedo_ptr", albedo_ptr), ("normal_depth_ptr", normal_depth_ptr)):
-        if v is not None and (not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 0):
-            raise ValueError("%s: a device pointer (int) or None expected, got %r" % (name, v))
+    _positive_ints(("w", w), ("h", h), ("iterations", iterations))
+    _pointers(("colour_ptr", colour_ptr), ("out_ptr", out_ptr), ("albedo_ptr", albedo_ptr), ("normal_depth_ptr", normal_depth_ptr))
     if not colour_ptr or not out_ptr:
         raise ValueError("colour_ptr, out_ptr: device buffers are required")
-    for name, v in (("sigma_colour", sigma_colour), ("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth)):
-        if not isinstance(v, (int, float, np.integer, np.floating)) or isinstance(v, bool) or not v >= 0 or v == float("inf"):
-            raise ValueError("%s: a finite float >= 0 expected, got %r" % (name, v))
+    _sigmas(("sigma_colour", sigma_colour), ("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth))
     if demodulate is None:
         demodulate = bool(albedo_ptr)
     if demodulate and not albedo_ptr:
@@ -483,12 +494,8 @@ def draw_device_moments(time, frame, w, h, tile_ptr, moments_ptr, flags, albedo_
     """draw_device_aov (same tile bits, same ray count, the same planes where given; both may be None) plus the luminance moments of the
     frame's samples, blended into moments_ptr (a device buffer of h*w*4 floats) with the tile's lerp factor: {mean l, mean l^2, 0} of
     l = (0.2126 r + 0.7152 g) + 0.0722 b, .w kept.  Ordered on the context's stream like the tile."""
-    for name, v in (("w", w), ("h", h)):
-        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v <= 0:
-            raise ValueError("%s: a positive int expected, got %r" % (name, v))
-    for name, v in (("tile_ptr", tile_ptr), ("moments_ptr", moments_ptr), ("albedo_ptr", albedo_ptr), ("normal_depth_ptr", normal_depth_ptr)):
-        if v is not None and (not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 0):
-            raise ValueError("%s: a device pointer (int) or None expected, got %r" % (name, v))
+    _positive_ints(("w", w), ("h", h))
+    _pointers(("tile_ptr", tile_ptr), ("moments_ptr", moments_ptr), ("albedo_ptr", albedo_ptr), ("normal_depth_ptr", normal_depth_ptr))
     if not tile_ptr or not moments_ptr:
         raise ValueError("tile_ptr, moments_ptr: device buffers are required")
     _chk(load_library().tptDrawDeviceMoments(time, frame, w, h, C.c_void_p(tile_ptr), C.c_void_p(albedo_ptr) if albedo_ptr else None,
@@ -523,22 +530,16 @@ def denoise_device_variance(w, h, colour_ptr, moments_ptr, samples, out_ptr, alb
     the per-pixel variance of draw_device_moments' moments (moments_ptr) over `samples` samples (moment_samples).  Guides and demodulate
     as denoise_device; a progressive caller passes guide planes averaged over its frames like the tile (include/tpt_hip.h).  Ordered on
     the context's stream."""
-    for name, v in (("w", w), ("h", h), ("iterations", iterations)):
-        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v <= 0:
-            raise ValueError("%s: a positive int expected, got %r" % (name, v))
-    for name, v in (("colour_ptr", colour_ptr), ("moments_ptr", moments_ptr), ("out_ptr", out_ptr), ("albedo_ptr", albedo_ptr),
-                    ("normal_depth_ptr", normal_depth_ptr)):
-        if v is not None and (not isinstance(v, (int, np.integer)) or isinstance(v, bool) or v < 0):
-            raise ValueError("%s: a device pointer (int) or None expected, got %r" % (name, v))
+    _positive_ints(("w", w), ("h", h), ("iterations", iterations))
+    _pointers(("colour_ptr", colour_ptr), ("moments_ptr", moments_ptr), ("out_ptr", out_ptr), ("albedo_ptr", albedo_ptr),
+              ("normal_depth_ptr", normal_depth_ptr))
     if not colour_ptr or not out_ptr or not moments_ptr:
         raise ValueError("colour_ptr, moments_ptr, out_ptr: device buffers are required")
     if not isinstance(samples, (int, float, np.integer, np.floating)) or isinstance(samples, bool) or not 1 <= samples < float("inf"):
         raise ValueError("samples: a finite number >= 1 expected, got %r" % (samples,))
     if not isinstance(sigma_luminance, (int, float, np.integer, np.floating)) or isinstance(sigma_luminance, bool) or not 0 < sigma_luminance <= 1e6:
         raise ValueError("sigma_luminance: a float in (0, 1e6] expected, got %r" % (sigma_luminance,))
-    for name, v in (("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth)):
-        if not isinstance(v, (int, float, np.integer, np.floating)) or isinstance(v, bool) or not v >= 0 or v == float("inf"):
-            raise ValueError("%s: a finite float >= 0 expected, got %r" % (name, v))
+    _sigmas(("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth))
     if demodulate is None:
         demodulate = bool(albedo_ptr)
     if demodulate and not albedo_ptr:

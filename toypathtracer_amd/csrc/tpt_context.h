@@ -352,6 +352,16 @@ inline int refuse(const std::string& what)
     g.err = what;
     return kRefused;
 }
+// Does the buffer at p share a byte with one of `others` (null ones skipped)?  All are `bytes` long.
+inline bool overlapsAny(const void* p, std::initializer_list<const void*> others, uintptr_t bytes)
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    for (const void* other : others) {
+        const uintptr_t o = reinterpret_cast<uintptr_t>(other);
+        if (other && a < o + bytes && o < a + bytes) return true;
+    }
+    return false;
+}
 #define HIPCHK(x)                                   \
     do {                                            \
         hipError_t _e = (x);                        \

@@ -77,6 +77,48 @@ int traceAhead(int frameCount, int w, int h, unsigned testFlags, unsigned long l
     return 0;
 }
 
+// What tptDenoiseDevice and tptDenoiseDeviceVariance refuse, in the order they check it (fn: the entry point).  The variance filter
+// (`variance`) also requires deviceMoments, an input like the others, and checks `samples` and its luminance sigma (`sigma0`) before the
+// guides' sigmas; the plain filter checks its colour sigma (`sigma0`) with them.
+static int checkDenoise(const char* fn, bool variance, int w, int h, const float* colour, const float* albedo, const float* normalDepth,
+                        const float* moments, const float* out, int iterations, float samples, float sigma0, float sigmaNormal,
+                        float sigmaDepth, unsigned flags)
+{
+    const std::string f(fn);
+    if (w < 1 || w > 8192 || h < 1 || h > 8192) return fail(f + ": w and h must lie in 1..8192");
+    if (!colour || !out) return fail(f + ": deviceColour and deviceOut are required");
+    if (variance && !moments) return fail(f + ": deviceMoments is required");
+    if (overlapsAny(out, {colour, albedo, normalDepth, moments}, (uintptr_t)w * (uintptr_t)h * 16u)) return fail(f + ": deviceOut overlaps an input");
+    if (iterations < 1 || iterations > 8) return fail(f + ": iterations must lie in 1..8");
+    auto sigmaOk = [](float s) { return s == 0.0f || (s >= 1e-6f && s <= 1e6f); }; // (NaN fails both comparisons)
+    if (variance) {
+        if (!(samples >= 1.0f && samples <= 3.40282347e38f)) return fail(f + ": samples must be finite and at least 1"); // (NaN and +inf fail)
+        if (!(sigma0 > 0.0f && sigma0 <= 1e6f)) return fail(f + ": sigmaLuminance must lie in (0, 1e6]");
+        if (!sigmaOk(sigmaNormal) || !sigmaOk(sigmaDepth)) return fail(f + ": sigmaNormal and sigmaDepth must be 0 or lie in [1e-6, 1e6]");
+    } else if (!sigmaOk(sigma0) || !sigmaOk(sigmaNormal) || !sigmaOk(sigmaDepth)) {
+        return fail(f + ": every sigma must be 0 or lie in [1e-6, 1e6]");
+    }
+    if ((sigmaNormal != 0.0f || sigmaDepth != 0.0f) && !normalDepth) return fail(f + ": sigmaNormal and sigmaDepth need deviceNormalDepth");
+    if (flags & ~(unsigned)TPT_DENOISE_DEMODULATE) return fail(f + ": unknown flag bits");
+    if ((flags & TPT_DENOISE_DEMODULATE) && !albedo) return fail(f + ": TPT_DENOISE_DEMODULATE needs deviceAlbedo");
+    return 0;
+}
+
+// The context's scratch plane of both a-trous filters, grown to a w x h plane when a call needs more.
+static int ensureDenoisePlane(int w, int h)
+{
+    const uintptr_t bytes = (uintptr_t)w * (uintptr_t)h * 16u;
+    if (bytes <= g.denoiseBytes) return 0;
+    // (an earlier call's iterations may still be reading the plane being replaced; only the context stream uses it)
+    HIPCHK(hipStreamSynchronize(g.stream));
+    (void)hipFree(g.dDenoise);
+    g.dDenoise = nullptr;
+    g.denoiseBytes = 0;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dDenoise), bytes));
+    g.denoiseBytes = bytes;
+    return 0;
+}
+
 } // namespace tpth
 
 extern "C" {
@@ -295,36 +337,15 @@ int tptDenoiseDevice(int w, int h, const float* deviceColour, const float* devic
                      int iterations, float sigmaColour, float sigmaNormal, float sigmaDepth, unsigned denoiseFlags)
 {
     if (requireInit()) return -1;
-    if (w < 1 || w > 8192 || h < 1 || h > 8192) return fail("tptDenoiseDevice: w and h must lie in 1..8192");
-    if (!deviceColour || !deviceOut) return fail("tptDenoiseDevice: deviceColour and deviceOut are required");
-    const uintptr_t bytes = (uintptr_t)w * (uintptr_t)h * 16u;
-    const uintptr_t o = reinterpret_cast<uintptr_t>(deviceOut);
-    for (const float* in : {deviceColour, deviceAlbedo, deviceNormalDepth}) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(in);
-        if (in && o < a + bytes && a < o + bytes) return fail("tptDenoiseDevice: deviceOut overlaps an input");
-    }
-    if (iterations < 1 || iterations > 8) return fail("tptDenoiseDevice: iterations must lie in 1..8");
-    for (float s : {sigmaColour, sigmaNormal, sigmaDepth}) // (NaN fails both comparisons)
-        if (!(s == 0.0f || (s >= 1e-6f && s <= 1e6f)))
-            return fail("tptDenoiseDevice: every sigma must be 0 or lie in [1e-6, 1e6]");
-    if ((sigmaNormal != 0.0f || sigmaDepth != 0.0f) && !deviceNormalDepth)
-        return fail("tptDenoiseDevice: sigmaNormal and sigmaDepth need deviceNormalDepth");
-    if (denoiseFlags & ~(unsigned)TPT_DENOISE_DEMODULATE) return fail("tptDenoiseDevice: unknown flag bits");
-    const bool demodulate = (denoiseFlags & TPT_DENOISE_DEMODULATE) != 0;
-    if (demodulate && !deviceAlbedo) return fail("tptDenoiseDevice: TPT_DENOISE_DEMODULATE needs deviceAlbedo");
+    int rc = checkDenoise("tptDenoiseDevice", false, w, h, deviceColour, deviceAlbedo, deviceNormalDepth, nullptr, deviceOut, iterations, 0.0f,
+                          sigmaColour, sigmaNormal, sigmaDepth, denoiseFlags);
+    if (rc) return rc;
     if (!tptLaunchDenoise) return fail("tptDenoiseDevice: this build has no a-trous kernel");
-    if (iterations > 1 && bytes > g.denoiseBytes) {
-        // (an earlier call's iterations may still be reading the plane being replaced; only the context stream uses it)
-        HIPCHK(hipStreamSynchronize(g.stream));
-        (void)hipFree(g.dDenoise);
-        g.dDenoise = nullptr;
-        g.denoiseBytes = 0;
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dDenoise), bytes));
-        g.denoiseBytes = bytes;
-    }
+    if (iterations > 1 && (rc = ensureDenoisePlane(w, h))) return rc;
     auto inv2 = [](float s) { return s > 0.0f ? 1.0f / (s * s) : 0.0f; };
     HIPCHK(tptLaunchDenoise(deviceColour, deviceAlbedo, deviceNormalDepth, deviceOut, reinterpret_cast<float*>(g.dDenoise), w, h,
-                            iterations, inv2(sigmaColour), inv2(sigmaNormal), inv2(sigmaDepth), demodulate, g.stream));
+                            iterations, inv2(sigmaColour), inv2(sigmaNormal), inv2(sigmaDepth), (denoiseFlags & TPT_DENOISE_DEMODULATE) != 0,
+                            g.stream));
     return 0;
 }
 
@@ -335,41 +356,15 @@ int tptDenoiseDeviceVariance(int w, int h, const float* deviceColour, const floa
                              float sigmaNormal, float sigmaDepth, unsigned denoiseFlags)
 {
     if (requireInit()) return -1;
-    if (w < 1 || w > 8192 || h < 1 || h > 8192) return fail("tptDenoiseDeviceVariance: w and h must lie in 1..8192");
-    if (!deviceColour || !deviceOut) return fail("tptDenoiseDeviceVariance: deviceColour and deviceOut are required");
-    if (!deviceMoments) return fail("tptDenoiseDeviceVariance: deviceMoments is required");
-    const uintptr_t bytes = (uintptr_t)w * (uintptr_t)h * 16u;
-    const uintptr_t o = reinterpret_cast<uintptr_t>(deviceOut);
-    for (const float* in : {deviceColour, deviceAlbedo, deviceNormalDepth, deviceMoments}) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(in);
-        if (in && o < a + bytes && a < o + bytes) return fail("tptDenoiseDeviceVariance: deviceOut overlaps an input");
-    }
-    if (iterations < 1 || iterations > 8) return fail("tptDenoiseDeviceVariance: iterations must lie in 1..8");
-    if (!(samples >= 1.0f && samples <= 3.40282347e38f)) // (NaN and +inf fail)
-        return fail("tptDenoiseDeviceVariance: samples must be finite and at least 1");
-    if (!(sigmaLuminance > 0.0f && sigmaLuminance <= 1e6f)) return fail("tptDenoiseDeviceVariance: sigmaLuminance must lie in (0, 1e6]");
-    for (float s : {sigmaNormal, sigmaDepth}) // (NaN fails both comparisons)
-        if (!(s == 0.0f || (s >= 1e-6f && s <= 1e6f)))
-            return fail("tptDenoiseDeviceVariance: sigmaNormal and sigmaDepth must be 0 or lie in [1e-6, 1e6]");
-    if ((sigmaNormal != 0.0f || sigmaDepth != 0.0f) && !deviceNormalDepth)
-        return fail("tptDenoiseDeviceVariance: sigmaNormal and sigmaDepth need deviceNormalDepth");
-    if (denoiseFlags & ~(unsigned)TPT_DENOISE_DEMODULATE) return fail("tptDenoiseDeviceVariance: unknown flag bits");
-    const bool demodulate = (denoiseFlags & TPT_DENOISE_DEMODULATE) != 0;
-    if (demodulate && !deviceAlbedo) return fail("tptDenoiseDeviceVariance: TPT_DENOISE_DEMODULATE needs deviceAlbedo");
+    int rc = checkDenoise("tptDenoiseDeviceVariance", true, w, h, deviceColour, deviceAlbedo, deviceNormalDepth, deviceMoments, deviceOut,
+                          iterations, samples, sigmaLuminance, sigmaNormal, sigmaDepth, denoiseFlags);
+    if (rc) return rc;
     if (!tptLaunchDenoiseVariance) return fail("tptDenoiseDeviceVariance: this build has no variance-guided a-trous kernel");
-    if (iterations > 1 && bytes > g.denoiseBytes) {
-        // (an earlier call's iterations may still be reading the plane being replaced; only the context stream uses it)
-        HIPCHK(hipStreamSynchronize(g.stream));
-        (void)hipFree(g.dDenoise);
-        g.dDenoise = nullptr;
-        g.denoiseBytes = 0;
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dDenoise), bytes));
-        g.denoiseBytes = bytes;
-    }
+    if (iterations > 1 && (rc = ensureDenoisePlane(w, h))) return rc;
     auto inv2 = [](float s) { return s > 0.0f ? 1.0f / (s * s) : 0.0f; };
     HIPCHK(tptLaunchDenoiseVariance(deviceColour, deviceAlbedo, deviceNormalDepth, deviceMoments, deviceOut,
                                     reinterpret_cast<float*>(g.dDenoise), w, h, iterations, samples, sigmaLuminance * sigmaLuminance,
-                                    inv2(sigmaNormal), inv2(sigmaDepth), demodulate, g.stream));
+                                    inv2(sigmaNormal), inv2(sigmaDepth), (denoiseFlags & TPT_DENOISE_DEMODULATE) != 0, g.stream));
     return 0;
 }
 

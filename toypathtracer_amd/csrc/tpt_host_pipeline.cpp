@@ -106,6 +106,13 @@ int reserveSlotBuffers(int nSlots, size_t colourBytes, size_t stackBytes)
     return 0;
 }
 
+// The context is set up for the path-queue kernel: persistent 3, two-phase HitSpheres, per-pixel seeds, the recursive fold, and at most
+// 2047 spp (its 64-B path record holds 11 bits of sample index).  chooseKernel adds what a frame and a scene must fit.
+static bool pathQueueContext()
+{
+    return g.persist == 3 && g.hs == HS_TWO_PHASE && g.seedMode == SEED_PER_PIXEL && g.foldMode == FOLD_RECURSIVE && g.spp <= 2047;
+}
+
 // Which kernel runs this frame, how much LDS it takes, how many workgroups fit on a CU.
 int chooseKernel(FramePlan& P)
 {
@@ -119,11 +126,9 @@ int chooseKernel(FramePlan& P)
     // bounce stack: the lane-refill kernel keeps the first levels in LDS and spills the rare deep ones to global memory
     a.ldsStackLevels = g.foldMode == FOLD_RECURSIVE ? g.ldsStackLevels : TPT_MAX_DEPTH;
     const size_t ldsV1 = tptLdsBytes(a, g.foldMode, P.ldsScene);
-    // path-queue kernel: PER_PIXEL seeds, recursive fold, two-phase HitSpheres
-    // (it packs a pixel as x | y << 16 and a path id as 16 bits: larger frames take the lane-refill kernel)
-    // (so does its 64-B path record: 11 bits of sample index, 16 of sphere id)
-    P.queued = g.persist == 3 && !P.rowSerial && g.hs == HS_TWO_PHASE && g.foldMode == FOLD_RECURSIVE && a.fc.width <= 65535 &&
-               a.fc.height <= 65535 && g.spp <= 2047 && a.scene.nSpheres <= 65534;
+    // path-queue kernel: it packs a pixel as x | y << 16 and a path id as 16 bits (larger frames take the lane-refill kernel), and its
+    // path record 16 bits of sphere id
+    P.queued = pathQueueContext() && a.fc.width <= 65535 && a.fc.height <= 65535 && a.scene.nSpheres <= 65534;
     // grouped scene on the path-queue kernel: the second level of the bounds filter reads the groups' pair records per lane -- from LDS
     // when they fit the area the grouped instantiation's smaller path pool leaves (<= 544 groups), else from global memory; the host
     // that asked for the FLAT filter (hitSpheres variant 3: the A/B) or for the matrix cores (variant 4) gets neither
@@ -650,6 +655,53 @@ int enqueueResolve(const TraceTicket& T, float* deviceTile, const unsigned long 
 }
 
 
+// What the draws beside the frame pipeline (tptDrawDeviceViews, tptDrawDeviceAov, tptDrawDeviceMoments, tptDrawDeviceAnimation) refuse,
+// in the order they check it.  `fn`: the entry point; `things`: its output with the verb of the messages ("views are", "animation is").
+// `own()`: the entry's own check, right behind the frame size (0 when it passes).  kQueueKernel: the configuration of the path-queue
+// kernel (Views leave its spp limit to enqueueTrace; Animation needs none of it, it falls back to one launch per frame), kQueueSpp: its
+// spp limit.
+enum { kQueueKernel = 1, kQueueSpp = 2 };
+template <typename Own>
+static int checkPathQueueDraw(const char* fn, const char* things, int w, int h, unsigned checks, Own own)
+{
+    const std::string f(fn);
+    if (!g.updated || w != g.updatedW || h != g.updatedH) return fail(f + ": call tptUpdate (UpdateTest) at this size first");
+    if (w > 8192 || h > 8192) return fail(f + ": frames of at most 8192 x 8192");
+    if (int rc = own()) return rc;
+    if (checks & kQueueKernel) {
+        if (g.seedMode == SEED_ROW_SERIAL) return fail(f + ": needs per-pixel seeds (tptSetSeedMode(1)); row-serial " + things + " not supported");
+        if (g.foldMode != FOLD_RECURSIVE) return fail(f + ": needs the recursive fold (tptSetFoldMode(0))");
+        if (g.persist != 3 || g.hs != HS_TWO_PHASE) return fail(f + ": needs the path-queue kernel (tptSetKernelVariant(0, 3, ..))");
+    }
+    if ((checks & kQueueSpp) && g.spp > 2047) return fail(f + ": at most 2047 samples per pixel (the path-queue kernel)");
+    if (g.numParts > 1 || g.shard.active) return fail(f + ": not with row sharding or a communicator (sharded " + things + " not supported)");
+    if (g.mirror) return fail(f + ": not with a tile mirror (tptSetTileMirror)");
+    return 0;
+}
+
+// The blends of a launch whose frames count their rays apart (tptDrawDeviceViews, tptDrawDeviceAnimation), in frame order on the
+// context's stream.  Frame j is blended into tiles + j * tileStep floats -- with the launch's lerp factor (views: n cameras of one frame)
+// or, `ownLerp`, its own (the frames of an animation) -- and adds its rays to the running total; given `images`, the tile as it then
+// stands is written to image j.  The per-frame counts go to `rays` first: the slot's counters are free again once its last blend has
+// run (the next launch on this slot waits for that).
+static int enqueuePlaneResolves(const TraceTicket& T, float* tiles, size_t tileStep, bool ownLerp, float* images, int64_t* rays)
+{
+    const Context::ViewSlot& V = g.views[T.slot];
+    if (T.pipelined) HIPCHK(hipStreamWaitEvent(g.stream, g.evTrace[T.slot], 0));
+    if (rays) HIPCHK(hipMemcpyAsync(rays, V.rays, sizeof(unsigned long long) * (size_t)T.batch, hipMemcpyDeviceToDevice, g.stream));
+    const size_t plane = (size_t)T.nPixels * 4;
+    for (int j = 0; j < T.batch; ++j) {
+        const TraceTicket P = T.plane(j);
+        HIPCHK(tptLaunchResolve(tiles + (size_t)j * tileStep, P.colour, T.nPixels, ownLerp ? P.lerpFac : T.lerpFac,
+                                images ? images + (size_t)j * plane : nullptr, g.dRays, nullptr, V.rays + j, g.stream));
+    }
+    if (T.pipelined) {
+        HIPCHK(hipEventRecord(g.evResolve[T.slot], g.stream));
+        g.resolveRecorded[T.slot] = true;
+    }
+    return 0;
+}
+
 } // namespace tpth
 
 extern "C" {
@@ -702,8 +754,7 @@ int tptDrawDevice(float time, int frameCount, int w, int h, float* deviceTile, u
             if ((rc = Q.discard())) return rc; // (also closes a stream batch that did not continue as guessed)
             g.streamNext = -1;
             int nBatch = 1;
-            if (g.streamBatch && pipelined && stable && seqStreak >= 2 && g.persist == 3 && g.seedMode == SEED_PER_PIXEL && g.foldMode == FOLD_RECURSIVE &&
-                g.hs == HS_TWO_PHASE && w <= 8192 && h <= 8192 && g.spp <= 2047) {
+            if (g.streamBatch && pipelined && stable && seqStreak >= 2 && pathQueueContext() && w <= 8192 && h <= 8192) {
                 // how many frames make a launch long enough to amortise its fixed cost at this pipeline depth (tpt_stream_batch.h)
                 g.streamRun = continues ? g.streamRun + 1 : 0;
                 nBatch = streamBatchFrames((long long)localRows(h) * w * g.spp, effectiveOverlap(), Context::kMaxOverlap, g.streamRun,
@@ -785,15 +836,11 @@ int tptDrawDeviceViews(float time, int frameCount, int w, int h, int nViews, con
     if (requireInit()) return -1;
     if (nViews < 1 || nViews > kMaxBatch) return fail("tptDrawDeviceViews: nViews must be 1.." + std::to_string(kMaxBatch));
     if (!views || !deviceTiles || w <= 0 || h <= 0) return fail("tptDrawDeviceViews: bad arguments (views, deviceTiles, size)");
-    if (!g.updated || w != g.updatedW || h != g.updatedH) return fail("tptDrawDeviceViews: call tptUpdate (UpdateTest) at this size first");
-    if (w > 8192 || h > 8192) return fail("tptDrawDeviceViews: frames of at most 8192 x 8192");
-    if ((size_t)h * (size_t)w * sizeof(f4) * (size_t)nViews > (4ull << 30))
-        return refuse("tptDrawDeviceViews: " + std::to_string(((size_t)h * w * sizeof(f4) * nViews) >> 20) + " MiB of view colour per launch: over the 4096 MiB limit, use fewer views");
-    if (g.seedMode == SEED_ROW_SERIAL) return fail("tptDrawDeviceViews: needs per-pixel seeds (tptSetSeedMode(1)); row-serial views are not supported");
-    if (g.foldMode != FOLD_RECURSIVE) return fail("tptDrawDeviceViews: needs the recursive fold (tptSetFoldMode(0))");
-    if (g.persist != 3 || g.hs != HS_TWO_PHASE) return fail("tptDrawDeviceViews: needs the path-queue kernel (tptSetKernelVariant(0, 3, ..))");
-    if (g.numParts > 1 || g.shard.active) return fail("tptDrawDeviceViews: not with row sharding or a communicator (sharded views are not supported)");
-    if (g.mirror) return fail("tptDrawDeviceViews: not with a tile mirror (tptSetTileMirror)");
+    int rc = checkPathQueueDraw("tptDrawDeviceViews", "views are", w, h, kQueueKernel, [&] {
+        const size_t colour = (size_t)h * (size_t)w * sizeof(f4) * (size_t)nViews;
+        return colour > (4ull << 30) ? refuse("tptDrawDeviceViews: " + std::to_string(colour >> 20) + " MiB of view colour per launch: over the 4096 MiB limit, use fewer views") : 0;
+    });
+    if (rc) return rc;
     // the cameras exactly as tptSetCamera + tptUpdate at this size would build them (Test.cpp:309-319, 341)
     CameraPOD cams[kMaxBatch];
     for (int v = 0; v < nViews; ++v) {
@@ -808,28 +855,14 @@ int tptDrawDeviceViews(float time, int frameCount, int w, int h, int nViews, con
         cs.focusDist = p[8];
         cams[v] = makeCamera(cs, float(w) / float(h));
     }
-    int rc = g.pending.discard();
-    if (rc) return rc;
+    if ((rc = g.pending.discard())) return rc;
     // one launch: the views are the frames of a batch (colour planes nPixels apart in the slot's buffer, a ray counter each)
     TraceTicket T;
     BatchTable table;
     table.cams = cams;
     if ((rc = enqueueTrace(frameCount, w, h, testFlags, nullptr, T, nViews, 1, &table))) return rc;
-    if (!T.valid) return 0;
-    // the blends, in view order on the context's stream, each into its own tile with the frame's lerp factor; blend v also adds view
-    // v's rays to the running total.  The per-view counts go to the caller first: the slot's counters are free again once its last
-    // blend has run (the next launch on this slot waits for that).
-    const Context::ViewSlot& V = g.views[T.slot];
-    if (T.pipelined) HIPCHK(hipStreamWaitEvent(g.stream, g.evTrace[T.slot], 0));
-    if (deviceViewRays) HIPCHK(hipMemcpyAsync(deviceViewRays, V.rays, sizeof(unsigned long long) * (size_t)nViews, hipMemcpyDeviceToDevice, g.stream));
-    for (int v = 0; v < nViews; ++v)
-        HIPCHK(tptLaunchResolve(deviceTiles + (size_t)v * (size_t)T.nPixels * 4, T.colour + (size_t)v * (size_t)T.nPixels, T.nPixels, T.lerpFac,
-                                nullptr, g.dRays, nullptr, V.rays + v, g.stream));
-    if (T.pipelined) {
-        HIPCHK(hipEventRecord(g.evResolve[T.slot], g.stream));
-        g.resolveRecorded[T.slot] = true;
-    }
-    return 0;
+    // the blends, in view order, each into its own tile with the frame's lerp factor
+    return T.valid ? enqueuePlaneResolves(T, deviceTiles, (size_t)T.nPixels * 4, false, nullptr, deviceViewRays) : 0;
 }
 
 // nFrames frames of the scene as tptUpdate(times[j], firstFrame + j, ...) animates it, each followed by tptDrawDevice: the same bits,
@@ -845,21 +878,16 @@ int tptDrawDeviceAnimation(int firstFrame, int nFrames, const float* times, int 
     if (requireInit()) return -1;
     if (nFrames < 1) return fail("tptDrawDeviceAnimation: nFrames must be at least 1");
     if (!times || !deviceTile || w <= 0 || h <= 0) return fail("tptDrawDeviceAnimation: bad arguments (times, deviceTile, size)");
-    if (!g.updated || w != g.updatedW || h != g.updatedH) return fail("tptDrawDeviceAnimation: call tptUpdate (UpdateTest) at this size first");
-    if (w > 8192 || h > 8192) return fail("tptDrawDeviceAnimation: frames of at most 8192 x 8192");
     // (the tptUpdate guard, Test.cpp:304: a scene of 8 spheres or fewer does not move)
     const bool animate = (testFlags & TPT_FLAG_ANIMATE) && g.spheres.size() > 8;
     // one launch per kMaxBatch frames on the path-queue kernel; the animation kernel also wants a flat scene (its exact tests are
     // those of the flat filters); everything else: one launch per frame, the kernels of tptDrawDevice
-    const bool pathQueue = g.persist == 3 && g.hs == HS_TWO_PHASE && g.seedMode == SEED_PER_PIXEL && g.foldMode == FOLD_RECURSIVE && g.spp <= 2047;
-    const int perLaunch = pathQueue && (!animate || g.spheres.size() < TPT_GROUP_MIN_SPHERES) ? kMaxBatch : 1;
-    const size_t colour = (size_t)h * (size_t)w * sizeof(f4) * (size_t)(nFrames < perLaunch ? nFrames : perLaunch);
-    if (colour > (4ull << 30))
-        return refuse("tptDrawDeviceAnimation: " + std::to_string(colour >> 20) + " MiB of frame colour per launch: over the 4096 MiB limit");
-    if (g.numParts > 1 || g.shard.active) return fail("tptDrawDeviceAnimation: not with row sharding or a communicator (sharded animation is not supported)");
-    if (g.mirror) return fail("tptDrawDeviceAnimation: not with a tile mirror (tptSetTileMirror)");
-    int rc = g.pending.discard();
-    if (rc) return rc;
+    const int perLaunch = pathQueueContext() && (!animate || g.spheres.size() < TPT_GROUP_MIN_SPHERES) ? kMaxBatch : 1;
+    int rc = checkPathQueueDraw("tptDrawDeviceAnimation", "animation is", w, h, 0, [&] {
+        const size_t colour = (size_t)h * (size_t)w * sizeof(f4) * (size_t)(nFrames < perLaunch ? nFrames : perLaunch);
+        return colour > (4ull << 30) ? refuse("tptDrawDeviceAnimation: " + std::to_string(colour >> 20) + " MiB of frame colour per launch: over the 4096 MiB limit") : 0;
+    });
+    if (rc || (rc = g.pending.discard())) return rc;
     // the camera as every tptUpdate of the sequence builds it (Test.cpp:309-313, 341)
     CameraSetup cs = g.camSetup;
     if (g.config & CFG_MITSUBA_COMPARE) cs.aperture = 0.0f;
@@ -886,22 +914,10 @@ int tptDrawDeviceAnimation(int firstFrame, int nFrames, const float* times, int 
         }
         TraceTicket T;
         if ((rc = enqueueTrace(firstFrame + f, w, h, testFlags, nullptr, T, n, 1, &table))) return rc;
-        if (!T.valid) continue;
-        // the blends, in frame order on the context's stream: blend j adds frame j's rays to the running total and writes the tile as it
-        // stands to image j.  The per-frame counts go to the caller first (the slot's counters are free once its last blend has run).
-        const Context::ViewSlot& V = g.views[T.slot];
-        if (T.pipelined) HIPCHK(hipStreamWaitEvent(g.stream, g.evTrace[T.slot], 0));
-        if (deviceFrameRays)
-            HIPCHK(hipMemcpyAsync(deviceFrameRays + f, V.rays, sizeof(unsigned long long) * (size_t)n, hipMemcpyDeviceToDevice, g.stream));
-        for (int j = 0; j < n; ++j) {
-            const TraceTicket P = T.plane(j);
-            float* image = deviceFrameImages ? deviceFrameImages + (size_t)(f + j) * (size_t)T.nPixels * 4 : nullptr;
-            HIPCHK(tptLaunchResolve(deviceTile, P.colour, T.nPixels, P.lerpFac, image, g.dRays, nullptr, V.rays + j, g.stream));
-        }
-        if (T.pipelined) {
-            HIPCHK(hipEventRecord(g.evResolve[T.slot], g.stream));
-            g.resolveRecorded[T.slot] = true;
-        }
+        // the blends, in frame order, each into the one tile with its frame's lerp factor
+        if (T.valid && (rc = enqueuePlaneResolves(T, deviceTile, 0, true, deviceFrameImages ? deviceFrameImages + (size_t)f * (size_t)T.nPixels * 4 : nullptr,
+                                                  deviceFrameRays ? deviceFrameRays + f : nullptr)))
+            return rc;
     }
     return 0;
 }
@@ -917,16 +933,8 @@ int tptDrawDeviceAov(float time, int frameCount, int w, int h, float* deviceTile
     if (requireInit()) return -1;
     if (!deviceTile || (!deviceAlbedo && !deviceNormalDepth) || w <= 0 || h <= 0)
         return fail("tptDrawDeviceAov: bad arguments (deviceTile, at least one of deviceAlbedo / deviceNormalDepth, size)");
-    if (!g.updated || w != g.updatedW || h != g.updatedH) return fail("tptDrawDeviceAov: call tptUpdate (UpdateTest) at this size first");
-    if (w > 8192 || h > 8192) return fail("tptDrawDeviceAov: frames of at most 8192 x 8192");
-    if (g.seedMode == SEED_ROW_SERIAL) return fail("tptDrawDeviceAov: needs per-pixel seeds (tptSetSeedMode(1)); row-serial planes are not supported");
-    if (g.foldMode != FOLD_RECURSIVE) return fail("tptDrawDeviceAov: needs the recursive fold (tptSetFoldMode(0))");
-    if (g.persist != 3 || g.hs != HS_TWO_PHASE) return fail("tptDrawDeviceAov: needs the path-queue kernel (tptSetKernelVariant(0, 3, ..))");
-    if (g.spp > 2047) return fail("tptDrawDeviceAov: at most 2047 samples per pixel (the path-queue kernel)");
-    if (g.numParts > 1 || g.shard.active) return fail("tptDrawDeviceAov: not with row sharding or a communicator (sharded planes are not supported)");
-    if (g.mirror) return fail("tptDrawDeviceAov: not with a tile mirror (tptSetTileMirror)");
-    int rc = g.pending.discard();
-    if (rc) return rc;
+    int rc = checkPathQueueDraw("tptDrawDeviceAov", "planes are", w, h, kQueueKernel | kQueueSpp, [] { return 0; });
+    if (rc || (rc = g.pending.discard())) return rc;
     TraceTicket T;
     AovPlanes aov;
     aov.albedo = reinterpret_cast<f4*>(deviceAlbedo);
@@ -946,22 +954,11 @@ int tptDrawDeviceMoments(float time, int frameCount, int w, int h, float* device
     if (requireInit()) return -1;
     if (!deviceTile || !deviceMoments || w <= 0 || h <= 0)
         return fail("tptDrawDeviceMoments: bad arguments (deviceTile, deviceMoments, size)");
-    if (!g.updated || w != g.updatedW || h != g.updatedH) return fail("tptDrawDeviceMoments: call tptUpdate (UpdateTest) at this size first");
-    if (w > 8192 || h > 8192) return fail("tptDrawDeviceMoments: frames of at most 8192 x 8192");
-    const uintptr_t bytes = (uintptr_t)w * (uintptr_t)h * 16u;
-    const uintptr_t m = reinterpret_cast<uintptr_t>(deviceMoments);
-    for (const float* other : {(const float*)deviceTile, (const float*)deviceAlbedo, (const float*)deviceNormalDepth}) {
-        const uintptr_t o = reinterpret_cast<uintptr_t>(other);
-        if (other && m < o + bytes && o < m + bytes) return fail("tptDrawDeviceMoments: deviceMoments overlaps the tile or a plane");
-    }
-    if (g.seedMode == SEED_ROW_SERIAL) return fail("tptDrawDeviceMoments: needs per-pixel seeds (tptSetSeedMode(1)); row-serial moments are not supported");
-    if (g.foldMode != FOLD_RECURSIVE) return fail("tptDrawDeviceMoments: needs the recursive fold (tptSetFoldMode(0))");
-    if (g.persist != 3 || g.hs != HS_TWO_PHASE) return fail("tptDrawDeviceMoments: needs the path-queue kernel (tptSetKernelVariant(0, 3, ..))");
-    if (g.spp > 2047) return fail("tptDrawDeviceMoments: at most 2047 samples per pixel (the path-queue kernel)");
-    if (g.numParts > 1 || g.shard.active) return fail("tptDrawDeviceMoments: not with row sharding or a communicator (sharded moments are not supported)");
-    if (g.mirror) return fail("tptDrawDeviceMoments: not with a tile mirror (tptSetTileMirror)");
-    int rc = g.pending.discard();
-    if (rc) return rc;
+    int rc = checkPathQueueDraw("tptDrawDeviceMoments", "moments are", w, h, kQueueKernel | kQueueSpp, [&] {
+        return overlapsAny(deviceMoments, {deviceTile, deviceAlbedo, deviceNormalDepth}, (uintptr_t)w * (uintptr_t)h * 16u)
+                   ? fail("tptDrawDeviceMoments: deviceMoments overlaps the tile or a plane") : 0;
+    });
+    if (rc || (rc = g.pending.discard())) return rc;
     TraceTicket T;
     AovPlanes aov;
     aov.albedo = reinterpret_cast<f4*>(deviceAlbedo);

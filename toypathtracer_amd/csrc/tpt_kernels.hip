@@ -220,6 +220,32 @@ __global__ void __launch_bounds__(256) tptDisplayKernel(const f4* __restrict__ t
     rgba[i] = to8(c.x) | (to8(c.y) << 8) | (to8(c.z) << 16) | 0xff000000u;
 }
 
+// What both a-trous kernels compute alike, in the operation order the filters are stated in (include/tpt_hip.h):
+// demod(c, a) = a > 0 ? c / a : c per colour channel, .w left alone
+__device__ __forceinline__ f4 atrousDemodulate(f4 c, const f4 a)
+{
+    c.x = a.x > 0.0f ? c.x / a.x : c.x;
+    c.y = a.y > 0.0f ? c.y / a.y : c.y;
+    c.z = a.z > 0.0f ? c.z / a.z : c.z;
+    return c;
+}
+// remod(f, a) = a > 0 ? f * a : f per colour channel
+__device__ __forceinline__ void atrousRemodulate(f4& f, const f4 a)
+{
+    f.x = a.x > 0.0f ? f.x * a.x : f.x;
+    f.y = a.y > 0.0f ? f.y * a.y : f.y;
+    f.z = a.z > 0.0f ? f.z * a.z : f.z;
+}
+// a tap's weight denominator times the guides' factors: (1 + |nq - np|^2 in) (1 + (dq - dp)^2 id), normal in .xyz, depth in .w
+__device__ __forceinline__ float atrousGuide(float den, const f4 np, const f4 nq, float in, float id)
+{
+    const float dx = nq.x - np.x, dy = nq.y - np.y, dz = nq.z - np.z;
+    const float dn = (dx * dx + dy * dy) + dz * dz;
+    den = den * (1.0f + dn * in);
+    const float dd = nq.w - np.w;
+    return den * (1.0f + (dd * dd) * id);
+}
+
 // One iteration of tptDenoiseDevice's edge-avoiding a-trous filter (include/tpt_hip.h states it; tests/denoise_checker.c restates it):
 // step `step`, inverse squared sigmas ic (already x 4^i), in, id.  One lane per pixel, a wave along 64 pixels of a row, so every tap
 // is one 1-KiB coalesced load of 16 B per lane; the centre's colour and guides stay in registers.  FIRST reads the caller's colour
@@ -237,12 +263,7 @@ __global__ void __launch_bounds__(256) tptDenoiseKernel(const f4* __restrict__ s
     constexpr float hk[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
     auto tap = [&](size_t q) -> f4 {
         f4 c = src[q];
-        if (FIRST && demod) { // demod(c, a) = a > 0 ? c / a : c
-            const f4 a = albedo[q];
-            c.x = a.x > 0.0f ? c.x / a.x : c.x;
-            c.y = a.y > 0.0f ? c.y / a.y : c.y;
-            c.z = a.z > 0.0f ? c.z / a.z : c.z;
-        }
+        if (FIRST && demod) c = atrousDemodulate(c, albedo[q]);
         return c;
     };
     const size_t p = (size_t)y * width + x;
@@ -263,14 +284,7 @@ __global__ void __launch_bounds__(256) tptDenoiseKernel(const f4* __restrict__ s
             const float dr = cq.x - cp.x, dg = cq.y - cp.y, db = cq.z - cp.z;
             const float dc = (dr * dr + dg * dg) + db * db;
             float den = 1.0f + dc * ic;
-            if (GUIDE) {
-                const f4 nq = nd[q];
-                const float dx = nq.x - np.x, dy = nq.y - np.y, dz = nq.z - np.z;
-                const float dn = (dx * dx + dy * dy) + dz * dz;
-                den = den * (1.0f + dn * in);
-                const float dd = nq.w - np.w;
-                den = den * (1.0f + (dd * dd) * id);
-            }
+            if (GUIDE) den = atrousGuide(den, np, nd[q], in, id);
             const float w = tdivSafeNum(hk[ky] * hk[kx], den);
             sumW += w;
             sumR += w * cq.x;
@@ -283,12 +297,7 @@ __global__ void __launch_bounds__(256) tptDenoiseKernel(const f4* __restrict__ s
     o.y = sumG / sumW;
     o.z = sumB / sumW;
     o.w = cp.w; // (the colour's alpha: demodulation leaves it alone)
-    if (LAST && demod) { // remod(f, a) = a > 0 ? f * a : f
-        const f4 a = albedo[p];
-        o.x = a.x > 0.0f ? o.x * a.x : o.x;
-        o.y = a.y > 0.0f ? o.y * a.y : o.y;
-        o.z = a.z > 0.0f ? o.z * a.z : o.z;
-    }
+    if (LAST && demod) atrousRemodulate(o, albedo[p]);
     dst[p] = o;
 }
 
@@ -318,11 +327,9 @@ __global__ void __launch_bounds__(256) tptVarianceAtrousKernel(const f4* __restr
             const f4 m = moments[q];
             const float d = m.y - m.x * m.x;
             c.w = (d > 0.0f ? d : 0.0f) / samples;
-            if (demod) { // demod(c, a) = a > 0 ? c / a : c;  v / lum(a)^2 where that square is > 0
+            if (demod) { // v / lum(a)^2 where that square is > 0
                 const f4 a = albedo[q];
-                c.x = a.x > 0.0f ? c.x / a.x : c.x;
-                c.y = a.y > 0.0f ? c.y / a.y : c.y;
-                c.z = a.z > 0.0f ? c.z / a.z : c.z;
+                c = atrousDemodulate(c, a);
                 const float la = lum(a.x, a.y, a.z);
                 const float la2 = la * la;
                 c.w = la2 > 0.0f ? c.w / la2 : c.w;
@@ -365,14 +372,7 @@ __global__ void __launch_bounds__(256) tptVarianceAtrousKernel(const f4* __restr
             const f4 cq = tap(q);
             const float dl = lum(cq.x, cq.y, cq.z) - lp;
             float den = 1.0f + (dl * dl) * il;
-            if (GUIDE) {
-                const f4 nq = nd[q];
-                const float dx = nq.x - np.x, dy = nq.y - np.y, dz = nq.z - np.z;
-                const float dn = (dx * dx + dy * dy) + dz * dz;
-                den = den * (1.0f + dn * in);
-                const float dd = nq.w - np.w;
-                den = den * (1.0f + (dd * dd) * id);
-            }
+            if (GUIDE) den = atrousGuide(den, np, nd[q], in, id);
             const float w = tdivSafeNum(hk[ky] * hk[kx], den);
             sumW += w;
             sumR += w * cq.x;
@@ -387,12 +387,7 @@ __global__ void __launch_bounds__(256) tptVarianceAtrousKernel(const f4* __restr
     o.z = sumB / sumW;
     if (LAST) {
         o.w = colour[p].w; // (the caller's alpha)
-        if (demod) { // remod(f, a) = a > 0 ? f * a : f
-            const f4 a = albedo[p];
-            o.x = a.x > 0.0f ? o.x * a.x : o.x;
-            o.y = a.y > 0.0f ? o.y * a.y : o.y;
-            o.z = a.z > 0.0f ? o.z * a.z : o.z;
-        }
+        if (demod) atrousRemodulate(o, albedo[p]);
     } else {
         o.w = sumV / (sumW * sumW);
     }
@@ -2304,77 +2299,33 @@ size_t tptQueueLdsBytes(const KernelArgs& a, bool ldsScene)
 #endif
     return bytes;
 }
-template <bool LDS_SCENE, bool BATCH>
-static hipError_t launchTraceQueue(const KernelArgs& a, int blocks, size_t lds, hipStream_t stream)
+// One launch of a path-queue kernel: its dynamic LDS, then the grid.
+static hipError_t launchQueueKernel(void (*k)(KernelArgs), const KernelArgs& a, int blocks, size_t lds, hipStream_t stream)
 {
-    auto k = tptTraceQueueKernel<LDS_SCENE, BATCH>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k, dim3(blocks), dim3(TPT_Q_T), lds, stream, a);
-    return hipSuccess;
-}
-template <bool LDS_SCENE>
-static hipError_t launchTraceViews(const KernelArgs& a, int blocks, size_t lds, hipStream_t stream)
-{
-    auto k = tptTraceViewsKernel<LDS_SCENE>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(TPT_Q_T), lds, stream, a);
-    return hipSuccess;
-}
-template <bool LDS_SCENE>
-static hipError_t launchTraceAnimation(const KernelArgs& a, int blocks, size_t lds, hipStream_t stream)
-{
-    auto k = tptTraceAnimationKernel<LDS_SCENE>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(TPT_Q_T), lds, stream, a);
-    return hipSuccess;
-}
-template <bool LDS_SCENE>
-static hipError_t launchTraceAov(const KernelArgs& a, int blocks, size_t lds, hipStream_t stream)
-{
-    auto k = tptTraceAovKernel<LDS_SCENE>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(TPT_Q_T), lds, stream, a);
-    return hipSuccess;
-}
-template <bool LDS_SCENE>
-static hipError_t launchTraceMoments(const KernelArgs& a, int blocks, size_t lds, hipStream_t stream)
-{
-    auto k = tptTraceMomentsKernel<LDS_SCENE>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(blocks), dim3(TPT_Q_T), lds, stream, a);
-    return hipSuccess;
+    return hipGetLastError();
 }
 hipError_t tptLaunchTraceQueue(const KernelArgs& a, bool ldsScene, int blocks, size_t lds, hipStream_t stream)
 {
     if (a.viewCams) { // (tptDrawDeviceViews: 1 .. TPT_Q_VIEWS_MAX views, the frames of the batch)
         if (a.batchFrames < 1 || a.batchFrames > TPT_Q_VIEWS_MAX) return hipErrorInvalidValue;
-        hipError_t e = ldsScene ? launchTraceViews<true>(a, blocks, lds, stream) : launchTraceViews<false>(a, blocks, lds, stream);
-        if (e != hipSuccess) return e;
-        return hipGetLastError();
+        return launchQueueKernel(ldsScene ? tptTraceViewsKernel<true> : tptTraceViewsKernel<false>, a, blocks, lds, stream);
     }
     if (a.aovSums) { // (tptDrawDeviceAov, tptDrawDeviceMoments with a.momentsOut: a single frame)
         if (a.batchFrames != 1 || a.viewCams || a.moveCentres) return hipErrorInvalidValue;
-        hipError_t e = a.momentsOut ? (ldsScene ? launchTraceMoments<true>(a, blocks, lds, stream) : launchTraceMoments<false>(a, blocks, lds, stream))
-                                    : (ldsScene ? launchTraceAov<true>(a, blocks, lds, stream) : launchTraceAov<false>(a, blocks, lds, stream));
-        if (e != hipSuccess) return e;
-        return hipGetLastError();
+        if (a.momentsOut) return launchQueueKernel(ldsScene ? tptTraceMomentsKernel<true> : tptTraceMomentsKernel<false>, a, blocks, lds, stream);
+        return launchQueueKernel(ldsScene ? tptTraceAovKernel<true> : tptTraceAovKernel<false>, a, blocks, lds, stream);
     }
     if (a.moveCentres) { // (tptDrawDeviceAnimation: 1 .. TPT_Q_VIEWS_MAX frames of the batch, a flat scene)
         if (a.batchFrames < 1 || a.batchFrames > TPT_Q_VIEWS_MAX || a.scene.nGroups > 0) return hipErrorInvalidValue;
-        hipError_t e = ldsScene ? launchTraceAnimation<true>(a, blocks, lds, stream) : launchTraceAnimation<false>(a, blocks, lds, stream);
-        if (e != hipSuccess) return e;
-        return hipGetLastError();
+        return launchQueueKernel(ldsScene ? tptTraceAnimationKernel<true> : tptTraceAnimationKernel<false>, a, blocks, lds, stream);
     }
     const bool batch = a.batchFrames > 1;
-    hipError_t e = ldsScene ? (batch ? launchTraceQueue<true, true>(a, blocks, lds, stream) : launchTraceQueue<true, false>(a, blocks, lds, stream))
-                            : (batch ? launchTraceQueue<false, true>(a, blocks, lds, stream) : launchTraceQueue<false, false>(a, blocks, lds, stream));
-    if (e != hipSuccess) return e;
-    return hipGetLastError();
+    return launchQueueKernel(ldsScene ? (batch ? tptTraceQueueKernel<true, true> : tptTraceQueueKernel<true, false>)
+                                      : (batch ? tptTraceQueueKernel<false, true> : tptTraceQueueKernel<false, false>),
+                             a, blocks, lds, stream);
 }
 #if defined(TPT_TEST_HOOKS)
 // hooks build: run-time sizes of the three-stage dealing's entry areas (0, 0, 0: the compiled ones); each between 64 and its compiled size
@@ -2408,6 +2359,22 @@ hipError_t tptLaunchDisplay(const float* tile, unsigned char* rgba, int width, i
     return hipGetLastError();
 }
 
+// The ping-pong of both a-trous filters: iteration i (step 2^i) reads the previous iteration's plane -- the caller's colour first -- and
+// writes `scratch` or `out`, in the parity that makes the last iteration write `out`.  `launch(i, src, dst)` enqueues iteration i.
+template <typename Launch>
+static hipError_t atrousIterations(const float* colour, float* out, float* scratch, int iterations, Launch launch)
+{
+    const f4* src = reinterpret_cast<const f4*>(colour);
+    for (int i = 0; i < iterations; ++i) {
+        f4* dst = reinterpret_cast<f4*>(((iterations - 1 - i) & 1) ? scratch : out);
+        launch(i, src, dst);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        src = dst;
+    }
+    return hipSuccess;
+}
+
 template <bool GUIDE>
 static void launchDenoiseIteration(bool first, bool last, dim3 grid, hipStream_t stream, const f4* src, const f4* albedo, const f4* nd,
                                    f4* dst, int width, int height, int step, float ic, float in, float id, int demod)
@@ -2420,23 +2387,13 @@ hipError_t tptLaunchDenoise(const float* colour, const float* albedo, const floa
                             int height, int iterations, float ic, float in, float id, bool demodulate, hipStream_t stream)
 {
     const dim3 grid((unsigned)(width + 63) / 64, (unsigned)(height + 3) / 4);
-    const f4* src = reinterpret_cast<const f4*>(colour);
-    for (int i = 0; i < iterations; ++i) {
-        // (the parity that makes the last iteration write `out`)
-        f4* dst = reinterpret_cast<f4*>(((iterations - 1 - i) & 1) ? scratch : out);
+    const f4* a = reinterpret_cast<const f4*>(albedo);
+    const f4* nd = reinterpret_cast<const f4*>(normalDepth);
+    return atrousIterations(colour, out, scratch, iterations, [&](int i, const f4* src, f4* dst) {
         const float scale = (float)(1u << (2 * i)); // 4^i: ic0 * 4^i is exact (a power of two; the sigmas are bounded on the host)
-        if (normalDepth)
-            launchDenoiseIteration<true>(i == 0, i == iterations - 1, grid, stream, src, reinterpret_cast<const f4*>(albedo),
-                                         reinterpret_cast<const f4*>(normalDepth), dst, width, height, 1 << i, ic * scale, in, id,
-                                         demodulate ? 1 : 0);
-        else
-            launchDenoiseIteration<false>(i == 0, i == iterations - 1, grid, stream, src, reinterpret_cast<const f4*>(albedo), nullptr,
-                                          dst, width, height, 1 << i, ic * scale, in, id, demodulate ? 1 : 0);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        src = dst;
-    }
-    return hipSuccess;
+        (nd ? launchDenoiseIteration<true> : launchDenoiseIteration<false>)(i == 0, i == iterations - 1, grid, stream, src, a, nd, dst, width,
+                                                                           height, 1 << i, ic * scale, in, id, demodulate ? 1 : 0);
+    });
 }
 
 template <bool GUIDE>
@@ -2455,23 +2412,14 @@ hipError_t tptLaunchDenoiseVariance(const float* colour, const float* albedo, co
 {
     const dim3 grid((unsigned)(width + 63) / 64, (unsigned)(height + 3) / 4);
     const f4* c = reinterpret_cast<const f4*>(colour);
-    const f4* src = c;
-    for (int i = 0; i < iterations; ++i) {
-        // (the parity that makes the last iteration write `out`)
-        f4* dst = reinterpret_cast<f4*>(((iterations - 1 - i) & 1) ? scratch : out);
-        if (normalDepth)
-            launchDenoiseVarianceIteration<true>(i == 0, i == iterations - 1, grid, stream, src, c, reinterpret_cast<const f4*>(albedo),
-                                                 reinterpret_cast<const f4*>(normalDepth), reinterpret_cast<const f4*>(moments), dst,
-                                                 width, height, 1 << i, samples, sl2, in, id, demodulate ? 1 : 0);
-        else
-            launchDenoiseVarianceIteration<false>(i == 0, i == iterations - 1, grid, stream, src, c, reinterpret_cast<const f4*>(albedo),
-                                                  nullptr, reinterpret_cast<const f4*>(moments), dst, width, height, 1 << i, samples, sl2,
-                                                  in, id, demodulate ? 1 : 0);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        src = dst;
-    }
-    return hipSuccess;
+    const f4* a = reinterpret_cast<const f4*>(albedo);
+    const f4* nd = reinterpret_cast<const f4*>(normalDepth);
+    const f4* m = reinterpret_cast<const f4*>(moments);
+    return atrousIterations(colour, out, scratch, iterations, [&](int i, const f4* src, f4* dst) {
+        (nd ? launchDenoiseVarianceIteration<true> : launchDenoiseVarianceIteration<false>)(i == 0, i == iterations - 1, grid, stream, src, c, a,
+                                                                                           nd, m, dst, width, height, 1 << i, samples, sl2,
+                                                                                           in, id, demodulate ? 1 : 0);
+    });
 }
 
 hipError_t tptLaunchAssemble(const float* gathered, float* image, int width, int height, int stripeRows, int nRanks, int padRows, hipStream_t stream)
