@@ -231,6 +231,53 @@ TPT_API int tptDrawDeviceMoments(float time, int frameCount, int screenWidth, in
 TPT_API int tptDenoiseDeviceVariance(int screenWidth, int screenHeight, const float* deviceColour, const float* deviceAlbedo,
                                      const float* deviceNormalDepth, const float* deviceMoments, float samples, float* deviceOut,
                                      int iterations, float sigmaLuminance, float sigmaNormal, float sigmaDepth, unsigned denoiseFlags);
+/* The temporal part of SVGF: this frame's planes blended with a history that is fetched through the previous camera and kept only where
+ * it shows the same surface.  Its outputs feed tptDenoiseDeviceVariance.  camera / prevCamera: HOST pointers to 88-byte Camera records
+ * (tptGetSceneDesc's outCam), read at call time.  All twelve device buffers are h*w*4 floats, row-major like the tile.  deviceColour,
+ * deviceAlbedo, deviceNormalDepth, deviceMoments: what one tptDrawDeviceMoments call without TPT_FLAG_PROGRESSIVE on a zeroed tile and
+ * moments plane writes.  devicePrevColour / devicePrevAlbedo / devicePrevMoments: the OUTPUTS of the previous call of this function;
+ * devicePrevNormalDepth: the previous frame's own normal / depth plane; prevCamera: the camera that frame was traced with (a caller
+ * ping-pongs two sets).  The four prev planes and prevCamera are all NULL for the first frame of a sequence.  deviceOutMoments.w carries
+ * the pixel's history length N (>= 1); devicePrevMoments.w is read as N.
+ * Binary32, in the order written, no FMA, correctly rounded division and square root, sums from +0;  dot(a, b) = (a.x*b.x + a.y*b.y)
+ * + a.z*b.z;  vectors component by component.  Camera fields o = origin, ll = lowerLeftCorner, H = horizontal, V = vertical, w = ww;
+ * primed: prevCamera's.  Once per call:  a = ll' - o';  f = -dot(a, w');  hh = dot(H', H');  vv = dot(V', V').
+ * Per pixel p = (x, y), with cur = the four current planes at p and c = albedo[p].w (the coverage):
+ *   1. s = (x + 0.5f) / width;  t = (y + 0.5f) / height;  v = ((ll + s*H) + t*V) - o;  dir = v * (1.0f / sqrt(dot(v, v)))
+ *      c > 0:  d = nd[p].w / c;  n = nd[p].xyz / c;  rel = (o + dir*d) - o'        otherwise (sky):  rel = dir
+ *   2. z = -dot(rel, w');  no history unless z > 0.  k = f / z;  q = rel*k - a;  s' = dot(q, H') / hh;  t' = dot(q, V') / vv;
+ *      px = s' * width - 0.5f;  py = t' * height - 0.5f;  no history unless px and py are finite
+ *   3. ix = floor(px);  fx = px - ix;  fx < TPT_TEMPORAL_SNAP: fx = 0;  else fx > 1 - TPT_TEMPORAL_SNAP: ix = ix + 1, fx = 0;  likewise
+ *      iy, fy  (a camera that has not moved reads exactly its own pixel)
+ *   4. the taps (ix + i, iy + j), i, j in {0, 1}, j outer, with b = (i ? fx : 1 - fx) * (j ? fy : 1 - fy).  A tap counts if b > 0, it
+ *      lies inside the image, N' = prevMoments.w of the tap is finite and >= 1, prevColour.rgb of the tap is finite, and, with
+ *      c' = prevAlbedo.w of the tap,  |c - c'| <= coverageTolerance  and either
+ *        c == 0 and c' == 0  (sky), or
+ *        c > 0 and c' > 0,  |e - d'| <= depthTolerance * e  with e = sqrt(dot(rel, rel)), d' = prevNd.w / c',  and
+ *        (dx*dx + dy*dy) + dz*dz <= normalTolerance  with (dx, dy, dz) = n - prevNd.xyz / c'
+ *   5. B = sum of b over the counted taps.  None counted, no history, or the first frame:  N = 1 and out = cur.  Otherwise
+ *      hist = (sum of b * value') / B  for colour.rgb, albedo.xyzw, moments.xy and N';  N = histN + 1, maxHistory if that is smaller;
+ *      lerp = (N - 1) / N;  out = hist * lerp + cur * (1 - lerp)  -- the tile's own blend: with agreeing history and an unmoved camera
+ *      the colour is the progressive tile of N frames, byte for byte
+ *   6. outColour = {out.rgb, colour[p].a};  outAlbedo = out.xyzw;  outMoments = {m.x, m.y, 0, N};
+ *      outVariance = {0, (dd > 0 ? dd : 0) / N, 0, N},  dd = m.y - m.x*m.x,  m = out's moments
+ * deviceOutVariance is the plane to hand to tptDenoiseDeviceVariance as its deviceMoments with samples = spp: its first component is 0,
+ * so the filter's v_0 becomes variance / (spp * N) per pixel -- a freshly disoccluded pixel is filtered as the one-frame pixel it is.
+ * The filter's other inputs are deviceOutColour, deviceOutAlbedo and this frame's normal / depth plane.  The coverage test keeps a
+ * silhouette pixel from inheriting a fully covered neighbour's history.  Objects that move are not followed: their
+ * points are reprojected as if they stood still, and the depth and normal tests decide.
+ * Asynchronous on the context stream; needs tptInitialize only and leaves every other state alone.  The inputs are never written.
+ * Refused (non-zero, tptGetLastError, nothing enqueued, no output written): no context; w or h outside 1..8192; camera NULL; a current
+ * plane or an output NULL; the prev planes and prevCamera neither all NULL nor all given; an output overlapping an input or another
+ * output; maxHistory not in [1, 65536]; a tolerance negative, NaN or infinite; a camera with a non-finite field, dot(H, H) == 0,
+ * dot(V, V) == 0 or f <= 0. */
+#define TPT_TEMPORAL_SNAP (1.0f / 128)
+TPT_API int tptTemporalAccumulateDevice(int screenWidth, int screenHeight, const void* camera, const void* prevCamera,
+                                        const float* deviceColour, const float* deviceAlbedo, const float* deviceNormalDepth,
+                                        const float* deviceMoments, const float* devicePrevColour, const float* devicePrevAlbedo,
+                                        const float* devicePrevNormalDepth, const float* devicePrevMoments, float* deviceOutColour,
+                                        float* deviceOutAlbedo, float* deviceOutMoments, float* deviceOutVariance, float maxHistory,
+                                        float depthTolerance, float normalTolerance, float coverageTolerance);
 /* nViews (1..32) cameras of the scene as of the last tptUpdate, traced by ONE launch.  views: nViews x 9 floats
  * {lookFrom xyz, lookAt xyz, vfovDegrees, aperture, focusDist} -- tptSetCamera's arguments; aspect = w / h, vup (0,1,0),
  * aperture forced to 0 in Mitsuba-compare mode, as tptUpdate does.  deviceTiles: nViews consecutive device tiles of h*w*4

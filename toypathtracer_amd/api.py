@@ -39,7 +39,7 @@ C_ABI_SYMBOLS = [
     "tptSetSamplesPerPixel", "tptSetConfig", "tptSetSeedMode", "tptSetFoldMode", "tptSetScene", "tptSetCamera", "tptSetStream",
     "tptSetRowShard", "tptLocalRowCount", "tptLocalRowToGlobal", "tptDrawDevice", "tptRayCounterRead", "tptSetRayCounter", "tptSetFrameOverlap", "tptDisplayRGBA8", "tptKernelTimingBegin", "tptKernelTimingEnd",
     "tptSynchronize", "tptTimerBegin", "tptTimerEnd", "tptSetKernelVariant",
-    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDenoiseDeviceVariance", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
+    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
 ]
 # include/tpt_test_hooks.h: exported by the second build (libtoypathtracer_hip_hooks.so) only
 HOOK_SYMBOLS = ["tptTestMath", "tptTestMathExhaustive", "tptTestHitSpheres", "tptTestMatrixFilter", "tptTestGroupFilter", "tptTestSetDealCapacities", "tptDebugStats", "tptDebugChunkOrder"]
@@ -78,7 +78,7 @@ def _bind(path, hooks):
         "tptSetRayCounter": [p], "tptSetTileMirror": [p, p], "tptSetFrameOverlap": [i], "tptDisplayRGBA8": [p, i, i, p], "tptKernelTimingBegin": [i],
         "tptKernelTimingEnd": [C.POINTER(f), C.POINTER(i)],
         "tptSynchronize": [], "tptTimerBegin": [], "tptTimerEnd": [C.POINTER(f)], "tptSetKernelVariant": [i, i, i],
-        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
+        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
     }
     if hooks:
         sigs.update({"tptDebugStats": [p, i], "tptDebugChunkOrder": [p, p, i], "tptTestMath": [i, p, p, p, i], "tptTestMathExhaustive": [i, u, u, p, p],
@@ -550,6 +550,57 @@ def denoise_device_variance(w, h, colour_ptr, moments_ptr, samples, out_ptr, alb
                                                  C.c_void_p(normal_depth_ptr) if normal_depth_ptr else None, C.c_void_p(moments_ptr),
                                                  samples, C.c_void_p(out_ptr), iterations, sigma_luminance, sigma_normal, sigma_depth,
                                                  DENOISE_DEMODULATE if demodulate else 0), "tptDenoiseDeviceVariance")
+
+
+# temporal_accumulate_device's defaults, chosen by tools/temporal_rate.py's sweep
+TEMPORAL_DEFAULTS = dict(max_history=4.0, depth_tolerance=0.1, normal_tolerance=0.25, coverage_tolerance=0.0)
+
+
+def _camera_bytes(name, cam):
+    """a CAMERA_DT record (GetSceneDesc's third result, or one element of it) -> its 88 bytes as a ctypes buffer; ValueError otherwise"""
+    if not isinstance(cam, (np.ndarray, np.void)) or cam.dtype != CAMERA_DT or cam.size != 1:
+        raise ValueError("%s: one CAMERA_DT record expected, got %r" % (name, cam))
+    return C.create_string_buffer(np.ascontiguousarray(cam).tobytes(), CAMERA_DT.itemsize)
+
+
+def temporal_accumulate_device(w, h, camera, colour_ptr, albedo_ptr, normal_depth_ptr, moments_ptr, out_colour_ptr, out_albedo_ptr,
+                               out_moments_ptr, out_variance_ptr, prev=None, max_history=TEMPORAL_DEFAULTS["max_history"],
+                               depth_tolerance=TEMPORAL_DEFAULTS["depth_tolerance"],
+                               normal_tolerance=TEMPORAL_DEFAULTS["normal_tolerance"],
+                               coverage_tolerance=TEMPORAL_DEFAULTS["coverage_tolerance"]):
+    """tptTemporalAccumulateDevice: this frame's planes (one non-progressive draw_device_moments call on a zeroed tile and moments plane)
+    blended with the history reprojected through the previous camera, into the four out planes (device buffers of h*w*4 floats each).
+    camera: this frame's CAMERA_DT record (GetSceneDesc()[2]).  prev: None for the first frame of a sequence, else (camera, colour_ptr,
+    albedo_ptr, normal_depth_ptr, moments_ptr) -- the previous frame's camera, the previous call's out_colour / out_albedo / out_moments
+    and the previous frame's own normal/depth plane.  out_moments' .w carries the per-pixel history length; out_variance is the plane
+    for denoise_device_variance's moments_ptr with samples = spp, beside out_colour, out_albedo and this frame's normal/depth plane.
+    Ordered on the context's stream."""
+    _positive_ints(("w", w), ("h", h))
+    cur = (("colour_ptr", colour_ptr), ("albedo_ptr", albedo_ptr), ("normal_depth_ptr", normal_depth_ptr), ("moments_ptr", moments_ptr),
+           ("out_colour_ptr", out_colour_ptr), ("out_albedo_ptr", out_albedo_ptr), ("out_moments_ptr", out_moments_ptr),
+           ("out_variance_ptr", out_variance_ptr))
+    _pointers(*cur)
+    if not all(v for _, v in cur):
+        raise ValueError("%s: device buffers are required" % ", ".join(n for n, v in cur if not v))
+    cam = _camera_bytes("camera", camera)
+    prev_cam, prev_ptrs = None, (None,) * 4
+    if prev is not None:
+        if not isinstance(prev, (tuple, list)) or len(prev) != 5:
+            raise ValueError("prev: None or (camera, colour_ptr, albedo_ptr, normal_depth_ptr, moments_ptr) expected, got %r" % (prev,))
+        prev_cam = _camera_bytes("prev camera", prev[0])
+        named = tuple(zip(("prev colour_ptr", "prev albedo_ptr", "prev normal_depth_ptr", "prev moments_ptr"), prev[1:]))
+        _pointers(*named)
+        if not all(v for _, v in named):
+            raise ValueError("prev: all four device buffers are required")
+        prev_ptrs = tuple(C.c_void_p(v) for v in prev[1:])
+    if not isinstance(max_history, (int, float, np.integer, np.floating)) or isinstance(max_history, bool) or not 1 <= max_history <= 65536:
+        raise ValueError("max_history: a number in 1..65536 expected, got %r" % (max_history,))
+    _sigmas(("depth_tolerance", depth_tolerance), ("normal_tolerance", normal_tolerance), ("coverage_tolerance", coverage_tolerance))
+    _chk(load_library().tptTemporalAccumulateDevice(w, h, cam, prev_cam, C.c_void_p(colour_ptr), C.c_void_p(albedo_ptr),
+                                                    C.c_void_p(normal_depth_ptr), C.c_void_p(moments_ptr), *prev_ptrs,
+                                                    C.c_void_p(out_colour_ptr), C.c_void_p(out_albedo_ptr), C.c_void_p(out_moments_ptr),
+                                                    C.c_void_p(out_variance_ptr), max_history, depth_tolerance, normal_tolerance,
+                                                    coverage_tolerance), "tptTemporalAccumulateDevice")
 
 
 def sharded_finish():

@@ -99,6 +99,21 @@ __attribute__((weak)) hipError_t tptLaunchDenoiseVariance(const float* colour, c
                                                           const float* moments, float* out, float* scratch, int width, int height,
                                                           int iterations, float samples, float sl2, float in, float id, bool demodulate,
                                                           hipStream_t stream);
+// tptTemporalAccumulateDevice: what the kernel needs of the two cameras and the call, made on the host in the order include/tpt_hip.h
+// states (host and device are built with -ffp-contract=off); by value in the kernel arguments.
+struct tptTemporalConsts {
+    float o[3], ll[3], H[3], V[3];          // this frame's camera
+    float po[3], pa[3], pw[3], pH[3], pV[3]; // the previous camera: origin, a = ll' - o', ww, horizontal, vertical
+    float pf, phh, pvv;                      // f = -dot(a, w'), dot(H', H'), dot(V', V')
+    float maxHistory, depthTol, normalTol, coverageTol;
+};
+// One launch of the temporal accumulation kernel; the four prev planes are all null (first frame: k's previous camera is unused) or
+// all given.  Weak for the same reason as tptLaunchDenoise.
+__attribute__((weak)) hipError_t tptLaunchTemporal(const float* colour, const float* albedo, const float* normalDepth, const float* moments,
+                                                   const float* prevColour, const float* prevAlbedo, const float* prevNormalDepth,
+                                                   const float* prevMoments, float* outColour, float* outAlbedo, float* outMoments,
+                                                   float* outVariance, int width, int height, const tptTemporalConsts& k,
+                                                   hipStream_t stream);
 hipError_t tptLaunchAssemble(const float* gathered, float* image, int width, int height, int stripeRows, int nRanks, int padRows, hipStream_t stream);
 hipError_t tptLaunchQueueProbe(unsigned long long ticks, hipStream_t stream);
 hipError_t tptLaunchChunkOrder(const unsigned* cost, unsigned* snap, unsigned* order, int numChunks, hipStream_t stream);

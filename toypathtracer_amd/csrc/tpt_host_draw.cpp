@@ -368,4 +368,67 @@ int tptDenoiseDeviceVariance(int w, int h, const float* deviceColour, const floa
     return 0;
 }
 
+// The temporal accumulation pass (include/tpt_hip.h states it): a post-process on the context stream like the two filters, one launch,
+// no scratch plane.  Both cameras are read here; what the kernel needs of them is made in the stated order and travels by value.
+int tptTemporalAccumulateDevice(int w, int h, const void* camera, const void* prevCamera, const float* deviceColour,
+                                const float* deviceAlbedo, const float* deviceNormalDepth, const float* deviceMoments,
+                                const float* devicePrevColour, const float* devicePrevAlbedo, const float* devicePrevNormalDepth,
+                                const float* devicePrevMoments, float* deviceOutColour, float* deviceOutAlbedo, float* deviceOutMoments,
+                                float* deviceOutVariance, float maxHistory, float depthTolerance, float normalTolerance,
+                                float coverageTolerance)
+{
+    if (requireInit()) return -1;
+    const std::string f("tptTemporalAccumulateDevice");
+    if (w < 1 || w > 8192 || h < 1 || h > 8192) return fail(f + ": w and h must lie in 1..8192");
+    if (!camera) return fail(f + ": camera is required");
+    if (!deviceColour || !deviceAlbedo || !deviceNormalDepth || !deviceMoments) return fail(f + ": the four planes of this frame are required");
+    if (!deviceOutColour || !deviceOutAlbedo || !deviceOutMoments || !deviceOutVariance) return fail(f + ": the four output planes are required");
+    const int nPrev = (prevCamera != nullptr) + (devicePrevColour != nullptr) + (devicePrevAlbedo != nullptr) +
+                      (devicePrevNormalDepth != nullptr) + (devicePrevMoments != nullptr);
+    if (nPrev != 0 && nPrev != 5) return fail(f + ": prevCamera and the four prev planes must be all NULL or all given");
+    const uintptr_t bytes = (uintptr_t)w * (uintptr_t)h * 16u;
+    const float* outs[4] = {deviceOutColour, deviceOutAlbedo, deviceOutMoments, deviceOutVariance};
+    for (int i = 0; i < 4; ++i) {
+        if (overlapsAny(outs[i], {deviceColour, deviceAlbedo, deviceNormalDepth, deviceMoments, devicePrevColour, devicePrevAlbedo,
+                                  devicePrevNormalDepth, devicePrevMoments}, bytes))
+            return fail(f + ": an output overlaps an input");
+        for (int j = 0; j < i; ++j)
+            if (overlapsAny(outs[i], {outs[j]}, bytes)) return fail(f + ": two outputs overlap");
+    }
+    if (!(maxHistory >= 1.0f && maxHistory <= 65536.0f)) return fail(f + ": maxHistory must lie in 1..65536"); // (NaN fails)
+    auto tolOk = [](float t) { return t >= 0.0f && t <= 3.40282347e38f; };
+    if (!tolOk(depthTolerance) || !tolOk(normalTolerance) || !tolOk(coverageTolerance))
+        return fail(f + ": every tolerance must be finite and at least 0");
+    auto dot3 = [](const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
+    // a camera the pass can project through: finite, a frame that spans two directions, in front of its origin; a = ll - o, f = -dot(a, ww)
+    // The reference's Camera is 22 consecutive floats: origin, lowerLeftCorner, horizontal, vertical, uu, vv, ww, lensRadius.  A camera
+    // the pass can project through is finite, its frame spans two directions and lies in front of its origin; a = ll - o, f = -dot(a, ww).
+    auto cameraOk = [&](const float* c, float* a, float& fc) {
+        for (int i = 0; i < 22; ++i)
+            if (!(fabsf(c[i]) <= 3.40282347e38f)) return false;
+        for (int i = 0; i < 3; ++i) a[i] = c[3 + i] - c[i];
+        fc = -dot3(a, c + 18);
+        return dot3(c + 6, c + 6) != 0.0f && dot3(c + 9, c + 9) != 0.0f && fc > 0.0f;
+    };
+    static_assert(sizeof(CameraPOD) == 22 * sizeof(float), "the reference's Camera");
+    float cam[22], prev[22], a[3], fc;
+    tptTemporalConsts k = {};
+    memcpy(cam, camera, sizeof cam);
+    if (!cameraOk(cam, a, fc)) return fail(f + ": camera has a non-finite field, a degenerate frame or its frame behind its origin");
+    memcpy(k.o, cam, 12); memcpy(k.ll, cam + 3, 12); memcpy(k.H, cam + 6, 12); memcpy(k.V, cam + 9, 12);
+    if (prevCamera) {
+        memcpy(prev, prevCamera, sizeof prev);
+        if (!cameraOk(prev, k.pa, k.pf)) return fail(f + ": prevCamera has a non-finite field, a degenerate frame or its frame behind its origin");
+        memcpy(k.po, prev, 12); memcpy(k.pH, prev + 6, 12); memcpy(k.pV, prev + 9, 12); memcpy(k.pw, prev + 18, 12);
+        k.phh = dot3(prev + 6, prev + 6);
+        k.pvv = dot3(prev + 9, prev + 9);
+    }
+    k.maxHistory = maxHistory; k.depthTol = depthTolerance; k.normalTol = normalTolerance; k.coverageTol = coverageTolerance;
+    if (!tptLaunchTemporal) return fail(f + ": this build has no temporal accumulation kernel");
+    HIPCHK(tptLaunchTemporal(deviceColour, deviceAlbedo, deviceNormalDepth, deviceMoments, devicePrevColour, devicePrevAlbedo,
+                             devicePrevNormalDepth, devicePrevMoments, deviceOutColour, deviceOutAlbedo, deviceOutMoments,
+                             deviceOutVariance, w, h, k, g.stream));
+    return 0;
+}
+
 } // extern "C"

@@ -394,6 +394,107 @@ __global__ void __launch_bounds__(256) tptVarianceAtrousKernel(const f4* __restr
     dst[p] = o;
 }
 
+// tptTemporalAccumulateDevice (include/tpt_hip.h states it; tests/temporal_checker.c restates it): this frame's planes blended with the
+// history fetched through the previous camera.  The layout of the a-trous kernels -- one lane per pixel, a wave along 64 pixels of a
+// row -- so the four current planes and the four stores are coalesced 16-B accesses; the 2 x 2 taps are gathers, coalesced wherever the
+// motion is smooth, and a tap of weight 0 (all but one under a camera that stands still) is not loaded.  The cameras' constants come as
+// kernel arguments.  HISTORY = false is the first frame of a sequence: no prev plane is touched.  Every quotient is a plain IEEE
+// division, the square roots tpt_math.h's.
+template <bool HISTORY>
+__global__ void __launch_bounds__(256) tptTemporalKernel(const f4* __restrict__ colour, const f4* __restrict__ albedo, const f4* __restrict__ nd,
+                                                         const f4* __restrict__ moments, const f4* __restrict__ prevColour,
+                                                         const f4* __restrict__ prevAlbedo, const f4* __restrict__ prevNd,
+                                                         const f4* __restrict__ prevMoments, f4* __restrict__ outColour,
+                                                         f4* __restrict__ outAlbedo, f4* __restrict__ outMoments,
+                                                         f4* __restrict__ outVariance, int width, int height, const tptTemporalConsts k)
+{
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x >= width || y >= height) return;
+    const size_t p = (size_t)y * width + x;
+    const f4 cc = colour[p], ca = albedo[p], cn = nd[p], cm = moments[p];
+    // out: colour rgb, albedo xyzw, moments xy -- this frame's unless a history is found
+    float o0 = cc.x, o1 = cc.y, o2 = cc.z, o3 = ca.x, o4 = ca.y, o5 = ca.z, o6 = ca.w, o7 = cm.x, o8 = cm.y;
+    float N = 1.0f;
+    if (HISTORY) {
+        const float c = ca.w;
+        const f3 o = ld3(k.o), po = ld3(k.po), pw = ld3(k.pw), pa = ld3(k.pa);
+        const float s = ((float)x + 0.5f) / (float)width, t = ((float)y + 0.5f) / (float)height;
+        const f3 dir = normalize(((ld3(k.ll) + s * ld3(k.H)) + t * ld3(k.V)) - o);
+        f3 rel = dir, n = mk3(0.0f, 0.0f, 0.0f);
+        if (c > 0.0f) {
+            const float d = cn.w / c;
+            n = mk3(cn.x / c, cn.y / c, cn.z / c);
+            rel = (o + dir * d) - po;
+        }
+        const float z = -dot(rel, pw);
+        const float kz = k.pf / z;
+        const f3 q = rel * kz - pa;
+        const float px = dot(q, ld3(k.pH)) / k.phh * (float)width - 0.5f;
+        const float py = dot(q, ld3(k.pV)) / k.pvv * (float)height - 0.5f;
+        // (outside [-1, size) no tap lies inside the image; NaN and the infinities fail here too, and what passes fits an int)
+        if (z > 0.0f && px >= -1.0f && px < (float)width && py >= -1.0f && py < (float)height) {
+            constexpr float snap = TPT_TEMPORAL_SNAP, big = 3.40282347e38f;
+            float fx0 = __builtin_floorf(px), fy0 = __builtin_floorf(py);
+            float fx = px - fx0, fy = py - fy0;
+            if (fx < snap) fx = 0.0f;
+            else if (fx > 1.0f - snap) { fx0 += 1.0f; fx = 0.0f; }
+            if (fy < snap) fy = 0.0f;
+            else if (fy > 1.0f - snap) { fy0 += 1.0f; fy = 0.0f; }
+            const int ix = (int)fx0, iy = (int)fy0;
+            const float e = tsqrt(dot(rel, rel));
+            float B = 0.0f, h0 = 0.0f, h1 = 0.0f, h2 = 0.0f, h3 = 0.0f, h4 = 0.0f, h5 = 0.0f, h6 = 0.0f, h7 = 0.0f, h8 = 0.0f, hN = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const float b = (i ? fx : 1.0f - fx) * (j ? fy : 1.0f - fy);
+                    const int qx = ix + i, qy = iy + j;
+                    if (!(b > 0.0f) || qx < 0 || qx >= width || qy < 0 || qy >= height) continue;
+                    const size_t t4 = (size_t)qy * width + qx;
+                    const f4 pm = prevMoments[t4], pc = prevColour[t4], pal = prevAlbedo[t4];
+                    if (!(pm.w >= 1.0f && pm.w <= big)) continue;
+                    if (!(__builtin_fabsf(pc.x) <= big && __builtin_fabsf(pc.y) <= big && __builtin_fabsf(pc.z) <= big)) continue;
+                    const float c1 = pal.w;
+                    if (!(__builtin_fabsf(c - c1) <= k.coverageTol)) continue;
+                    if (c > 0.0f && c1 > 0.0f) {
+                        const f4 pn = prevNd[t4];
+                        const float d1 = pn.w / c1;
+                        if (!(__builtin_fabsf(e - d1) <= k.depthTol * e)) continue;
+                        const float dx = n.x - pn.x / c1, dy = n.y - pn.y / c1, dz = n.z - pn.z / c1;
+                        if (!((dx * dx + dy * dy) + dz * dz <= k.normalTol)) continue;
+                    } else if (!(c == 0.0f && c1 == 0.0f)) {
+                        continue;
+                    }
+                    B += b;
+                    h0 += b * pc.x; h1 += b * pc.y; h2 += b * pc.z;
+                    h3 += b * pal.x; h4 += b * pal.y; h5 += b * pal.z; h6 += b * pal.w;
+                    h7 += b * pm.x; h8 += b * pm.y;
+                    hN += b * pm.w;
+                }
+            }
+            if (B > 0.0f) {
+                N = hN / B + 1.0f;
+                if (N > k.maxHistory) N = k.maxHistory;
+                const float lerp = (N - 1.0f) / N, one = 1.0f - lerp;
+                o0 = (h0 / B) * lerp + o0 * one; o1 = (h1 / B) * lerp + o1 * one; o2 = (h2 / B) * lerp + o2 * one;
+                o3 = (h3 / B) * lerp + o3 * one; o4 = (h4 / B) * lerp + o4 * one; o5 = (h5 / B) * lerp + o5 * one;
+                o6 = (h6 / B) * lerp + o6 * one;
+                o7 = (h7 / B) * lerp + o7 * one; o8 = (h8 / B) * lerp + o8 * one;
+            }
+        }
+    }
+    const float dd = o8 - o7 * o7;
+    f4 r;
+    r.x = o0; r.y = o1; r.z = o2; r.w = cc.w;
+    outColour[p] = r;
+    r.x = o3; r.y = o4; r.z = o5; r.w = o6;
+    outAlbedo[p] = r;
+    r.x = o7; r.y = o8; r.z = 0.0f; r.w = N;
+    outMoments[p] = r;
+    r.x = 0.0f; r.y = (dd > 0.0f ? dd : 0.0f) / N; r.z = 0.0f; r.w = N;
+    outVariance[p] = r;
+}
+
 template <int HS, int FOLD, bool LDS_SCENE>
 // 112 VGPRs x 4 waves/SIMD leaves 64 registers per SIMD lane for the resolve kernel's waves (see tptTraceQueueKernel;
 // amdgpu_num_vgpr counts half of the unified file on gfx90a+, so 56 means 112)
@@ -2420,6 +2521,20 @@ hipError_t tptLaunchDenoiseVariance(const float* colour, const float* albedo, co
                                                                                            nd, m, dst, width, height, 1 << i, samples, sl2,
                                                                                            in, id, demodulate ? 1 : 0);
     });
+}
+
+hipError_t tptLaunchTemporal(const float* colour, const float* albedo, const float* normalDepth, const float* moments, const float* prevColour,
+                             const float* prevAlbedo, const float* prevNormalDepth, const float* prevMoments, float* outColour,
+                             float* outAlbedo, float* outMoments, float* outVariance, int width, int height, const tptTemporalConsts& k,
+                             hipStream_t stream)
+{
+    const dim3 grid((unsigned)(width + 63) / 64, (unsigned)(height + 3) / 4);
+    auto in = [](const float* q) { return reinterpret_cast<const f4*>(q); };
+    auto out = [](float* q) { return reinterpret_cast<f4*>(q); };
+    hipLaunchKernelGGL(prevColour ? tptTemporalKernel<true> : tptTemporalKernel<false>, grid, dim3(64, 4), 0, stream, in(colour), in(albedo),
+                       in(normalDepth), in(moments), in(prevColour), in(prevAlbedo), in(prevNormalDepth), in(prevMoments), out(outColour),
+                       out(outAlbedo), out(outMoments), out(outVariance), width, height, k);
+    return hipGetLastError();
 }
 
 hipError_t tptLaunchAssemble(const float* gathered, float* image, int width, int height, int stripeRows, int nRanks, int padRows, hipStream_t stream)
