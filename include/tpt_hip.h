@@ -202,6 +202,35 @@ TPT_API int tptDenoiseDevice(int screenWidth, int screenHeight, const float* dev
  * refused: deviceMoments NULL, or overlapping the tile or a given plane.  A refused call writes nothing. */
 TPT_API int tptDrawDeviceMoments(float time, int frameCount, int screenWidth, int screenHeight, float* deviceTile,
                                  float* deviceAlbedo, float* deviceNormalDepth, float* deviceMoments, unsigned testFlags);
+/* The frames of an ANIMATED clip, each with the planes the denoising chain reads (tptTemporalAccumulateDevice, tptDenoiseDeviceVariance),
+ * up to 32 per launch: tptDrawDeviceAnimation with tptDrawDeviceMoments' outputs.  Frame j (0 <= j < nFrames) is bit-identical to
+ *   tptUpdate(times[j], firstFrame + j, w, h, testFlags);
+ *   tptDrawDeviceMoments(times[j], firstFrame + j, w, h, deviceTile, albedo_j, normalDepth_j, deviceMoments, testFlags);
+ * with albedo_j = deviceFrameAlbedo + j*h*w*4 (NULL if deviceFrameAlbedo is NULL), likewise normalDepth_j, and the same ray count.
+ * deviceTile and deviceMoments (both required, h*w*4 floats) end as that sequence leaves them: blended with the tile's lerp factor per
+ * frame, .w of the moments untouched.  The five per-frame outputs are each optional (NULL): deviceFrameImages, deviceFrameAlbedo,
+ * deviceFrameNormalDepth, deviceFrameMoments -- nFrames consecutive device planes of h*w*4 floats each -- and deviceFrameRays, nFrames
+ * int64 in device memory.  Image j is the tile, and moments plane j is deviceMoments (all four channels), as they stand right after
+ * frame j's blends (what a host copying them after each frame sees); deviceFrameRays[j] is OVERWRITTEN with frame j's rays and the
+ * context's counter advances by their sum.  Without TPT_FLAG_PROGRESSIVE every frame image and moments plane is that frame's own:
+ * plane j of each per-frame output is the input tptTemporalAccumulateDevice asks for.  Asynchronous on the context's stream, ordered
+ * behind earlier work there.  Afterwards the context is where tptDrawDeviceAnimation leaves it: spheres 1 and 8 at times[nFrames - 1],
+ * that scene staged, the camera of tptUpdate; frames traced ahead and stream-batch planes are dropped first.  A non-finite time affects
+ * its own frame only.
+ * One trace launch per 32 frames while the scene moves (kFlagAnimate, more than 8 spheres) and has fewer than 256 spheres.  Animated
+ * scenes of 256 spheres and more, and scenes in which nothing moves (no kFlagAnimate, or 8 spheres or fewer), take one launch per
+ * frame (tptDrawDeviceMoments' kernel), with the same bits.  The launches of one call overlap (each waits for the blends of the launch
+ * before the previous one only); separate calls are ordered on the context stream, so a long clip is best passed in one call.  The
+ * library stages colour and moments of a launch's frames: up to 3 * h*w*16 bytes per frame of a launch beside the colour slots.
+ * Refused (non-zero, tptGetLastError names the function, nothing enqueued, no buffer written, spheres not moved): nFrames < 1; times,
+ * deviceTile or deviceMoments NULL; no tptUpdate at this size; w or h over 8192; colour and moments staging of one launch (2 * h*w*16
+ * bytes per frame of the launch) over 4096 MiB; any two of the seven buffers overlapping, each taken at its full extent; row-serial
+ * seeds, the forward fold, a kernel variant other than the path-queue kernel, spp over 2047, more than 65534 spheres; row sharding or a
+ * communicator; a tile mirror.  A failure after the first launch was enqueued is tptDrawDeviceAnimation's. */
+TPT_API int tptDrawDeviceAnimationMoments(int firstFrame, int nFrames, const float* times, int screenWidth, int screenHeight,
+                                          float* deviceTile, float* deviceMoments,
+                                          float* deviceFrameImages, float* deviceFrameAlbedo, float* deviceFrameNormalDepth,
+                                          float* deviceFrameMoments, int64_t* deviceFrameRays, unsigned testFlags);
 /* The spatial filter of SVGF (Schied et al., HPG 2017) in tptDenoiseDevice's rational form: an a-trous filter whose luminance term is
  * scaled by a per-pixel variance made from tptDrawDeviceMoments' moments and carried through the iterations.  All six buffers are
  * device buffers of h*w*4 floats; deviceAlbedo and deviceNormalDepth may be NULL.  samples: how many samples the colour and the moments

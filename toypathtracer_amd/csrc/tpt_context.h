@@ -41,6 +41,7 @@ struct TraceTicket {
     const f4* colour = nullptr;
     int batch = 1;           // frames traced by the launch; their colour planes lie nPixels apart
     tptLerpTable lerp = {};  // batch > 1: each frame's lerp factor
+    const f4* moments = nullptr; // a launch with moments: where it staged them (Context::dMoments; a clip launch's half), a plane per frame
     TraceTicket plane(int j) const // frame j of the launch, as a ticket of its own (a single-frame launch: plane 0 is itself)
     {
         TraceTicket t = *this;
@@ -234,6 +235,12 @@ struct Context {
     // one plane serves them all.  Its sums are a third f4 per path column of dAovSums.
     f4* dMoments = nullptr;
     size_t momentsBytes = 0;
+    // tptDrawDeviceAnimationMoments: the launches of one call alternate between two halves of dAovSums and dMoments (both twice the
+    // launch's need), so launch k + 1 waits only for the blends of launch k - 1, whose halves it takes over, and is traced beside the
+    // blends of launch k.  evClip[h]: recorded on the context stream when a launch on half h ^ 1 is enqueued, i.e. behind the blends of
+    // the previous launch on half h.  The first launch of a call waits for the whole context stream, as every other AOV launch does.
+    hipEvent_t evClip[2] = {nullptr, nullptr};
+    unsigned clipSeq = 0;
     // tptDenoiseDevice: the plane the a-trous iterations ping-pong through beside the caller's output ([h][w] f4 of the largest frame
     // denoised so far), made by the first call that iterates more than once, grown when a later one needs more, freed by tptShutdown.
     // Only the context stream uses it, so stream order alone keeps one call's iterations from another's.
@@ -394,6 +401,7 @@ struct AovPlanes {
     f4* albedo = nullptr;
     f4* normalDepth = nullptr;
     bool moments = false; // tptDrawDeviceMoments: tptTraceMomentsKernel, into Context::dMoments
+    bool continues = false; // tptDrawDeviceAnimationMoments: a later launch of the call (Context::evClip)
 };
 int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long long* frameRays, TraceTicket& T, int batch = 1, int rayStride = 0,
                  const BatchTable* table = nullptr, const AovPlanes* aov = nullptr);

@@ -70,6 +70,10 @@ struct KernelArgs {
     // ... and its luminance moments (tptDrawDeviceMoments): a third f4 of sums per path, aovSums[3 x column .. + 2], and the frame's
     // means {l, l^2, 0, 0} stored into momentsOut ([nLocalRows][width] f4); the launch takes tptTraceMomentsKernel.  Null otherwise.
     f4* momentsOut = nullptr;
+    // The frames of an animated clip with their planes (tptDrawDeviceAnimationMoments: moveCentres and aovSums both given, the launch
+    // takes tptTraceClipKernel): frame j of the batch stores its first-hit planes at aovAlbedo / aovNormalDepth + j * aovPlane pixels (the
+    // caller's per-frame buffers) and its moments at momentsOut + j * framePlane (staging, beside its colour plane).
+    int aovPlane = 0;
 };
 
 } // namespace tpt

@@ -433,6 +433,8 @@ int tptShutdown(void)
     (void)hipFree(g.dAovSums); g.dAovSums = nullptr;
     g.aovSumsBytes = 0;
     if (g.evAov) { (void)hipEventDestroy(g.evAov); g.evAov = nullptr; }
+    for (hipEvent_t& e : g.evClip)
+        if (e) { (void)hipEventDestroy(e); e = nullptr; }
     (void)hipFree(g.dMoments); g.dMoments = nullptr;
     g.momentsBytes = 0;
     (void)hipFree(g.dDenoise); g.dDenoise = nullptr;

@@ -426,11 +426,15 @@ int ensureViewSlots()
 
 // tptDrawDeviceAov: the per-path sums (Context::dAovSums) for the largest grid this frame shape can take, and the ordering event;
 // made by the first AOV call, grown (after a drain) when a later one asks for more.  tptDrawDeviceMoments (`momentsBytes` > 0): a
-// third f4 per path, and the frame's moments plane (Context::dMoments) of that many bytes.
-int ensureAovSums(const FramePlan& P, size_t momentsBytes)
+// third f4 per path, and the frame's moments plane (Context::dMoments) of that many bytes -- one plane per frame of the launch for
+// tptDrawDeviceAnimationMoments, which (`halves` 2) takes both buffers twice: its launches alternate between the halves (Context::evClip).
+int ensureAovSums(const FramePlan& P, size_t momentsBytes, int halves)
 {
     if (!g.evAov) HIPCHK(hipEventCreateWithFlags(&g.evAov, kOrderingEvent));
-    const size_t need = (momentsBytes ? 3 : 2) * sizeof(f4) * (size_t)maxGridBlocks(P) * (size_t)tptQueuePathsPerBlock();
+    for (hipEvent_t& e : g.evClip)
+        if (!e) HIPCHK(hipEventCreateWithFlags(&e, kOrderingEvent));
+    const size_t need = (momentsBytes ? 3 : 2) * sizeof(f4) * (size_t)maxGridBlocks(P) * (size_t)tptQueuePathsPerBlock() * (size_t)halves;
+    momentsBytes *= (size_t)halves;
     if (need <= g.aovSumsBytes && momentsBytes <= g.momentsBytes) return 0;
     int rc = syncAllStreams(); // (an earlier AOV launch, or its blend, may still be reading the old buffers)
     if (rc) return rc;
@@ -456,7 +460,8 @@ int ensureAovSums(const FramePlan& P, size_t momentsBytes)
 // `table` (tptDrawDeviceViews, tptDrawDeviceAnimation): what differs between the batch's frames (host memory, copied to the slot's
 // table on the frame's stream) -- cameras: `batch` views of frame frameCount, traced by the views kernel; centres: `batch` frames of an
 // animated scene, traced by the animation kernel; neither: the plain kernel.  Every frame counts its rays into the slot's counters.
-// `aov` (tptDrawDeviceAov, a single frame): the caller's first-hit planes, written by the AOV kernel behind the context stream.
+// `aov` (tptDrawDeviceAov, a single frame): the caller's first-hit planes, written by the AOV kernel behind the context stream.  With
+// moments and a centres table (tptDrawDeviceAnimationMoments): the planes of `batch` frames, h * w pixels apart, and as many moments planes.
 int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long long* frameRays, TraceTicket& T, int batch, int rayStride,
                  const BatchTable* table, const AovPlanes* aov)
 {
@@ -531,7 +536,8 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
         return refuse("tptDrawDeviceViews: needs the path-queue kernel (per-pixel seeds, recursive fold, two-phase HitSpheres, at most 2047 spp)");
     if (centres && (!P.queued || a.scene.nGroups > 0))
         return refuse("tptDrawDeviceAnimation: one launch per batch needs the path-queue kernel and a flat scene");
-    if (aov && (!P.queued || batch != 1 || table))
+    const bool clip = aov && aov->moments && centres; // (the frames of an animated clip with their planes: tptTraceClipKernel)
+    if (aov && (!P.queued || !(clip || (batch == 1 && !viewCams && !centres))))
         return refuse("tptDrawDeviceAov: needs the path-queue kernel (per-pixel seeds, recursive fold, two-phase HitSpheres, at most 2047 spp)");
     // a batch is traced by the path-queue kernel (per-pixel seeds) or, in the reference's own seed mode, by the lane-refill
     // kernel: one lane per (frame, row) -- rows AND frames are independent RNG streams there (Test.cpp:280)
@@ -541,11 +547,15 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
     if ((rc = ensureFrameBuffers(P, w))) return rc;
     a.aovSums = a.aovAlbedo = a.aovNormalDepth = a.momentsOut = nullptr;
     if (aov) {
-        if ((rc = ensureAovSums(P, aov->moments ? (size_t)a.nLocalRows * (size_t)w * sizeof(f4) : 0))) return rc;
-        a.aovSums = g.dAovSums;
+        if ((rc = ensureAovSums(P, aov->moments ? (size_t)a.nLocalRows * (size_t)w * sizeof(f4) * (size_t)batch : 0, clip ? 2 : 1))) return rc;
+        // (a clip launch's half: the second one starts half the CAPACITY in, in whole f4 -- the buffers only change after a drain, so
+        //  launches of different sizes agree where it lies)
+        const size_t half = clip ? (size_t)(g.clipSeq & 1u) : 0;
+        a.aovSums = g.dAovSums + half * (g.aovSumsBytes / (2 * sizeof(f4)));
         a.aovAlbedo = aov->albedo;
         a.aovNormalDepth = aov->normalDepth;
-        if (aov->moments) a.momentsOut = g.dMoments;
+        if (aov->moments) a.momentsOut = g.dMoments + half * (g.momentsBytes / (2 * sizeof(f4)));
+        a.aovPlane = clip ? h * w : 0;
     }
     if (frameRays) a.rayCounter = frameRays;
     a.rayCounterStride = rayStride; // (batched row-serial launch for the host path: one counter per frame of the batch)
@@ -581,9 +591,18 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
     if (aov && ts != g.stream) {
         // the caller's planes: written after everything enqueued on the context stream before this call (its blend, like the tile's,
         // follows the launch there); this also keeps the AOV launches, and their one buffer of sums, one after the other
-        HIPCHK(hipEventRecord(g.evAov, g.stream));
-        HIPCHK(hipStreamWaitEvent(ts, g.evAov, 0));
+        // ... except the later launches of one tptDrawDeviceAnimationMoments call, which alternate between two halves of the sums and
+        // the staging and write planes of their own: each waits for the blends of the launch before the previous one (Context::evClip)
+        if (clip) {
+            const unsigned h = g.clipSeq & 1u;
+            HIPCHK(hipEventRecord(g.evClip[h ^ 1u], g.stream)); // (behind the previous launch's blends: what the next launch waits for)
+            HIPCHK(hipStreamWaitEvent(ts, aov->continues ? g.evClip[h] : g.evClip[h ^ 1u], 0));
+        } else {
+            HIPCHK(hipEventRecord(g.evAov, g.stream));
+            HIPCHK(hipStreamWaitEvent(ts, g.evAov, 0));
+        }
     }
+    if (clip) g.clipSeq++;
     if (viewCams || centres) {
         // the launch's table, behind the same wait: the slot's previous launch has read its table; the previous copy out of the
         // slot's pinned staging (an earlier call on this slot) has left the host before the staging is overwritten
@@ -630,6 +649,7 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
     T.pipelined = pipelined;
     T.lerpFac = a.fc.lerpFac;
     T.colour = a.frameColour;
+    T.moments = a.momentsOut;
     T.batch = batch;
     for (int j = 0; j < batch && batch > 1; ++j)
         T.lerp.v[j] = makeFrameConsts(g.cam, w, h, g.spp, frameCount + j, testFlags, g.seedMode, g.config, g.animateSmoothing).lerpFac;
@@ -683,8 +703,11 @@ static int checkPathQueueDraw(const char* fn, const char* things, int w, int h, 
 // context's stream.  Frame j is blended into tiles + j * tileStep floats -- with the launch's lerp factor (views: n cameras of one frame)
 // or, `ownLerp`, its own (the frames of an animation) -- and adds its rays to the running total; given `images`, the tile as it then
 // stands is written to image j.  The per-frame counts go to `rays` first: the slot's counters are free again once its last blend has
-// run (the next launch on this slot waits for that).
-static int enqueuePlaneResolves(const TraceTicket& T, float* tiles, size_t tileStep, bool ownLerp, float* images, int64_t* rays)
+// run (the next launch on this slot waits for that).  Given `moments` (tptDrawDeviceAnimationMoments), frame j's plane of the moments
+// staging is blended into it right behind frame j's tile blend, with the same lerp factor (.w kept), and `momentImages`, if given,
+// receives the plane as it then stands.
+static int enqueuePlaneResolves(const TraceTicket& T, float* tiles, size_t tileStep, bool ownLerp, float* images, int64_t* rays,
+                                float* moments = nullptr, float* momentImages = nullptr)
 {
     const Context::ViewSlot& V = g.views[T.slot];
     if (T.pipelined) HIPCHK(hipStreamWaitEvent(g.stream, g.evTrace[T.slot], 0));
@@ -694,10 +717,66 @@ static int enqueuePlaneResolves(const TraceTicket& T, float* tiles, size_t tileS
         const TraceTicket P = T.plane(j);
         HIPCHK(tptLaunchResolve(tiles + (size_t)j * tileStep, P.colour, T.nPixels, ownLerp ? P.lerpFac : T.lerpFac,
                                 images ? images + (size_t)j * plane : nullptr, g.dRays, nullptr, V.rays + j, g.stream));
+        if (moments)
+            HIPCHK(tptLaunchResolve(moments, T.moments + (size_t)j * (size_t)T.nPixels, T.nPixels, ownLerp ? P.lerpFac : T.lerpFac,
+                                    momentImages ? momentImages + (size_t)j * plane : nullptr, g.dRays, nullptr, nullptr, g.stream));
     }
     if (T.pipelined) {
         HIPCHK(hipEventRecord(g.evResolve[T.slot], g.stream));
         g.resolveRecorded[T.slot] = true;
+    }
+    return 0;
+}
+
+// The launches and blends of tptDrawDeviceAnimation and, with `planes`, tptDrawDeviceAnimationMoments, behind their checks: frames traced
+// ahead are dropped, the camera is the one every tptUpdate of the sequence builds, then `perLaunch` frames per launch.
+struct ClipPlanes {
+    float *moments, *frameAlbedo, *frameNormalDepth, *frameMoments; // (deviceMoments, and the per-frame outputs or null)
+};
+static int enqueueAnimation(int firstFrame, int nFrames, const float* times, int w, int h, float* deviceTile, float* deviceFrameImages,
+                            int64_t* deviceFrameRays, unsigned testFlags, bool animate, int perLaunch, const ClipPlanes* planes)
+{
+    int rc = g.pending.discard();
+    if (rc) return rc;
+    // the camera as every tptUpdate of the sequence builds it (Test.cpp:309-313, 341)
+    CameraSetup cs = g.camSetup;
+    if (g.config & CFG_MITSUBA_COMPARE) cs.aperture = 0.0f;
+    g.cam = makeCamera(cs, float(w) / float(h));
+    for (int f = 0; f < nFrames; f += perLaunch) {
+        const int n = nFrames - f < perLaunch ? nFrames - f : perLaunch;
+        BatchTable table;
+        f4 centres[2 * kMaxBatch];
+        if (animate) {
+            // each frame's centres of spheres 1 and 8 exactly as tptUpdate moves them (a non-finite time touches its own frame only); the
+            // context's spheres end at the batch's last time
+            const SpherePOD s1 = g.spheres[1], s8 = g.spheres[8];
+            for (int j = 0; j < n; ++j) {
+                const float t = times[f + j];
+                centres[2 * j] = f4{s1.cx, animatedY1(t), s1.cz, 0.0f};
+                centres[2 * j + 1] = f4{s8.cx, s8.cy, animatedZ8(t), 0.0f};
+            }
+            g.spheres[1].cy = centres[2 * (n - 1)].y;
+            g.spheres[8].cz = centres[2 * (n - 1) + 1].z;
+            // the staged scene is the batch's last frame: exact for the spheres that do not move, and the animation kernel reads spheres
+            // 1 and 8 from the table and tests them for every ray (tpt_trace.h, movedSphere)
+            if (perLaunch > 1) table.centres = centres;
+            if ((rc = stageScene())) return rc;
+        }
+        TraceTicket T;
+        AovPlanes aov; // (the launch's frames' planes in the caller's per-frame buffers)
+        const size_t at = (size_t)f * (size_t)h * (size_t)w * 4;
+        if (planes) {
+            aov.albedo = planes->frameAlbedo ? reinterpret_cast<f4*>(planes->frameAlbedo + at) : nullptr;
+            aov.normalDepth = planes->frameNormalDepth ? reinterpret_cast<f4*>(planes->frameNormalDepth + at) : nullptr;
+            aov.moments = true;
+            aov.continues = f > 0;
+        }
+        if ((rc = enqueueTrace(firstFrame + f, w, h, testFlags, nullptr, T, n, 1, &table, planes ? &aov : nullptr))) return rc;
+        // the blends, in frame order, each into the one tile with its frame's lerp factor (and the frame's moments behind it)
+        if (T.valid && (rc = enqueuePlaneResolves(T, deviceTile, 0, true, deviceFrameImages ? deviceFrameImages + at : nullptr,
+                                                  deviceFrameRays ? deviceFrameRays + f : nullptr, planes ? planes->moments : nullptr,
+                                                  planes && planes->frameMoments ? planes->frameMoments + at : nullptr)))
+            return rc;
     }
     return 0;
 }
@@ -887,39 +966,46 @@ int tptDrawDeviceAnimation(int firstFrame, int nFrames, const float* times, int 
         const size_t colour = (size_t)h * (size_t)w * sizeof(f4) * (size_t)(nFrames < perLaunch ? nFrames : perLaunch);
         return colour > (4ull << 30) ? refuse("tptDrawDeviceAnimation: " + std::to_string(colour >> 20) + " MiB of frame colour per launch: over the 4096 MiB limit") : 0;
     });
-    if (rc || (rc = g.pending.discard())) return rc;
-    // the camera as every tptUpdate of the sequence builds it (Test.cpp:309-313, 341)
-    CameraSetup cs = g.camSetup;
-    if (g.config & CFG_MITSUBA_COMPARE) cs.aperture = 0.0f;
-    g.cam = makeCamera(cs, float(w) / float(h));
-    for (int f = 0; f < nFrames; f += perLaunch) {
-        const int n = nFrames - f < perLaunch ? nFrames - f : perLaunch;
-        BatchTable table;
-        f4 centres[2 * kMaxBatch];
-        if (animate) {
-            // each frame's centres of spheres 1 and 8 exactly as tptUpdate moves them (a non-finite time touches its own frame only); the
-            // context's spheres end at the batch's last time
-            const SpherePOD s1 = g.spheres[1], s8 = g.spheres[8];
-            for (int j = 0; j < n; ++j) {
-                const float t = times[f + j];
-                centres[2 * j] = f4{s1.cx, animatedY1(t), s1.cz, 0.0f};
-                centres[2 * j + 1] = f4{s8.cx, s8.cy, animatedZ8(t), 0.0f};
+    if (rc) return rc;
+    return enqueueAnimation(firstFrame, nFrames, times, w, h, deviceTile, deviceFrameImages, deviceFrameRays, testFlags, animate, perLaunch, nullptr);
+}
+
+// nFrames frames of the scene as tptUpdate(times[j], firstFrame + j, ...) animates it, each followed by tptDrawDeviceMoments into the
+// frame's own albedo and normal / depth planes: the same bits, the same ray counts.  tptDrawDeviceAnimation's loop with the planes
+// beside the centres table: up to kMaxBatch frames per launch (tptTraceClipKernel) while the scene moves and is flat; a scene that does
+// not move, or a grouped one, goes frame by frame through the single-frame moments kernel.  The moments of a launch's frames are staged in
+// Context::dMoments, a plane per frame, and blended into deviceMoments behind each frame's tile blend.
+int tptDrawDeviceAnimationMoments(int firstFrame, int nFrames, const float* times, int w, int h, float* deviceTile, float* deviceMoments,
+                                  float* deviceFrameImages, float* deviceFrameAlbedo, float* deviceFrameNormalDepth, float* deviceFrameMoments,
+                                  int64_t* deviceFrameRays, unsigned testFlags)
+{
+    const std::string fn = "tptDrawDeviceAnimationMoments";
+    if (int rc_ = flushShardDeferred()) return rc_; // (see tptDrawDevice)
+    if (requireInit()) return -1;
+    if (nFrames < 1) return fail(fn + ": nFrames must be at least 1");
+    if (!times || !deviceTile || !deviceMoments || w <= 0 || h <= 0) return fail(fn + ": bad arguments (times, deviceTile, deviceMoments, size)");
+    const bool animate = (testFlags & TPT_FLAG_ANIMATE) && g.spheres.size() > 8; // (the tptUpdate guard, Test.cpp:304)
+    const int perLaunch = animate && g.spheres.size() < TPT_GROUP_MIN_SPHERES ? kMaxBatch : 1;
+    int rc = checkPathQueueDraw(fn.c_str(), "clip planes are", w, h, kQueueKernel | kQueueSpp, [&] {
+        const size_t plane = (size_t)h * (size_t)w * sizeof(f4), staged = 2 * plane * (size_t)(nFrames < perLaunch ? nFrames : perLaunch);
+        if (staged > (4ull << 30))
+            return refuse(fn + ": " + std::to_string(staged >> 20) + " MiB of frame colour and moments per launch: over the 4096 MiB limit");
+        if (g.spheres.size() > 65534) return fail(fn + ": at most 65534 spheres (the path-queue kernel)");
+        // the seven buffers, each at its full extent: no two may share a byte
+        const struct { const void* p; size_t bytes; } bufs[7] = {
+            {deviceTile, plane}, {deviceMoments, plane}, {deviceFrameImages, plane * (size_t)nFrames}, {deviceFrameAlbedo, plane * (size_t)nFrames},
+            {deviceFrameNormalDepth, plane * (size_t)nFrames}, {deviceFrameMoments, plane * (size_t)nFrames},
+            {deviceFrameRays, sizeof(int64_t) * (size_t)nFrames}};
+        for (int i = 0; i < 7; ++i)
+            for (int k = i + 1; k < 7; ++k) {
+                const uintptr_t a = reinterpret_cast<uintptr_t>(bufs[i].p), b = reinterpret_cast<uintptr_t>(bufs[k].p);
+                if (a && b && a < b + bufs[k].bytes && b < a + bufs[i].bytes) return fail(fn + ": two of the tile, moments and per-frame buffers overlap");
             }
-            g.spheres[1].cy = centres[2 * (n - 1)].y;
-            g.spheres[8].cz = centres[2 * (n - 1) + 1].z;
-            // the staged scene is the batch's last frame: exact for the spheres that do not move, and the animation kernel reads spheres
-            // 1 and 8 from the table and tests them for every ray (tpt_trace.h, movedSphere)
-            if (perLaunch > 1) table.centres = centres;
-            if ((rc = stageScene())) return rc;
-        }
-        TraceTicket T;
-        if ((rc = enqueueTrace(firstFrame + f, w, h, testFlags, nullptr, T, n, 1, &table))) return rc;
-        // the blends, in frame order, each into the one tile with its frame's lerp factor
-        if (T.valid && (rc = enqueuePlaneResolves(T, deviceTile, 0, true, deviceFrameImages ? deviceFrameImages + (size_t)f * (size_t)T.nPixels * 4 : nullptr,
-                                                  deviceFrameRays ? deviceFrameRays + f : nullptr)))
-            return rc;
-    }
-    return 0;
+        return 0;
+    });
+    if (rc) return rc;
+    const ClipPlanes planes{deviceMoments, deviceFrameAlbedo, deviceFrameNormalDepth, deviceFrameMoments};
+    return enqueueAnimation(firstFrame, nFrames, times, w, h, deviceTile, deviceFrameImages, deviceFrameRays, testFlags, animate, perLaunch, &planes);
 }
 
 // One frame blended into the tile exactly as tptDrawDevice blends it (same bits, same ray count), plus the first-hit planes of its

@@ -1445,6 +1445,10 @@ __device__ __forceinline__ int hitSpheresGroupedDeal(const SceneView& sv, bool g
 // into a.aovAlbedo / a.aovNormalDepth.  Its own kernel (tptTraceAovKernel) for the same reason.
 // MOMENTS (with AOV; tptDrawDeviceMoments): a third f4 per path in a.aovSums sums every sample's luminance l and l^2, and the means
 // go into a.momentsOut, the frame's moments plane, beside the colour.  Its own kernel (tptTraceMomentsKernel) for the same reason.
+// BATCH + MOVING + AOV + MOMENTS (tptDrawDeviceAnimationMoments): the frames of an animated clip with their planes -- the path's frame
+// picks the plane of every store (albedo and normal / depth a.aovPlane pixels apart in the caller's buffers, the moments a.framePlane
+// apart in the library's staging, like the colour), and a camera ray's normal on sphere 1 or 8 is taken from that frame's centre.  Its
+// own kernel (tptTraceClipKernel) for the same reason.
 template <bool LDS_SCENE, bool BATCH, bool VIEWS = false, bool MOVING = false, bool AOV = false, bool MOMENTS = false>
 __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
 {
@@ -1455,7 +1459,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     //  0: phase 2 then addresses a sphere with sphere index x 16 and an immediate, like the path records)
     static_assert(BATCH || !VIEWS, "views are frames of a batched launch");
     static_assert((BATCH || !MOVING) && !(VIEWS && MOVING), "animation frames are frames of a batched launch of their own");
-    static_assert(!AOV || !BATCH, "first-hit planes are made by single-frame launches");
+    static_assert(!AOV || !BATCH || (MOVING && MOMENTS), "first-hit planes are made by single-frame launches, or beside the moments of an animated clip's frames");
     static_assert(!MOMENTS || AOV, "moments are summed beside the first-hit sums");
     constexpr int kPaths = (LDS_SCENE ? TPT_Q_PATHS : TPT_Q_PATHS_GROUPED) - (VIEWS ? TPT_Q_VIEW_PATHS : 0) -
                            (MOVING ? TPT_Q_ANIM_PATHS : 0); // paths this workgroup owns
@@ -1804,11 +1808,13 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                     const f3 out = col * fc.invSpp; // Test.cpp:291
                     a.frameColour[plane + globalRowToLocal(a, py) * fc.width + px] = mk4(out.x, out.y, out.z, 0.0f); // one 16-B store per pixel
                     if (AOV) { // the means of the first-hit sums, in the form of Test.cpp:291; one 16-B store per plane (either may be absent)
-                        const size_t at = (size_t)globalRowToLocal(a, py) * fc.width + px;
+                        const size_t px0 = (size_t)globalRowToLocal(a, py) * fc.width + px;
+                        // (a clip's frame: its planes in the caller's buffers, its moments plane in the staging beside its colour plane)
+                        const size_t at = px0 + (BATCH ? (size_t)(f2u(c3.w) >> 26) * (size_t)a.aovPlane : 0);
                         const f4 s0 = aovSum()[0], s1 = aovSum()[1];
                         if (a.aovAlbedo) a.aovAlbedo[at] = mk4(s0.x * fc.invSpp, s0.y * fc.invSpp, s0.z * fc.invSpp, s0.w * fc.invSpp);
                         if (a.aovNormalDepth) a.aovNormalDepth[at] = mk4(s1.x * fc.invSpp, s1.y * fc.invSpp, s1.z * fc.invSpp, s1.w * fc.invSpp);
-                        if (MOMENTS) a.momentsOut[at] = mk4(mom.x * fc.invSpp, mom.y * fc.invSpp, 0.0f, 0.0f);
+                        if (MOMENTS) a.momentsOut[px0 + plane] = mk4(mom.x * fc.invSpp, mom.y * fc.invSpp, 0.0f, 0.0f);
                     }
                     toFree = true;
                 }
@@ -1928,8 +1934,9 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                 if (hitId >= 0) ro = ro + rd * hitT; // the hit position (Maths.cpp:195), all the class code needs of {orig, t}
                 if (AOV && depth == 0 && hitId >= 0) {
                     // a camera ray's nearest hit (every bounce ray has depth >= 1 here): add the sample's albedo, coverage, normal (the
-                    // class code's qNormal, Maths.cpp:196-197) and t.  A miss adds zeros: nothing to do.
-                    const f3 nrm = qNormal(sv, hitId, ro);
+                    // class code's qNormal, Maths.cpp:196-197, on a moving sphere with its frame's centre) and t.  A miss adds zeros:
+                    // nothing to do.
+                    const f3 nrm = qNormal<MOVING>(sv, hitId, ro, movedLds + movedAt);
                     const f4 m0 = sv.mats[hitId * 3];
                     f4* sum = aovSum();
                     const f4 s0 = sum[0], s1 = sum[1];
@@ -2109,6 +2116,20 @@ __global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute
 tptTraceMomentsKernel<false>(const KernelArgs a)
 {
     traceQueueBody<false, false, false, false, true, true>(a);
+}
+// Frames of an animated clip per launch, each with its first-hit planes and luminance moments (tptDrawDeviceAnimationMoments): the
+// animation kernel plus the moments kernel's per-path sums.  A kernel of its own for the same reason; <false> as the animation kernel's.
+template <bool LDS_SCENE>
+__global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute__((amdgpu_num_vgpr(TPT_Q_MAX_VGPR)))
+tptTraceClipKernel(const KernelArgs a)
+{
+    traceQueueBody<LDS_SCENE, true, false, true, true, true>(a);
+}
+template <>
+__global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute__((amdgpu_num_vgpr(TPT_Q_MAX_VGPR_GROUPED)))
+tptTraceClipKernel<false>(const KernelArgs a)
+{
+    traceQueueBody<false, true, false, true, true, true>(a);
 }
 
 #if defined(TPT_TEST_HOOKS)
@@ -2386,7 +2407,7 @@ size_t tptQueueLdsBytes(const KernelArgs& a, bool ldsScene)
     const int nPad = a.scene.nPairs * 2;
     const bool views = a.viewCams != nullptr; // (tptTraceViewsKernel: the cameras in LDS, TPT_Q_VIEW_PATHS path records fewer)
     const bool moving = a.moveCentres != nullptr; // (tptTraceAnimationKernel: the centres in LDS, TPT_Q_ANIM_PATHS path records fewer)
-    // (tptTraceAovKernel and tptTraceMomentsKernel, a.aovSums: the LDS of their single-frame twin -- their sums live in global memory)
+    // (tptTraceAovKernel, tptTraceMomentsKernel and tptTraceClipKernel, a.aovSums: the LDS of their twin without planes -- their sums live in global memory)
     size_t bytes = 0;
     if (ldsScene) bytes += TPT_Q_SPH_FIXED + ((size_t)nPad * 16 <= TPT_Q_SPH_FIXED ? 0 : (size_t)nPad * 16) + (((size_t)nPad * 4 + 15) & ~(size_t)15) + (size_t)a.scene.nSpheres * 48;
     bytes += (size_t)a.scene.nLights * 32;
@@ -2413,6 +2434,10 @@ hipError_t tptLaunchTraceQueue(const KernelArgs& a, bool ldsScene, int blocks, s
     if (a.viewCams) { // (tptDrawDeviceViews: 1 .. TPT_Q_VIEWS_MAX views, the frames of the batch)
         if (a.batchFrames < 1 || a.batchFrames > TPT_Q_VIEWS_MAX) return hipErrorInvalidValue;
         return launchQueueKernel(ldsScene ? tptTraceViewsKernel<true> : tptTraceViewsKernel<false>, a, blocks, lds, stream);
+    }
+    if (a.aovSums && a.moveCentres) { // (tptDrawDeviceAnimationMoments: 1 .. TPT_Q_VIEWS_MAX frames of the batch with their planes, a flat scene)
+        if (a.batchFrames < 1 || a.batchFrames > TPT_Q_VIEWS_MAX || a.scene.nGroups > 0 || !a.momentsOut) return hipErrorInvalidValue;
+        return launchQueueKernel(ldsScene ? tptTraceClipKernel<true> : tptTraceClipKernel<false>, a, blocks, lds, stream);
     }
     if (a.aovSums) { // (tptDrawDeviceAov, tptDrawDeviceMoments with a.momentsOut: a single frame)
         if (a.batchFrames != 1 || a.viewCams || a.moveCentres) return hipErrorInvalidValue;
