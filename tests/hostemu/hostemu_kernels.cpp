@@ -5,6 +5,7 @@
 // The per-ray arithmetic is the lane state machine / the path-queue class code that tests/lane_emu.cpp already holds against the
 // oracle; what THIS file exists for is everything csrc/tpt_host.cpp builds around the kernels.
 #include "tpt_device.h"
+#include "tpt_queue_layout.h" // the path-queue kernel's LDS layout, the sizes the host derives from it, tptQueueVariant: the product's own
 #include "tpt_shard.h"
 #include <algorithm>
 #include <stdio.h>
@@ -15,26 +16,6 @@
 using namespace tpt;
 
 namespace {
-// (mirrors of constants that live in tpt_kernels.hip: path records, rings, control block of the path-queue kernel)
-const int kQPaths = 952, kQPathsGrouped = 608, kQRing = 1024, kQClasses = 6, kQThreads = 512, kQWaves = 8;
-const size_t kQCtlBytes = 256, kQDealWaveBytes = (256 + 256 + 128) * 4 + 16; // (entry areas of the three-stage dealing)
-const size_t kQGroupPairStride = ((TPT_SUPER / 2) * 8 + 4) * 4, kQGroupLdsBytes = 9808; // (144 B per super-group of 8 groups in LDS: TPT_GPAIR_LDS_STRIDE)
-
-bool mapItem(const KernelArgs& a, int idx, int& x, int& ly) // tpt_kernels.hip: mapItem
-{
-    if (a.fc.seedMode == SEED_ROW_SERIAL) {
-        x = 0;
-        ly = idx;
-        return ly < a.nLocalRows;
-    }
-    const int tile = idx >> 6, within = idx & 63;
-    const int tx = tile % a.tilesX, ty = tile / a.tilesX;
-    x = tx * 8 + (within & 7);
-    ly = ty * 8 + (within >> 3);
-    return x < a.fc.width && ly < a.nLocalRows;
-}
-int localRowToGlobal(const KernelArgs& a, int ly) { return shardKernelLocalToGlobal(ly, a.stripeRows, a.stripeStride, a.stripeOffset); }
-
 long long g_helperGrids[3] = {0, 0, 0}; // helper grids that found their launch closed / the pool dry / took chunks
 
 struct TraceJob {
@@ -315,38 +296,11 @@ void runOrder(void* p)
 void runNothing(void*) {}
 } // namespace
 
-size_t tptLdsBytes(const KernelArgs& a, int fold, bool ldsScene) // = tpt_kernels.hip
-{
-    const int nPad = a.scene.nPairs * 2;
-    size_t bytes = 0;
-    if (ldsScene) bytes += (size_t)nPad * 16 + (((size_t)nPad * 4 + 15) & ~(size_t)15);
-    bytes += (size_t)a.scene.nLights * 32;
-    if (ldsScene) bytes += (size_t)a.scene.nSpheres * 48;
-    if (fold == FOLD_RECURSIVE) bytes += (size_t)a.ldsStackLevels * TPT_BLOCK * 16;
-    return bytes;
-}
+// What is deliberately this file's own answer and not the product's: an emulated occupancy, and a build that packs both operand tables
+// of the matrix cores (the filter's and the groups' bounds') so that the host code that makes them runs here.
 int tptTraceOccupancy(int, int, bool, size_t lds) { const int byLds = (int)(160 * 1024 / (lds + 256)); return byLds < 1 ? 1 : (byLds > 16 ? 16 : byLds); }
-size_t tptQueueLdsBytes(const KernelArgs& a, bool ldsScene) // = tpt_kernels.hip (constants mirrored above)
-{
-    const int nPad = a.scene.nPairs * 2;
-    size_t bytes = 0;
-    if (ldsScene) bytes += 1024 + ((size_t)nPad * 16 <= 1024 ? 0 : (size_t)nPad * 16) + (((size_t)nPad * 4 + 15) & ~(size_t)15) + (size_t)a.scene.nSpheres * 48;
-    bytes += (size_t)a.scene.nLights * 32;
-    bytes += (size_t)4 * (ldsScene ? kQPaths : kQPathsGrouped) * 16 + (size_t)kQClasses * kQRing * 2 + kQCtlBytes + ((sizeof(FrameConsts) + 15) & ~(size_t)15);
-    if (!ldsScene) bytes += (size_t)kQWaves * kQDealWaveBytes + (a.ldsGroupPairs > 0 ? 16 + (size_t)(a.ldsGroupPairs / (TPT_SUPER / 2)) * kQGroupPairStride : 0);
-    if (ldsScene && a.scene.mxR1 >= 0) bytes += TPT_MXH_TABLE_DWORDS * sizeof(uint32_t) + 64;
-    return bytes;
-}
-int tptQueuePathsPerBlock() { return kQPaths; }
-int tptQueueGroupPairsInLds(int nGroups, int nSuperPairs) // = tpt_kernels.hip
-{
-    if (nGroups <= 0 || nSuperPairs <= 0) return 0;
-    const int pairs = ((nGroups + TPT_SUPER - 1) / TPT_SUPER) * (TPT_SUPER / 2);
-    return (size_t)(pairs / (TPT_SUPER / 2)) * kQGroupPairStride + 16 <= kQGroupLdsBytes ? pairs : 0;
-}
 int tptQueueMatrixFilter() { return 1; }
 int tptQueueGroupMatrixBounds() { return 1; }
-int tptQueueThreadsPerBlock() { return kQThreads; }
 
 hipError_t tptLaunchTrace(const KernelArgs& a, int hs, int fold, bool ldsScene, int blocks, size_t, hipStream_t stream)
 {
@@ -357,7 +311,7 @@ hipError_t tptLaunchTrace(const KernelArgs& a, int hs, int fold, bool ldsScene, 
 }
 hipError_t tptLaunchTraceQueue(const KernelArgs& a, bool ldsScene, int blocks, size_t lds, hipStream_t stream)
 {
-    if (blocks < 1 || lds > 160 * 1024) return hipErrorInvalidValue;
+    if (blocks < 1 || lds > 160 * 1024 || tptQueueVariant(a) == QV_INVALID) return hipErrorInvalidValue;
     TraceJob J; J.a = a; J.hs = 0; J.fold = FOLD_RECURSIVE; J.ldsScene = ldsScene; J.queue = true;
     hostemuEnqueue(stream, runTrace, &J, sizeof(J));
     return hipSuccess;
@@ -408,7 +362,7 @@ hipError_t tptLaunchResolveBatch(float* tile, const f4* frameColour, int nPixels
     hostemuEnqueue(stream, runResolve, &J, sizeof(J));
     return hipSuccess;
 }
-int tptReadStats(unsigned long long*) { return -1; }
+int tptReadStats(unsigned long long*) { return -1; } // (no statistics here)
 int tptResetStats() { return -1; }
 extern "C" void hostemu_helper_stats(long long* out3)
 {

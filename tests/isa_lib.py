@@ -18,7 +18,14 @@ OBJDUMP = os.path.join(LLVM, "llvm-objdump")
 READELF = os.path.join(LLVM, "llvm-readelf")
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 HAVE_TOOLS = all(os.path.exists(p) for p in (BUNDLER, OBJDUMP, READELF)) and shutil.which("objcopy") is not None
+# the path-queue kernel and its variants by their mangled names
 QUEUE = "_ZN3tpt19tptTraceQueueKernelILb%dELb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE, BATCH>
+VIEWS = "_ZN3tpt19tptTraceViewsKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
+ANIM = "_ZN3tpt23tptTraceAnimationKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
+AOV = "_ZN3tpt17tptTraceAovKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
+MOMENTS = "_ZN3tpt21tptTraceMomentsKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
+# (not "tptTraceAnimationMomentsKernel": tests/test_moments_abi.py counts the kernels whose names hold "Moments")
+CLIP = "_ZN3tpt18tptTraceClipKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
 
 
 @pytest.fixture(scope="module")

@@ -12,12 +12,11 @@ import subprocess
 import numpy as np
 import pytest
 
-from isa_lib import QUEUE, code_object, count, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
+from isa_lib import ANIM, QUEUE, code_object, count, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
 from oracle_lib import ROOT
 
 INC = os.path.join(ROOT, "toypathtracer_amd", "csrc")
 SHIM = os.path.join(ROOT, "tests", "animation_filter.cpp")
-ANIM = "_ZN3tpt23tptTraceAnimationKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
 
 
 def test_header_declares_the_entry_point():
@@ -106,8 +105,8 @@ def test_animation_kernels_keep_the_queue_kernel_contract(code_object, lds):  # 
 
 def test_animation_kernel_takes_the_lds_of_its_single_frame_twin():
     """the centres table replaces path records byte for byte: tptQueueLdsBytes is unchanged by it, so the default scene keeps two
-    workgroups per CU and the matrix-core filter (checked by the static_asserts of tpt_kernels.hip, restated here from its constants)"""
-    src = open(os.path.join(INC, "tpt_kernels.hip")).read()
+    workgroups per CU and the matrix-core filter (checked by the static_asserts of tpt_queue_layout.h, restated here from its constants)"""
+    src = open(os.path.join(INC, "tpt_queue_layout.h")).read()
     assert "#define TPT_Q_ANIM_TABLE_BYTES (TPT_Q_VIEWS_MAX * 2 * 16)" in src
     assert "#define TPT_Q_ANIM_PATHS ((TPT_Q_ANIM_TABLE_BYTES + TPT_Q_NF4 * 16 - 1) / (TPT_Q_NF4 * 16))" in src
     assert re.search(r"#define TPT_Q_VIEWS_MAX 32\b", src) and re.search(r"#define TPT_Q_NF4 4\b", src)

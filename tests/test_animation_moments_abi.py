@@ -8,13 +8,9 @@ import subprocess
 
 import pytest
 
-from isa_lib import QUEUE, code_object, count, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
+from isa_lib import ANIM, CLIP, MOMENTS, QUEUE, code_object, count, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
 from oracle_lib import ROOT
-from test_animation_abi import ANIM
-from test_moments_abi import MOMENTS
 
-# (not "tptTraceAnimationMomentsKernel": tests/test_moments_abi.py counts the kernels whose names hold "Moments")
-CLIP = "_ZN3tpt18tptTraceClipKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
 NAME = "tptDrawDeviceAnimationMoments"
 
 
@@ -88,11 +84,12 @@ def test_clip_kernels_keep_the_queue_kernel_contract(code_object, lds):  # noqa:
 def test_clip_kernel_takes_the_lds_of_its_twins():
     """tptQueueLdsBytes sees the centres table alone (a.moveCentres): the planes add no LDS, so the default scene keeps two workgroups per
     CU; and the per-path sums are addressed with the pool size the host sizes their buffer with"""
-    src = open(os.path.join(ROOT, "toypathtracer_amd", "csrc", "tpt_kernels.hip")).read()
+    csrc = os.path.join(ROOT, "toypathtracer_amd", "csrc")
+    src = open(os.path.join(csrc, "tpt_queue_layout.h")).read()
     assert "if (moving) bytes += (size_t)TPT_Q_ANIM_TABLE_BYTES - (size_t)TPT_Q_NF4 * TPT_Q_ANIM_PATHS * 16;" in src
-    assert "a.aovSums + kAovSums * ((size_t)(blockIdx.x + (unsigned)a.helperBase) * TPT_Q_PATHS + p)" in src
+    assert "a.aovSums + kAovSums * ((size_t)(blockIdx.x + (unsigned)a.helperBase) * TPT_Q_PATHS + p)" in open(os.path.join(csrc, "tpt_kernels.hip")).read()
     assert "int tptQueuePathsPerBlock() { return TPT_Q_PATHS; }" in src
-    host = open(os.path.join(ROOT, "toypathtracer_amd", "csrc", "tpt_host_pipeline.cpp")).read()
+    host = open(os.path.join(csrc, "tpt_host_pipeline.cpp")).read()
     assert "(momentsBytes ? 3 : 2) * sizeof(f4) * (size_t)maxGridBlocks(P) * (size_t)tptQueuePathsPerBlock()" in host
 
 

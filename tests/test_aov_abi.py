@@ -7,9 +7,7 @@ import subprocess
 
 import pytest
 
-from isa_lib import QUEUE, code_object, count, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
-
-AOV = "_ZN3tpt17tptTraceAovKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
+from isa_lib import AOV, QUEUE, code_object, count, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
 
 
 def test_header_declares_the_entry_point():

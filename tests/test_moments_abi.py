@@ -8,10 +8,8 @@ import subprocess
 
 import pytest
 
-from isa_lib import QUEUE, code_object, count, header, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
-from test_aov_abi import AOV
+from isa_lib import AOV, MOMENTS, QUEUE, code_object, count, header, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
 
-MOMENTS = "_ZN3tpt21tptTraceMomentsKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
 VARIANCE = "_ZN3tpt23tptVarianceAtrousKernelILb%dELb%dELb%dEEEvPKNS_2f4ES3_S3_S3_S3_PS1_iiiffffi"  # <FIRST, LAST, GUIDE>
 
 

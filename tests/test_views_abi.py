@@ -6,9 +6,7 @@ import subprocess
 
 import pytest
 
-from isa_lib import code_object, count, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
-
-VIEWS = "_ZN3tpt19tptTraceViewsKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
+from isa_lib import VIEWS, code_object, count, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
 
 
 def test_header_declares_the_entry_point():

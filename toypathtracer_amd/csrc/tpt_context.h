@@ -2,11 +2,16 @@
 // functions its translation units share.  Not an interface of the library: include/tpt_hip.h is.
 //
 //   tpt_host.cpp           context, initialisation, scene staging, the setters, UpdateTest, the reference's C++ symbols
-//   tpt_host_pipeline.cpp  one frame: plan, buffers, trace launch, ordered blend; tail helpers; tptDrawDevice / tptDrawDeviceBatch
+//   tpt_host_pipeline.cpp  one frame: plan, buffers, trace launch, ordered blend; tail helpers; tptDrawDevice and its variants (Batch,
+//                          Views, Animation, AnimationMoments, Aov, Moments)
 //   tpt_host_draw.cpp      the queue of launches traced ahead of their call (LaunchQueue); DrawTest on a host backbuffer: banded
-//                          copies; display conversion
+//                          copies; display conversion; the denoiser's entry points (tptDenoiseDevice, tptDenoiseDeviceVariance,
+//                          tptTemporalAccumulateDevice)
 //   tpt_host_shard.cpp     multi-GPU inside the library: RCCL (dlopen), tptDrawSharded, tptShardedFinish
 //   tpt_host_hooks.cpp     unit-test / profiling entry points (include/tpt_test_hooks.h; the second build only)
+// and, of the headers they share with the kernels (tpt_kernels.hip): tpt_device.h, the kernels' argument block and the launch functions;
+// tpt_queue_layout.h, the path-queue kernel's LDS layout, the sizes the plan derives from it (tptLdsBytes, tptQueueLdsBytes,
+// tptQueuePathsPerBlock, tptQueueGroupPairsInLds, tptQueueThreadsPerBlock) and the variant a launch takes (tptQueueVariant).
 #pragma once
 #include "../../include/tpt_hip.h"
 #if defined(TPT_TEST_HOOKS)
@@ -14,6 +19,7 @@
 #endif
 #include "../../include/tpt_test_api.h"
 #include "tpt_device.h"
+#include "tpt_queue_layout.h"
 #include "tpt_scene.h"
 #include "tpt_shard.h"
 #include "tpt_stream_batch.h"
@@ -34,6 +40,7 @@ using namespace tpt;
 
 // What a trace launch leaves behind for the blend that follows it (now, or -- host path with look-ahead -- later).
 const int kMaxBatch = 32; // frames per batched launch (tptDrawDeviceBatch): 6 bits in the path record, 32 lerp factors by value
+static_assert(kMaxBatch == TPT_Q_VIEWS_MAX, "a batch's cameras, centres and ray counts have their places in the path-queue kernel's LDS");
 struct TraceTicket {
     int slot = 0, nPixels = 0;
     bool pipelined = false, valid = false;

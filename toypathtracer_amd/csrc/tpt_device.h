@@ -1,4 +1,6 @@
-// tpt_device.h -- kernel argument block shared by tpt_kernels.hip (device) and tpt_host.cpp (host).
+// tpt_device.h -- kernel argument block shared by tpt_kernels.hip (device) and tpt_host.cpp (host), and the launch functions.  The LDS
+// layout of the path-queue kernel, the sizes derived from it (tptLdsBytes, tptQueueLdsBytes, tptQueuePathsPerBlock, ...) and the
+// variant a launch takes (tptQueueVariant): tpt_queue_layout.h, which includes this header.
 #pragma once
 #include "tpt_trace.h"
 
@@ -78,16 +80,11 @@ struct KernelArgs {
 
 } // namespace tpt
 
-size_t tptLdsBytes(const tpt::KernelArgs& a, int fold, bool ldsScene); // uses a.ldsStackLevels
 hipError_t tptLaunchTrace(const tpt::KernelArgs& a, int hs, int fold, bool ldsScene, int blocks, size_t lds, hipStream_t stream);
 int tptTraceOccupancy(int hs, int fold, bool ldsScene, size_t lds);
-size_t tptQueueLdsBytes(const tpt::KernelArgs& a, bool ldsScene);
 hipError_t tptLaunchTraceQueue(const tpt::KernelArgs& a, bool ldsScene, int blocks, size_t lds, hipStream_t stream);
-int tptQueuePathsPerBlock();
-int tptQueueGroupPairsInLds(int nGroups, int nSuperPairs);
 int tptQueueMatrixFilter();
 int tptQueueGroupMatrixBounds(); // 1: this build carries the groups' bounds on the matrix cores (hooks build only)
-int tptQueueThreadsPerBlock();
 hipError_t tptLaunchDisplay(const float* tile, unsigned char* rgba, int width, int height, hipStream_t stream);
 // tptDenoiseDevice: `iterations` launches of the a-trous kernel, ping-ponging between out and scratch (both [h][w] f4, neither
 // overlapping an input) so that the last one writes out; albedo / normalDepth may be null (ic, in, id: the first iteration's
