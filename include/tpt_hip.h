@@ -307,6 +307,59 @@ TPT_API int tptTemporalAccumulateDevice(int screenWidth, int screenHeight, const
                                         const float* devicePrevNormalDepth, const float* devicePrevMoments, float* deviceOutColour,
                                         float* deviceOutAlbedo, float* deviceOutMoments, float* deviceOutVariance, float maxHistory,
                                         float depthTolerance, float normalTolerance, float coverageTolerance);
+/* ADAPTIVE SAMPLING: tptDrawDeviceMoments with a sample count per pixel, so that the moments can steer the next pass (the counts come
+ * from tptAdaptiveSamplesDevice below, or from the caller).  deviceSampleCounts (required): h*w int32 in DEVICE memory, row-major like the
+ * tile, read by the kernels only.  Per pixel p, n = deviceSampleCounts[p] clamped to 0 .. 2047 (the path record holds 11 bits of sample
+ * index); the value of tptSetSamplesPerPixel plays no part.
+ *   n == 0: the pixel is not traced.  Its entries of deviceTile, deviceMoments (all four channels), deviceAlbedo and deviceNormalDepth are
+ *           left untouched, and it adds no rays.
+ *   n >= 1: the frame's values are byte for byte what tptDrawDeviceMoments computes for that pixel and frameCount under
+ *           tptSetSamplesPerPixel(n): the pixel's own seed, its n samples drawn in sequence from that one stream, the same rays;
+ *           colour = sum * (1.0f / n), moments {sum l, sum l*l, 0} * (1.0f / n), the albedo and normal / depth means * (1.0f / n)
+ *           (overwritten), 1.0f / n a correctly rounded binary32 quotient.
+ * The blend is weighted by SAMPLES, not by frame number, and deviceMoments.w carries the pixel's running sample count (binary32):
+ *   S = deviceMoments[p].w if TPT_FLAG_PROGRESSIVE is set and that value is finite and >= 1, else 0;   S' = S + n;
+ *   lerp = S / S' (correctly rounded);   tile.rgb = tile.rgb * lerp + colour * (1 - lerp), deviceMoments.xyz likewise;
+ *   deviceMoments.w = S';   the tile's alpha is untouched.
+ * A caller whose counts are all n and whose moments plane starts zeroed gets lerp = frame / (frame + 1): tile and moments.xyz are then
+ * byte-identical to tptDrawDeviceMoments at n spp.  TPT_FLAG_ANIMATE moves the scene through tptUpdate as always, but the
+ * animate-smoothing factor (tptSetConfig) does NOT enter this blend.
+ * One pixel's samples run one after another in one path (the single random stream per pixel is what makes the output checkable), so a
+ * launch lasts at least as long as its largest count takes: a few pixels at 2047 bound the launch from below.
+ * Ordering, state and the ray counter are tptDrawDeviceMoments' (asynchronous on the context stream, ordered behind earlier work there;
+ * the counter advances by the rays traced; frames traced ahead and stream-batch planes dropped; camera and scene unchanged).
+ * Refused (non-zero, tptGetLastError names the function, nothing enqueued, nothing written): everything tptDrawDeviceMoments refuses
+ * except a context spp over 2047; deviceSampleCounts NULL; deviceSampleCounts overlapping the tile, the moments or a given plane;
+ * deviceMoments overlapping the tile or a given plane. */
+TPT_API int tptDrawDeviceAdaptive(float time, int frameCount, int screenWidth, int screenHeight, float* deviceTile, float* deviceAlbedo,
+                                  float* deviceNormalDepth, float* deviceMoments, const int32_t* deviceSampleCounts,
+                                  unsigned testFlags);
+/* Moments to sample counts: how many MORE samples each pixel should get for the relative standard error of its mean luminance to reach
+ * targetError.  deviceMoments: h*w*4 floats as tptDrawDeviceAdaptive leaves them ({mean l, mean l*l, 0, S}, S the samples so far).
+ * Binary32, in the order written, no FMA, correctly rounded division, sums from +0 in the order written (jy outer);
+ * gk = {1/4, 1/2, 1/4}.  Per pixel p:
+ *   1. m = moments[p];  S = m.w;  p is VALID if S is finite and >= 1
+ *   2. d = m.y - m.x*m.x;  var = d > 0 ? d : 0
+ *   3. b = m.x + TPT_ADAPTIVE_LUM_FLOOR;  r = var / (b*b)            (the relative variance of one sample)
+ *   4. R = sum of (gk[jy]*gk[jx]) * r[q] over the VALID q = p + (j - 1) of the 3x3 unit neighbourhood inside the image,
+ *          / sum of those (gk[jy]*gk[jx])                             (guards a 4-sample pixel whose samples happen to agree)
+ *   5. p invalid, or no q valid:  n = minSamples > 1 ? minSamples : 1;  steps 6 and 7 are skipped
+ *   6. need = R / (targetError*targetError);  extra = need - S
+ *   7. n = minSamples if !(extra > minSamples);  else maxSamples if extra >= maxSamples;  else (int)ceilf(extra)   (a NaN: minSamples)
+ * deviceSampleCounts (required, h*w int32) receives n.  deviceOutVariance (optional, h*w*4 floats) receives {0, var / S, 0, S} for valid
+ * pixels and {0, 0, 0, 0} for the others -- the form of tptTemporalAccumulateDevice's variance plane: tptDenoiseDeviceVariance(...,
+ * deviceMoments = that plane, samples = 1) then filters each pixel by the variance of its own mean.  deviceTotalSamples (optional, one
+ * int64 in device memory) is overwritten with the sum of n over the image: the next pass's budget, known before it is launched.
+ * maxSamples bounds more than the budget: one pixel's samples are traced one after another (tptDrawDeviceAdaptive), so the next
+ * launch lasts at least as long as maxSamples samples of one pixel take.
+ * Asynchronous on the context stream; needs tptInitialize only and leaves every other state alone.  The input is never written.
+ * Refused (non-zero, tptGetLastError names the function, nothing enqueued, no output written): no context; w or h outside 1..8192;
+ * deviceMoments or deviceSampleCounts NULL; targetError not finite or not in (0, 1e6]; minSamples < 0; maxSamples > 2047;
+ * minSamples > maxSamples; an output overlapping the input or another output. */
+#define TPT_ADAPTIVE_LUM_FLOOR 1e-2f
+TPT_API int tptAdaptiveSamplesDevice(int screenWidth, int screenHeight, const float* deviceMoments, float targetError, int minSamples,
+                                     int maxSamples, int32_t* deviceSampleCounts, float* deviceOutVariance,
+                                     int64_t* deviceTotalSamples);
 /* nViews (1..32) cameras of the scene as of the last tptUpdate, traced by ONE launch.  views: nViews x 9 floats
  * {lookFrom xyz, lookAt xyz, vfovDegrees, aperture, focusDist} -- tptSetCamera's arguments; aspect = w / h, vup (0,1,0),
  * aperture forced to 0 in Mitsuba-compare mode, as tptUpdate does.  deviceTiles: nViews consecutive device tiles of h*w*4

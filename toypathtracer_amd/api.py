@@ -39,7 +39,7 @@ C_ABI_SYMBOLS = [
     "tptSetSamplesPerPixel", "tptSetConfig", "tptSetSeedMode", "tptSetFoldMode", "tptSetScene", "tptSetCamera", "tptSetStream",
     "tptSetRowShard", "tptLocalRowCount", "tptLocalRowToGlobal", "tptDrawDevice", "tptRayCounterRead", "tptSetRayCounter", "tptSetFrameOverlap", "tptDisplayRGBA8", "tptKernelTimingBegin", "tptKernelTimingEnd",
     "tptSynchronize", "tptTimerBegin", "tptTimerEnd", "tptSetKernelVariant",
-    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceAnimationMoments", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
+    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceAnimationMoments", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptDrawDeviceAdaptive", "tptAdaptiveSamplesDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
 ]
 # include/tpt_test_hooks.h: exported by the second build (libtoypathtracer_hip_hooks.so) only
 HOOK_SYMBOLS = ["tptTestMath", "tptTestMathExhaustive", "tptTestHitSpheres", "tptTestMatrixFilter", "tptTestGroupFilter", "tptTestSetDealCapacities", "tptDebugStats", "tptDebugChunkOrder"]
@@ -78,7 +78,7 @@ def _bind(path, hooks):
         "tptSetRayCounter": [p], "tptSetTileMirror": [p, p], "tptSetFrameOverlap": [i], "tptDisplayRGBA8": [p, i, i, p], "tptKernelTimingBegin": [i],
         "tptKernelTimingEnd": [C.POINTER(f), C.POINTER(i)],
         "tptSynchronize": [], "tptTimerBegin": [], "tptTimerEnd": [C.POINTER(f)], "tptSetKernelVariant": [i, i, i],
-        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDrawDeviceAnimationMoments": [i, i, p, i, i] + [p] * 7 + [u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
+        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDrawDeviceAnimationMoments": [i, i, p, i, i] + [p] * 7 + [u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptDrawDeviceAdaptive": [f, i, i, i, p, p, p, p, p, u], "tptAdaptiveSamplesDevice": [i, i, p, f, i, i, p, p, p], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
     }
     if hooks:
         sigs.update({"tptDebugStats": [p, i], "tptDebugChunkOrder": [p, p, i], "tptTestMath": [i, p, p, p, i], "tptTestMathExhaustive": [i, u, u, p, p],
@@ -621,6 +621,46 @@ def temporal_accumulate_device(w, h, camera, colour_ptr, albedo_ptr, normal_dept
                                                     C.c_void_p(out_colour_ptr), C.c_void_p(out_albedo_ptr), C.c_void_p(out_moments_ptr),
                                                     C.c_void_p(out_variance_ptr), max_history, depth_tolerance, normal_tolerance,
                                                     coverage_tolerance), "tptTemporalAccumulateDevice")
+
+
+ADAPTIVE_MAX_SAMPLES = 2047  # one pixel's samples of one launch (include/tpt_hip.h: 11 bits of sample index in the path record)
+
+
+def draw_device_adaptive(time, frame, w, h, tile_ptr, moments_ptr, counts_ptr, flags, albedo_ptr=None, normal_depth_ptr=None):
+    """tptDrawDeviceAdaptive: draw_device_moments with a sample count per pixel.  counts_ptr: a device buffer of h*w int32, row-major like
+    the tile, each clamped to 0..2047 by the kernel; a pixel with 0 is not traced and nothing of it is written.  The blend is weighted by
+    samples: moments_ptr's .w carries each pixel's running sample count (include/tpt_hip.h).  Ordered on the context's stream."""
+    _positive_ints(("w", w), ("h", h))
+    _pointers(("tile_ptr", tile_ptr), ("moments_ptr", moments_ptr), ("counts_ptr", counts_ptr), ("albedo_ptr", albedo_ptr),
+              ("normal_depth_ptr", normal_depth_ptr))
+    if not tile_ptr or not moments_ptr or not counts_ptr:
+        raise ValueError("tile_ptr, moments_ptr, counts_ptr: device buffers are required")
+    _chk(load_library().tptDrawDeviceAdaptive(time, frame, w, h, C.c_void_p(tile_ptr), C.c_void_p(albedo_ptr) if albedo_ptr else None,
+                                              C.c_void_p(normal_depth_ptr) if normal_depth_ptr else None, C.c_void_p(moments_ptr),
+                                              C.c_void_p(counts_ptr), flags), "tptDrawDeviceAdaptive")
+
+
+def adaptive_samples_device(w, h, moments_ptr, target_error, counts_ptr, min_samples=0, max_samples=64, out_variance_ptr=None,
+                            total_ptr=None):
+    """tptAdaptiveSamplesDevice: draw_device_adaptive's moments (moments_ptr, .w the samples so far) -> the next pass's count per pixel
+    in counts_ptr (h*w int32), in min_samples..max_samples, for a relative standard error of target_error of the mean luminance.
+    out_variance_ptr: None or h*w*4 floats, the plane for denoise_device_variance's moments_ptr with samples = 1.  total_ptr: None or one
+    int64 in device memory, overwritten with the sum of the counts.  A launch lasts at least as long as max_samples samples of one pixel
+    take.  Ordered on the context's stream."""
+    _positive_ints(("w", w), ("h", h))
+    _pointers(("moments_ptr", moments_ptr), ("counts_ptr", counts_ptr), ("out_variance_ptr", out_variance_ptr), ("total_ptr", total_ptr))
+    if not moments_ptr or not counts_ptr:
+        raise ValueError("moments_ptr, counts_ptr: device buffers are required")
+    if not isinstance(target_error, (int, float, np.integer, np.floating)) or isinstance(target_error, bool) or not 0 < target_error <= 1e6:
+        raise ValueError("target_error: a float in (0, 1e6] expected, got %r" % (target_error,))
+    for name, v in (("min_samples", min_samples), ("max_samples", max_samples)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= v <= ADAPTIVE_MAX_SAMPLES:
+            raise ValueError("%s: an int in 0..%d expected, got %r" % (name, ADAPTIVE_MAX_SAMPLES, v))
+    if min_samples > max_samples:
+        raise ValueError("min_samples: at most max_samples (%d) expected, got %d" % (max_samples, min_samples))
+    _chk(load_library().tptAdaptiveSamplesDevice(w, h, C.c_void_p(moments_ptr), target_error, min_samples, max_samples,
+                                                 C.c_void_p(counts_ptr), C.c_void_p(out_variance_ptr) if out_variance_ptr else None,
+                                                 C.c_void_p(total_ptr) if total_ptr else None), "tptAdaptiveSamplesDevice")
 
 
 def sharded_finish():

@@ -409,6 +409,7 @@ struct AovPlanes {
     f4* normalDepth = nullptr;
     bool moments = false; // tptDrawDeviceMoments: tptTraceMomentsKernel, into Context::dMoments
     bool continues = false; // tptDrawDeviceAnimationMoments: a later launch of the call (Context::evClip)
+    const int32_t* sampleCounts = nullptr; // tptDrawDeviceAdaptive (with moments): the caller's count per pixel, tptTraceAdaptiveKernel
 };
 int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long long* frameRays, TraceTicket& T, int batch = 1, int rayStride = 0,
                  const BatchTable* table = nullptr, const AovPlanes* aov = nullptr);

@@ -76,6 +76,10 @@ struct KernelArgs {
     // takes tptTraceClipKernel): frame j of the batch stores its first-hit planes at aovAlbedo / aovNormalDepth + j * aovPlane pixels (the
     // caller's per-frame buffers) and its moments at momentsOut + j * framePlane (staging, beside its colour plane).
     int aovPlane = 0;
+    // A single frame with its planes and moments whose pixels take a sample count each (tptDrawDeviceAdaptive): [nLocalRows][width]
+    // int32 in device memory, read where a lane claims a pixel and clamped there to 0 .. 2047 (0: the pixel is not traced, nothing of it
+    // is stored); fc.spp and fc.invSpp play no part.  The launch takes tptTraceAdaptiveKernel.  Null for every other launch.
+    const int32_t* sampleCounts = nullptr;
 };
 
 } // namespace tpt
@@ -115,6 +119,16 @@ __attribute__((weak)) hipError_t tptLaunchTemporal(const float* colour, const fl
                                                    const float* prevMoments, float* outColour, float* outAlbedo, float* outMoments,
                                                    float* outVariance, int width, int height, const tptTemporalConsts& k,
                                                    hipStream_t stream);
+// tptDrawDeviceAdaptive's blend: tile.rgb and moments.xyz with lerp = S / (S + n) per pixel, S the running sample count in moments.w
+// (0 unless `progressive`), n the pixel's clamped count; moments.w = S + n; pixels with n == 0 untouched.  Weak for the same reason as
+// tptLaunchDenoise.
+__attribute__((weak)) hipError_t tptLaunchAdaptiveResolve(float* tile, float* moments, const tpt::f4* frameColour, const tpt::f4* stagedMoments,
+                                                          const int32_t* counts, int nPixels, bool progressive, hipStream_t stream);
+// tptAdaptiveSamplesDevice: one launch of the plan kernel (outVariance / totalSamples may be null; totalSamples is zeroed first).  Weak
+// for the same reason as tptLaunchDenoise.
+__attribute__((weak)) hipError_t tptLaunchAdaptivePlan(const float* moments, int32_t* counts, float* outVariance, int64_t* totalSamples,
+                                                       int width, int height, float targetError, int minSamples, int maxSamples,
+                                                       hipStream_t stream);
 hipError_t tptLaunchAssemble(const float* gathered, float* image, int width, int height, int stripeRows, int nRanks, int padRows, hipStream_t stream);
 hipError_t tptLaunchQueueProbe(unsigned long long ticks, hipStream_t stream);
 hipError_t tptLaunchChunkOrder(const unsigned* cost, unsigned* snap, unsigned* order, int numChunks, hipStream_t stream);

@@ -431,4 +431,32 @@ int tptTemporalAccumulateDevice(int w, int h, const void* camera, const void* pr
     return 0;
 }
 
+// The plan pass of adaptive sampling (include/tpt_hip.h states it): a post-process on the context stream like the filters, one launch
+// (and the memset of the total it adds to).
+int tptAdaptiveSamplesDevice(int w, int h, const float* deviceMoments, float targetError, int minSamples, int maxSamples,
+                             int32_t* deviceSampleCounts, float* deviceOutVariance, int64_t* deviceTotalSamples)
+{
+    if (requireInit()) return -1;
+    const std::string f("tptAdaptiveSamplesDevice");
+    if (w < 1 || w > 8192 || h < 1 || h > 8192) return fail(f + ": w and h must lie in 1..8192");
+    if (!deviceMoments || !deviceSampleCounts) return fail(f + ": deviceMoments and deviceSampleCounts are required");
+    if (!(targetError > 0.0f && targetError <= 1e6f)) return fail(f + ": targetError must lie in (0, 1e6]"); // (NaN fails)
+    if (minSamples < 0 || maxSamples > 2047 || minSamples > maxSamples) return fail(f + ": 0 <= minSamples <= maxSamples <= 2047 expected");
+    // the input and the three outputs, each at its own extent: no output may share a byte with the input or with another output
+    const struct { const void* p; uintptr_t bytes; } bufs[4] = {{deviceMoments, (uintptr_t)w * (uintptr_t)h * 16u},
+                                                                {deviceSampleCounts, (uintptr_t)w * (uintptr_t)h * 4u},
+                                                                {deviceOutVariance, (uintptr_t)w * (uintptr_t)h * 16u},
+                                                                {deviceTotalSamples, sizeof(int64_t)}};
+    for (int i = 0; i < 4; ++i)
+        for (int k = i + 1; k < 4; ++k) {
+            const uintptr_t a = reinterpret_cast<uintptr_t>(bufs[i].p), b = reinterpret_cast<uintptr_t>(bufs[k].p);
+            if (a && b && a < b + bufs[k].bytes && b < a + bufs[i].bytes)
+                return fail(f + (i == 0 ? ": an output overlaps deviceMoments" : ": two outputs overlap"));
+        }
+    if (!tptLaunchAdaptivePlan) return fail(f + ": this build has no adaptive plan kernel");
+    HIPCHK(tptLaunchAdaptivePlan(deviceMoments, deviceSampleCounts, deviceOutVariance, deviceTotalSamples, w, h, targetError, minSamples,
+                                 maxSamples, g.stream));
+    return 0;
+}
+
 } // extern "C"

@@ -108,10 +108,11 @@ int reserveSlotBuffers(int nSlots, size_t colourBytes, size_t stackBytes)
 
 // The context is set up for the path-queue kernel: persistent 3, two-phase HitSpheres, per-pixel seeds, the recursive fold, and at most
 // 2047 spp (its 64-B path record holds 11 bits of sample index).  chooseKernel adds what a frame and a scene must fit.
-static bool pathQueueContext()
+static bool pathQueueContext(int spp)
 {
-    return g.persist == 3 && g.hs == HS_TWO_PHASE && g.seedMode == SEED_PER_PIXEL && g.foldMode == FOLD_RECURSIVE && g.spp <= 2047;
+    return g.persist == 3 && g.hs == HS_TWO_PHASE && g.seedMode == SEED_PER_PIXEL && g.foldMode == FOLD_RECURSIVE && spp <= 2047;
 }
+static bool pathQueueContext() { return pathQueueContext(g.spp); }
 
 // Which kernel runs this frame, how much LDS it takes, how many workgroups fit on a CU.
 int chooseKernel(FramePlan& P)
@@ -128,7 +129,8 @@ int chooseKernel(FramePlan& P)
     const size_t ldsV1 = tptLdsBytes(a, g.foldMode, P.ldsScene);
     // path-queue kernel: it packs a pixel as x | y << 16 and a path id as 16 bits (larger frames take the lane-refill kernel), and its
     // path record 16 bits of sphere id
-    P.queued = pathQueueContext() && a.fc.width <= 65535 && a.fc.height <= 65535 && a.scene.nSpheres <= 65534;
+    // (a launch with a sample count per pixel, tptDrawDeviceAdaptive: the context's spp plays no part)
+    P.queued = pathQueueContext(a.sampleCounts ? 1 : g.spp) && a.fc.width <= 65535 && a.fc.height <= 65535 && a.scene.nSpheres <= 65534;
     // grouped scene on the path-queue kernel: the second level of the bounds filter reads the groups' pair records per lane -- from LDS
     // when they fit the area the grouped instantiation's smaller path pool leaves (<= 544 groups), else from global memory; the host
     // that asked for the FLAT filter (hitSpheres variant 3: the A/B) or for the matrix cores (variant 4) gets neither
@@ -523,6 +525,7 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
     int rc = 0;
     a.viewCams = nullptr;
     a.moveCentres = nullptr;
+    a.sampleCounts = aov ? aov->sampleCounts : nullptr; // (before chooseKernel: the context's spp plays no part in such a launch)
     if (table) {
         if ((rc = ensureViewSlots())) return rc;
         // (before chooseKernel: the views and animation kernels' LDS differs)
@@ -1055,6 +1058,50 @@ int tptDrawDeviceMoments(float time, int frameCount, int w, int h, float* device
     if (!T.valid) return 0;
     // (behind the tile's blend, so behind the trace; .xyz blended, .w kept; no ray count: the tile's blend has taken it)
     HIPCHK(tptLaunchResolve(deviceMoments, g.dMoments, T.nPixels, T.lerpFac, nullptr, g.dRays, nullptr, nullptr, g.stream));
+    return 0;
+}
+
+// tptDrawDeviceMoments with a sample count per pixel (tptTraceAdaptiveKernel reads the caller's plane) and a blend weighted by samples:
+// one launch of the adaptive resolve kernel takes the place of the tile's and the moments' blends.  It follows the trace on the context
+// stream like them; the kernel has added its rays to the running total itself.
+int tptDrawDeviceAdaptive(float time, int frameCount, int w, int h, float* deviceTile, float* deviceAlbedo, float* deviceNormalDepth,
+                          float* deviceMoments, const int32_t* deviceSampleCounts, unsigned testFlags)
+{
+    (void)time; // (the scene state is that of the last tptUpdate, as for tptDrawDevice)
+    const std::string fn = "tptDrawDeviceAdaptive";
+    if (int rc_ = flushShardDeferred()) return rc_; // (see tptDrawDevice)
+    if (requireInit()) return -1;
+    if (!deviceTile || !deviceMoments || !deviceSampleCounts || w <= 0 || h <= 0)
+        return fail(fn + ": bad arguments (deviceTile, deviceMoments, deviceSampleCounts, size)");
+    int rc = checkPathQueueDraw(fn.c_str(), "sample counts are", w, h, kQueueKernel, [&] {
+        const uintptr_t plane = (uintptr_t)w * (uintptr_t)h * 16u, counts = (uintptr_t)w * (uintptr_t)h * 4u;
+        if (overlapsAny(deviceMoments, {deviceTile, deviceAlbedo, deviceNormalDepth}, plane))
+            return fail(fn + ": deviceMoments overlaps the tile or a plane");
+        const uintptr_t c = reinterpret_cast<uintptr_t>(deviceSampleCounts);
+        for (const void* out : {(const void*)deviceTile, (const void*)deviceMoments, (const void*)deviceAlbedo, (const void*)deviceNormalDepth}) {
+            const uintptr_t o = reinterpret_cast<uintptr_t>(out);
+            if (out && c < o + plane && o < c + counts) return fail(fn + ": deviceSampleCounts overlaps the tile, the moments or a plane");
+        }
+        return 0;
+    });
+    if (rc) return rc;
+    if (!tptLaunchAdaptiveResolve) return fail(fn + ": this build has no adaptive blend kernel");
+    if ((rc = g.pending.discard())) return rc;
+    TraceTicket T;
+    AovPlanes aov;
+    aov.albedo = reinterpret_cast<f4*>(deviceAlbedo);
+    aov.normalDepth = reinterpret_cast<f4*>(deviceNormalDepth);
+    aov.moments = true;
+    aov.sampleCounts = deviceSampleCounts;
+    if ((rc = enqueueTrace(frameCount, w, h, testFlags, nullptr, T, 1, 0, nullptr, &aov))) return rc;
+    if (!T.valid) return 0;
+    if (T.pipelined) HIPCHK(hipStreamWaitEvent(g.stream, g.evTrace[T.slot], 0));
+    HIPCHK(tptLaunchAdaptiveResolve(deviceTile, deviceMoments, T.colour, T.moments, deviceSampleCounts, T.nPixels,
+                                    (testFlags & TPT_FLAG_PROGRESSIVE) != 0, g.stream));
+    if (T.pipelined) { // (what enqueueResolve records: the slot's colour plane is free again behind this blend)
+        HIPCHK(hipEventRecord(g.evResolve[T.slot], g.stream));
+        g.resolveRecorded[T.slot] = true;
+    }
     return 0;
 }
 

@@ -114,6 +114,109 @@ __global__ void __launch_bounds__(256) tptResolveBatchKernel(float* __restrict__
     }
 }
 
+// The blend of tptDrawDeviceAdaptive (include/tpt_hip.h states it): weighted by samples, not by frame number.  The pixel's running
+// sample count S travels in moments.w; this frame's n comes from the caller's plane, clamped as the trace kernel clamps it.  A pixel
+// with n == 0 was not traced -- its entries of `colour` and `staged` were never written -- and is left alone.  lerp = S / (S + n), an
+// IEEE quotient; tile.rgb and moments.xyz through blendPixel, moments.w = S + n, the tile's alpha kept.  HBM-bound: 100 B per traced
+// pixel (the count; tile, colour, moments and staged moments read; tile and moments written), 4 B per skipped one.
+__global__ void __launch_bounds__(256) tptAdaptiveResolveKernel(float* __restrict__ tile, float* __restrict__ moments, const f4* __restrict__ colour,
+                                                                const f4* __restrict__ staged, const int* __restrict__ counts, int nPixels,
+                                                                int progressive)
+{
+    __builtin_amdgcn_s_setprio(3); // see tptResolveKernel
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < nPixels; i += gridDim.x * 256) {
+        const int c = counts[i];
+        const int n = c < 0 ? 0 : (c > 2047 ? 2047 : c);
+        if (n == 0) continue;
+        f4 t = reinterpret_cast<const f4*>(tile)[i];
+        f4 m = reinterpret_cast<const f4*>(moments)[i];
+        const f4 fcol = colour[i], fm = staged[i];
+        // (finite and >= 1: one comparison pair, false for a NaN)
+        const float S = (progressive && m.w >= 1.0f && m.w <= 3.40282347e38f) ? m.w : 0.0f;
+        const float S1 = S + (float)n;
+        const float lerpFac = S / S1;
+        const f3 r = blendPixel(mk3(t.x, t.y, t.z), mk3(fcol.x, fcol.y, fcol.z), lerpFac);
+        const f3 q = blendPixel(mk3(m.x, m.y, m.z), mk3(fm.x, fm.y, fm.z), lerpFac);
+        t.x = r.x; t.y = r.y; t.z = r.z;
+        reinterpret_cast<f4*>(tile)[i] = t;
+        m.x = q.x; m.y = q.y; m.z = q.z; m.w = S1;
+        reinterpret_cast<f4*>(moments)[i] = m;
+    }
+}
+
+// tptAdaptiveSamplesDevice (include/tpt_hip.h states it; tests/adaptive_checker.c restates it): the next pass's sample count of every
+// pixel from the accumulated moments.  The layout of the a-trous kernels -- one lane per pixel, a wave along 64 pixels of a row: the
+// pixel's own f4 and 8 neighbour loads that the neighbouring lanes and rows share through L1 / L2, one 4-B store and, when asked for,
+// one 16-B store: HBM-bound at 20 - 36 B per pixel.  The counts are summed within the wave and added to *total with one 64-bit
+// vector atomic per wave (the launcher zeroes it first).  Every quotient is a plain IEEE one.
+__global__ void __launch_bounds__(256) tptAdaptivePlanKernel(const f4* __restrict__ moments, int* __restrict__ counts, f4* __restrict__ outVariance,
+                                                             unsigned long long* __restrict__ total, int width, int height, float te2,
+                                                             int minSamples, int maxSamples)
+{
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    const bool inside = x < width && y < height;
+    constexpr float gk[3] = {0.25f, 0.5f, 0.25f};
+    unsigned n = 0u;
+    if (inside) {
+        auto validS = [](float S) { return S >= 1.0f && S <= 3.40282347e38f; }; // (finite and >= 1; false for a NaN)
+        auto relVar = [](const f4& m, float& var) { // the relative variance of one sample
+            const float d = m.y - m.x * m.x;
+            var = d > 0.0f ? d : 0.0f;
+            const float b = m.x + TPT_ADAPTIVE_LUM_FLOOR;
+            return var / (b * b);
+        };
+        const size_t p = (size_t)y * width + x;
+        const f4 mp = moments[p];
+        const float S = mp.w;
+        const bool valid = validS(S);
+        float varP;
+        const float rP = relVar(mp, varP);
+        float gv = 0.0f, gw = 0.0f;
+#pragma unroll
+        for (int jy = 0; jy < 3; ++jy) {
+            const int qy = y + jy - 1;
+            if (qy < 0 || qy >= height) continue;
+#pragma unroll
+            for (int jx = 0; jx < 3; ++jx) {
+                const int qx = x + jx - 1;
+                if (qx < 0 || qx >= width) continue;
+                const float k = gk[jy] * gk[jx];
+                float r = rP;
+                bool v = valid;
+                if (jy != 1 || jx != 1) {
+                    const f4 mq = moments[(size_t)qy * width + qx];
+                    float varQ;
+                    r = relVar(mq, varQ);
+                    v = validS(mq.w);
+                }
+                if (v) {
+                    gv += k * r;
+                    gw += k;
+                }
+            }
+        }
+        int cnt = minSamples > 1 ? minSamples : 1;
+        if (valid && gw > 0.0f) {
+            const float R = gv / gw;
+            const float need = R / te2;
+            const float extra = need - S;
+            // (written so that a NaN lands on minSamples)
+            cnt = !(extra > (float)minSamples) ? minSamples : (extra >= (float)maxSamples ? maxSamples : (int)ceilf(extra));
+        }
+        counts[p] = cnt;
+        if (outVariance) {
+            f4 o;
+            o.x = 0.0f; o.y = valid ? varP / S : 0.0f; o.z = 0.0f; o.w = valid ? S : 0.0f;
+            outVariance[p] = o;
+        }
+        n = (unsigned)cnt;
+    }
+    if (total) { // (every lane of the wave arrives here: lanes outside the image add 0)
+        const unsigned waveSum = waveReduceAdd(n);
+        if (threadIdx.x == 0 && waveSum != 0u) atomicAdd(total, (unsigned long long)waveSum);
+    }
+}
+
 // Rank 0 of a sharded frame: the gathered tiles [rank][padRows + 1][width] f4 (row stripes dealt round-robin, one extra row
 // per rank whose first 8 bytes carry that rank's ray counter) -> the image [height][width] f4.  HBM-bound copy, one f4 per
 // lane, coalesced on both sides; replaces the per-row joins of DrawTest's task set (Test.cpp:357-361).
@@ -1333,7 +1436,11 @@ __device__ __forceinline__ int hitSpheresGroupedDeal(const SceneView& sv, bool g
 // picks the plane of every store (albedo and normal / depth a.aovPlane pixels apart in the caller's buffers, the moments a.framePlane
 // apart in the library's staging, like the colour), and a camera ray's normal on sphere 1 or 8 is taken from that frame's centre.  Its
 // own kernel (tptTraceClipKernel) for the same reason.
-template <bool LDS_SCENE, bool BATCH, bool VIEWS = false, bool MOVING = false, bool AOV = false, bool MOMENTS = false>
+// ADAPTIVE (with AOV + MOMENTS, a single frame; tptDrawDeviceAdaptive): the pixel's sample count comes from a.sampleCounts where a lane
+// claims the pixel (clamped to 0 .. 2047; 0: the pixel is finished at once, like a padding slot of a partially covered tile) and is
+// kept in .z of the path's third f4 of sums; the means are the sums x 1 / count, a correctly rounded quotient made when the pixel ends.
+// Its own kernel (tptTraceAdaptiveKernel) for the same reason.
+template <bool LDS_SCENE, bool BATCH, bool VIEWS = false, bool MOVING = false, bool AOV = false, bool MOMENTS = false, bool ADAPTIVE = false>
 __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1345,6 +1452,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     static_assert((BATCH || !MOVING) && !(VIEWS && MOVING), "animation frames are frames of a batched launch of their own");
     static_assert(!AOV || !BATCH || (MOVING && MOMENTS), "first-hit planes are made by single-frame launches, or beside the moments of an animated clip's frames");
     static_assert(!MOMENTS || AOV, "moments are summed beside the first-hit sums");
+    static_assert(!ADAPTIVE || (MOMENTS && !BATCH), "a count per pixel belongs to a single frame with its moments");
     constexpr int kPaths = (LDS_SCENE ? TPT_Q_PATHS : TPT_Q_PATHS_GROUPED) - (VIEWS ? TPT_Q_VIEW_PATHS : 0) -
                            (MOVING ? TPT_Q_ANIM_PATHS : 0); // paths this workgroup owns
     constexpr int kOffSt = LDS_SCENE ? TPT_Q_SPH_FIXED : 0;
@@ -1591,6 +1699,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
             // ---- start pixels on free paths (this wave's chunk pool, refilled from the global counter)
             bool need = mine, got = false;
             int px = 0, py = 0, laneFrame = 0;
+            [[maybe_unused]] uint32_t laneCount = 0u; // ADAPTIVE: the samples of the pixel this lane took
             for (;;) {
                 const unsigned long long needMask = __ballot(need);
                 if (needMask == 0ull) break;
@@ -1626,7 +1735,13 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                 const int take = want < availPx ? want : availPx;
                 if (need && rank < take) {
                     int x, ly;
-                    if (mapItem(a, chunkNext + rank, x, ly)) {
+                    bool take1 = mapItem(a, chunkNext + rank, x, ly);
+                    if (ADAPTIVE && take1) { // a pixel that asks for no sample is done: the lane goes on looking, the pool counts it as taken
+                        const int c = a.sampleCounts[(size_t)ly * fc.width + x];
+                        laneCount = (uint32_t)(c < 0 ? 0 : (c > 2047 ? 2047 : c));
+                        take1 = laneCount != 0u;
+                    }
+                    if (take1) {
                         px = x;
                         py = localRowToGlobal(a, ly);
                         laneFrame = chunkFrame;
@@ -1644,7 +1759,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                                              : ((uint32_t)px | ((uint32_t)py << 16));
                 colSum[p] = mk4(0.0f, 0.0f, 0.0f, u2f(where));
                 if (AOV) aovSum()[0] = aovSum()[1] = mk4(0.0f, 0.0f, 0.0f, 0.0f);
-                if (MOMENTS) aovSum()[2] = mk4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (MOMENTS) aovSum()[2] = mk4(0.0f, 0.0f, ADAPTIVE ? u2f(laneCount) : 0.0f, 0.0f);
                 if (MOVING) movedAt = 2 * laneFrame;
                 if (VIEWS)
                     qCameraView(ldsCams[laneFrame], *ldsFc, px, py, rng, ro, rd);
@@ -1675,10 +1790,10 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                 if (MOMENTS) {
                     const float l = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
                     const f4 m = aovSum()[2];
-                    mom = mk4(m.x + l, m.y + l * l, 0.0f, 0.0f);
+                    mom = mk4(m.x + l, m.y + l * l, ADAPTIVE ? m.z : 0.0f, 0.0f);
                 }
                 sample++;
-                if (sample < fc.spp) {
+                if (sample < (ADAPTIVE ? (int)f2u(mom.z) : fc.spp)) {
                     colSum[p] = mk4(col.x, col.y, col.z, c3.w);
                     if (MOMENTS) aovSum()[2] = mom;
                     if (VIEWS)
@@ -1689,16 +1804,18 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                     doMatE = true;
                     ray = true;
                 } else {
-                    const f3 out = col * fc.invSpp; // Test.cpp:291
+                    // (ADAPTIVE: 1.0f / count, correctly rounded -- what makeFrameConsts' fc.invSpp is for a frame of that many samples)
+                    const float invSpp = ADAPTIVE ? tdivSafeNum(1.0f, (float)f2u(mom.z)) : fc.invSpp;
+                    const f3 out = col * invSpp; // Test.cpp:291
                     a.frameColour[plane + globalRowToLocal(a, py) * fc.width + px] = mk4(out.x, out.y, out.z, 0.0f); // one 16-B store per pixel
                     if (AOV) { // the means of the first-hit sums, in the form of Test.cpp:291; one 16-B store per plane (either may be absent)
                         const size_t px0 = (size_t)globalRowToLocal(a, py) * fc.width + px;
                         // (a clip's frame: its planes in the caller's buffers, its moments plane in the staging beside its colour plane)
                         const size_t at = px0 + (BATCH ? (size_t)(f2u(c3.w) >> 26) * (size_t)a.aovPlane : 0);
                         const f4 s0 = aovSum()[0], s1 = aovSum()[1];
-                        if (a.aovAlbedo) a.aovAlbedo[at] = mk4(s0.x * fc.invSpp, s0.y * fc.invSpp, s0.z * fc.invSpp, s0.w * fc.invSpp);
-                        if (a.aovNormalDepth) a.aovNormalDepth[at] = mk4(s1.x * fc.invSpp, s1.y * fc.invSpp, s1.z * fc.invSpp, s1.w * fc.invSpp);
-                        if (MOMENTS) a.momentsOut[px0 + plane] = mk4(mom.x * fc.invSpp, mom.y * fc.invSpp, 0.0f, 0.0f);
+                        if (a.aovAlbedo) a.aovAlbedo[at] = mk4(s0.x * invSpp, s0.y * invSpp, s0.z * invSpp, s0.w * invSpp);
+                        if (a.aovNormalDepth) a.aovNormalDepth[at] = mk4(s1.x * invSpp, s1.y * invSpp, s1.z * invSpp, s1.w * invSpp);
+                        if (MOMENTS) a.momentsOut[px0 + plane] = mk4(mom.x * invSpp, mom.y * invSpp, 0.0f, 0.0f);
                     }
                     toFree = true;
                 }
@@ -1948,25 +2065,28 @@ tptTraceQueueKernel<false, true>(const KernelArgs a)
 // The variants of traceQueueBody beyond <LDS_SCENE, BATCH>, from one list.  Each is a kernel of its own, not another template argument of
 // tptTraceQueueKernel: names and code of the existing kernels stay (tests look them up by name).  <false>: no scene in LDS -- grouped scenes
 // and flat scenes whose arrays stay in global memory (the moving variants take flat scenes only) --, with the grouped register cap.
-enum { QF_BATCH = 1, QF_VIEWS = 2, QF_MOVING = 4, QF_AOV = 8, QF_MOMENTS = 16 };
+enum { QF_BATCH = 1, QF_VIEWS = 2, QF_MOVING = 4, QF_AOV = 8, QF_MOMENTS = 16, QF_ADAPTIVE = 32 };
 #define TPT_QUEUE_VARIANT_KERNEL(NAME, F)                                                                                                    \
     template <bool LDS_SCENE>                                                                                                                \
     __global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute__((amdgpu_num_vgpr(TPT_Q_MAX_VGPR)))                    \
     NAME(const KernelArgs a)                                                                                                                 \
     {                                                                                                                                        \
-        traceQueueBody<LDS_SCENE, ((F) & QF_BATCH) != 0, ((F) & QF_VIEWS) != 0, ((F) & QF_MOVING) != 0, ((F) & QF_AOV) != 0, ((F) & QF_MOMENTS) != 0>(a); \
+        traceQueueBody<LDS_SCENE, ((F) & QF_BATCH) != 0, ((F) & QF_VIEWS) != 0, ((F) & QF_MOVING) != 0, ((F) & QF_AOV) != 0, ((F) & QF_MOMENTS) != 0, \
+                       ((F) & QF_ADAPTIVE) != 0>(a);                                                                                         \
     }                                                                                                                                        \
     template <>                                                                                                                              \
     __global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute__((amdgpu_num_vgpr(TPT_Q_MAX_VGPR_GROUPED)))            \
     NAME<false>(const KernelArgs a)                                                                                                          \
     {                                                                                                                                        \
-        traceQueueBody<false, ((F) & QF_BATCH) != 0, ((F) & QF_VIEWS) != 0, ((F) & QF_MOVING) != 0, ((F) & QF_AOV) != 0, ((F) & QF_MOMENTS) != 0>(a); \
+        traceQueueBody<false, ((F) & QF_BATCH) != 0, ((F) & QF_VIEWS) != 0, ((F) & QF_MOVING) != 0, ((F) & QF_AOV) != 0, ((F) & QF_MOMENTS) != 0, \
+                       ((F) & QF_ADAPTIVE) != 0>(a);                                                                                         \
     }
 TPT_QUEUE_VARIANT_KERNEL(tptTraceViewsKernel, QF_BATCH | QF_VIEWS)                           // tptDrawDeviceViews: several views of one frame, a camera per frame of the batch
 TPT_QUEUE_VARIANT_KERNEL(tptTraceAnimationKernel, QF_BATCH | QF_MOVING)                      // tptDrawDeviceAnimation: frames of an animated scene, spheres 1 and 8 where each frame has them
 TPT_QUEUE_VARIANT_KERNEL(tptTraceAovKernel, QF_AOV)                                          // tptDrawDeviceAov: a single frame plus the per-path sums of its first-hit planes
 TPT_QUEUE_VARIANT_KERNEL(tptTraceMomentsKernel, QF_AOV | QF_MOMENTS)                         // tptDrawDeviceMoments: the AOV kernel plus a third f4 of sums per path, the luminance moments
 TPT_QUEUE_VARIANT_KERNEL(tptTraceClipKernel, QF_BATCH | QF_MOVING | QF_AOV | QF_MOMENTS)     // tptDrawDeviceAnimationMoments: the animation kernel plus the moments kernel's per-path sums
+TPT_QUEUE_VARIANT_KERNEL(tptTraceAdaptiveKernel, QF_AOV | QF_MOMENTS | QF_ADAPTIVE)             // tptDrawDeviceAdaptive: the moments kernel with each pixel's sample count from a plane
 #undef TPT_QUEUE_VARIANT_KERNEL
 
 #if defined(TPT_TEST_HOOKS)
@@ -2234,6 +2354,7 @@ hipError_t tptLaunchTraceQueue(const KernelArgs& a, bool ldsScene, int blocks, s
         /* QV_AOV       */ {tptTraceAovKernel<false>, tptTraceAovKernel<true>},
         /* QV_MOMENTS   */ {tptTraceMomentsKernel<false>, tptTraceMomentsKernel<true>},
         /* QV_CLIP      */ {tptTraceClipKernel<false>, tptTraceClipKernel<true>},
+        /* QV_ADAPTIVE  */ {tptTraceAdaptiveKernel<false>, tptTraceAdaptiveKernel<true>},
     };
     const QueueVariant variant = tptQueueVariant(a);
     if (variant == QV_INVALID) return hipErrorInvalidValue;
@@ -2381,6 +2502,28 @@ hipError_t tptLaunchResolveBatch(float* tile, const f4* frameColour, int nPixels
     if (nPixels <= 0) return hipSuccess;
     hipLaunchKernelGGL(tptResolveBatchKernel, dim3(tptResolveBlocks(nPixels)), dim3(256), 0, stream, tile, frameColour, nPixels, planeStride, nFrames, lerp,
                        reinterpret_cast<f4*>(mirror), rayCounter, counterOut);
+    return hipGetLastError();
+}
+
+hipError_t tptLaunchAdaptiveResolve(float* tile, float* moments, const f4* frameColour, const f4* stagedMoments, const int32_t* counts,
+                                    int nPixels, bool progressive, hipStream_t stream)
+{
+    if (nPixels <= 0) return hipSuccess;
+    hipLaunchKernelGGL(tptAdaptiveResolveKernel, dim3(tptResolveBlocks(nPixels)), dim3(256), 0, stream, tile, moments, frameColour, stagedMoments,
+                       counts, nPixels, progressive ? 1 : 0);
+    return hipGetLastError();
+}
+hipError_t tptLaunchAdaptivePlan(const float* moments, int32_t* counts, float* outVariance, int64_t* totalSamples, int width, int height,
+                                 float targetError, int minSamples, int maxSamples, hipStream_t stream)
+{
+    if (totalSamples) {
+        hipError_t e = hipMemsetAsync(totalSamples, 0, sizeof(int64_t), stream);
+        if (e != hipSuccess) return e;
+    }
+    const dim3 grid((unsigned)(width + 63) / 64, (unsigned)(height + 3) / 4);
+    hipLaunchKernelGGL(tptAdaptivePlanKernel, grid, dim3(64, 4), 0, stream, reinterpret_cast<const f4*>(moments), counts,
+                       reinterpret_cast<f4*>(outVariance), reinterpret_cast<unsigned long long*>(totalSamples), width, height,
+                       targetError * targetError, minSamples, maxSamples);
     return hipGetLastError();
 }
 

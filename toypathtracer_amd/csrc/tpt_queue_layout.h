@@ -148,9 +148,13 @@ TPT_HD int globalRowToLocal(const KernelArgs& a, int gy) { return shardKernelGlo
 
 // Which variant of the path-queue kernel a launch takes: what its argument block holds decides, here and nowhere else.  QV_INVALID: a
 // combination no entry point builds (tptLaunchTraceQueue refuses it).
-enum QueueVariant { QV_FRAME, QV_BATCH, QV_VIEWS, QV_ANIMATION, QV_AOV, QV_MOMENTS, QV_CLIP, QV_INVALID };
+enum QueueVariant { QV_FRAME, QV_BATCH, QV_VIEWS, QV_ANIMATION, QV_AOV, QV_MOMENTS, QV_CLIP, QV_ADAPTIVE, QV_INVALID };
 inline QueueVariant tptQueueVariant(const tpt::KernelArgs& a)
 {
+    if (a.sampleCounts) { // (tptDrawDeviceAdaptive: a single frame with its planes and moments, a sample count per pixel)
+        if (a.batchFrames != 1 || a.viewCams || a.moveCentres || !a.aovSums || !a.momentsOut) return QV_INVALID;
+        return QV_ADAPTIVE;
+    }
     if (a.viewCams) { // (tptDrawDeviceViews: 1 .. TPT_Q_VIEWS_MAX views, the frames of the batch)
         if (a.batchFrames < 1 || a.batchFrames > TPT_Q_VIEWS_MAX) return QV_INVALID;
         return QV_VIEWS;
@@ -187,7 +191,8 @@ inline size_t tptQueueLdsBytes(const tpt::KernelArgs& a, bool ldsScene)
     const QueueVariant variant = tptQueueVariant(a);
     const bool views = variant == QV_VIEWS; // (tptTraceViewsKernel: the cameras in LDS, TPT_Q_VIEW_PATHS path records fewer)
     const bool moving = variant == QV_ANIMATION || variant == QV_CLIP; // (tptTraceAnimationKernel: the centres in LDS, TPT_Q_ANIM_PATHS path records fewer)
-    // (tptTraceAovKernel, tptTraceMomentsKernel and tptTraceClipKernel, a.aovSums: the LDS of their twin without planes -- their sums live in global memory)
+    // (tptTraceAovKernel, tptTraceMomentsKernel, tptTraceAdaptiveKernel and tptTraceClipKernel, a.aovSums: the LDS of their twin without
+    //  planes -- their sums live in global memory)
     size_t bytes = 0;
     if (ldsScene) bytes += TPT_Q_SPH_FIXED + ((size_t)nPad * 16 <= TPT_Q_SPH_FIXED ? 0 : (size_t)nPad * 16) + (((size_t)nPad * 4 + 15) & ~(size_t)15) + (size_t)a.scene.nSpheres * 48;
     bytes += (size_t)a.scene.nLights * 32;
