@@ -231,6 +231,32 @@ TPT_API int tptDrawDeviceAnimationMoments(int firstFrame, int nFrames, const flo
                                           float* deviceTile, float* deviceMoments,
                                           float* deviceFrameImages, float* deviceFrameAlbedo, float* deviceFrameNormalDepth,
                                           float* deviceFrameMoments, int64_t* deviceFrameRays, unsigned testFlags);
+/* tptDrawDeviceAnimationMoments with a CAMERA PER FRAME: a turntable or fly-through with the planes the denoising chain reads, or the
+ * views of a multi-view dataset with depth, normal and albedo each, up to 32 per launch.  views: host memory, nFrames x 9 floats in
+ * tptDrawDeviceViews' layout {lookFrom[3], lookAt[3], vfovDegrees, aperture, focusDist}.  Frame j (0 <= j < nFrames) is bit-identical to
+ *   tptSetCamera(views + 9*j, views + 9*j + 3, views[9*j + 6], views[9*j + 7], views[9*j + 8]);
+ *   tptUpdate(times[j], firstFrame + j, w, h, testFlags);
+ *   tptDrawDeviceMoments(times[j], firstFrame + j, w, h, deviceTile, albedo_j, normalDepth_j, deviceMoments, testFlags);
+ * with the same ray count: the seeds are those of frame firstFrame + j (not one frame's for all, as tptDrawDeviceViews'), the lerp factor
+ * is the frame's own, spheres 1 and 8 stand at times[j] (kFlagAnimate), the aperture is 0 in Mitsuba-compare mode, the aspect is w / h
+ * and vup (0, 1, 0).  Every other argument, the per-frame outputs (plane j of the images and of the moments: the tile and deviceMoments
+ * as they stand after frame j's blends) and the ordering are tptDrawDeviceAnimationMoments'.  outCameras: NULL, or host memory of
+ * nFrames * 88 bytes, written AT CALL TIME with each frame's Camera record -- byte for byte what tptGetSceneDesc returns after that
+ * frame's tptUpdate, the record tptTemporalAccumulateDevice takes as curCamera / prevCamera.
+ * Afterwards the context is where that sequence leaves it: the camera set-up is views[nFrames - 1] (as after tptSetCamera), the camera
+ * that of its tptUpdate, spheres 1 and 8 at times[nFrames - 1], that scene staged; frames traced ahead and stream-batch planes are
+ * dropped first.
+ * One trace launch per 32 frames on a scene of more than 8 and fewer than 256 spheres, whether it moves (kFlagAnimate) or not: the
+ * kernel reads each frame's camera and its centres of spheres 1 and 8 from tables, and for a clip in which nothing moves the centres
+ * table repeats the scene's own.  Scenes of 8 spheres or fewer and of 256 and more take one launch per frame (tptDrawDeviceMoments'
+ * kernel, the camera set per frame), with the same bits.  The launches of one call overlap as tptDrawDeviceAnimationMoments' do.
+ * Refused (non-zero, tptGetLastError names this function, nothing enqueued, no buffer and no byte of outCameras written, camera and
+ * spheres unchanged): everything tptDrawDeviceAnimationMoments refuses -- the overlap rule covers the same seven device buffers --, and
+ * views NULL. */
+TPT_API int tptDrawDeviceCameraClip(int firstFrame, int nFrames, const float* times, const float* views,
+                                    int screenWidth, int screenHeight, float* deviceTile, float* deviceMoments,
+                                    float* deviceFrameImages, float* deviceFrameAlbedo, float* deviceFrameNormalDepth,
+                                    float* deviceFrameMoments, int64_t* deviceFrameRays, void* outCameras, unsigned testFlags);
 /* The spatial filter of SVGF (Schied et al., HPG 2017) in tptDenoiseDevice's rational form: an a-trous filter whose luminance term is
  * scaled by a per-pixel variance made from tptDrawDeviceMoments' moments and carried through the iterations.  All six buffers are
  * device buffers of h*w*4 floats; deviceAlbedo and deviceNormalDepth may be NULL.  samples: how many samples the colour and the moments

@@ -39,7 +39,7 @@ C_ABI_SYMBOLS = [
     "tptSetSamplesPerPixel", "tptSetConfig", "tptSetSeedMode", "tptSetFoldMode", "tptSetScene", "tptSetCamera", "tptSetStream",
     "tptSetRowShard", "tptLocalRowCount", "tptLocalRowToGlobal", "tptDrawDevice", "tptRayCounterRead", "tptSetRayCounter", "tptSetFrameOverlap", "tptDisplayRGBA8", "tptKernelTimingBegin", "tptKernelTimingEnd",
     "tptSynchronize", "tptTimerBegin", "tptTimerEnd", "tptSetKernelVariant",
-    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceAnimationMoments", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptDrawDeviceAdaptive", "tptAdaptiveSamplesDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
+    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceAnimationMoments", "tptDrawDeviceCameraClip", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptDrawDeviceAdaptive", "tptAdaptiveSamplesDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
 ]
 # include/tpt_test_hooks.h: exported by the second build (libtoypathtracer_hip_hooks.so) only
 HOOK_SYMBOLS = ["tptTestMath", "tptTestMathExhaustive", "tptTestHitSpheres", "tptTestMatrixFilter", "tptTestGroupFilter", "tptTestSetDealCapacities", "tptDebugStats", "tptDebugChunkOrder"]
@@ -78,7 +78,7 @@ def _bind(path, hooks):
         "tptSetRayCounter": [p], "tptSetTileMirror": [p, p], "tptSetFrameOverlap": [i], "tptDisplayRGBA8": [p, i, i, p], "tptKernelTimingBegin": [i],
         "tptKernelTimingEnd": [C.POINTER(f), C.POINTER(i)],
         "tptSynchronize": [], "tptTimerBegin": [], "tptTimerEnd": [C.POINTER(f)], "tptSetKernelVariant": [i, i, i],
-        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDrawDeviceAnimationMoments": [i, i, p, i, i] + [p] * 7 + [u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptDrawDeviceAdaptive": [f, i, i, i, p, p, p, p, p, u], "tptAdaptiveSamplesDevice": [i, i, p, f, i, i, p, p, p], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
+        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDrawDeviceAnimationMoments": [i, i, p, i, i] + [p] * 7 + [u], "tptDrawDeviceCameraClip": [i, i, p, p, i, i] + [p] * 8 + [u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptDrawDeviceAdaptive": [f, i, i, i, p, p, p, p, p, u], "tptAdaptiveSamplesDevice": [i, i, p, f, i, i, p, p, p], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
     }
     if hooks:
         sigs.update({"tptDebugStats": [p, i], "tptDebugChunkOrder": [p, p, i], "tptTestMath": [i, p, p, p, i], "tptTestMathExhaustive": [i, u, u, p, p],
@@ -521,6 +521,35 @@ def draw_device_animation_moments(times, first_frame, w, h, tile_ptr, moments_pt
     _chk(load_library().tptDrawDeviceAnimationMoments(first_frame, t.shape[0], t.ctypes.data if t.size else None, w, h, C.c_void_p(tile_ptr),
                                                       C.c_void_p(moments_ptr), *[C.c_void_p(v) if v else None for _, v in outs], flags),
          "tptDrawDeviceAnimationMoments")
+
+
+def draw_device_camera_clip(times, views, first_frame, w, h, tile_ptr, moments_ptr, flags, images_ptr=None, albedo_ptr=None,
+                            normal_depth_ptr=None, frame_moments_ptr=None, rays_ptr=None, cameras=True):
+    """draw_device_animation_moments with a camera per frame, in launches of up to 32 frames.  views: array-like (N, 9) of {lookFrom xyz,
+    lookAt xyz, vfov, aperture, focusDist} with N = len(times).  Frame j equals set_camera(views[j]) + UpdateTest(times[j],
+    first_frame + j) + draw_device_moments on tile_ptr and moments_ptr with plane j of albedo_ptr / normal_depth_ptr; the other outputs
+    as draw_device_animation_moments'.  Returns the frames' cameras as a CAMERA_DT array of N records, each what GetSceneDesc()[2] is
+    after that frame's UpdateTest and ready for temporal_accumulate_device (cameras=False: not asked for, returns None)."""
+    t = np.ascontiguousarray(times, dtype=np.float32)
+    if t.ndim != 1:
+        raise ValueError("times: a 1-D sequence expected, got shape %r" % (t.shape,))
+    v = np.ascontiguousarray(views, dtype=np.float32)
+    if v.ndim != 2 or v.shape[1] != 9:
+        raise ValueError("views: shape (N, 9) expected, got %r" % (v.shape,))
+    if v.shape[0] != t.shape[0]:
+        raise ValueError("views: one view per time expected, got %d views for %d times" % (v.shape[0], t.shape[0]))
+    _positive_ints(("w", w), ("h", h))
+    outs = (("images_ptr", images_ptr), ("albedo_ptr", albedo_ptr), ("normal_depth_ptr", normal_depth_ptr),
+            ("frame_moments_ptr", frame_moments_ptr), ("rays_ptr", rays_ptr))
+    _pointers(("tile_ptr", tile_ptr), ("moments_ptr", moments_ptr), *outs)
+    if not tile_ptr or not moments_ptr:
+        raise ValueError("tile_ptr, moments_ptr: device buffers are required")
+    cams = np.zeros(t.shape[0], CAMERA_DT) if cameras else None
+    _chk(load_library().tptDrawDeviceCameraClip(first_frame, t.shape[0], t.ctypes.data if t.size else None, v.ctypes.data if v.size else None,
+                                                w, h, C.c_void_p(tile_ptr), C.c_void_p(moments_ptr),
+                                                *[C.c_void_p(x) if x else None for _, x in outs],
+                                                cams.ctypes.data if cameras and cams.size else None, flags), "tptDrawDeviceCameraClip")
+    return cams
 
 
 def moment_samples(spp, frame=None, flags=0):

@@ -221,11 +221,12 @@ struct Context {
     // tptDrawDeviceViews / tptDrawDeviceAnimation: per frame slot, the launch's BatchTable (device table the kernel stages in LDS, pinned
     // host staging) and its frames' ray counters.  Per slot, because up to kMaxSlots launches are in flight: the table of one call must
     // not be overwritten while an earlier launch still reads it (the upload is stream-ordered behind the slot's previous blend, like its
-    // colour buffer).  The moving centres of an animation batch (2 x 16 B per frame) take the room of its first 12 cameras.
+    // colour buffer).  The moving centres of an animation batch (2 x 16 B per frame) take the room of its first 12 cameras; a launch
+    // that takes both tables (tptDrawDeviceCameraClip) has its centres behind the whole camera table.
     struct ViewSlot {
-        CameraPOD* dev = nullptr;       // [kMaxBatch] cameras (or [kMaxBatch][2] centres)
+        CameraPOD* dev = nullptr;       // [kMaxBatch] cameras (or [kMaxBatch][2] centres), then [kMaxBatch][2] centres beside cameras
         unsigned long long* rays = nullptr; // [kMaxBatch] rays of each view
-        CameraPOD* stage = nullptr;     // pinned [kMaxBatch]
+        CameraPOD* stage = nullptr;     // pinned, the same layout
         hipEvent_t evUploaded = nullptr;
         bool copyEnqueued = false;
     } views[kMaxSlots];
@@ -397,7 +398,8 @@ int effectiveOverlap();
 // tpt_host_pipeline.cpp
 // What differs between the frames of one launch besides their seeds (tptDrawDeviceViews, tptDrawDeviceAnimation).  The table is copied
 // to the slot's device table on the frame's stream, and every frame counts its rays into the slot's counters (Context::ViewSlot).  With
-// neither table the launch is the plain (batched) kernel with those per-frame counters.
+// neither table the launch is the plain (batched) kernel with those per-frame counters; with both (and the planes of a clip) it is
+// tptCameraClipKernel: a camera and the centres per frame, every frame with its own seeds.
 struct BatchTable {
     const CameraPOD* cams = nullptr; // [batch] cameras, every frame with the seeds of frameCount: tptTraceViewsKernel
     const f4* centres = nullptr;     // [batch][2] {x, y, z, -} of spheres 1 and 8 (Test.cpp:304-308): tptTraceAnimationKernel

@@ -76,6 +76,8 @@ struct KernelArgs {
     // takes tptTraceClipKernel): frame j of the batch stores its first-hit planes at aovAlbedo / aovNormalDepth + j * aovPlane pixels (the
     // caller's per-frame buffers) and its moments at momentsOut + j * framePlane (staging, beside its colour plane).
     int aovPlane = 0;
+    // ... with a camera per frame (tptDrawDeviceCameraClip: viewCams and moveCentres both given, with aovSums and momentsOut; the launch
+    // takes tptCameraClipKernel): frame j reads camera viewCams[j] where a sample starts, its seeds stay those of frame fc.frame + j.
     // A single frame with its planes and moments whose pixels take a sample count each (tptDrawDeviceAdaptive): [nLocalRows][width]
     // int32 in device memory, read where a lane claims a pixel and clamped there to 0 .. 2047 (0: the pixel is not traced, nothing of it
     // is stored); fc.spp and fc.invSpp play no part.  The launch takes tptTraceAdaptiveKernel.  Null for every other launch.

@@ -401,15 +401,17 @@ int enqueueChunkOrder(FramePlan& P, hipStream_t ts)
     return 0;
 }
 
+static const size_t kViewCamBytes = sizeof(CameraPOD) * kMaxBatch; // a slot's cameras; its centres lie behind them when a launch takes both
 // tptDrawDeviceViews: the per-slot camera tables and view ray counters (Context::ViewSlot), allocated by the first views call (a
 // context that never draws views never holds them).
 int ensureViewSlots()
 {
     if (g.dViews) return 0;
-    const size_t camBytes = sizeof(CameraPOD) * kMaxBatch, perSlot = camBytes + sizeof(unsigned long long) * kMaxBatch;
-    static_assert((sizeof(CameraPOD) * kMaxBatch) % 16 == 0, "the ray counters behind a slot's cameras stay aligned");
+    // (a slot's table: the cameras, then the centres of a launch that takes both -- tptDrawDeviceCameraClip --, then the ray counters)
+    const size_t camBytes = kViewCamBytes, tableBytes = camBytes + 2 * sizeof(f4) * kMaxBatch, perSlot = tableBytes + sizeof(unsigned long long) * kMaxBatch;
+    static_assert(kViewCamBytes % 16 == 0, "the centres and the ray counters behind a slot's cameras stay aligned");
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dViews), perSlot * Context::kMaxSlots));
-    if (hipHostMalloc(reinterpret_cast<void**>(&g.hViewsStage), camBytes * Context::kMaxSlots, 0) != hipSuccess) {
+    if (hipHostMalloc(reinterpret_cast<void**>(&g.hViewsStage), tableBytes * Context::kMaxSlots, 0) != hipSuccess) {
         (void)hipFree(g.dViews);
         g.dViews = nullptr;
         g.hViewsStage = nullptr;
@@ -418,8 +420,8 @@ int ensureViewSlots()
     for (int k = 0; k < Context::kMaxSlots; ++k) {
         Context::ViewSlot& V = g.views[k];
         V.dev = reinterpret_cast<CameraPOD*>(g.dViews + perSlot * k);
-        V.rays = reinterpret_cast<unsigned long long*>(g.dViews + perSlot * k + camBytes);
-        V.stage = g.hViewsStage + (size_t)kMaxBatch * k;
+        V.rays = reinterpret_cast<unsigned long long*>(g.dViews + perSlot * k + tableBytes);
+        V.stage = reinterpret_cast<CameraPOD*>(reinterpret_cast<char*>(g.hViewsStage) + tableBytes * k);
         V.copyEnqueued = false;
         if (!V.evUploaded) HIPCHK(hipEventCreateWithFlags(&V.evUploaded, kOrderingEvent));
     }
@@ -461,7 +463,8 @@ int ensureAovSums(const FramePlan& P, size_t momentsBytes, int halves)
 // count (the context's counter, or a per-slot one for frames that are traced ahead of their DrawTest call).
 // `table` (tptDrawDeviceViews, tptDrawDeviceAnimation): what differs between the batch's frames (host memory, copied to the slot's
 // table on the frame's stream) -- cameras: `batch` views of frame frameCount, traced by the views kernel; centres: `batch` frames of an
-// animated scene, traced by the animation kernel; neither: the plain kernel.  Every frame counts its rays into the slot's counters.
+// animated scene, traced by the animation kernel; neither: the plain kernel; both (with the planes of a clip, tptDrawDeviceCameraClip): a
+// camera and the centres per frame, every frame with its own seeds.  Every frame counts its rays into the slot's counters.
 // `aov` (tptDrawDeviceAov, a single frame): the caller's first-hit planes, written by the AOV kernel behind the context stream.  With
 // moments and a centres table (tptDrawDeviceAnimationMoments): the planes of `batch` frames, h * w pixels apart, and as many moments planes.
 int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long long* frameRays, TraceTicket& T, int batch, int rayStride,
@@ -530,7 +533,7 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
         if ((rc = ensureViewSlots())) return rc;
         // (before chooseKernel: the views and animation kernels' LDS differs)
         if (viewCams) a.viewCams = g.views[P.slot].dev;
-        if (centres) a.moveCentres = reinterpret_cast<const f4*>(g.views[P.slot].dev);
+        if (centres) a.moveCentres = reinterpret_cast<const f4*>(reinterpret_cast<const char*>(g.views[P.slot].dev) + (viewCams ? kViewCamBytes : 0));
         frameRays = g.views[P.slot].rays; // every frame counts its own rays (the blends add them to the running total)
         rayStride = 1;
     }
@@ -539,7 +542,8 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
         return refuse("tptDrawDeviceViews: needs the path-queue kernel (per-pixel seeds, recursive fold, two-phase HitSpheres, at most 2047 spp)");
     if (centres && (!P.queued || a.scene.nGroups > 0))
         return refuse("tptDrawDeviceAnimation: one launch per batch needs the path-queue kernel and a flat scene");
-    const bool clip = aov && aov->moments && centres; // (the frames of an animated clip with their planes: tptTraceClipKernel)
+    const bool clip = aov && aov->moments && centres; // (the frames of an animated clip with their planes: tptTraceClipKernel, tptCameraClipKernel)
+    if (viewCams && centres && !clip) return fail("enqueueTrace: a camera and the centres per frame go with a clip's planes");
     if (aov && (!P.queued || !(clip || (batch == 1 && !viewCams && !centres))))
         return refuse("tptDrawDeviceAov: needs the path-queue kernel (per-pixel seeds, recursive fold, two-phase HitSpheres, at most 2047 spp)");
     // a batch is traced by the path-queue kernel (per-pixel seeds) or, in the reference's own seed mode, by the lane-refill
@@ -611,9 +615,11 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
         // slot's pinned staging (an earlier call on this slot) has left the host before the staging is overwritten
         static_assert(2 * sizeof(f4) * kMaxBatch <= sizeof(CameraPOD) * kMaxBatch, "a batch's moving centres fit the slot's camera table");
         Context::ViewSlot& V = g.views[slot];
-        const size_t bytes = viewCams ? sizeof(CameraPOD) * (size_t)batch : 2 * sizeof(f4) * (size_t)batch;
+        const size_t camBytes = sizeof(CameraPOD) * (size_t)batch, centreBytes = 2 * sizeof(f4) * (size_t)batch;
+        const size_t bytes = viewCams && centres ? kViewCamBytes + centreBytes : (viewCams ? camBytes : centreBytes); // (both: one copy, the centres behind the whole camera table)
         if (V.copyEnqueued) HIPCHK(hipEventSynchronize(V.evUploaded));
-        memcpy(V.stage, viewCams ? static_cast<const void*>(viewCams) : static_cast<const void*>(centres), bytes);
+        if (viewCams) memcpy(V.stage, viewCams, camBytes);
+        if (centres) memcpy(reinterpret_cast<char*>(V.stage) + (viewCams ? kViewCamBytes : 0), centres, centreBytes);
         HIPCHK(hipMemcpyAsync(V.dev, V.stage, bytes, hipMemcpyHostToDevice, ts));
         HIPCHK(hipEventRecord(V.evUploaded, ts));
         V.copyEnqueued = true;
@@ -731,24 +737,68 @@ static int enqueuePlaneResolves(const TraceTicket& T, float* tiles, size_t tileS
     return 0;
 }
 
-// The launches and blends of tptDrawDeviceAnimation and, with `planes`, tptDrawDeviceAnimationMoments, behind their checks: frames traced
-// ahead are dropped, the camera is the one every tptUpdate of the sequence builds, then `perLaunch` frames per launch.
+// A view {lookFrom, lookAt, vfovDegrees, aperture, focusDist} as tptSetCamera stores it (vup (0, 1, 0)), and its camera exactly as
+// tptSetCamera + tptUpdate at this size would build it (Test.cpp:309-319, 341).
+static CameraSetup viewSetup(const float* p)
+{
+    CameraSetup cs = defaultCameraSetup(); // (vup (0, 1, 0))
+    for (int i = 0; i < 3; ++i) {
+        cs.lookFrom[i] = p[i];
+        cs.lookAt[i] = p[3 + i];
+    }
+    cs.vfov = p[6];
+    cs.aperture = p[7];
+    cs.focusDist = p[8];
+    return cs;
+}
+static CameraPOD viewCamera(CameraSetup cs, int w, int h)
+{
+    if (g.config & CFG_MITSUBA_COMPARE) cs.aperture = 0.0f; // Test.cpp:312-313
+    return makeCamera(cs, float(w) / float(h));
+}
+
+// The launches and blends of tptDrawDeviceAnimation and, with `planes`, tptDrawDeviceAnimationMoments and tptDrawDeviceCameraClip, behind
+// their checks: frames traced ahead are dropped, the camera is the one every tptUpdate of the sequence builds -- given `views`, frame j's
+// own, as tptSetCamera(views[j]) before its tptUpdate leaves it (also written to outCameras[j], if given) --, then `perLaunch` frames per
+// launch.  A launch of several frames with `views` takes both tables (tptCameraClipKernel); when nothing moves, its centres table repeats
+// the scene's own centres of spheres 1 and 8: the kernel's exact tests read the same numbers from the table as from the scene.
 struct ClipPlanes {
     float *moments, *frameAlbedo, *frameNormalDepth, *frameMoments; // (deviceMoments, and the per-frame outputs or null)
 };
 static int enqueueAnimation(int firstFrame, int nFrames, const float* times, int w, int h, float* deviceTile, float* deviceFrameImages,
-                            int64_t* deviceFrameRays, unsigned testFlags, bool animate, int perLaunch, const ClipPlanes* planes)
+                            int64_t* deviceFrameRays, unsigned testFlags, bool animate, int perLaunch, const ClipPlanes* planes,
+                            const float* views = nullptr, CameraPOD* outCameras = nullptr)
 {
     int rc = g.pending.discard();
     if (rc) return rc;
     // the camera as every tptUpdate of the sequence builds it (Test.cpp:309-313, 341)
-    CameraSetup cs = g.camSetup;
-    if (g.config & CFG_MITSUBA_COMPARE) cs.aperture = 0.0f;
-    g.cam = makeCamera(cs, float(w) / float(h));
+    g.cam = viewCamera(g.camSetup, w, h);
+    if (views) g.configEpoch++; // (as every tptSetCamera of the sequence)
     for (int f = 0; f < nFrames; f += perLaunch) {
         const int n = nFrames - f < perLaunch ? nFrames - f : perLaunch;
         BatchTable table;
         f4 centres[2 * kMaxBatch];
+        CameraPOD cams[kMaxBatch];
+        if (views) {
+            // each frame's camera; the context's camera ends at the launch's last view
+            for (int j = 0; j < n; ++j) {
+                g.camSetup = viewSetup(views + 9 * (size_t)(f + j));
+                cams[j] = viewCamera(g.camSetup, w, h);
+                if (outCameras) outCameras[f + j] = cams[j];
+            }
+            g.cam = cams[n - 1];
+            if (perLaunch > 1) {
+                table.cams = cams;
+                if (!animate) { // nothing moves: every frame's centres are the scene's own
+                    const SpherePOD s1 = g.spheres[1], s8 = g.spheres[8];
+                    for (int j = 0; j < n; ++j) {
+                        centres[2 * j] = f4{s1.cx, s1.cy, s1.cz, 0.0f};
+                        centres[2 * j + 1] = f4{s8.cx, s8.cy, s8.cz, 0.0f};
+                    }
+                    table.centres = centres;
+                }
+            }
+        }
         if (animate) {
             // each frame's centres of spheres 1 and 8 exactly as tptUpdate moves them (a non-finite time touches its own frame only); the
             // context's spheres end at the batch's last time
@@ -782,6 +832,46 @@ static int enqueueAnimation(int firstFrame, int nFrames, const float* times, int
             return rc;
     }
     return 0;
+}
+
+// What tptDrawDeviceAnimationMoments and (`cameras`: a view per frame) tptDrawDeviceCameraClip share: the checks, in one order and with
+// the entry point's name, then enqueueAnimation with the planes.  A refused call has touched nothing.
+static int drawClip(const char* name, int firstFrame, int nFrames, const float* times, bool cameras, const float* views, int w, int h,
+                    float* deviceTile, const ClipPlanes& planes, float* deviceFrameImages, int64_t* deviceFrameRays, CameraPOD* outCameras,
+                    unsigned testFlags)
+{
+    const std::string fn = name;
+    float* const deviceMoments = planes.moments;
+    if (int rc_ = flushShardDeferred()) return rc_; // (see tptDrawDevice)
+    if (requireInit()) return -1;
+    if (nFrames < 1) return fail(fn + ": nFrames must be at least 1");
+    if (!times || (cameras && !views) || !deviceTile || !deviceMoments || w <= 0 || h <= 0)
+        return fail(fn + (cameras ? ": bad arguments (times, views, deviceTile, deviceMoments, size)" : ": bad arguments (times, deviceTile, deviceMoments, size)"));
+    const bool animate = (testFlags & TPT_FLAG_ANIMATE) && g.spheres.size() > 8; // (the tptUpdate guard, Test.cpp:304)
+    // one launch per kMaxBatch frames on a flat scene: while it moves, or -- with a camera per frame, where the kernel takes a centres
+    // table anyway -- whenever it has the two spheres the table is about
+    const bool flat = g.spheres.size() < TPT_GROUP_MIN_SPHERES;
+    const int perLaunch = flat && (animate || (cameras && g.spheres.size() > 8)) ? kMaxBatch : 1;
+    int rc = checkPathQueueDraw(fn.c_str(), "clip planes are", w, h, kQueueKernel | kQueueSpp, [&] {
+        const size_t plane = (size_t)h * (size_t)w * sizeof(f4), staged = 2 * plane * (size_t)(nFrames < perLaunch ? nFrames : perLaunch);
+        if (staged > (4ull << 30))
+            return refuse(fn + ": " + std::to_string(staged >> 20) + " MiB of frame colour and moments per launch: over the 4096 MiB limit");
+        if (g.spheres.size() > 65534) return fail(fn + ": at most 65534 spheres (the path-queue kernel)");
+        // the seven buffers, each at its full extent: no two may share a byte
+        const struct { const void* p; size_t bytes; } bufs[7] = {
+            {deviceTile, plane}, {deviceMoments, plane}, {deviceFrameImages, plane * (size_t)nFrames}, {planes.frameAlbedo, plane * (size_t)nFrames},
+            {planes.frameNormalDepth, plane * (size_t)nFrames}, {planes.frameMoments, plane * (size_t)nFrames},
+            {deviceFrameRays, sizeof(int64_t) * (size_t)nFrames}};
+        for (int i = 0; i < 7; ++i)
+            for (int k = i + 1; k < 7; ++k) {
+                const uintptr_t a = reinterpret_cast<uintptr_t>(bufs[i].p), b = reinterpret_cast<uintptr_t>(bufs[k].p);
+                if (a && b && a < b + bufs[k].bytes && b < a + bufs[i].bytes) return fail(fn + ": two of the tile, moments and per-frame buffers overlap");
+            }
+        return 0;
+    });
+    if (rc) return rc;
+    return enqueueAnimation(firstFrame, nFrames, times, w, h, deviceTile, deviceFrameImages, deviceFrameRays, testFlags, animate, perLaunch, &planes,
+                            views, outCameras);
 }
 
 } // namespace tpth
@@ -925,18 +1015,7 @@ int tptDrawDeviceViews(float time, int frameCount, int w, int h, int nViews, con
     if (rc) return rc;
     // the cameras exactly as tptSetCamera + tptUpdate at this size would build them (Test.cpp:309-319, 341)
     CameraPOD cams[kMaxBatch];
-    for (int v = 0; v < nViews; ++v) {
-        const float* p = views + 9 * v;
-        CameraSetup cs = defaultCameraSetup(); // (vup (0, 1, 0))
-        for (int i = 0; i < 3; ++i) {
-            cs.lookFrom[i] = p[i];
-            cs.lookAt[i] = p[3 + i];
-        }
-        cs.vfov = p[6];
-        cs.aperture = (g.config & CFG_MITSUBA_COMPARE) ? 0.0f : p[7]; // Test.cpp:312-313
-        cs.focusDist = p[8];
-        cams[v] = makeCamera(cs, float(w) / float(h));
-    }
+    for (int v = 0; v < nViews; ++v) cams[v] = viewCamera(viewSetup(views + 9 * v), w, h);
     if ((rc = g.pending.discard())) return rc;
     // one launch: the views are the frames of a batch (colour planes nPixels apart in the slot's buffer, a ray counter each)
     TraceTicket T;
@@ -982,33 +1061,23 @@ int tptDrawDeviceAnimationMoments(int firstFrame, int nFrames, const float* time
                                   float* deviceFrameImages, float* deviceFrameAlbedo, float* deviceFrameNormalDepth, float* deviceFrameMoments,
                                   int64_t* deviceFrameRays, unsigned testFlags)
 {
-    const std::string fn = "tptDrawDeviceAnimationMoments";
-    if (int rc_ = flushShardDeferred()) return rc_; // (see tptDrawDevice)
-    if (requireInit()) return -1;
-    if (nFrames < 1) return fail(fn + ": nFrames must be at least 1");
-    if (!times || !deviceTile || !deviceMoments || w <= 0 || h <= 0) return fail(fn + ": bad arguments (times, deviceTile, deviceMoments, size)");
-    const bool animate = (testFlags & TPT_FLAG_ANIMATE) && g.spheres.size() > 8; // (the tptUpdate guard, Test.cpp:304)
-    const int perLaunch = animate && g.spheres.size() < TPT_GROUP_MIN_SPHERES ? kMaxBatch : 1;
-    int rc = checkPathQueueDraw(fn.c_str(), "clip planes are", w, h, kQueueKernel | kQueueSpp, [&] {
-        const size_t plane = (size_t)h * (size_t)w * sizeof(f4), staged = 2 * plane * (size_t)(nFrames < perLaunch ? nFrames : perLaunch);
-        if (staged > (4ull << 30))
-            return refuse(fn + ": " + std::to_string(staged >> 20) + " MiB of frame colour and moments per launch: over the 4096 MiB limit");
-        if (g.spheres.size() > 65534) return fail(fn + ": at most 65534 spheres (the path-queue kernel)");
-        // the seven buffers, each at its full extent: no two may share a byte
-        const struct { const void* p; size_t bytes; } bufs[7] = {
-            {deviceTile, plane}, {deviceMoments, plane}, {deviceFrameImages, plane * (size_t)nFrames}, {deviceFrameAlbedo, plane * (size_t)nFrames},
-            {deviceFrameNormalDepth, plane * (size_t)nFrames}, {deviceFrameMoments, plane * (size_t)nFrames},
-            {deviceFrameRays, sizeof(int64_t) * (size_t)nFrames}};
-        for (int i = 0; i < 7; ++i)
-            for (int k = i + 1; k < 7; ++k) {
-                const uintptr_t a = reinterpret_cast<uintptr_t>(bufs[i].p), b = reinterpret_cast<uintptr_t>(bufs[k].p);
-                if (a && b && a < b + bufs[k].bytes && b < a + bufs[i].bytes) return fail(fn + ": two of the tile, moments and per-frame buffers overlap");
-            }
-        return 0;
-    });
-    if (rc) return rc;
     const ClipPlanes planes{deviceMoments, deviceFrameAlbedo, deviceFrameNormalDepth, deviceFrameMoments};
-    return enqueueAnimation(firstFrame, nFrames, times, w, h, deviceTile, deviceFrameImages, deviceFrameRays, testFlags, animate, perLaunch, &planes);
+    return drawClip("tptDrawDeviceAnimationMoments", firstFrame, nFrames, times, false, nullptr, w, h, deviceTile, planes, deviceFrameImages,
+                    deviceFrameRays, nullptr, testFlags);
+}
+
+// tptDrawDeviceAnimationMoments with a camera per frame: frame j as tptSetCamera(views[j]), tptUpdate(times[j], firstFrame + j, ...) and
+// tptDrawDeviceMoments trace it -- the same bits, the same ray counts --, its Camera record written to outCameras[j] at call time.  Up to
+// kMaxBatch frames per launch (tptCameraClipKernel: the cameras beside the centres table) on a flat scene of more than 8 spheres, whether
+// it moves or not; smaller and grouped scenes go frame by frame through the single-frame moments kernel with the camera set per frame.
+// The context is left as the sequence leaves it: the camera set-up of the last view, the spheres at the last time.
+int tptDrawDeviceCameraClip(int firstFrame, int nFrames, const float* times, const float* views, int w, int h, float* deviceTile,
+                            float* deviceMoments, float* deviceFrameImages, float* deviceFrameAlbedo, float* deviceFrameNormalDepth,
+                            float* deviceFrameMoments, int64_t* deviceFrameRays, void* outCameras, unsigned testFlags)
+{
+    const ClipPlanes planes{deviceMoments, deviceFrameAlbedo, deviceFrameNormalDepth, deviceFrameMoments};
+    return drawClip("tptDrawDeviceCameraClip", firstFrame, nFrames, times, true, views, w, h, deviceTile, planes, deviceFrameImages,
+                    deviceFrameRays, static_cast<CameraPOD*>(outCameras), testFlags);
 }
 
 // One frame blended into the tile exactly as tptDrawDevice blends it (same bits, same ray count), plus the first-hit planes of its

@@ -1440,7 +1440,11 @@ __device__ __forceinline__ int hitSpheresGroupedDeal(const SceneView& sv, bool g
 // claims the pixel (clamped to 0 .. 2047; 0: the pixel is finished at once, like a padding slot of a partially covered tile) and is
 // kept in .z of the path's third f4 of sums; the means are the sums x 1 / count, a correctly rounded quotient made when the pixel ends.
 // Its own kernel (tptTraceAdaptiveKernel) for the same reason.
-template <bool LDS_SCENE, bool BATCH, bool VIEWS = false, bool MOVING = false, bool AOV = false, bool MOMENTS = false, bool ADAPTIVE = false>
+// CAMERAS (with BATCH + MOVING + AOV + MOMENTS; tptDrawDeviceCameraClip): the clip kernel with a camera per frame -- a.viewCams[j] staged
+// in LDS beside the centres, read where a sample starts like a view's; the seeds stay those of frame fc.frame + j (MOVING's rule, not
+// VIEWS'), and everything else is the clip kernel's.  Its own kernel (tptCameraClipKernel) for the same reason.
+template <bool LDS_SCENE, bool BATCH, bool VIEWS = false, bool MOVING = false, bool AOV = false, bool MOMENTS = false, bool ADAPTIVE = false,
+          bool CAMERAS = false>
 __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1453,7 +1457,9 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     static_assert(!AOV || !BATCH || (MOVING && MOMENTS), "first-hit planes are made by single-frame launches, or beside the moments of an animated clip's frames");
     static_assert(!MOMENTS || AOV, "moments are summed beside the first-hit sums");
     static_assert(!ADAPTIVE || (MOMENTS && !BATCH), "a count per pixel belongs to a single frame with its moments");
-    constexpr int kPaths = (LDS_SCENE ? TPT_Q_PATHS : TPT_Q_PATHS_GROUPED) - (VIEWS ? TPT_Q_VIEW_PATHS : 0) -
+    static_assert(!CAMERAS || (BATCH && MOVING && AOV && MOMENTS && !VIEWS && !ADAPTIVE), "a camera per frame belongs to the frames of a clip with their planes");
+    constexpr bool CAM_TABLE = VIEWS || CAMERAS; // (the cameras of the batch's frames in LDS)
+    constexpr int kPaths = (LDS_SCENE ? TPT_Q_PATHS : TPT_Q_PATHS_GROUPED) - (CAM_TABLE ? TPT_Q_VIEW_PATHS : 0) -
                            (MOVING ? TPT_Q_ANIM_PATHS : 0); // paths this workgroup owns
     constexpr int kOffSt = LDS_SCENE ? TPT_Q_SPH_FIXED : 0;
     constexpr int kOffQ = kOffSt + TPT_Q_NF4 * kPaths * 16;
@@ -1462,7 +1468,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     constexpr int kDealBytes = (!LDS_SCENE && TPT_GROUP_DEAL) ? TPT_Q_WAVES * TPT_GROUP_DEAL_WAVE_BYTES : 0; // pair lists of the grouped traversal
     constexpr int kOffFc = kOffDeal + kDealBytes;
     constexpr int kOffCams = kOffFc + (((int)sizeof(FrameConsts) + 15) & ~15);
-    constexpr int kOffMoved = kOffCams + (VIEWS ? TPT_Q_VIEW_CAM_BYTES : 0);
+    constexpr int kOffMoved = kOffCams + (CAM_TABLE ? TPT_Q_VIEW_CAM_BYTES : 0);
     constexpr int kOffScene = kOffMoved + (MOVING ? TPT_Q_ANIM_TABLE_BYTES : 0);
     f4* st = reinterpret_cast<f4*>(smem + kOffSt);
     LdsRing q = (LdsRing)(smem + kOffQ);
@@ -1470,7 +1476,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     // the frame constants the camera code reads (22 camera floats, 1/w, 1/h): in LDS, read where a sample starts, instead of
     // ~30 SGPRs held (and spilled) across the whole loop
     FrameConsts* ldsFc = reinterpret_cast<FrameConsts*>(smem + kOffFc);
-    CameraPOD* ldsCams = reinterpret_cast<CameraPOD*>(smem + kOffCams); // (VIEWS: the cameras of the batch's views)
+    CameraPOD* ldsCams = reinterpret_cast<CameraPOD*>(smem + kOffCams); // (VIEWS, CAMERAS: the cameras of the batch's views / frames)
     f4* ldsMoved = reinterpret_cast<f4*>(smem + kOffMoved);              // (MOVING: the centres of spheres 1 and 8, two per frame)
     const LdsMovedPtr movedLds = (LdsMovedPtr)ldsMoved;                  // (... as the readers take them)
     const int nPad = a.scene.nPairs * 2;
@@ -1543,7 +1549,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
 #endif
 #endif
     for (int i = tid; i < (int)(sizeof(FrameConsts) / 4); i += TPT_Q_T) reinterpret_cast<uint32_t*>(ldsFc)[i] = reinterpret_cast<const uint32_t*>(&a.fc)[i];
-    if (VIEWS)
+    if (CAM_TABLE)
         for (int i = tid; i < a.batchFrames * (int)(sizeof(CameraPOD) / 4); i += TPT_Q_T)
             reinterpret_cast<uint32_t*>(ldsCams)[i] = reinterpret_cast<const uint32_t*>(a.viewCams)[i];
     if (MOVING)
@@ -1761,7 +1767,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                 if (AOV) aovSum()[0] = aovSum()[1] = mk4(0.0f, 0.0f, 0.0f, 0.0f);
                 if (MOMENTS) aovSum()[2] = mk4(0.0f, 0.0f, ADAPTIVE ? u2f(laneCount) : 0.0f, 0.0f);
                 if (MOVING) movedAt = 2 * laneFrame;
-                if (VIEWS)
+                if (CAM_TABLE)
                     qCameraView(ldsCams[laneFrame], *ldsFc, px, py, rng, ro, rd);
                 else
                     qCamera(*ldsFc, px, py, rng, ro, rd);
@@ -1796,7 +1802,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                 if (sample < (ADAPTIVE ? (int)f2u(mom.z) : fc.spp)) {
                     colSum[p] = mk4(col.x, col.y, col.z, c3.w);
                     if (MOMENTS) aovSum()[2] = mom;
-                    if (VIEWS)
+                    if (CAM_TABLE)
                         qCameraView(ldsCams[f2u(c3.w) >> 26], *ldsFc, px, py, rng, ro, rd);
                     else
                         qCamera(*ldsFc, px, py, rng, ro, rd);
@@ -2065,21 +2071,21 @@ tptTraceQueueKernel<false, true>(const KernelArgs a)
 // The variants of traceQueueBody beyond <LDS_SCENE, BATCH>, from one list.  Each is a kernel of its own, not another template argument of
 // tptTraceQueueKernel: names and code of the existing kernels stay (tests look them up by name).  <false>: no scene in LDS -- grouped scenes
 // and flat scenes whose arrays stay in global memory (the moving variants take flat scenes only) --, with the grouped register cap.
-enum { QF_BATCH = 1, QF_VIEWS = 2, QF_MOVING = 4, QF_AOV = 8, QF_MOMENTS = 16, QF_ADAPTIVE = 32 };
+enum { QF_BATCH = 1, QF_VIEWS = 2, QF_MOVING = 4, QF_AOV = 8, QF_MOMENTS = 16, QF_ADAPTIVE = 32, QF_CAMERAS = 64 };
 #define TPT_QUEUE_VARIANT_KERNEL(NAME, F)                                                                                                    \
     template <bool LDS_SCENE>                                                                                                                \
     __global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute__((amdgpu_num_vgpr(TPT_Q_MAX_VGPR)))                    \
     NAME(const KernelArgs a)                                                                                                                 \
     {                                                                                                                                        \
         traceQueueBody<LDS_SCENE, ((F) & QF_BATCH) != 0, ((F) & QF_VIEWS) != 0, ((F) & QF_MOVING) != 0, ((F) & QF_AOV) != 0, ((F) & QF_MOMENTS) != 0, \
-                       ((F) & QF_ADAPTIVE) != 0>(a);                                                                                         \
+                       ((F) & QF_ADAPTIVE) != 0, ((F) & QF_CAMERAS) != 0>(a);                                                                \
     }                                                                                                                                        \
     template <>                                                                                                                              \
     __global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute__((amdgpu_num_vgpr(TPT_Q_MAX_VGPR_GROUPED)))            \
     NAME<false>(const KernelArgs a)                                                                                                          \
     {                                                                                                                                        \
         traceQueueBody<false, ((F) & QF_BATCH) != 0, ((F) & QF_VIEWS) != 0, ((F) & QF_MOVING) != 0, ((F) & QF_AOV) != 0, ((F) & QF_MOMENTS) != 0, \
-                       ((F) & QF_ADAPTIVE) != 0>(a);                                                                                         \
+                       ((F) & QF_ADAPTIVE) != 0, ((F) & QF_CAMERAS) != 0>(a);                                                                \
     }
 TPT_QUEUE_VARIANT_KERNEL(tptTraceViewsKernel, QF_BATCH | QF_VIEWS)                           // tptDrawDeviceViews: several views of one frame, a camera per frame of the batch
 TPT_QUEUE_VARIANT_KERNEL(tptTraceAnimationKernel, QF_BATCH | QF_MOVING)                      // tptDrawDeviceAnimation: frames of an animated scene, spheres 1 and 8 where each frame has them
@@ -2087,6 +2093,7 @@ TPT_QUEUE_VARIANT_KERNEL(tptTraceAovKernel, QF_AOV)                             
 TPT_QUEUE_VARIANT_KERNEL(tptTraceMomentsKernel, QF_AOV | QF_MOMENTS)                         // tptDrawDeviceMoments: the AOV kernel plus a third f4 of sums per path, the luminance moments
 TPT_QUEUE_VARIANT_KERNEL(tptTraceClipKernel, QF_BATCH | QF_MOVING | QF_AOV | QF_MOMENTS)     // tptDrawDeviceAnimationMoments: the animation kernel plus the moments kernel's per-path sums
 TPT_QUEUE_VARIANT_KERNEL(tptTraceAdaptiveKernel, QF_AOV | QF_MOMENTS | QF_ADAPTIVE)             // tptDrawDeviceAdaptive: the moments kernel with each pixel's sample count from a plane
+TPT_QUEUE_VARIANT_KERNEL(tptCameraClipKernel, QF_BATCH | QF_MOVING | QF_AOV | QF_MOMENTS | QF_CAMERAS) // tptDrawDeviceCameraClip: the clip kernel with a camera per frame (not "tptTrace...": tests count those names)
 #undef TPT_QUEUE_VARIANT_KERNEL
 
 #if defined(TPT_TEST_HOOKS)
@@ -2355,6 +2362,7 @@ hipError_t tptLaunchTraceQueue(const KernelArgs& a, bool ldsScene, int blocks, s
         /* QV_MOMENTS   */ {tptTraceMomentsKernel<false>, tptTraceMomentsKernel<true>},
         /* QV_CLIP      */ {tptTraceClipKernel<false>, tptTraceClipKernel<true>},
         /* QV_ADAPTIVE  */ {tptTraceAdaptiveKernel<false>, tptTraceAdaptiveKernel<true>},
+        /* QV_CAMERA_CLIP */ {tptCameraClipKernel<false>, tptCameraClipKernel<true>},
     };
     const QueueVariant variant = tptQueueVariant(a);
     if (variant == QV_INVALID) return hipErrorInvalidValue;

@@ -79,6 +79,7 @@ static_assert(TPT_GROUP_DEAL_ENTRIES >= TPT_GROUP_DEAL_CAP, "the flat variants' 
 // in the place of 16 path records (16 x 64 B): the same LDS per launch as the single-frame twin, as for the views.
 #define TPT_Q_ANIM_TABLE_BYTES (TPT_Q_VIEWS_MAX * 2 * 16)
 #define TPT_Q_ANIM_PATHS ((TPT_Q_ANIM_TABLE_BYTES + TPT_Q_NF4 * 16 - 1) / (TPT_Q_NF4 * 16))
+// A camera per frame of a clip (tptCameraClipKernel): both tables, in the place of TPT_Q_VIEW_PATHS + TPT_Q_ANIM_PATHS path records.
 #ifndef TPT_Q_PATHS_GROUPED
 // ... and of the instantiation for GROUPED scenes (no scene staging, no matrix-filter table): 608.  The LDS the smaller pool frees holds
 // the entry areas of the three-stage dealing (640 entries per wave) and the groups' bounding spheres (pair records, 144 B per super-group
@@ -148,12 +149,16 @@ TPT_HD int globalRowToLocal(const KernelArgs& a, int gy) { return shardKernelGlo
 
 // Which variant of the path-queue kernel a launch takes: what its argument block holds decides, here and nowhere else.  QV_INVALID: a
 // combination no entry point builds (tptLaunchTraceQueue refuses it).
-enum QueueVariant { QV_FRAME, QV_BATCH, QV_VIEWS, QV_ANIMATION, QV_AOV, QV_MOMENTS, QV_CLIP, QV_ADAPTIVE, QV_INVALID };
+enum QueueVariant { QV_FRAME, QV_BATCH, QV_VIEWS, QV_ANIMATION, QV_AOV, QV_MOMENTS, QV_CLIP, QV_ADAPTIVE, QV_CAMERA_CLIP, QV_INVALID };
 inline QueueVariant tptQueueVariant(const tpt::KernelArgs& a)
 {
     if (a.sampleCounts) { // (tptDrawDeviceAdaptive: a single frame with its planes and moments, a sample count per pixel)
         if (a.batchFrames != 1 || a.viewCams || a.moveCentres || !a.aovSums || !a.momentsOut) return QV_INVALID;
         return QV_ADAPTIVE;
+    }
+    if (a.viewCams && a.moveCentres) { // (tptDrawDeviceCameraClip: 1 .. TPT_Q_VIEWS_MAX frames of the batch with their planes, a camera and the centres per frame, a flat scene)
+        if (a.batchFrames < 1 || a.batchFrames > TPT_Q_VIEWS_MAX || a.scene.nGroups > 0 || !a.aovSums || !a.momentsOut) return QV_INVALID;
+        return QV_CAMERA_CLIP;
     }
     if (a.viewCams) { // (tptDrawDeviceViews: 1 .. TPT_Q_VIEWS_MAX views, the frames of the batch)
         if (a.batchFrames < 1 || a.batchFrames > TPT_Q_VIEWS_MAX) return QV_INVALID;
@@ -189,10 +194,11 @@ inline size_t tptQueueLdsBytes(const tpt::KernelArgs& a, bool ldsScene)
     using namespace tpt;
     const int nPad = a.scene.nPairs * 2;
     const QueueVariant variant = tptQueueVariant(a);
-    const bool views = variant == QV_VIEWS; // (tptTraceViewsKernel: the cameras in LDS, TPT_Q_VIEW_PATHS path records fewer)
-    const bool moving = variant == QV_ANIMATION || variant == QV_CLIP; // (tptTraceAnimationKernel: the centres in LDS, TPT_Q_ANIM_PATHS path records fewer)
+    const bool views = variant == QV_VIEWS || variant == QV_CAMERA_CLIP; // (tptTraceViewsKernel: the cameras in LDS, TPT_Q_VIEW_PATHS path records fewer)
+    const bool moving = variant == QV_ANIMATION || variant == QV_CLIP || variant == QV_CAMERA_CLIP; // (tptTraceAnimationKernel: the centres in LDS, TPT_Q_ANIM_PATHS path records fewer)
+    // (tptCameraClipKernel: both tables, in the place of both shares of path records)
     // (tptTraceAovKernel, tptTraceMomentsKernel, tptTraceAdaptiveKernel and tptTraceClipKernel, a.aovSums: the LDS of their twin without
-    //  planes -- their sums live in global memory)
+    //  planes -- their sums live in global memory; tptCameraClipKernel likewise)
     size_t bytes = 0;
     if (ldsScene) bytes += TPT_Q_SPH_FIXED + ((size_t)nPad * 16 <= TPT_Q_SPH_FIXED ? 0 : (size_t)nPad * 16) + (((size_t)nPad * 4 + 15) & ~(size_t)15) + (size_t)a.scene.nSpheres * 48;
     bytes += (size_t)a.scene.nLights * 32;
