@@ -320,7 +320,7 @@ TPT_API int tptDenoiseDeviceVariance(int screenWidth, int screenHeight, const fl
  * so the filter's v_0 becomes variance / (spp * N) per pixel -- a freshly disoccluded pixel is filtered as the one-frame pixel it is.
  * The filter's other inputs are deviceOutColour, deviceOutAlbedo and this frame's normal / depth plane.  The coverage test keeps a
  * silhouette pixel from inheriting a fully covered neighbour's history.  Objects that move are not followed: their
- * points are reprojected as if they stood still, and the depth and normal tests decide.
+ * points are reprojected as if they stood still, and the depth and normal tests decide (tptTemporalAccumulateObjectsDevice below follows them).
  * Asynchronous on the context stream; needs tptInitialize only and leaves every other state alone.  The inputs are never written.
  * Refused (non-zero, tptGetLastError, nothing enqueued, no output written): no context; w or h outside 1..8192; camera NULL; a current
  * plane or an output NULL; the prev planes and prevCamera neither all NULL nor all given; an output overlapping an input or another
@@ -333,6 +333,64 @@ TPT_API int tptTemporalAccumulateDevice(int screenWidth, int screenHeight, const
                                         const float* devicePrevNormalDepth, const float* devicePrevMoments, float* deviceOutColour,
                                         float* deviceOutAlbedo, float* deviceOutMoments, float* deviceOutVariance, float maxHistory,
                                         float depthTolerance, float normalTolerance, float coverageTolerance);
+/* THE OBJECT PLANE: which sphere each pixel sees first, for nFrames frames.  deviceFrameObjects (required): nFrames consecutive DEVICE
+ * planes of h*w int32, row-major like the tile (row 0 at the bottom).  cameras: HOST memory, nFrames x 88-byte Camera records
+ * (tptDrawDeviceCameraClip's outCameras, or tptGetSceneDesc's outCam), or NULL: the camera of the last tptUpdate for every frame, and
+ * w x h must then be that update's size.  times: HOST memory, nFrames floats, or NULL.
+ * The scene of frame j is the context's scene as of the last tptUpdate; when times is given, TPT_FLAG_ANIMATE is set and the scene has
+ * more than 8 spheres, spheres 1 and 8 stand where tptUpdate(times[j], ...) puts them (centre 1's y = cosf(t) + 1.0f, centre 8's
+ * z = sinf(t) * 0.3f, the same bits).  The context's own spheres are not moved.  A non-finite time affects its own frame only.
+ * (More exactly the scene is what the context last staged for a launch: tptDrawDeviceAnimation, tptDrawDeviceAnimationMoments and
+ * tptDrawDeviceCameraClip stage their last frame's scene, and leave the context's spheres there, as the tptUpdate calls they stand for
+ * would.  It shows only when times is NULL: after such a clip the plane is that of the clip's last frame.)
+ * Binary32, in the order written, no FMA; correctly rounded division and square root; dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.  Per
+ * pixel (x, y) of frame j, with o, ll, H, V the camera's origin, lowerLeftCorner, horizontal and vertical:
+ *   s = (x + 0.5f) / width;  t = (y + 0.5f) / height;  v = ((ll + s*H) + t*V) - o;  dir = v * (1.0f / sqrt(dot(v, v)))
+ *   (step 1 of tptTemporalAccumulateDevice: the ray through the pixel's centre and the lens centre, whatever spp is)
+ *   id = HitWorld({o, dir}, 0.001f, 1e7f) in the reference's arithmetic and order (Maths.cpp:165-202): every sphere in index order, the
+ *   nearest hit wins and equal distances go to the lowest index.  The plane receives id, or -1 for a miss.
+ * An id cannot be averaged over samples: a silhouette pixel carries the id of its centre ray, whatever its coverage says.
+ * Asynchronous on the context stream, ordered like tptDenoiseDevice; one launch per frame, the exact test for every sphere (grouped
+ * scenes too: DESIGN.md 3.12 has the cost).  Leaves every context state alone: frames traced ahead and stream batches are kept,
+ * camera and scene are unchanged.
+ * Refused (non-zero, tptGetLastError names the function, nothing enqueued, nothing written): no context; no tptUpdate yet; nFrames
+ * outside 1..4096; w or h outside 1..8192; deviceFrameObjects NULL; cameras NULL with a size other than the last update's; a camera
+ * with a non-finite field in origin, lowerLeftCorner, horizontal or vertical; a flag bit other than the two TPT_FLAG_*. */
+TPT_API int tptObjectPlaneDevice(int nFrames, const float* times, const void* cameras, int screenWidth, int screenHeight,
+                                 int32_t* deviceFrameObjects, unsigned testFlags);
+/* The animated scene's displacement per sphere between two times, for tptTemporalAccumulateObjectsDevice's table.  Host arithmetic only.
+ * outTable: HOST memory, count x 4 floats, count = tptGetObjectCount's.  Entry i = {prevCentre_i - centre_i, 0} under tptUpdate's
+ * animation rule: all zero, except that with TPT_FLAG_ANIMATE and more than 8 spheres
+ *   entry 1's .y = (cosf(prevTime) + 1.0f) - (cosf(time) + 1.0f)      entry 8's .z = sinf(prevTime) * 0.3f - sinf(time) * 0.3f
+ * (the two centres as tptUpdate computes them, then one subtraction).  The .w (the history cap) is 0: the caller sets caps, and uploads
+ * the table.  Needs tptInitialize only; no GPU work, no state change.  Refused: no context; outTable NULL; capacity < count. */
+TPT_API int tptObjectMotionTable(float time, float prevTime, unsigned testFlags, float* outTable, int capacity);
+/* TEMPORAL ACCUMULATION THAT FOLLOWS OBJECTS: tptTemporalAccumulateDevice with the object planes of both frames and a table of what
+ * each object did in between.  The first twenty parameters are tptTemporalAccumulateDevice's.  deviceObject (required): h*w int32, this
+ * frame's object plane (tptObjectPlaneDevice).  devicePrevObject: the previous frame's plane, NULL exactly when prevCamera and the prev
+ * planes are NULL.  deviceObjectMotion: DEVICE memory, nObjects x 4 floats, entry i = m_i = {where object i's points stood in the previous
+ * frame minus where they stand now, m.w = the longest history a pixel of that object may carry; 0: no cap}; NULL with nObjects == 0:
+ * nothing moves and nothing is capped.  The statement is tptTemporalAccumulateDevice's, with three changes:
+ *   1. id = object[p].  If c > 0, the table is given and 0 <= id < nObjects:  m = motion[id]  and  rel = ((o + dir*d) + m.xyz) - o'.
+ *      In every other case no entry is read and rel is exactly the plain pass's (nothing is added, so no zero changes its sign).
+ *   4. a tap additionally counts only if prevObject[tap] == id -- one rule for hits, misses (-1) and silhouette pixels whose centre ray
+ *      misses.  The depth test keeps its form: e = sqrt(dot(rel, rel)) is now the distance of the MOVED point from the previous
+ *      camera.  The normal test is unchanged: spheres only translate.
+ *   5. after N = histN + 1, maxHistory if that is smaller:  if m was read and m.w >= 1 and m.w < N, then N = m.w;  then the lerp as before.
+ *      (A cap of 1 leaves a mirror or a glass sphere, whose reflections do not move with its surface, this frame's values alone.)
+ * With the table NULL the pass differs from the plain one by the id test alone.  Ordering and state are tptTemporalAccumulateDevice's;
+ * the inputs are never written.
+ * Refused (non-zero, tptGetLastError names the function, nothing enqueued, no output written): everything tptTemporalAccumulateDevice
+ * refuses; deviceObject NULL; devicePrevObject given without the prev planes or NULL with them; nObjects < 0 or > 65534; exactly one of
+ * deviceObjectMotion and nObjects set; an output overlapping an object plane or the table, each taken at its full extent. */
+TPT_API int tptTemporalAccumulateObjectsDevice(int screenWidth, int screenHeight, const void* camera, const void* prevCamera,
+                                               const float* deviceColour, const float* deviceAlbedo, const float* deviceNormalDepth,
+                                               const float* deviceMoments, const float* devicePrevColour, const float* devicePrevAlbedo,
+                                               const float* devicePrevNormalDepth, const float* devicePrevMoments, float* deviceOutColour,
+                                               float* deviceOutAlbedo, float* deviceOutMoments, float* deviceOutVariance, float maxHistory,
+                                               float depthTolerance, float normalTolerance, float coverageTolerance,
+                                               const int32_t* deviceObject, const int32_t* devicePrevObject,
+                                               const float* deviceObjectMotion, int nObjects);
 /* ADAPTIVE SAMPLING: tptDrawDeviceMoments with a sample count per pixel, so that the moments can steer the next pass (the counts come
  * from tptAdaptiveSamplesDevice below, or from the caller).  deviceSampleCounts (required): h*w int32 in DEVICE memory, row-major like the
  * tile, read by the kernels only.  Per pixel p, n = deviceSampleCounts[p] clamped to 0 .. 2047 (the path record holds 11 bits of sample

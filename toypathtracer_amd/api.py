@@ -39,7 +39,7 @@ C_ABI_SYMBOLS = [
     "tptSetSamplesPerPixel", "tptSetConfig", "tptSetSeedMode", "tptSetFoldMode", "tptSetScene", "tptSetCamera", "tptSetStream",
     "tptSetRowShard", "tptLocalRowCount", "tptLocalRowToGlobal", "tptDrawDevice", "tptRayCounterRead", "tptSetRayCounter", "tptSetFrameOverlap", "tptDisplayRGBA8", "tptKernelTimingBegin", "tptKernelTimingEnd",
     "tptSynchronize", "tptTimerBegin", "tptTimerEnd", "tptSetKernelVariant",
-    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceAnimationMoments", "tptDrawDeviceCameraClip", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptDrawDeviceAdaptive", "tptAdaptiveSamplesDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
+    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceAnimationMoments", "tptDrawDeviceCameraClip", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptObjectPlaneDevice", "tptObjectMotionTable", "tptTemporalAccumulateObjectsDevice", "tptDrawDeviceAdaptive", "tptAdaptiveSamplesDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
 ]
 # include/tpt_test_hooks.h: exported by the second build (libtoypathtracer_hip_hooks.so) only
 HOOK_SYMBOLS = ["tptTestMath", "tptTestMathExhaustive", "tptTestHitSpheres", "tptTestMatrixFilter", "tptTestGroupFilter", "tptTestSetDealCapacities", "tptDebugStats", "tptDebugChunkOrder"]
@@ -78,7 +78,7 @@ def _bind(path, hooks):
         "tptSetRayCounter": [p], "tptSetTileMirror": [p, p], "tptSetFrameOverlap": [i], "tptDisplayRGBA8": [p, i, i, p], "tptKernelTimingBegin": [i],
         "tptKernelTimingEnd": [C.POINTER(f), C.POINTER(i)],
         "tptSynchronize": [], "tptTimerBegin": [], "tptTimerEnd": [C.POINTER(f)], "tptSetKernelVariant": [i, i, i],
-        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDrawDeviceAnimationMoments": [i, i, p, i, i] + [p] * 7 + [u], "tptDrawDeviceCameraClip": [i, i, p, p, i, i] + [p] * 8 + [u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptDrawDeviceAdaptive": [f, i, i, i, p, p, p, p, p, u], "tptAdaptiveSamplesDevice": [i, i, p, f, i, i, p, p, p], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
+        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDrawDeviceAnimationMoments": [i, i, p, i, i] + [p] * 7 + [u], "tptDrawDeviceCameraClip": [i, i, p, p, i, i] + [p] * 8 + [u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptObjectPlaneDevice": [i, p, p, i, i, p, u], "tptObjectMotionTable": [f, f, u, p, i], "tptTemporalAccumulateObjectsDevice": [i, i] + [p] * 14 + [f] * 4 + [p, p, p, i], "tptDrawDeviceAdaptive": [f, i, i, i, p, p, p, p, p, u], "tptAdaptiveSamplesDevice": [i, i, p, f, i, i, p, p, p], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
     }
     if hooks:
         sigs.update({"tptDebugStats": [p, i], "tptDebugChunkOrder": [p, p, i], "tptTestMath": [i, p, p, p, i], "tptTestMathExhaustive": [i, u, u, p, p],
@@ -650,6 +650,127 @@ def temporal_accumulate_device(w, h, camera, colour_ptr, albedo_ptr, normal_dept
                                                     C.c_void_p(out_colour_ptr), C.c_void_p(out_albedo_ptr), C.c_void_p(out_moments_ptr),
                                                     C.c_void_p(out_variance_ptr), max_history, depth_tolerance, normal_tolerance,
                                                     coverage_tolerance), "tptTemporalAccumulateDevice")
+
+
+OBJECT_PLANE_MAX_FRAMES = 4096  # include/tpt_hip.h: tptObjectPlaneDevice's nFrames
+OBJECT_MOTION_MAX_OBJECTS = 65534  # include/tpt_hip.h: tptTemporalAccumulateObjectsDevice's nObjects
+
+
+def object_plane_device(w, h, objects_ptr, flags=0, times=None, cameras=None, frames=None):
+    """tptObjectPlaneDevice: the index of the first sphere the ray through each pixel's centre meets (-1: none) into objects_ptr, a
+    device buffer of N consecutive planes of h*w int32.  cameras: None (the camera of the last UpdateTest for every frame, whose size
+    w x h must be) or a CAMERA_DT array of N records (draw_device_camera_clip's result, GetSceneDesc()[2]).  times: None or N floats;
+    with kFlagAnimate spheres 1 and 8 of frame j stand where UpdateTest(times[j]) puts them.  N is len(cameras), len(times) or
+    `frames` (default 1); what is given must agree.  The context is left as it is.  Ordered on the context's stream."""
+    _positive_ints(("w", w), ("h", h))
+    _pointers(("objects_ptr", objects_ptr))
+    if not objects_ptr:
+        raise ValueError("objects_ptr: a device buffer is required")
+    if not isinstance(flags, (int, np.integer)) or isinstance(flags, bool) or flags & ~(kFlagAnimate | kFlagProgressive):
+        raise ValueError("flags: kFlagAnimate | kFlagProgressive bits expected, got %r" % (flags,))
+    counts = []
+    t = c = None
+    if times is not None:
+        t = np.ascontiguousarray(times, dtype=np.float32)
+        if t.ndim != 1:
+            raise ValueError("times: a 1-D sequence expected, got shape %r" % (t.shape,))
+        counts.append(t.shape[0])
+    if cameras is not None:
+        if not isinstance(cameras, np.ndarray) or cameras.dtype != CAMERA_DT or cameras.ndim != 1:
+            raise ValueError("cameras: a 1-D CAMERA_DT array expected, got %r" % (cameras,))
+        c = np.ascontiguousarray(cameras)
+        counts.append(c.shape[0])
+    if frames is not None:
+        _positive_ints(("frames", frames))
+        counts.append(frames)
+    n = counts[0] if counts else 1
+    if any(k != n for k in counts):
+        raise ValueError("times, cameras, frames: one frame count expected, got %r" % (counts,))
+    if not 1 <= n <= OBJECT_PLANE_MAX_FRAMES:
+        raise ValueError("frames: 1..%d expected, got %d" % (OBJECT_PLANE_MAX_FRAMES, n))
+    _chk(load_library().tptObjectPlaneDevice(n, t.ctypes.data if t is not None else None, c.ctypes.data if c is not None else None, w, h,
+                                             C.c_void_p(objects_ptr), flags), "tptObjectPlaneDevice")
+
+
+def object_motion_table(time, prev_time, flags):
+    """tptObjectMotionTable: float32 (count, 4), entry i = {where sphere i stood at prev_time minus where it stands at time, 0} under
+    UpdateTest's animation rule (kFlagAnimate: spheres 1 and 8; zero otherwise).  Set .w (the history caps) and upload it for
+    temporal_accumulate_objects_device."""
+    for name, v in (("time", time), ("prev_time", prev_time)):
+        if not isinstance(v, (int, float, np.integer, np.floating)) or isinstance(v, bool):
+            raise ValueError("%s: a number expected, got %r" % (name, v))
+    if not isinstance(flags, (int, np.integer)) or isinstance(flags, bool) or flags < 0:
+        raise ValueError("flags: an int >= 0 expected, got %r" % (flags,))
+    n = GetObjectCount()[0]
+    table = np.zeros((n, 4), np.float32)
+    _chk(load_library().tptObjectMotionTable(time, prev_time, flags, table.ctypes.data, n), "tptObjectMotionTable")
+    return table
+
+
+def motion_table(prev_spheres, cur_spheres, caps=None):
+    """The table of temporal_accumulate_objects_device for a caller who moves spheres with set_scene: two GetSceneDesc sphere arrays
+    (SPHERE_DT, the same length) -> float32 (count, 4), .xyz = previous centre minus current centre (one float32 subtraction each),
+    .w = caps (None: 0, no cap; a number, or one per sphere)."""
+    for name, s in (("prev_spheres", prev_spheres), ("cur_spheres", cur_spheres)):
+        if not isinstance(s, np.ndarray) or s.dtype != SPHERE_DT or s.ndim != 1:
+            raise ValueError("%s: a 1-D SPHERE_DT array expected, got %r" % (name, s))
+    if prev_spheres.shape != cur_spheres.shape:
+        raise ValueError("prev_spheres, cur_spheres: the same length expected, got %d and %d" % (len(prev_spheres), len(cur_spheres)))
+    table = np.zeros((len(cur_spheres), 4), np.float32)
+    for k, field in enumerate(("cx", "cy", "cz")):
+        table[:, k] = prev_spheres[field] - cur_spheres[field]
+    if caps is not None:
+        w = np.asarray(caps, dtype=np.float32)
+        if w.ndim > 1 or (w.ndim == 1 and w.shape[0] != len(cur_spheres)) or not np.all(w >= 0):
+            raise ValueError("caps: a number >= 0 or one per sphere expected, got %r" % (caps,))
+        table[:, 3] = w
+    return table
+
+
+def temporal_accumulate_objects_device(w, h, camera, colour_ptr, albedo_ptr, normal_depth_ptr, moments_ptr, object_ptr, out_colour_ptr,
+                                       out_albedo_ptr, out_moments_ptr, out_variance_ptr, prev=None, motion_ptr=None, n_objects=0,
+                                       max_history=TEMPORAL_DEFAULTS["max_history"],
+                                       depth_tolerance=TEMPORAL_DEFAULTS["depth_tolerance"],
+                                       normal_tolerance=TEMPORAL_DEFAULTS["normal_tolerance"],
+                                       coverage_tolerance=TEMPORAL_DEFAULTS["coverage_tolerance"]):
+    """tptTemporalAccumulateObjectsDevice: temporal_accumulate_device that follows objects.  object_ptr: this frame's object plane
+    (object_plane_device; h*w int32).  prev: None for the first frame, else (camera, colour_ptr, albedo_ptr, normal_depth_ptr,
+    moments_ptr, object_ptr) of the previous frame.  motion_ptr: None (nothing moves, nothing is capped; n_objects 0) or a device buffer
+    of n_objects x 4 floats (object_motion_table / motion_table, uploaded): .xyz where the object's points stood in the previous frame
+    minus where they stand now, .w its history cap (0: none).  A tap counts only where the previous object plane holds the pixel's id.
+    Ordered on the context's stream."""
+    _positive_ints(("w", w), ("h", h))
+    cur = (("colour_ptr", colour_ptr), ("albedo_ptr", albedo_ptr), ("normal_depth_ptr", normal_depth_ptr), ("moments_ptr", moments_ptr),
+           ("object_ptr", object_ptr), ("out_colour_ptr", out_colour_ptr), ("out_albedo_ptr", out_albedo_ptr),
+           ("out_moments_ptr", out_moments_ptr), ("out_variance_ptr", out_variance_ptr))
+    _pointers(*cur)
+    if not all(v for _, v in cur):
+        raise ValueError("%s: device buffers are required" % ", ".join(n for n, v in cur if not v))
+    cam = _camera_bytes("camera", camera)
+    prev_cam, prev_ptrs = None, (None,) * 5
+    if prev is not None:
+        if not isinstance(prev, (tuple, list)) or len(prev) != 6:
+            raise ValueError("prev: None or (camera, colour_ptr, albedo_ptr, normal_depth_ptr, moments_ptr, object_ptr) expected, got %r"
+                             % (prev,))
+        prev_cam = _camera_bytes("prev camera", prev[0])
+        named = tuple(zip(("prev colour_ptr", "prev albedo_ptr", "prev normal_depth_ptr", "prev moments_ptr", "prev object_ptr"), prev[1:]))
+        _pointers(*named)
+        if not all(v for _, v in named):
+            raise ValueError("prev: all five device buffers are required")
+        prev_ptrs = tuple(C.c_void_p(v) for v in prev[1:])
+    _pointers(("motion_ptr", motion_ptr))
+    if not isinstance(n_objects, (int, np.integer)) or isinstance(n_objects, bool) or not 0 <= n_objects <= OBJECT_MOTION_MAX_OBJECTS:
+        raise ValueError("n_objects: an int in 0..%d expected, got %r" % (OBJECT_MOTION_MAX_OBJECTS, n_objects))
+    if bool(motion_ptr) != (n_objects > 0):
+        raise ValueError("motion_ptr, n_objects: both or neither expected, got %r and %r" % (motion_ptr, n_objects))
+    if not isinstance(max_history, (int, float, np.integer, np.floating)) or isinstance(max_history, bool) or not 1 <= max_history <= 65536:
+        raise ValueError("max_history: a number in 1..65536 expected, got %r" % (max_history,))
+    _sigmas(("depth_tolerance", depth_tolerance), ("normal_tolerance", normal_tolerance), ("coverage_tolerance", coverage_tolerance))
+    _chk(load_library().tptTemporalAccumulateObjectsDevice(
+        w, h, cam, prev_cam, C.c_void_p(colour_ptr), C.c_void_p(albedo_ptr), C.c_void_p(normal_depth_ptr), C.c_void_p(moments_ptr),
+        *prev_ptrs[:4], C.c_void_p(out_colour_ptr), C.c_void_p(out_albedo_ptr), C.c_void_p(out_moments_ptr), C.c_void_p(out_variance_ptr),
+        max_history, depth_tolerance, normal_tolerance, coverage_tolerance, C.c_void_p(object_ptr), prev_ptrs[4],
+        C.c_void_p(motion_ptr) if motion_ptr else None, n_objects), "tptTemporalAccumulateObjectsDevice")
 
 
 ADAPTIVE_MAX_SAMPLES = 2047  # one pixel's samples of one launch (include/tpt_hip.h: 11 bits of sample index in the path record)

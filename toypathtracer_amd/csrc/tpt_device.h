@@ -121,6 +121,30 @@ __attribute__((weak)) hipError_t tptLaunchTemporal(const float* colour, const fl
                                                    const float* prevMoments, float* outColour, float* outAlbedo, float* outMoments,
                                                    float* outVariance, int width, int height, const tptTemporalConsts& k,
                                                    hipStream_t stream);
+// tptObjectPlaneDevice: one frame's camera {origin, lowerLeftCorner, horizontal, vertical} and where spheres 1 and 8 stand in that
+// frame (the scene's own centres when nothing moves; unused entries for scenes without such a sphere); by value in the kernel arguments.
+struct tptObjectPlaneConsts {
+    float o[3], ll[3], H[3], V[3];
+    float c1[3], c8[3];
+};
+// One launch of the object-plane kernel: `out` ([h][w] int32) receives the index of the first sphere the ray through each pixel's
+// centre meets, -1 for none; sph4 = SceneView::sph4 of nSpheres records in device memory.  Weak for the same reason as tptLaunchDenoise.
+__attribute__((weak)) hipError_t tptLaunchObjectPlane(const tpt::f4* sph4, int nSpheres, int32_t* out, int width, int height,
+                                                      const tptObjectPlaneConsts& k, hipStream_t stream);
+// tptTemporalAccumulateObjectsDevice: the plain pass's constants, made the same way.  (A struct of its own name: the kernel's mangled
+// name carries its parameter types, and tests count kernels by the words in their names.)
+struct tptReprojectConsts {
+    tptTemporalConsts t;
+};
+// One launch of the object-following accumulation kernel; the four prev planes and prevObject are all null (first frame) or all
+// given; motion ([nObjects] f4 in device memory) may be null with nObjects == 0.  Weak for the same reason as tptLaunchDenoise.
+__attribute__((weak)) hipError_t tptLaunchReprojectObjects(const float* colour, const float* albedo, const float* normalDepth,
+                                                           const float* moments, const float* prevColour, const float* prevAlbedo,
+                                                           const float* prevNormalDepth, const float* prevMoments, float* outColour,
+                                                           float* outAlbedo, float* outMoments, float* outVariance,
+                                                           const int32_t* object, const int32_t* prevObject, const float* motion,
+                                                           int nObjects, int width, int height, const tptReprojectConsts& k,
+                                                           hipStream_t stream);
 // tptDrawDeviceAdaptive's blend: tile.rgb and moments.xyz with lerp = S / (S + n) per pixel, S the running sample count in moments.w
 // (0 unless `progressive`), n the pixel's clamped count; moments.w = S + n; pixels with n == 0 untouched.  Weak for the same reason as
 // tptLaunchDenoise.

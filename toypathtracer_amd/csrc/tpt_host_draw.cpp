@@ -119,6 +119,62 @@ static int ensureDenoisePlane(int w, int h)
     return 0;
 }
 
+// What tptTemporalAccumulateDevice and tptTemporalAccumulateObjectsDevice refuse, in the order they check it (f: the entry point), and
+// what the kernels need of the two cameras, made here in the stated order (k).
+static int checkTemporal(const std::string& f, int w, int h, const void* camera, const void* prevCamera, const float* deviceColour,
+                         const float* deviceAlbedo, const float* deviceNormalDepth, const float* deviceMoments,
+                         const float* devicePrevColour, const float* devicePrevAlbedo, const float* devicePrevNormalDepth,
+                         const float* devicePrevMoments, float* deviceOutColour, float* deviceOutAlbedo, float* deviceOutMoments,
+                         float* deviceOutVariance, float maxHistory, float depthTolerance, float normalTolerance, float coverageTolerance,
+                         tptTemporalConsts& k)
+{
+    if (w < 1 || w > 8192 || h < 1 || h > 8192) return fail(f + ": w and h must lie in 1..8192");
+    if (!camera) return fail(f + ": camera is required");
+    if (!deviceColour || !deviceAlbedo || !deviceNormalDepth || !deviceMoments) return fail(f + ": the four planes of this frame are required");
+    if (!deviceOutColour || !deviceOutAlbedo || !deviceOutMoments || !deviceOutVariance) return fail(f + ": the four output planes are required");
+    const int nPrev = (prevCamera != nullptr) + (devicePrevColour != nullptr) + (devicePrevAlbedo != nullptr) +
+                      (devicePrevNormalDepth != nullptr) + (devicePrevMoments != nullptr);
+    if (nPrev != 0 && nPrev != 5) return fail(f + ": prevCamera and the four prev planes must be all NULL or all given");
+    const uintptr_t bytes = (uintptr_t)w * (uintptr_t)h * 16u;
+    const float* outs[4] = {deviceOutColour, deviceOutAlbedo, deviceOutMoments, deviceOutVariance};
+    for (int i = 0; i < 4; ++i) {
+        if (overlapsAny(outs[i], {deviceColour, deviceAlbedo, deviceNormalDepth, deviceMoments, devicePrevColour, devicePrevAlbedo,
+                                  devicePrevNormalDepth, devicePrevMoments}, bytes))
+            return fail(f + ": an output overlaps an input");
+        for (int j = 0; j < i; ++j)
+            if (overlapsAny(outs[i], {outs[j]}, bytes)) return fail(f + ": two outputs overlap");
+    }
+    if (!(maxHistory >= 1.0f && maxHistory <= 65536.0f)) return fail(f + ": maxHistory must lie in 1..65536"); // (NaN fails)
+    auto tolOk = [](float t) { return t >= 0.0f && t <= 3.40282347e38f; };
+    if (!tolOk(depthTolerance) || !tolOk(normalTolerance) || !tolOk(coverageTolerance))
+        return fail(f + ": every tolerance must be finite and at least 0");
+    auto dot3 = [](const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
+    // The reference's Camera is 22 consecutive floats: origin, lowerLeftCorner, horizontal, vertical, uu, vv, ww, lensRadius.  A camera
+    // the pass can project through is finite, its frame spans two directions and lies in front of its origin; a = ll - o, f = -dot(a, ww).
+    auto cameraOk = [&](const float* c, float* a, float& fc) {
+        for (int i = 0; i < 22; ++i)
+            if (!(fabsf(c[i]) <= 3.40282347e38f)) return false;
+        for (int i = 0; i < 3; ++i) a[i] = c[3 + i] - c[i];
+        fc = -dot3(a, c + 18);
+        return dot3(c + 6, c + 6) != 0.0f && dot3(c + 9, c + 9) != 0.0f && fc > 0.0f;
+    };
+    static_assert(sizeof(CameraPOD) == 22 * sizeof(float), "the reference's Camera");
+    float cam[22], prev[22], a[3], fc;
+    k = {};
+    memcpy(cam, camera, sizeof cam);
+    if (!cameraOk(cam, a, fc)) return fail(f + ": camera has a non-finite field, a degenerate frame or its frame behind its origin");
+    memcpy(k.o, cam, 12); memcpy(k.ll, cam + 3, 12); memcpy(k.H, cam + 6, 12); memcpy(k.V, cam + 9, 12);
+    if (prevCamera) {
+        memcpy(prev, prevCamera, sizeof prev);
+        if (!cameraOk(prev, k.pa, k.pf)) return fail(f + ": prevCamera has a non-finite field, a degenerate frame or its frame behind its origin");
+        memcpy(k.po, prev, 12); memcpy(k.pH, prev + 6, 12); memcpy(k.pV, prev + 9, 12); memcpy(k.pw, prev + 18, 12);
+        k.phh = dot3(prev + 6, prev + 6);
+        k.pvv = dot3(prev + 9, prev + 9);
+    }
+    k.maxHistory = maxHistory; k.depthTol = depthTolerance; k.normalTol = normalTolerance; k.coverageTol = coverageTolerance;
+    return 0;
+}
+
 } // namespace tpth
 
 extern "C" {
@@ -379,55 +435,120 @@ int tptTemporalAccumulateDevice(int w, int h, const void* camera, const void* pr
 {
     if (requireInit()) return -1;
     const std::string f("tptTemporalAccumulateDevice");
-    if (w < 1 || w > 8192 || h < 1 || h > 8192) return fail(f + ": w and h must lie in 1..8192");
-    if (!camera) return fail(f + ": camera is required");
-    if (!deviceColour || !deviceAlbedo || !deviceNormalDepth || !deviceMoments) return fail(f + ": the four planes of this frame are required");
-    if (!deviceOutColour || !deviceOutAlbedo || !deviceOutMoments || !deviceOutVariance) return fail(f + ": the four output planes are required");
-    const int nPrev = (prevCamera != nullptr) + (devicePrevColour != nullptr) + (devicePrevAlbedo != nullptr) +
-                      (devicePrevNormalDepth != nullptr) + (devicePrevMoments != nullptr);
-    if (nPrev != 0 && nPrev != 5) return fail(f + ": prevCamera and the four prev planes must be all NULL or all given");
-    const uintptr_t bytes = (uintptr_t)w * (uintptr_t)h * 16u;
-    const float* outs[4] = {deviceOutColour, deviceOutAlbedo, deviceOutMoments, deviceOutVariance};
-    for (int i = 0; i < 4; ++i) {
-        if (overlapsAny(outs[i], {deviceColour, deviceAlbedo, deviceNormalDepth, deviceMoments, devicePrevColour, devicePrevAlbedo,
-                                  devicePrevNormalDepth, devicePrevMoments}, bytes))
-            return fail(f + ": an output overlaps an input");
-        for (int j = 0; j < i; ++j)
-            if (overlapsAny(outs[i], {outs[j]}, bytes)) return fail(f + ": two outputs overlap");
-    }
-    if (!(maxHistory >= 1.0f && maxHistory <= 65536.0f)) return fail(f + ": maxHistory must lie in 1..65536"); // (NaN fails)
-    auto tolOk = [](float t) { return t >= 0.0f && t <= 3.40282347e38f; };
-    if (!tolOk(depthTolerance) || !tolOk(normalTolerance) || !tolOk(coverageTolerance))
-        return fail(f + ": every tolerance must be finite and at least 0");
-    auto dot3 = [](const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
-    // a camera the pass can project through: finite, a frame that spans two directions, in front of its origin; a = ll - o, f = -dot(a, ww)
-    // The reference's Camera is 22 consecutive floats: origin, lowerLeftCorner, horizontal, vertical, uu, vv, ww, lensRadius.  A camera
-    // the pass can project through is finite, its frame spans two directions and lies in front of its origin; a = ll - o, f = -dot(a, ww).
-    auto cameraOk = [&](const float* c, float* a, float& fc) {
-        for (int i = 0; i < 22; ++i)
-            if (!(fabsf(c[i]) <= 3.40282347e38f)) return false;
-        for (int i = 0; i < 3; ++i) a[i] = c[3 + i] - c[i];
-        fc = -dot3(a, c + 18);
-        return dot3(c + 6, c + 6) != 0.0f && dot3(c + 9, c + 9) != 0.0f && fc > 0.0f;
-    };
-    static_assert(sizeof(CameraPOD) == 22 * sizeof(float), "the reference's Camera");
-    float cam[22], prev[22], a[3], fc;
-    tptTemporalConsts k = {};
-    memcpy(cam, camera, sizeof cam);
-    if (!cameraOk(cam, a, fc)) return fail(f + ": camera has a non-finite field, a degenerate frame or its frame behind its origin");
-    memcpy(k.o, cam, 12); memcpy(k.ll, cam + 3, 12); memcpy(k.H, cam + 6, 12); memcpy(k.V, cam + 9, 12);
-    if (prevCamera) {
-        memcpy(prev, prevCamera, sizeof prev);
-        if (!cameraOk(prev, k.pa, k.pf)) return fail(f + ": prevCamera has a non-finite field, a degenerate frame or its frame behind its origin");
-        memcpy(k.po, prev, 12); memcpy(k.pH, prev + 6, 12); memcpy(k.pV, prev + 9, 12); memcpy(k.pw, prev + 18, 12);
-        k.phh = dot3(prev + 6, prev + 6);
-        k.pvv = dot3(prev + 9, prev + 9);
-    }
-    k.maxHistory = maxHistory; k.depthTol = depthTolerance; k.normalTol = normalTolerance; k.coverageTol = coverageTolerance;
+    tptTemporalConsts k;
+    int rc = checkTemporal(f, w, h, camera, prevCamera, deviceColour, deviceAlbedo, deviceNormalDepth, deviceMoments, devicePrevColour,
+                           devicePrevAlbedo, devicePrevNormalDepth, devicePrevMoments, deviceOutColour, deviceOutAlbedo, deviceOutMoments,
+                           deviceOutVariance, maxHistory, depthTolerance, normalTolerance, coverageTolerance, k);
+    if (rc) return rc;
     if (!tptLaunchTemporal) return fail(f + ": this build has no temporal accumulation kernel");
     HIPCHK(tptLaunchTemporal(deviceColour, deviceAlbedo, deviceNormalDepth, deviceMoments, devicePrevColour, devicePrevAlbedo,
                              devicePrevNormalDepth, devicePrevMoments, deviceOutColour, deviceOutAlbedo, deviceOutMoments,
                              deviceOutVariance, w, h, k, g.stream));
+    return 0;
+}
+
+// The temporal pass that follows objects (include/tpt_hip.h states it): the plain pass's checks, then those of the object planes and
+// the motion table; one launch of its own kernel.
+int tptTemporalAccumulateObjectsDevice(int w, int h, const void* camera, const void* prevCamera, const float* deviceColour,
+                                       const float* deviceAlbedo, const float* deviceNormalDepth, const float* deviceMoments,
+                                       const float* devicePrevColour, const float* devicePrevAlbedo, const float* devicePrevNormalDepth,
+                                       const float* devicePrevMoments, float* deviceOutColour, float* deviceOutAlbedo,
+                                       float* deviceOutMoments, float* deviceOutVariance, float maxHistory, float depthTolerance,
+                                       float normalTolerance, float coverageTolerance, const int32_t* deviceObject,
+                                       const int32_t* devicePrevObject, const float* deviceObjectMotion, int nObjects)
+{
+    if (requireInit()) return -1;
+    const std::string f("tptTemporalAccumulateObjectsDevice");
+    tptReprojectConsts k;
+    int rc = checkTemporal(f, w, h, camera, prevCamera, deviceColour, deviceAlbedo, deviceNormalDepth, deviceMoments, devicePrevColour,
+                           devicePrevAlbedo, devicePrevNormalDepth, devicePrevMoments, deviceOutColour, deviceOutAlbedo, deviceOutMoments,
+                           deviceOutVariance, maxHistory, depthTolerance, normalTolerance, coverageTolerance, k.t);
+    if (rc) return rc;
+    if (!deviceObject) return fail(f + ": deviceObject is required");
+    if ((devicePrevObject != nullptr) != (prevCamera != nullptr))
+        return fail(f + ": devicePrevObject must be given exactly when prevCamera and the prev planes are");
+    if (nObjects < 0 || nObjects > 65534) return fail(f + ": nObjects must lie in 0..65534");
+    if ((deviceObjectMotion != nullptr) != (nObjects > 0)) return fail(f + ": deviceObjectMotion and nObjects must be given together");
+    // no output may share a byte with an object plane or the table, each at its full extent
+    const uintptr_t plane = (uintptr_t)w * (uintptr_t)h;
+    const struct { const void* p; uintptr_t bytes; } more[3] = {{deviceObject, plane * 4u}, {devicePrevObject, plane * 4u},
+                                                                {deviceObjectMotion, (uintptr_t)nObjects * 16u}};
+    const float* outs[4] = {deviceOutColour, deviceOutAlbedo, deviceOutMoments, deviceOutVariance};
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const uintptr_t a = reinterpret_cast<uintptr_t>(outs[i]), b = reinterpret_cast<uintptr_t>(more[j].p);
+            if (b && a < b + more[j].bytes && b < a + plane * 16u) return fail(f + ": an output overlaps an object plane or the motion table");
+        }
+    if (!tptLaunchReprojectObjects) return fail(f + ": this build has no object-following accumulation kernel");
+    HIPCHK(tptLaunchReprojectObjects(deviceColour, deviceAlbedo, deviceNormalDepth, deviceMoments, devicePrevColour, devicePrevAlbedo,
+                                     devicePrevNormalDepth, devicePrevMoments, deviceOutColour, deviceOutAlbedo, deviceOutMoments,
+                                     deviceOutVariance, deviceObject, devicePrevObject, deviceObjectMotion, nObjects, w, h, k, g.stream));
+    return 0;
+}
+
+// The object plane (include/tpt_hip.h states it): per frame one launch on the context stream over the scene set of the last tptUpdate,
+// with the frame's camera and its centres of spheres 1 and 8 by value.  The host's spheres, camera, the launch queue and every setting
+// stay as they are.  One thing moves: a scene set that tptUpdate staged and no launch has uploaded yet is uploaded here, on the context
+// stream instead of the next draw's trace stream, and becomes the current set (enqueueSceneUpload).  Later launches wait for its
+// evUploaded as they do for any set another stream carried, so they read the same scene either way.
+int tptObjectPlaneDevice(int nFrames, const float* times, const void* cameras, int w, int h, int32_t* deviceFrameObjects,
+                         unsigned testFlags)
+{
+    if (requireInit()) return -1;
+    const std::string f("tptObjectPlaneDevice");
+    if (!g.updated) return fail(f + ": call tptUpdate first");
+    if (nFrames < 1 || nFrames > 4096) return fail(f + ": nFrames must lie in 1..4096");
+    if (w < 1 || w > 8192 || h < 1 || h > 8192) return fail(f + ": w and h must lie in 1..8192");
+    if (!deviceFrameObjects) return fail(f + ": deviceFrameObjects is required");
+    if (!cameras && (w != g.updatedW || h != g.updatedH)) return fail(f + ": without cameras the size must be the last tptUpdate's");
+    if (testFlags & ~(unsigned)(TPT_FLAG_ANIMATE | TPT_FLAG_PROGRESSIVE)) return fail(f + ": unknown flag bits");
+    static_assert(sizeof(CameraPOD) == 22 * sizeof(float), "the reference's Camera");
+    for (int j = 0; cameras && j < nFrames; ++j) {
+        float c[12];
+        memcpy(c, static_cast<const char*>(cameras) + sizeof(CameraPOD) * (size_t)j, sizeof c);
+        for (int i = 0; i < 12; ++i)
+            if (!(fabsf(c[i]) <= 3.40282347e38f)) return fail(f + ": a camera has a non-finite origin, lowerLeftCorner, horizontal or vertical");
+    }
+    Context::SceneSet* S = activeSet();
+    if (!S || !S->dev || S->nSpheres < 1) return fail(f + ": no scene staged (call tptUpdate first)");
+    if (!tptLaunchObjectPlane) return fail(f + ": this build has no object plane kernel");
+    // the scene as tptUpdate staged it: the records the kernel reads, and their host copy for the centres of spheres 1 and 8
+    const f4* staged = reinterpret_cast<const f4*>(S->stage + S->offSph4);
+    const f4* dev = reinterpret_cast<const f4*>(S->dev + S->offSph4);
+    const int n = S->nSpheres;
+    const bool animate = times && (testFlags & TPT_FLAG_ANIMATE) && n > 8; // (the tptUpdate guard, Test.cpp:304)
+    int rc = enqueueSceneUpload(g.stream);
+    if (rc) return rc;
+    for (int j = 0; j < nFrames; ++j) {
+        tptObjectPlaneConsts k = {};
+        float c[12];
+        memcpy(c, cameras ? static_cast<const char*>(cameras) + sizeof(CameraPOD) * (size_t)j : reinterpret_cast<const char*>(&g.cam), sizeof c);
+        memcpy(k.o, c, 12); memcpy(k.ll, c + 3, 12); memcpy(k.H, c + 6, 12); memcpy(k.V, c + 9, 12);
+        if (n > 1) { k.c1[0] = staged[1].x; k.c1[1] = staged[1].y; k.c1[2] = staged[1].z; }
+        if (n > 8) { k.c8[0] = staged[8].x; k.c8[1] = staged[8].y; k.c8[2] = staged[8].z; }
+        if (animate) {
+            k.c1[1] = animatedY1(times[j]);
+            k.c8[2] = animatedZ8(times[j]);
+        }
+        HIPCHK(tptLaunchObjectPlane(dev, n, deviceFrameObjects + (size_t)j * (size_t)w * (size_t)h, w, h, k, g.stream));
+    }
+    return 0;
+}
+
+// The animated scene's displacement per sphere between two times (include/tpt_hip.h states it): host arithmetic only.
+int tptObjectMotionTable(float time, float prevTime, unsigned testFlags, float* outTable, int capacity)
+{
+    if (requireInit()) return -1;
+    const std::string f("tptObjectMotionTable");
+    if (!outTable) return fail(f + ": outTable is required");
+    if (g.spheres.empty()) defaultScene(g.spheres, g.mats);
+    const int count = (int)g.spheres.size();
+    if (capacity < count) return fail(f + ": capacity is smaller than the object count");
+    memset(outTable, 0, sizeof(float) * 4 * (size_t)count);
+    if ((testFlags & TPT_FLAG_ANIMATE) && count > 8) { // (the tptUpdate guard, Test.cpp:304)
+        outTable[4 * 1 + 1] = animatedY1(prevTime) - animatedY1(time);
+        outTable[4 * 8 + 2] = animatedZ8(prevTime) - animatedZ8(time);
+    }
     return 0;
 }
 

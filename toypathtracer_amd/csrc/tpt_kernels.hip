@@ -581,6 +581,150 @@ __global__ void __launch_bounds__(256) tptTemporalKernel(const f4* __restrict__ 
     outVariance[p] = r;
 }
 
+// tptTemporalAccumulateObjectsDevice (include/tpt_hip.h states it; tests/object_checker.c restates it): tptTemporalKernel's pass, restated
+// (that kernel's code object is pinned by its tests), with the three changes the object plane brings.  The pixel's point is moved by
+// its object's entry of the motion table before it is projected, a tap counts only where the previous object plane holds the pixel's
+// own id, and the entry's .w caps the history length.  The id plane is one more coalesced 4-B load, the previous one one more 4-B
+// gather per tap, the table a 16-B gather that neighbouring lanes mostly share.
+template <bool HISTORY>
+__global__ void __launch_bounds__(256) tptReprojectObjectsKernel(const f4* __restrict__ colour, const f4* __restrict__ albedo,
+                                                                  const f4* __restrict__ nd, const f4* __restrict__ moments,
+                                                                  const f4* __restrict__ prevColour, const f4* __restrict__ prevAlbedo,
+                                                                  const f4* __restrict__ prevNd, const f4* __restrict__ prevMoments,
+                                                                  f4* __restrict__ outColour, f4* __restrict__ outAlbedo,
+                                                                  f4* __restrict__ outMoments, f4* __restrict__ outVariance,
+                                                                  const int32_t* __restrict__ object, const int32_t* __restrict__ prevObject,
+                                                                  const f4* __restrict__ motion, int nObjects, int width, int height,
+                                                                  const tptReprojectConsts kk)
+{
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x >= width || y >= height) return;
+    const tptTemporalConsts& k = kk.t;
+    const size_t p = (size_t)y * width + x;
+    const f4 cc = colour[p], ca = albedo[p], cn = nd[p], cm = moments[p];
+    float o0 = cc.x, o1 = cc.y, o2 = cc.z, o3 = ca.x, o4 = ca.y, o5 = ca.z, o6 = ca.w, o7 = cm.x, o8 = cm.y;
+    float N = 1.0f;
+    if (HISTORY) {
+        const float c = ca.w;
+        const int id = object[p];
+        const f3 o = ld3(k.o), po = ld3(k.po), pw = ld3(k.pw), pa = ld3(k.pa);
+        const float s = ((float)x + 0.5f) / (float)width, t = ((float)y + 0.5f) / (float)height;
+        const f3 dir = normalize(((ld3(k.ll) + s * ld3(k.H)) + t * ld3(k.V)) - o);
+        f3 rel = dir, n = mk3(0.0f, 0.0f, 0.0f);
+        // an entry of the table is read for a hit whose id the table holds (nObjects is 0 without a table)
+        const bool entry = c > 0.0f && (unsigned)id < (unsigned)nObjects;
+        if (c > 0.0f) {
+            const float d = cn.w / c;
+            n = mk3(cn.x / c, cn.y / c, cn.z / c);
+            f3 at = o + dir * d;
+            if (entry) {
+                const f4 m = motion[id];
+                at = at + mk3(m.x, m.y, m.z);
+            }
+            rel = at - po;
+        }
+        const float z = -dot(rel, pw);
+        const float kz = k.pf / z;
+        const f3 q = rel * kz - pa;
+        const float px = dot(q, ld3(k.pH)) / k.phh * (float)width - 0.5f;
+        const float py = dot(q, ld3(k.pV)) / k.pvv * (float)height - 0.5f;
+        if (z > 0.0f && px >= -1.0f && px < (float)width && py >= -1.0f && py < (float)height) {
+            constexpr float snap = TPT_TEMPORAL_SNAP, big = 3.40282347e38f;
+            float fx0 = __builtin_floorf(px), fy0 = __builtin_floorf(py);
+            float fx = px - fx0, fy = py - fy0;
+            if (fx < snap) fx = 0.0f;
+            else if (fx > 1.0f - snap) { fx0 += 1.0f; fx = 0.0f; }
+            if (fy < snap) fy = 0.0f;
+            else if (fy > 1.0f - snap) { fy0 += 1.0f; fy = 0.0f; }
+            const int ix = (int)fx0, iy = (int)fy0;
+            const float e = tsqrt(dot(rel, rel));
+            float B = 0.0f, h0 = 0.0f, h1 = 0.0f, h2 = 0.0f, h3 = 0.0f, h4 = 0.0f, h5 = 0.0f, h6 = 0.0f, h7 = 0.0f, h8 = 0.0f, hN = 0.0f;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const float b = (i ? fx : 1.0f - fx) * (j ? fy : 1.0f - fy);
+                    const int qx = ix + i, qy = iy + j;
+                    if (!(b > 0.0f) || qx < 0 || qx >= width || qy < 0 || qy >= height) continue;
+                    const size_t t4 = (size_t)qy * width + qx;
+                    if (prevObject[t4] != id) continue; // (the 4-B test first: a tap of another object loads nothing else)
+                    const f4 pm = prevMoments[t4], pc = prevColour[t4], pal = prevAlbedo[t4];
+                    if (!(pm.w >= 1.0f && pm.w <= big)) continue;
+                    if (!(__builtin_fabsf(pc.x) <= big && __builtin_fabsf(pc.y) <= big && __builtin_fabsf(pc.z) <= big)) continue;
+                    const float c1 = pal.w;
+                    if (!(__builtin_fabsf(c - c1) <= k.coverageTol)) continue;
+                    if (c > 0.0f && c1 > 0.0f) {
+                        const f4 pn = prevNd[t4];
+                        const float d1 = pn.w / c1;
+                        if (!(__builtin_fabsf(e - d1) <= k.depthTol * e)) continue;
+                        const float dx = n.x - pn.x / c1, dy = n.y - pn.y / c1, dz = n.z - pn.z / c1;
+                        if (!((dx * dx + dy * dy) + dz * dz <= k.normalTol)) continue;
+                    } else if (!(c == 0.0f && c1 == 0.0f)) {
+                        continue;
+                    }
+                    B += b;
+                    h0 += b * pc.x; h1 += b * pc.y; h2 += b * pc.z;
+                    h3 += b * pal.x; h4 += b * pal.y; h5 += b * pal.z; h6 += b * pal.w;
+                    h7 += b * pm.x; h8 += b * pm.y;
+                    hN += b * pm.w;
+                }
+            }
+            if (B > 0.0f) {
+                N = hN / B + 1.0f;
+                if (N > k.maxHistory) N = k.maxHistory;
+                if (entry) { // (the cap is fetched again here, not carried in a register through the taps)
+                    const float cap = motion[id].w;
+                    if (cap >= 1.0f && cap < N) N = cap;
+                }
+                const float lerp = (N - 1.0f) / N, one = 1.0f - lerp;
+                o0 = (h0 / B) * lerp + o0 * one; o1 = (h1 / B) * lerp + o1 * one; o2 = (h2 / B) * lerp + o2 * one;
+                o3 = (h3 / B) * lerp + o3 * one; o4 = (h4 / B) * lerp + o4 * one; o5 = (h5 / B) * lerp + o5 * one;
+                o6 = (h6 / B) * lerp + o6 * one;
+                o7 = (h7 / B) * lerp + o7 * one; o8 = (h8 / B) * lerp + o8 * one;
+            }
+        }
+    }
+    const float dd = o8 - o7 * o7;
+    f4 r;
+    r.x = o0; r.y = o1; r.z = o2; r.w = cc.w;
+    outColour[p] = r;
+    r.x = o3; r.y = o4; r.z = o5; r.w = o6;
+    outAlbedo[p] = r;
+    r.x = o7; r.y = o8; r.z = 0.0f; r.w = N;
+    outMoments[p] = r;
+    r.x = 0.0f; r.y = (dd > 0.0f ? dd : 0.0f) / N; r.z = 0.0f; r.w = N;
+    outVariance[p] = r;
+}
+
+// tptObjectPlaneDevice (include/tpt_hip.h states it; tests/object_checker.c restates it): the index of the first sphere the ray through
+// each pixel's centre and the lens centre meets.  One lane per pixel, a wave along 64 pixels of a row; the reference's exact test
+// (testSphere) for every sphere in index order, so the nearest hit wins and equal distances go to the lowest index.  The
+// {centre, r^2} records are the same for every lane: read through the constant address space they are scalar loads, and the test's
+// sphere operands sit in scalar registers.  Spheres 1 and 8 take the frame's centres from the kernel arguments.
+__global__ void __launch_bounds__(256) tptObjectPlaneKernel(const f4* __restrict__ sph, int nSpheres, int32_t* __restrict__ out, int width,
+                                                            int height, const tptObjectPlaneConsts k)
+{
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x >= width || y >= height) return;
+    const f3 o = ld3(k.o);
+    const float s = ((float)x + 0.5f) / (float)width, t = ((float)y + 0.5f) / (float)height;
+    const f3 dir = normalize(((ld3(k.ll) + s * ld3(k.H)) + t * ld3(k.V)) - o);
+    const PairPtr rec = pairPtr(reinterpret_cast<const float*>(sph));
+    float hitT = TPT_MAX_T;
+    int id = -1;
+    for (int i = 0; i < nSpheres; ++i) {
+        f4 s4;
+        s4.x = rec[4 * (size_t)i];
+        s4.y = rec[4 * (size_t)i + 1];
+        s4.z = rec[4 * (size_t)i + 2];
+        s4.w = rec[4 * (size_t)i + 3];
+        if (i == 1) { s4.x = k.c1[0]; s4.y = k.c1[1]; s4.z = k.c1[2]; }
+        if (i == 8) { s4.x = k.c8[0]; s4.y = k.c8[1]; s4.z = k.c8[2]; }
+        testSphere(s4, i, o, dir, TPT_MIN_T, hitT, id);
+    }
+    out[(size_t)y * width + x] = id;
+}
+
 template <int HS, int FOLD, bool LDS_SCENE>
 // 112 VGPRs x 4 waves/SIMD leaves 64 registers per SIMD lane for the resolve kernel's waves (see tptTraceQueueKernel;
 // amdgpu_num_vgpr counts half of the unified file on gfx90a+, so 56 means 112)
@@ -2464,6 +2608,30 @@ hipError_t tptLaunchTemporal(const float* colour, const float* albedo, const flo
     hipLaunchKernelGGL(prevColour ? tptTemporalKernel<true> : tptTemporalKernel<false>, grid, dim3(64, 4), 0, stream, in(colour), in(albedo),
                        in(normalDepth), in(moments), in(prevColour), in(prevAlbedo), in(prevNormalDepth), in(prevMoments), out(outColour),
                        out(outAlbedo), out(outMoments), out(outVariance), width, height, k);
+    return hipGetLastError();
+}
+
+hipError_t tptLaunchReprojectObjects(const float* colour, const float* albedo, const float* normalDepth, const float* moments,
+                                     const float* prevColour, const float* prevAlbedo, const float* prevNormalDepth, const float* prevMoments,
+                                     float* outColour, float* outAlbedo, float* outMoments, float* outVariance, const int32_t* object,
+                                     const int32_t* prevObject, const float* motion, int nObjects, int width, int height,
+                                     const tptReprojectConsts& k, hipStream_t stream)
+{
+    const dim3 grid((unsigned)(width + 63) / 64, (unsigned)(height + 3) / 4);
+    auto in = [](const float* q) { return reinterpret_cast<const f4*>(q); };
+    auto out = [](float* q) { return reinterpret_cast<f4*>(q); };
+    hipLaunchKernelGGL(prevColour ? tptReprojectObjectsKernel<true> : tptReprojectObjectsKernel<false>, grid, dim3(64, 4), 0, stream,
+                       in(colour), in(albedo), in(normalDepth), in(moments), in(prevColour), in(prevAlbedo), in(prevNormalDepth),
+                       in(prevMoments), out(outColour), out(outAlbedo), out(outMoments), out(outVariance), object, prevObject, in(motion),
+                       nObjects, width, height, k);
+    return hipGetLastError();
+}
+
+hipError_t tptLaunchObjectPlane(const f4* sph4, int nSpheres, int32_t* out, int width, int height, const tptObjectPlaneConsts& k,
+                                hipStream_t stream)
+{
+    const dim3 grid((unsigned)(width + 63) / 64, (unsigned)(height + 3) / 4);
+    hipLaunchKernelGGL(tptObjectPlaneKernel, grid, dim3(64, 4), 0, stream, sph4, nSpheres, out, width, height, k);
     return hipGetLastError();
 }
 
