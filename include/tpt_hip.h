@@ -257,6 +257,48 @@ TPT_API int tptDrawDeviceCameraClip(int firstFrame, int nFrames, const float* ti
                                     int screenWidth, int screenHeight, float* deviceTile, float* deviceMoments,
                                     float* deviceFrameImages, float* deviceFrameAlbedo, float* deviceFrameNormalDepth,
                                     float* deviceFrameMoments, int64_t* deviceFrameRays, void* outCameras, unsigned testFlags);
+/* tptDrawDeviceCameraClip with the motion given by the CALLER instead of by times: a clip of a scene the caller animates (a video export,
+ * a dataset of clips), with the planes the denoising chain reads, up to 32 frames per launch.  views: host memory, nFrames x 9 floats, as
+ * tptDrawDeviceCameraClip's (required).  movedIds: host memory, nMoved distinct sphere indices; centres: host memory, nFrames x nMoved x 3
+ * floats, frame-major: centres[(j*nMoved + k)*3 ..] is where sphere movedIds[k] stands in frame j.  nMoved == 0: both may be NULL and
+ * nothing moves.  Radii and materials are the scene's own: spheres only translate, as in tptTemporalAccumulateObjectsDevice's table.
+ * Let S_j be the context's spheres (tptGetSceneDesc) with the centres of the moved ids replaced by frame j's.  Frame j (0 <= j < nFrames)
+ * is bit-identical, with the same ray count, to
+ *   tptSetScene(S_j, materials, count);
+ *   tptSetCamera(views + 9*j, views + 9*j + 3, views[9*j + 6], views[9*j + 7], views[9*j + 8]);
+ *   tptUpdate(0.0f, firstFrame + j, w, h, testFlags);
+ *   tptDrawDeviceMoments(0.0f, firstFrame + j, w, h, deviceTile, albedo_j, normalDepth_j, deviceMoments, testFlags);
+ * the seeds are those of frame firstFrame + j, the lerp factor is the frame's own, the light list holds the moved centres of emissive
+ * spheres, the aperture is 0 in Mitsuba-compare mode.  deviceTile, deviceMoments, the five per-frame outputs, outCameras (written at call
+ * time) and the ordering are tptDrawDeviceCameraClip's.  deviceFrameObjects: NULL, or nFrames device planes of h*w int32; plane j holds
+ * the bytes tptObjectPlaneDevice(1, NULL, outCameras_j, w, h, plane_j, 0) writes right after frame j's tptUpdate in the sequence above:
+ * the centre ray's HitWorld id over S_j, -1 for a miss -- with the call's cameras and api.motion_table(S_{j-1}, S_j) the inputs of
+ * tptTemporalAccumulateObjectsDevice.
+ * testFlags: TPT_FLAG_PROGRESSIVE or 0.  TPT_FLAG_ANIMATE is REFUSED: the table is the motion, and the reference's rule for spheres 1 and 8
+ * is not applied on top of it (a caller who wants it passes those centres).
+ * Afterwards the context is where that sequence leaves it: its spheres are S_{nFrames-1} and that scene is staged, the camera set-up is
+ * views[nFrames - 1] (as after tptSetCamera), the camera that of its tptUpdate; frames traced ahead and stream-batch planes are dropped
+ * first.
+ * One trace launch per 32 frames when the scene has fewer than 256 spheres, nMoved <= 8 and every moved id is below 64: the kernel reads
+ * each frame's camera and its moved centres from tables and tests the moved spheres for every ray.  Every other accepted call -- nMoved
+ * over 8, an id of 64 or above, 256 spheres or more -- goes frame by frame (tptDrawDeviceMoments' kernel, the spheres and the camera set
+ * per frame), with the same bits.  The launches of one call overlap as tptDrawDeviceAnimationMoments' do.  For a call that asks for object
+ * planes the library keeps the {centre, r^2} arrays of two launches' frames, filled and copied launch by launch: at most
+ * 2 x 32 x count x 16 bytes of device memory and as much pinned host memory whatever nFrames is (67 MB each at 65534 spheres, 94 KB for
+ * the built-in scene), until tptShutdown.
+ * Refused (non-zero, tptGetLastError names this function, nothing enqueued, no buffer and no byte of outCameras written, camera and
+ * spheres unchanged): what tptDrawDeviceCameraClip refuses of sizes, a missing tptUpdate at this size, staging over 4096 MiB, seed mode,
+ * fold, kernel variant, spp over 2047, more than 65534 spheres, sharding or a communicator, a tile mirror, views NULL; nMoved < 0 or above
+ * the sphere count; movedIds or centres NULL with nMoved > 0; an id outside 0 .. count-1; a repeated id; a centre that is not finite; any
+ * flag bit other than TPT_FLAG_PROGRESSIVE; any two of the eight device buffers -- the camera clip's seven and the object planes --
+ * overlapping, each taken at its full extent; with deviceFrameObjects, a view whose camera tptObjectPlaneDevice refuses (a non-finite
+ * origin, lowerLeftCorner, horizontal or vertical). */
+TPT_API int tptDrawDeviceKeyframeClip(int firstFrame, int nFrames, const float* views,
+                                      int nMoved, const int32_t* movedIds, const float* centres,
+                                      int screenWidth, int screenHeight, float* deviceTile, float* deviceMoments,
+                                      float* deviceFrameImages, float* deviceFrameAlbedo, float* deviceFrameNormalDepth,
+                                      float* deviceFrameMoments, int64_t* deviceFrameRays, int32_t* deviceFrameObjects,
+                                      void* outCameras, unsigned testFlags);
 /* The spatial filter of SVGF (Schied et al., HPG 2017) in tptDenoiseDevice's rational form: an a-trous filter whose luminance term is
  * scaled by a per-pixel variance made from tptDrawDeviceMoments' moments and carried through the iterations.  All six buffers are
  * device buffers of h*w*4 floats; deviceAlbedo and deviceNormalDepth may be NULL.  samples: how many samples the colour and the moments

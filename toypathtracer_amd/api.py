@@ -39,7 +39,7 @@ C_ABI_SYMBOLS = [
     "tptSetSamplesPerPixel", "tptSetConfig", "tptSetSeedMode", "tptSetFoldMode", "tptSetScene", "tptSetCamera", "tptSetStream",
     "tptSetRowShard", "tptLocalRowCount", "tptLocalRowToGlobal", "tptDrawDevice", "tptRayCounterRead", "tptSetRayCounter", "tptSetFrameOverlap", "tptDisplayRGBA8", "tptKernelTimingBegin", "tptKernelTimingEnd",
     "tptSynchronize", "tptTimerBegin", "tptTimerEnd", "tptSetKernelVariant",
-    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceAnimationMoments", "tptDrawDeviceCameraClip", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptObjectPlaneDevice", "tptObjectMotionTable", "tptTemporalAccumulateObjectsDevice", "tptDrawDeviceAdaptive", "tptAdaptiveSamplesDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
+    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceAnimationMoments", "tptDrawDeviceCameraClip", "tptDrawDeviceKeyframeClip", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptObjectPlaneDevice", "tptObjectMotionTable", "tptTemporalAccumulateObjectsDevice", "tptDrawDeviceAdaptive", "tptAdaptiveSamplesDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
 ]
 # include/tpt_test_hooks.h: exported by the second build (libtoypathtracer_hip_hooks.so) only
 HOOK_SYMBOLS = ["tptTestMath", "tptTestMathExhaustive", "tptTestHitSpheres", "tptTestMatrixFilter", "tptTestGroupFilter", "tptTestSetDealCapacities", "tptDebugStats", "tptDebugChunkOrder"]
@@ -78,7 +78,7 @@ def _bind(path, hooks):
         "tptSetRayCounter": [p], "tptSetTileMirror": [p, p], "tptSetFrameOverlap": [i], "tptDisplayRGBA8": [p, i, i, p], "tptKernelTimingBegin": [i],
         "tptKernelTimingEnd": [C.POINTER(f), C.POINTER(i)],
         "tptSynchronize": [], "tptTimerBegin": [], "tptTimerEnd": [C.POINTER(f)], "tptSetKernelVariant": [i, i, i],
-        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDrawDeviceAnimationMoments": [i, i, p, i, i] + [p] * 7 + [u], "tptDrawDeviceCameraClip": [i, i, p, p, i, i] + [p] * 8 + [u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptObjectPlaneDevice": [i, p, p, i, i, p, u], "tptObjectMotionTable": [f, f, u, p, i], "tptTemporalAccumulateObjectsDevice": [i, i] + [p] * 14 + [f] * 4 + [p, p, p, i], "tptDrawDeviceAdaptive": [f, i, i, i, p, p, p, p, p, u], "tptAdaptiveSamplesDevice": [i, i, p, f, i, i, p, p, p], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
+        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDrawDeviceAnimationMoments": [i, i, p, i, i] + [p] * 7 + [u], "tptDrawDeviceCameraClip": [i, i, p, p, i, i] + [p] * 8 + [u], "tptDrawDeviceKeyframeClip": [i, i, p, i, p, p, i, i] + [p] * 9 + [u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptObjectPlaneDevice": [i, p, p, i, i, p, u], "tptObjectMotionTable": [f, f, u, p, i], "tptTemporalAccumulateObjectsDevice": [i, i] + [p] * 14 + [f] * 4 + [p, p, p, i], "tptDrawDeviceAdaptive": [f, i, i, i, p, p, p, p, p, u], "tptAdaptiveSamplesDevice": [i, i, p, f, i, i, p, p, p], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
     }
     if hooks:
         sigs.update({"tptDebugStats": [p, i], "tptDebugChunkOrder": [p, p, i], "tptTestMath": [i, p, p, p, i], "tptTestMathExhaustive": [i, u, u, p, p],
@@ -549,6 +549,42 @@ def draw_device_camera_clip(times, views, first_frame, w, h, tile_ptr, moments_p
                                                 w, h, C.c_void_p(tile_ptr), C.c_void_p(moments_ptr),
                                                 *[C.c_void_p(x) if x else None for _, x in outs],
                                                 cams.ctypes.data if cameras and cams.size else None, flags), "tptDrawDeviceCameraClip")
+    return cams
+
+
+def draw_device_keyframe_clip(views, moved_ids, centres, first_frame, w, h, tile_ptr, moments_ptr, flags, images_ptr=None, albedo_ptr=None,
+                              normal_depth_ptr=None, frame_moments_ptr=None, rays_ptr=None, objects_ptr=None, cameras=True):
+    """draw_device_camera_clip with the motion given by the caller, in launches of up to 32 frames.  views: array-like (N, 9); moved_ids:
+    (K,) distinct sphere indices; centres: (N, K, 3), centres[j, k] where sphere moved_ids[k] stands in frame j (K = 0: nothing moves).
+    Frame j equals set_scene(S_j) + set_camera(views[j]) + UpdateTest(0, first_frame + j) + draw_device_moments on tile_ptr and
+    moments_ptr with plane j of albedo_ptr / normal_depth_ptr, S_j the context's spheres with the moved centres replaced; the other
+    outputs as draw_device_camera_clip's.  objects_ptr: None or N device planes of h*w int32, plane j what object_plane_device gives for
+    frame j's camera over S_j.  flags: kFlagProgressive or 0 (kFlagAnimate is refused).  Returns the frames' cameras as a CAMERA_DT array
+    (cameras=False: not asked for, returns None)."""
+    v = np.ascontiguousarray(views, dtype=np.float32)
+    if v.ndim != 2 or v.shape[1] != 9:
+        raise ValueError("views: shape (N, 9) expected, got %r" % (v.shape,))
+    ids = np.asarray(moved_ids)
+    if ids.ndim != 1 or (ids.size and ids.dtype.kind not in "iu"):
+        raise ValueError("moved_ids: a 1-D sequence of integers expected, got shape %r of %s" % (ids.shape, ids.dtype))
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    c = np.ascontiguousarray(centres, dtype=np.float32)
+    if ids.size == 0 and c.size == 0:
+        c = np.zeros((v.shape[0], 0, 3), np.float32)
+    if c.ndim != 3 or c.shape != (v.shape[0], ids.shape[0], 3):
+        raise ValueError("centres: shape (N, K, 3) = (%d, %d, 3) expected, got %r" % (v.shape[0], ids.shape[0], c.shape))
+    _positive_ints(("w", w), ("h", h))
+    outs = (("images_ptr", images_ptr), ("albedo_ptr", albedo_ptr), ("normal_depth_ptr", normal_depth_ptr),
+            ("frame_moments_ptr", frame_moments_ptr), ("rays_ptr", rays_ptr), ("objects_ptr", objects_ptr))
+    _pointers(("tile_ptr", tile_ptr), ("moments_ptr", moments_ptr), *outs)
+    if not tile_ptr or not moments_ptr:
+        raise ValueError("tile_ptr, moments_ptr: device buffers are required")
+    cams = np.zeros(v.shape[0], CAMERA_DT) if cameras else None
+    _chk(load_library().tptDrawDeviceKeyframeClip(first_frame, v.shape[0], v.ctypes.data if v.size else None, ids.shape[0],
+                                                  ids.ctypes.data if ids.size else None, c.ctypes.data if c.size else None, w, h,
+                                                  C.c_void_p(tile_ptr), C.c_void_p(moments_ptr),
+                                                  *[C.c_void_p(x) if x else None for _, x in outs],
+                                                  cams.ctypes.data if cameras and cams.size else None, flags), "tptDrawDeviceKeyframeClip")
     return cams
 
 

@@ -222,9 +222,10 @@ struct Context {
     // host staging) and its frames' ray counters.  Per slot, because up to kMaxSlots launches are in flight: the table of one call must
     // not be overwritten while an earlier launch still reads it (the upload is stream-ordered behind the slot's previous blend, like its
     // colour buffer).  The moving centres of an animation batch (2 x 16 B per frame) take the room of its first 12 cameras; a launch
-    // that takes both tables (tptDrawDeviceCameraClip) has its centres behind the whole camera table.
+    // that takes both tables (tptDrawDeviceCameraClip) has its centres behind the whole camera table, and so has a launch with the
+    // caller's centres (tptDrawDeviceKeyframeClip: TPT_Q_KEYS_MAX x 16 B per frame).
     struct ViewSlot {
-        CameraPOD* dev = nullptr;       // [kMaxBatch] cameras (or [kMaxBatch][2] centres), then [kMaxBatch][2] centres beside cameras
+        CameraPOD* dev = nullptr;       // [kMaxBatch] cameras (or [kMaxBatch][2] centres), then [kMaxBatch][2 or TPT_Q_KEYS_MAX] centres beside cameras
         unsigned long long* rays = nullptr; // [kMaxBatch] rays of each view
         CameraPOD* stage = nullptr;     // pinned, the same layout
         hipEvent_t evUploaded = nullptr;
@@ -249,6 +250,17 @@ struct Context {
     // the previous launch on half h.  The first launch of a call waits for the whole context stream, as every other AOV launch does.
     hipEvent_t evClip[2] = {nullptr, nullptr};
     unsigned clipSeq = 0;
+    // tptDrawDeviceKeyframeClip's object planes: one {centre, r^2} array per frame of a LAUNCH (SceneView::sph4's records, the moved spheres
+    // at the frame's centres) for tptObjectPlaneKernel, copied on the context stream out of a pinned twin.  Two halves of keySphBytes each,
+    // taken in turn (keySphSeq), so that the host fills one launch's arrays while the previous launch's copy is still queued: at most
+    // 2 x 32 frames x count x 16 B of device memory and as much pinned, whatever the call's length; grown on demand (after a drain), kept
+    // until tptShutdown.  evKeySph[h]: half h's last copy has left the host (the launch after the next waits for it before it refills h).
+    f4* dKeySph = nullptr;
+    f4* hKeySph = nullptr;
+    size_t keySphBytes = 0;
+    hipEvent_t evKeySph[2] = {nullptr, nullptr};
+    bool keySphCopied[2] = {false, false};
+    unsigned keySphSeq = 0;
     // tptDenoiseDevice: the plane the a-trous iterations ping-pong through beside the caller's output ([h][w] f4 of the largest frame
     // denoised so far), made by the first call that iterates more than once, grown when a later one needs more, freed by tptShutdown.
     // Only the context stream uses it, so stream order alone keeps one call's iterations from another's.
@@ -403,6 +415,11 @@ int effectiveOverlap();
 struct BatchTable {
     const CameraPOD* cams = nullptr; // [batch] cameras, every frame with the seeds of frameCount: tptTraceViewsKernel
     const f4* centres = nullptr;     // [batch][2] {x, y, z, -} of spheres 1 and 8 (Test.cpp:304-308): tptTraceAnimationKernel
+    // tptDrawDeviceKeyframeClip (with cams and a clip's planes, without centres): [batch][TPT_Q_KEYS_MAX] {x, y, z, -} of the keyCount spheres
+    // of keyMask (sphere i at bit 63 - i) in ascending index, unused entries zero: tptKeyframeKernel
+    const f4* keyCentres = nullptr;
+    unsigned long long keyMask = 0;
+    int keyCount = 0;
 };
 // The caller's first-hit planes of a single frame (tptDrawDeviceAov): device [h][w] f4 each, either may be null (not both); the launch
 // is tptTraceAovKernel, ordered behind everything enqueued on the context stream so far.

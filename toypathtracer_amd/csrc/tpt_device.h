@@ -82,6 +82,14 @@ struct KernelArgs {
     // int32 in device memory, read where a lane claims a pixel and clamped there to 0 .. 2047 (0: the pixel is not traced, nothing of it
     // is stored); fc.spp and fc.invSpp play no part.  The launch takes tptTraceAdaptiveKernel.  Null for every other launch.
     const int32_t* sampleCounts = nullptr;
+    // The frames of a clip whose spheres the CALLER moves, with their planes and a camera per frame (tptDrawDeviceKeyframeClip: keyCentres
+    // given with viewCams, aovSums and momentsOut, moveCentres null; the launch takes tptKeyframeKernel): batchFrames x TPT_Q_KEYS_MAX
+    // centres {x, y, z, -} in device memory, frame j's at keyCentres[TPT_Q_KEYS_MAX x j ..], one per moved sphere in ascending sphere
+    // index (unused entries zero).  keyMask: the moved spheres, sphere i (< 64) at bit 63 - i, keyCount (<= TPT_Q_KEYS_MAX) of them;
+    // launch-uniform.  Everything else is the camera clip's.  Null / 0 for every other launch.
+    const f4* keyCentres = nullptr;
+    unsigned long long keyMask = 0;
+    int keyCount = 0;
 };
 
 } // namespace tpt

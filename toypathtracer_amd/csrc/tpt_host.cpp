@@ -437,6 +437,14 @@ int tptShutdown(void)
         if (e) { (void)hipEventDestroy(e); e = nullptr; }
     (void)hipFree(g.dMoments); g.dMoments = nullptr;
     g.momentsBytes = 0;
+    (void)hipFree(g.dKeySph); g.dKeySph = nullptr;
+    if (g.hKeySph) (void)hipHostFree(g.hKeySph);
+    g.hKeySph = nullptr;
+    g.keySphBytes = 0;
+    for (int i = 0; i < 2; ++i) {
+        g.keySphCopied[i] = false;
+        if (g.evKeySph[i]) { (void)hipEventDestroy(g.evKeySph[i]); g.evKeySph[i] = nullptr; }
+    }
     (void)hipFree(g.dDenoise); g.dDenoise = nullptr;
     g.denoiseBytes = 0;
     if (g.hViewsStage) (void)hipHostFree(g.hViewsStage);

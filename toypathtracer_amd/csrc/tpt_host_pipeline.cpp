@@ -408,7 +408,9 @@ int ensureViewSlots()
 {
     if (g.dViews) return 0;
     // (a slot's table: the cameras, then the centres of a launch that takes both -- tptDrawDeviceCameraClip --, then the ray counters)
-    const size_t camBytes = kViewCamBytes, tableBytes = camBytes + 2 * sizeof(f4) * kMaxBatch, perSlot = tableBytes + sizeof(unsigned long long) * kMaxBatch;
+    // (the widest centres table: tptDrawDeviceKeyframeClip's, TPT_Q_KEYS_MAX centres per frame)
+    static_assert(TPT_Q_KEY_TABLE_BYTES >= 2 * sizeof(f4) * kMaxBatch && TPT_Q_KEY_TABLE_BYTES == TPT_Q_KEYS_MAX * sizeof(f4) * kMaxBatch, "one table area serves both kinds of centres");
+    const size_t camBytes = kViewCamBytes, tableBytes = camBytes + TPT_Q_KEY_TABLE_BYTES, perSlot = tableBytes + sizeof(unsigned long long) * kMaxBatch;
     static_assert(kViewCamBytes % 16 == 0, "the centres and the ray counters behind a slot's cameras stay aligned");
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dViews), perSlot * Context::kMaxSlots));
     if (hipHostMalloc(reinterpret_cast<void**>(&g.hViewsStage), tableBytes * Context::kMaxSlots, 0) != hipSuccess) {
@@ -472,6 +474,7 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
 {
     const CameraPOD* viewCams = table ? table->cams : nullptr;
     const f4* centres = table ? table->centres : nullptr;
+    const f4* keyCentres = table ? table->keyCentres : nullptr; // (tptDrawDeviceKeyframeClip: the caller's centres, beside the cameras)
     if (g.sceneDirty || (g.curSet < 0 && g.pendingSet < 0)) { // tptSetScene after the last tptUpdate
         int rc = stageScene();
         if (rc) return rc;
@@ -528,22 +531,31 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
     int rc = 0;
     a.viewCams = nullptr;
     a.moveCentres = nullptr;
+    a.keyCentres = nullptr;
+    a.keyMask = 0;
+    a.keyCount = 0;
     a.sampleCounts = aov ? aov->sampleCounts : nullptr; // (before chooseKernel: the context's spp plays no part in such a launch)
     if (table) {
         if ((rc = ensureViewSlots())) return rc;
         // (before chooseKernel: the views and animation kernels' LDS differs)
         if (viewCams) a.viewCams = g.views[P.slot].dev;
         if (centres) a.moveCentres = reinterpret_cast<const f4*>(reinterpret_cast<const char*>(g.views[P.slot].dev) + (viewCams ? kViewCamBytes : 0));
+        if (keyCentres) {
+            a.keyCentres = reinterpret_cast<const f4*>(reinterpret_cast<const char*>(g.views[P.slot].dev) + kViewCamBytes);
+            a.keyMask = table->keyMask;
+            a.keyCount = table->keyCount;
+        }
         frameRays = g.views[P.slot].rays; // every frame counts its own rays (the blends add them to the running total)
         rayStride = 1;
     }
     if ((rc = chooseKernel(P))) return rc;
     if (viewCams && !P.queued)
         return refuse("tptDrawDeviceViews: needs the path-queue kernel (per-pixel seeds, recursive fold, two-phase HitSpheres, at most 2047 spp)");
-    if (centres && (!P.queued || a.scene.nGroups > 0))
-        return refuse("tptDrawDeviceAnimation: one launch per batch needs the path-queue kernel and a flat scene");
-    const bool clip = aov && aov->moments && centres; // (the frames of an animated clip with their planes: tptTraceClipKernel, tptCameraClipKernel)
+    if ((centres || keyCentres) && (!P.queued || a.scene.nGroups > 0))
+        return refuse(std::string(keyCentres ? "tptDrawDeviceKeyframeClip" : "tptDrawDeviceAnimation") + ": one launch per batch needs the path-queue kernel and a flat scene");
+    const bool clip = aov && aov->moments && (centres || keyCentres); // (the frames of an animated clip with their planes: tptTraceClipKernel, tptCameraClipKernel, tptKeyframeKernel)
     if (viewCams && centres && !clip) return fail("enqueueTrace: a camera and the centres per frame go with a clip's planes");
+    if (keyCentres && (!clip || !viewCams || centres)) return fail("enqueueTrace: the caller's centres per frame go with a clip's cameras and planes");
     if (aov && (!P.queued || !(clip || (batch == 1 && !viewCams && !centres))))
         return refuse("tptDrawDeviceAov: needs the path-queue kernel (per-pixel seeds, recursive fold, two-phase HitSpheres, at most 2047 spp)");
     // a batch is traced by the path-queue kernel (per-pixel seeds) or, in the reference's own seed mode, by the lane-refill
@@ -610,16 +622,17 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
         }
     }
     if (clip) g.clipSeq++;
-    if (viewCams || centres) {
+    if (viewCams || centres || keyCentres) {
         // the launch's table, behind the same wait: the slot's previous launch has read its table; the previous copy out of the
         // slot's pinned staging (an earlier call on this slot) has left the host before the staging is overwritten
         static_assert(2 * sizeof(f4) * kMaxBatch <= sizeof(CameraPOD) * kMaxBatch, "a batch's moving centres fit the slot's camera table");
         Context::ViewSlot& V = g.views[slot];
-        const size_t camBytes = sizeof(CameraPOD) * (size_t)batch, centreBytes = 2 * sizeof(f4) * (size_t)batch;
-        const size_t bytes = viewCams && centres ? kViewCamBytes + centreBytes : (viewCams ? camBytes : centreBytes); // (both: one copy, the centres behind the whole camera table)
+        const f4* behind = keyCentres ? keyCentres : centres; // (the centres of this launch, of either kind)
+        const size_t camBytes = sizeof(CameraPOD) * (size_t)batch, centreBytes = (keyCentres ? (size_t)TPT_Q_KEYS_MAX : 2) * sizeof(f4) * (size_t)batch;
+        const size_t bytes = viewCams && behind ? kViewCamBytes + centreBytes : (viewCams ? camBytes : centreBytes); // (both: one copy, the centres behind the whole camera table)
         if (V.copyEnqueued) HIPCHK(hipEventSynchronize(V.evUploaded));
         if (viewCams) memcpy(V.stage, viewCams, camBytes);
-        if (centres) memcpy(reinterpret_cast<char*>(V.stage) + (viewCams ? kViewCamBytes : 0), centres, centreBytes);
+        if (behind) memcpy(reinterpret_cast<char*>(V.stage) + (viewCams ? kViewCamBytes : 0), behind, centreBytes);
         HIPCHK(hipMemcpyAsync(V.dev, V.stage, bytes, hipMemcpyHostToDevice, ts));
         HIPCHK(hipEventRecord(V.evUploaded, ts));
         V.copyEnqueued = true;
@@ -762,15 +775,71 @@ static CameraPOD viewCamera(CameraSetup cs, int w, int h)
 // own, as tptSetCamera(views[j]) before its tptUpdate leaves it (also written to outCameras[j], if given) --, then `perLaunch` frames per
 // launch.  A launch of several frames with `views` takes both tables (tptCameraClipKernel); when nothing moves, its centres table repeats
 // the scene's own centres of spheres 1 and 8: the kernel's exact tests read the same numbers from the table as from the scene.
+// Given `keys` (tptDrawDeviceKeyframeClip, with `views` and `planes`, never with `animate`): the motion is the caller's -- frame j has sphere
+// ids[k] at centres[(j * nMoved + k) * 3 ..].  A launch of several frames takes the cameras and a table of those centres
+// (tptKeyframeKernel: TPT_Q_KEYS_MAX per frame in ascending sphere index, the spheres named by a mask); frame by frame the spheres are set
+// and staged per frame.  Either way the context's spheres end at the launch's last frame and that scene is staged, as the animated path
+// leaves it.  `objects`: a plane of first-hit sphere indices per frame (tptObjectPlaneKernel over the frame's own {centre, r^2} array,
+// on the context stream).
 struct ClipPlanes {
     float *moments, *frameAlbedo, *frameNormalDepth, *frameMoments; // (deviceMoments, and the per-frame outputs or null)
 };
+struct KeyMotion {
+    int nMoved;
+    const int32_t* ids;
+    const float* centres;
+    int32_t* objects; // (deviceFrameObjects or null)
+};
+// The {centre, r^2} arrays of one launch's frames (f .. f + n - 1 of the call) for the object planes, filled into the next half of the
+// pinned twin and copied on the context stream (Context::dKeySph: two halves of `perLaunch` frames, whatever the call's length).  The
+// spheres that stand still are the context's, which the call never moves; the moved ones take the frame's centres.  `hf`: the half taken.
+static int uploadKeySpheres(int f, int n, int perLaunch, const KeyMotion& keys, int& hf)
+{
+    const size_t count = g.spheres.size(), half = sizeof(f4) * count * (size_t)perLaunch;
+    for (int i = 0; i < 2; ++i)
+        if (!g.evKeySph[i]) HIPCHK(hipEventCreateWithFlags(&g.evKeySph[i], kOrderingEvent));
+    if (half > g.keySphBytes) {
+        if (int rc = syncAllStreams()) return rc; // (an earlier call's object launches may still read the old arrays)
+        (void)hipFree(g.dKeySph);
+        if (g.hKeySph) (void)hipHostFree(g.hKeySph);
+        g.dKeySph = g.hKeySph = nullptr;
+        g.keySphBytes = 0;
+        g.keySphCopied[0] = g.keySphCopied[1] = false;
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dKeySph), 2 * half));
+        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&g.hKeySph), 2 * half, hipHostMallocDefault));
+        g.keySphBytes = half;
+    }
+    hf = (int)(g.keySphSeq++ & 1u);
+    if (g.keySphCopied[hf]) HIPCHK(hipEventSynchronize(g.evKeySph[hf])); // the half's previous copy has left the pinned twin
+    f4* const host = g.hKeySph + (size_t)hf * (g.keySphBytes / sizeof(f4));
+    for (int j = 0; j < n; ++j) {
+        f4* sph = host + count * (size_t)j;
+        for (size_t i = 0; i < count; ++i) sph[i] = f4{g.spheres[i].cx, g.spheres[i].cy, g.spheres[i].cz, g.spheres[i].radius * g.spheres[i].radius}; // (packScene's records)
+        for (int k = 0; k < keys.nMoved; ++k) {
+            const float* c = keys.centres + ((size_t)(f + j) * (size_t)keys.nMoved + (size_t)k) * 3;
+            f4& v = sph[keys.ids[k]];
+            v.x = c[0]; v.y = c[1]; v.z = c[2];
+        }
+    }
+    HIPCHK(hipMemcpyAsync(g.dKeySph + (size_t)hf * (g.keySphBytes / sizeof(f4)), host, sizeof(f4) * count * (size_t)n, hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipEventRecord(g.evKeySph[hf], g.stream));
+    g.keySphCopied[hf] = true;
+    return 0;
+}
 static int enqueueAnimation(int firstFrame, int nFrames, const float* times, int w, int h, float* deviceTile, float* deviceFrameImages,
                             int64_t* deviceFrameRays, unsigned testFlags, bool animate, int perLaunch, const ClipPlanes* planes,
-                            const float* views = nullptr, CameraPOD* outCameras = nullptr)
+                            const float* views = nullptr, CameraPOD* outCameras = nullptr, const KeyMotion* keys = nullptr)
 {
     int rc = g.pending.discard();
     if (rc) return rc;
+    // tptDrawDeviceKeyframeClip: the moved spheres as a mask and each one's place in a frame's table, the number of moved spheres below it
+    unsigned long long keyMask = 0;
+    int keySlot[TPT_Q_KEYS_MAX] = {};
+    if (keys && perLaunch > 1) {
+        for (int k = 0; k < keys->nMoved; ++k) keyMask |= 1ull << (63 - keys->ids[k]);
+        for (int k = 0; k < keys->nMoved; ++k)
+            for (int m = 0; m < keys->nMoved; ++m) keySlot[k] += keys->ids[m] < keys->ids[k] ? 1 : 0;
+    }
     // the camera as every tptUpdate of the sequence builds it (Test.cpp:309-313, 341)
     g.cam = viewCamera(g.camSetup, w, h);
     if (views) g.configEpoch++; // (as every tptSetCamera of the sequence)
@@ -778,6 +847,7 @@ static int enqueueAnimation(int firstFrame, int nFrames, const float* times, int
         const int n = nFrames - f < perLaunch ? nFrames - f : perLaunch;
         BatchTable table;
         f4 centres[2 * kMaxBatch];
+        f4 keyCentres[TPT_Q_KEYS_MAX * kMaxBatch];
         CameraPOD cams[kMaxBatch];
         if (views) {
             // each frame's camera; the context's camera ends at the launch's last view
@@ -789,7 +859,17 @@ static int enqueueAnimation(int firstFrame, int nFrames, const float* times, int
             g.cam = cams[n - 1];
             if (perLaunch > 1) {
                 table.cams = cams;
-                if (!animate) { // nothing moves: every frame's centres are the scene's own
+                if (keys) { // the caller's centres of the launch's frames
+                    memset(keyCentres, 0, sizeof keyCentres);
+                    for (int j = 0; j < n; ++j)
+                        for (int k = 0; k < keys->nMoved; ++k) {
+                            const float* c = keys->centres + ((size_t)(f + j) * (size_t)keys->nMoved + (size_t)k) * 3;
+                            keyCentres[TPT_Q_KEYS_MAX * j + keySlot[k]] = f4{c[0], c[1], c[2], 0.0f};
+                        }
+                    table.keyCentres = keyCentres;
+                    table.keyMask = keyMask;
+                    table.keyCount = keys->nMoved;
+                } else if (!animate) { // nothing moves: every frame's centres are the scene's own
                     const SpherePOD s1 = g.spheres[1], s8 = g.spheres[8];
                     for (int j = 0; j < n; ++j) {
                         centres[2 * j] = f4{s1.cx, s1.cy, s1.cz, 0.0f};
@@ -815,6 +895,16 @@ static int enqueueAnimation(int firstFrame, int nFrames, const float* times, int
             if (perLaunch > 1) table.centres = centres;
             if ((rc = stageScene())) return rc;
         }
+        if (keys && keys->nMoved > 0) {
+            // the context's spheres at the launch's last frame (frame by frame: at the frame), that scene staged: exact for the spheres that
+            // stand still, and the keyframe kernel reads the moved ones from the table and tests them for every ray (tpt_trace.h, keyedSphere)
+            for (int k = 0; k < keys->nMoved; ++k) {
+                const float* c = keys->centres + ((size_t)(f + n - 1) * (size_t)keys->nMoved + (size_t)k) * 3;
+                SpherePOD& sp = g.spheres[keys->ids[k]];
+                sp.cx = c[0]; sp.cy = c[1]; sp.cz = c[2];
+            }
+            if ((rc = stageScene())) return rc;
+        }
         TraceTicket T;
         AovPlanes aov; // (the launch's frames' planes in the caller's per-frame buffers)
         const size_t at = (size_t)f * (size_t)h * (size_t)w * 4;
@@ -825,6 +915,22 @@ static int enqueueAnimation(int firstFrame, int nFrames, const float* times, int
             aov.continues = f > 0;
         }
         if ((rc = enqueueTrace(firstFrame + f, w, h, testFlags, nullptr, T, n, 1, &table, planes ? &aov : nullptr))) return rc;
+        if (keys && keys->objects) { // the launch's frames' object planes, on the context stream in front of their blends
+            const size_t count = g.spheres.size();
+            int hf = 0;
+            if ((rc = uploadKeySpheres(f, n, perLaunch, *keys, hf))) return rc;
+            const size_t at0 = (size_t)hf * (g.keySphBytes / sizeof(f4));
+            for (int j = 0; j < n; ++j) {
+                const f4* host = g.hKeySph + at0 + count * (size_t)j;
+                tptObjectPlaneConsts k = {};
+                float c[12];
+                memcpy(c, &cams[j], sizeof c);
+                memcpy(k.o, c, 12); memcpy(k.ll, c + 3, 12); memcpy(k.H, c + 6, 12); memcpy(k.V, c + 9, 12);
+                if (count > 1) { k.c1[0] = host[1].x; k.c1[1] = host[1].y; k.c1[2] = host[1].z; }
+                if (count > 8) { k.c8[0] = host[8].x; k.c8[1] = host[8].y; k.c8[2] = host[8].z; }
+                HIPCHK(tptLaunchObjectPlane(g.dKeySph + at0 + count * (size_t)j, (int)count, keys->objects + (size_t)(f + j) * (size_t)w * (size_t)h, w, h, k, g.stream));
+            }
+        }
         // the blends, in frame order, each into the one tile with its frame's lerp factor (and the frame's moments behind it)
         if (T.valid && (rc = enqueuePlaneResolves(T, deviceTile, 0, true, deviceFrameImages ? deviceFrameImages + at : nullptr,
                                                   deviceFrameRays ? deviceFrameRays + f : nullptr, planes ? planes->moments : nullptr,
@@ -835,43 +941,80 @@ static int enqueueAnimation(int firstFrame, int nFrames, const float* times, int
 }
 
 // What tptDrawDeviceAnimationMoments and (`cameras`: a view per frame) tptDrawDeviceCameraClip share: the checks, in one order and with
-// the entry point's name, then enqueueAnimation with the planes.  A refused call has touched nothing.
+// the entry point's name, then enqueueAnimation with the planes.  A refused call has touched nothing.  `keys` (tptDrawDeviceKeyframeClip,
+// with `cameras`): the caller's motion in the place of `times`, its own checks behind the shared ones, and an eighth buffer, the object planes.
 static int drawClip(const char* name, int firstFrame, int nFrames, const float* times, bool cameras, const float* views, int w, int h,
                     float* deviceTile, const ClipPlanes& planes, float* deviceFrameImages, int64_t* deviceFrameRays, CameraPOD* outCameras,
-                    unsigned testFlags)
+                    unsigned testFlags, const KeyMotion* keys = nullptr)
 {
     const std::string fn = name;
     float* const deviceMoments = planes.moments;
     if (int rc_ = flushShardDeferred()) return rc_; // (see tptDrawDevice)
     if (requireInit()) return -1;
     if (nFrames < 1) return fail(fn + ": nFrames must be at least 1");
-    if (!times || (cameras && !views) || !deviceTile || !deviceMoments || w <= 0 || h <= 0)
-        return fail(fn + (cameras ? ": bad arguments (times, views, deviceTile, deviceMoments, size)" : ": bad arguments (times, deviceTile, deviceMoments, size)"));
-    const bool animate = (testFlags & TPT_FLAG_ANIMATE) && g.spheres.size() > 8; // (the tptUpdate guard, Test.cpp:304)
+    if ((!keys && !times) || (cameras && !views) || !deviceTile || !deviceMoments || w <= 0 || h <= 0)
+        return fail(fn + (keys ? ": bad arguments (views, deviceTile, deviceMoments, size)"
+                               : (cameras ? ": bad arguments (times, views, deviceTile, deviceMoments, size)" : ": bad arguments (times, deviceTile, deviceMoments, size)")));
+    if (keys) {
+        if (keys->nMoved < 0) return fail(fn + ": nMoved must not be negative");
+        if (keys->nMoved > 0 && (!keys->ids || !keys->centres)) return fail(fn + ": movedIds and centres are required with nMoved > 0");
+        if (testFlags & ~(unsigned)TPT_FLAG_PROGRESSIVE)
+            return fail(fn + ": TPT_FLAG_PROGRESSIVE is the only flag (the centres are the motion: TPT_FLAG_ANIMATE is not applied on top of them)");
+    }
+    const bool animate = !keys && (testFlags & TPT_FLAG_ANIMATE) && g.spheres.size() > 8; // (the tptUpdate guard, Test.cpp:304)
     // one launch per kMaxBatch frames on a flat scene: while it moves, or -- with a camera per frame, where the kernel takes a centres
-    // table anyway -- whenever it has the two spheres the table is about
+    // table anyway -- whenever it has the two spheres the table is about; with the caller's motion, when the table holds it: at most
+    // TPT_Q_KEYS_MAX moved spheres, all among the first 64 (the candidate mask of the filters' first chunk)
     const bool flat = g.spheres.size() < TPT_GROUP_MIN_SPHERES;
-    const int perLaunch = flat && (animate || (cameras && g.spheres.size() > 8)) ? kMaxBatch : 1;
+    int perLaunch = flat && (animate || (cameras && g.spheres.size() > 8)) ? kMaxBatch : 1;
+    if (keys) {
+        perLaunch = flat && keys->nMoved <= TPT_Q_KEYS_MAX ? kMaxBatch : 1;
+        for (int k = 0; k < keys->nMoved && k < TPT_Q_KEYS_MAX; ++k)
+            if (keys->ids[k] < 0 || keys->ids[k] >= 64) perLaunch = 1; // (an id outside the scene is refused below)
+    }
     int rc = checkPathQueueDraw(fn.c_str(), "clip planes are", w, h, kQueueKernel | kQueueSpp, [&] {
         const size_t plane = (size_t)h * (size_t)w * sizeof(f4), staged = 2 * plane * (size_t)(nFrames < perLaunch ? nFrames : perLaunch);
         if (staged > (4ull << 30))
             return refuse(fn + ": " + std::to_string(staged >> 20) + " MiB of frame colour and moments per launch: over the 4096 MiB limit");
         if (g.spheres.size() > 65534) return fail(fn + ": at most 65534 spheres (the path-queue kernel)");
-        // the seven buffers, each at its full extent: no two may share a byte
-        const struct { const void* p; size_t bytes; } bufs[7] = {
+        if (keys) {
+            const int count = (int)g.spheres.size();
+            if (keys->nMoved > count) return fail(fn + ": nMoved is larger than the sphere count");
+            std::vector<bool> seen((size_t)count, false);
+            for (int k = 0; k < keys->nMoved; ++k) {
+                if (keys->ids[k] < 0 || keys->ids[k] >= count) return fail(fn + ": a moved id lies outside 0 .. count - 1");
+                if (seen[(size_t)keys->ids[k]]) return fail(fn + ": a moved id is repeated");
+                seen[(size_t)keys->ids[k]] = true;
+            }
+            for (size_t i = 0; i < (size_t)nFrames * (size_t)keys->nMoved * 3; ++i)
+                if (!(fabsf(keys->centres[i]) <= 3.40282347e38f)) return fail(fn + ": a centre is not finite");
+            // the object planes are tptObjectPlaneDevice's over the call's cameras, and so is what it refuses of a camera
+            for (int j = 0; keys->objects && j < nFrames; ++j) {
+                const CameraPOD cam = viewCamera(viewSetup(views + 9 * (size_t)j), w, h);
+                float c[12];
+                memcpy(c, &cam, sizeof c);
+                for (int i = 0; i < 12; ++i)
+                    if (!(fabsf(c[i]) <= 3.40282347e38f))
+                        return fail(fn + ": deviceFrameObjects with a view whose camera has a non-finite origin, lowerLeftCorner, horizontal or vertical");
+            }
+        }
+        // the seven buffers (with the caller's motion eight: the object planes), each at its full extent: no two may share a byte
+        const struct { const void* p; size_t bytes; } bufs[8] = {
             {deviceTile, plane}, {deviceMoments, plane}, {deviceFrameImages, plane * (size_t)nFrames}, {planes.frameAlbedo, plane * (size_t)nFrames},
             {planes.frameNormalDepth, plane * (size_t)nFrames}, {planes.frameMoments, plane * (size_t)nFrames},
-            {deviceFrameRays, sizeof(int64_t) * (size_t)nFrames}};
-        for (int i = 0; i < 7; ++i)
-            for (int k = i + 1; k < 7; ++k) {
+            {deviceFrameRays, sizeof(int64_t) * (size_t)nFrames},
+            {keys ? keys->objects : nullptr, sizeof(int32_t) * (size_t)h * (size_t)w * (size_t)nFrames}};
+        for (int i = 0; i < 8; ++i)
+            for (int k = i + 1; k < 8; ++k) {
                 const uintptr_t a = reinterpret_cast<uintptr_t>(bufs[i].p), b = reinterpret_cast<uintptr_t>(bufs[k].p);
                 if (a && b && a < b + bufs[k].bytes && b < a + bufs[i].bytes) return fail(fn + ": two of the tile, moments and per-frame buffers overlap");
             }
         return 0;
     });
     if (rc) return rc;
+    if (keys && keys->objects && !tptLaunchObjectPlane) return fail(fn + ": this build has no object plane kernel");
     return enqueueAnimation(firstFrame, nFrames, times, w, h, deviceTile, deviceFrameImages, deviceFrameRays, testFlags, animate, perLaunch, &planes,
-                            views, outCameras);
+                            views, outCameras, keys);
 }
 
 } // namespace tpth
@@ -1078,6 +1221,23 @@ int tptDrawDeviceCameraClip(int firstFrame, int nFrames, const float* times, con
     const ClipPlanes planes{deviceMoments, deviceFrameAlbedo, deviceFrameNormalDepth, deviceFrameMoments};
     return drawClip("tptDrawDeviceCameraClip", firstFrame, nFrames, times, true, views, w, h, deviceTile, planes, deviceFrameImages,
                     deviceFrameRays, static_cast<CameraPOD*>(outCameras), testFlags);
+}
+
+// tptDrawDeviceCameraClip with the motion given by the CALLER: frame j as tptSetScene(S_j), tptSetCamera(views[j]), tptUpdate(0, firstFrame
+// + j, ...) and tptDrawDeviceMoments trace it -- the same bits, the same ray counts --, S_j the context's spheres with the centres of
+// movedIds replaced by frame j's.  Up to kMaxBatch frames per launch (tptKeyframeKernel: the cameras beside a table of the moved centres,
+// the moved spheres named by a mask and tested for every ray) on a flat scene with at most TPT_Q_KEYS_MAX moved spheres among the first
+// 64; everything else goes frame by frame through the single-frame moments kernel with the spheres and the camera set per frame.  The
+// object planes are tptObjectPlaneKernel's over one {centre, r^2} array per frame.  The context is left as the sequence leaves it.
+int tptDrawDeviceKeyframeClip(int firstFrame, int nFrames, const float* views, int nMoved, const int32_t* movedIds, const float* centres, int w,
+                              int h, float* deviceTile, float* deviceMoments, float* deviceFrameImages, float* deviceFrameAlbedo,
+                              float* deviceFrameNormalDepth, float* deviceFrameMoments, int64_t* deviceFrameRays, int32_t* deviceFrameObjects,
+                              void* outCameras, unsigned testFlags)
+{
+    const ClipPlanes planes{deviceMoments, deviceFrameAlbedo, deviceFrameNormalDepth, deviceFrameMoments};
+    const KeyMotion keys{nMoved, movedIds, centres, deviceFrameObjects};
+    return drawClip("tptDrawDeviceKeyframeClip", firstFrame, nFrames, nullptr, true, views, w, h, deviceTile, planes, deviceFrameImages,
+                    deviceFrameRays, static_cast<CameraPOD*>(outCameras), testFlags, &keys);
 }
 
 // One frame blended into the tile exactly as tptDrawDevice blends it (same bits, same ray count), plus the first-hit planes of its

@@ -1587,8 +1587,12 @@ __device__ __forceinline__ int hitSpheresGroupedDeal(const SceneView& sv, bool g
 // CAMERAS (with BATCH + MOVING + AOV + MOMENTS; tptDrawDeviceCameraClip): the clip kernel with a camera per frame -- a.viewCams[j] staged
 // in LDS beside the centres, read where a sample starts like a view's; the seeds stay those of frame fc.frame + j (MOVING's rule, not
 // VIEWS'), and everything else is the clip kernel's.  Its own kernel (tptCameraClipKernel) for the same reason.
+// KEYS (with CAMERAS; tptDrawDeviceKeyframeClip): the camera-clip kernel with the CALLER's motion -- up to TPT_Q_KEYS_MAX of the first 64
+// spheres, named by the launch-uniform mask a.keyMask, at the centres a.keyCentres[TPT_Q_KEYS_MAX j ..] (staged in LDS at that fixed
+// stride) wherever MOVING reads the centres of spheres 1 and 8, and candidates of every ray in their place (tpt_trace.h, keyedSphere).
+// Its own kernel (tptKeyframeKernel) for the same reason.
 template <bool LDS_SCENE, bool BATCH, bool VIEWS = false, bool MOVING = false, bool AOV = false, bool MOMENTS = false, bool ADAPTIVE = false,
-          bool CAMERAS = false>
+          bool CAMERAS = false, bool KEYS = false>
 __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1602,9 +1606,11 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     static_assert(!MOMENTS || AOV, "moments are summed beside the first-hit sums");
     static_assert(!ADAPTIVE || (MOMENTS && !BATCH), "a count per pixel belongs to a single frame with its moments");
     static_assert(!CAMERAS || (BATCH && MOVING && AOV && MOMENTS && !VIEWS && !ADAPTIVE), "a camera per frame belongs to the frames of a clip with their planes");
+    static_assert(!KEYS || CAMERAS, "the caller's centres per frame belong to the frames of a clip with their cameras and planes");
     constexpr bool CAM_TABLE = VIEWS || CAMERAS; // (the cameras of the batch's frames in LDS)
+    constexpr int kMovedPerFrame = KEYS ? TPT_Q_KEYS_MAX : 2; // (MOVING: centres per frame in the table)
     constexpr int kPaths = (LDS_SCENE ? TPT_Q_PATHS : TPT_Q_PATHS_GROUPED) - (CAM_TABLE ? TPT_Q_VIEW_PATHS : 0) -
-                           (MOVING ? TPT_Q_ANIM_PATHS : 0); // paths this workgroup owns
+                           (MOVING ? (KEYS ? TPT_Q_KEY_PATHS : TPT_Q_ANIM_PATHS) : 0); // paths this workgroup owns
     constexpr int kOffSt = LDS_SCENE ? TPT_Q_SPH_FIXED : 0;
     constexpr int kOffQ = kOffSt + TPT_Q_NF4 * kPaths * 16;
     constexpr int kOffCtl = kOffQ + Q_COUNT * TPT_Q_P * 2;
@@ -1613,7 +1619,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     constexpr int kOffFc = kOffDeal + kDealBytes;
     constexpr int kOffCams = kOffFc + (((int)sizeof(FrameConsts) + 15) & ~15);
     constexpr int kOffMoved = kOffCams + (CAM_TABLE ? TPT_Q_VIEW_CAM_BYTES : 0);
-    constexpr int kOffScene = kOffMoved + (MOVING ? TPT_Q_ANIM_TABLE_BYTES : 0);
+    constexpr int kOffScene = kOffMoved + (MOVING ? (KEYS ? TPT_Q_KEY_TABLE_BYTES : TPT_Q_ANIM_TABLE_BYTES) : 0);
     f4* st = reinterpret_cast<f4*>(smem + kOffSt);
     LdsRing q = (LdsRing)(smem + kOffQ);
     QueueCtl* ctl = reinterpret_cast<QueueCtl*>(smem + kOffCtl);
@@ -1621,7 +1627,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     // ~30 SGPRs held (and spilled) across the whole loop
     FrameConsts* ldsFc = reinterpret_cast<FrameConsts*>(smem + kOffFc);
     CameraPOD* ldsCams = reinterpret_cast<CameraPOD*>(smem + kOffCams); // (VIEWS, CAMERAS: the cameras of the batch's views / frames)
-    f4* ldsMoved = reinterpret_cast<f4*>(smem + kOffMoved);              // (MOVING: the centres of spheres 1 and 8, two per frame)
+    f4* ldsMoved = reinterpret_cast<f4*>(smem + kOffMoved);              // (MOVING: the centres of spheres 1 and 8, two per frame; KEYS: of the keyed spheres, TPT_Q_KEYS_MAX per frame)
     const LdsMovedPtr movedLds = (LdsMovedPtr)ldsMoved;                  // (... as the readers take them)
     const int nPad = a.scene.nPairs * 2;
     const bool sphFixed = LDS_SCENE && nPad * 16 <= TPT_Q_SPH_FIXED;
@@ -1697,7 +1703,8 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
         for (int i = tid; i < a.batchFrames * (int)(sizeof(CameraPOD) / 4); i += TPT_Q_T)
             reinterpret_cast<uint32_t*>(ldsCams)[i] = reinterpret_cast<const uint32_t*>(a.viewCams)[i];
     if (MOVING)
-        for (int i = tid; i < a.batchFrames * 2; i += TPT_Q_T) ldsMoved[i] = a.moveCentres[i];
+        for (int i = tid; i < a.batchFrames * kMovedPerFrame; i += TPT_Q_T) ldsMoved[i] = KEYS ? a.keyCentres[i] : a.moveCentres[i];
+    const uint64_t keyMask = KEYS ? (uint64_t)a.keyMask : 0ull; // (KEYS: the moved spheres, sphere i at bit 63 - i)
     // every path starts in the FREE queue; all other queues empty (sentinel everywhere)
     for (int i = tid; i < Q_COUNT * TPT_Q_P; i += TPT_Q_T) q[i] = (unsigned short)(i < kPaths ? i : 0xFFFF);
     if (tid < 8) {
@@ -1831,9 +1838,9 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
         QLambert lam;
         lam.sdir = lam.nl = lam.albedo = lam.lightE = mk3(0, 0, 0);
         lam.cosAMax = 0.0f;
-        int movedAt = 0; // MOVING: where the centres of this path's frame start in ldsMoved (2 x its frame of the batch)
+        int movedAt = 0; // MOVING: where the centres of this path's frame start in ldsMoved (kMovedPerFrame x its frame of the batch)
         if (pick != Q_FREE && mine) {
-            if (MOVING) movedAt = 2 * (int)(f2u(colSum[p].w) >> 26);
+            if (MOVING) movedAt = kMovedPerFrame * (int)(f2u(colSum[p].w) >> 26);
             const f4 r0 = st[0 * kPaths + p], r1 = st[1 * kPaths + p];
             ro = mk3(r0.x, r0.y, r0.z);
             rng = f2u(r0.w);
@@ -1910,7 +1917,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                 colSum[p] = mk4(0.0f, 0.0f, 0.0f, u2f(where));
                 if (AOV) aovSum()[0] = aovSum()[1] = mk4(0.0f, 0.0f, 0.0f, 0.0f);
                 if (MOMENTS) aovSum()[2] = mk4(0.0f, 0.0f, ADAPTIVE ? u2f(laneCount) : 0.0f, 0.0f);
-                if (MOVING) movedAt = 2 * laneFrame;
+                if (MOVING) movedAt = kMovedPerFrame * laneFrame;
                 if (CAM_TABLE)
                     qCameraView(ldsCams[laneFrame], *ldsFc, px, py, rng, ro, rd);
                 else
@@ -1973,7 +1980,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
         } else if (pick == Q_DIEL) {
             if (mine) {
                 f3 e;
-                rd = qDielectric<MOVING>(sv, fc, ro, rd, recId, doMatE, rng, e, movedLds + movedAt);
+                rd = qDielectric<MOVING, KEYS>(sv, fc, ro, rd, recId, doMatE, rng, e, movedLds + movedAt, keyMask);
                 qStackPush(stack, depth, e, -1);
                 depth++;
                 doMatE = true; // Test.cpp:214
@@ -1982,7 +1989,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
         } else if (pick == Q_METAL) {
             if (mine) {
                 f3 e, nd;
-                if (qMetal<MOVING>(sv, fc, ro, rd, recId, doMatE, rng, e, nd, movedLds + movedAt)) {
+                if (qMetal<MOVING, KEYS>(sv, fc, ro, rd, recId, doMatE, rng, e, nd, movedLds + movedAt, keyMask)) {
                     qStackPush(stack, depth, e, recId);
                     depth++;
                     doMatE = true;
@@ -1994,7 +2001,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
             }
         } else { // Q_LAMBERT
             if (mine) {
-                qLambertBegin<MOVING>(sv, ro, rd, recId, rng, lam, movedLds + movedAt);
+                qLambertBegin<MOVING, KEYS>(sv, ro, rd, recId, rng, lam, movedLds + movedAt, keyMask);
                 ray = true;
             }
         }
@@ -2031,7 +2038,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                     lightId = (int)f2u(l1.w);
                     go = ray && lightId != recId; // Test.cpp:100: not the sphere itself
                     if (go) {
-                        const f4 l0 = MOVING ? movedSphere(sv.lights[j * 2], lightId, movedLds + movedAt) : sv.lights[j * 2];
+                        const f4 l0 = MOVING ? movedOrKeyedSphere<KEYS>(sv.lights[j * 2], lightId, movedLds + movedAt, keyMask) : sv.lights[j * 2];
                         d2 = qLightRay(l0, ro, rng, lam.cosAMax, (sv.flags & SCENE_LIGHT_R2_DIV_SAFE) != 0);
                     }
                 }
@@ -2059,11 +2066,11 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
 #endif
 #if TPT_MATRIX_FILTER
                     if (LDS_SCENE && useMatrix)
-                        id = hitSpheresCandidates<MOVING>(svM, cand, ro, d2, TPT_MIN_T, TPT_MAX_T, t, movedLds + movedAt);
+                        id = hitSpheresCandidates<MOVING, KEYS>(svM, cand, ro, d2, TPT_MIN_T, TPT_MAX_T, t, movedLds + movedAt, keyMask);
                     else
 #endif
                     if (MOVING) // (a flat scene: what hitSpheres runs for it, with the frame's centres)
-                        id = hitSpheresTwoPhase<true>(sv, ro, d2, TPT_MIN_T, TPT_MAX_T, t, movedLds + movedAt);
+                        id = hitSpheresTwoPhase<true, KEYS>(sv, ro, d2, TPT_MIN_T, TPT_MAX_T, t, movedLds + movedAt, keyMask);
                     else
                         id = hitSpheres<LDS_SCENE ? HS_TWO_PHASE : HS_TWO_PHASE_GROUPS>(sv, ro, d2, TPT_MIN_T, TPT_MAX_T, t);
                     if (BATCH) iterRays++; else myRays++;
@@ -2087,7 +2094,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                     // a camera ray's nearest hit (every bounce ray has depth >= 1 here): add the sample's albedo, coverage, normal (the
                     // class code's qNormal, Maths.cpp:196-197, on a moving sphere with its frame's centre) and t.  A miss adds zeros:
                     // nothing to do.
-                    const f3 nrm = qNormal<MOVING>(sv, hitId, ro, movedLds + movedAt);
+                    const f3 nrm = qNormal<MOVING, KEYS>(sv, hitId, ro, movedLds + movedAt, keyMask);
                     const f4 m0 = sv.mats[hitId * 3];
                     f4* sum = aovSum();
                     const f4 s0 = sum[0], s1 = sum[1];
@@ -2215,21 +2222,21 @@ tptTraceQueueKernel<false, true>(const KernelArgs a)
 // The variants of traceQueueBody beyond <LDS_SCENE, BATCH>, from one list.  Each is a kernel of its own, not another template argument of
 // tptTraceQueueKernel: names and code of the existing kernels stay (tests look them up by name).  <false>: no scene in LDS -- grouped scenes
 // and flat scenes whose arrays stay in global memory (the moving variants take flat scenes only) --, with the grouped register cap.
-enum { QF_BATCH = 1, QF_VIEWS = 2, QF_MOVING = 4, QF_AOV = 8, QF_MOMENTS = 16, QF_ADAPTIVE = 32, QF_CAMERAS = 64 };
+enum { QF_BATCH = 1, QF_VIEWS = 2, QF_MOVING = 4, QF_AOV = 8, QF_MOMENTS = 16, QF_ADAPTIVE = 32, QF_CAMERAS = 64, QF_KEYS = 128 };
 #define TPT_QUEUE_VARIANT_KERNEL(NAME, F)                                                                                                    \
     template <bool LDS_SCENE>                                                                                                                \
     __global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute__((amdgpu_num_vgpr(TPT_Q_MAX_VGPR)))                    \
     NAME(const KernelArgs a)                                                                                                                 \
     {                                                                                                                                        \
         traceQueueBody<LDS_SCENE, ((F) & QF_BATCH) != 0, ((F) & QF_VIEWS) != 0, ((F) & QF_MOVING) != 0, ((F) & QF_AOV) != 0, ((F) & QF_MOMENTS) != 0, \
-                       ((F) & QF_ADAPTIVE) != 0, ((F) & QF_CAMERAS) != 0>(a);                                                                \
+                       ((F) & QF_ADAPTIVE) != 0, ((F) & QF_CAMERAS) != 0, ((F) & QF_KEYS) != 0>(a);                                                             \
     }                                                                                                                                        \
     template <>                                                                                                                              \
     __global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute__((amdgpu_num_vgpr(TPT_Q_MAX_VGPR_GROUPED)))            \
     NAME<false>(const KernelArgs a)                                                                                                          \
     {                                                                                                                                        \
         traceQueueBody<false, ((F) & QF_BATCH) != 0, ((F) & QF_VIEWS) != 0, ((F) & QF_MOVING) != 0, ((F) & QF_AOV) != 0, ((F) & QF_MOMENTS) != 0, \
-                       ((F) & QF_ADAPTIVE) != 0, ((F) & QF_CAMERAS) != 0>(a);                                                                \
+                       ((F) & QF_ADAPTIVE) != 0, ((F) & QF_CAMERAS) != 0, ((F) & QF_KEYS) != 0>(a);                                                             \
     }
 TPT_QUEUE_VARIANT_KERNEL(tptTraceViewsKernel, QF_BATCH | QF_VIEWS)                           // tptDrawDeviceViews: several views of one frame, a camera per frame of the batch
 TPT_QUEUE_VARIANT_KERNEL(tptTraceAnimationKernel, QF_BATCH | QF_MOVING)                      // tptDrawDeviceAnimation: frames of an animated scene, spheres 1 and 8 where each frame has them
@@ -2238,6 +2245,7 @@ TPT_QUEUE_VARIANT_KERNEL(tptTraceMomentsKernel, QF_AOV | QF_MOMENTS)            
 TPT_QUEUE_VARIANT_KERNEL(tptTraceClipKernel, QF_BATCH | QF_MOVING | QF_AOV | QF_MOMENTS)     // tptDrawDeviceAnimationMoments: the animation kernel plus the moments kernel's per-path sums
 TPT_QUEUE_VARIANT_KERNEL(tptTraceAdaptiveKernel, QF_AOV | QF_MOMENTS | QF_ADAPTIVE)             // tptDrawDeviceAdaptive: the moments kernel with each pixel's sample count from a plane
 TPT_QUEUE_VARIANT_KERNEL(tptCameraClipKernel, QF_BATCH | QF_MOVING | QF_AOV | QF_MOMENTS | QF_CAMERAS) // tptDrawDeviceCameraClip: the clip kernel with a camera per frame (not "tptTrace...": tests count those names)
+TPT_QUEUE_VARIANT_KERNEL(tptKeyframeKernel, QF_BATCH | QF_MOVING | QF_AOV | QF_MOMENTS | QF_CAMERAS | QF_KEYS) // tptDrawDeviceKeyframeClip: the camera-clip kernel with the caller's centres per frame (a name without the words tests count kernels by)
 #undef TPT_QUEUE_VARIANT_KERNEL
 
 #if defined(TPT_TEST_HOOKS)
@@ -2506,6 +2514,7 @@ hipError_t tptLaunchTraceQueue(const KernelArgs& a, bool ldsScene, int blocks, s
         /* QV_MOMENTS   */ {tptTraceMomentsKernel<false>, tptTraceMomentsKernel<true>},
         /* QV_CLIP      */ {tptTraceClipKernel<false>, tptTraceClipKernel<true>},
         /* QV_ADAPTIVE  */ {tptTraceAdaptiveKernel<false>, tptTraceAdaptiveKernel<true>},
+        /* QV_KEYFRAME_CLIP */ {tptKeyframeKernel<false>, tptKeyframeKernel<true>},
         /* QV_CAMERA_CLIP */ {tptCameraClipKernel<false>, tptCameraClipKernel<true>},
     };
     const QueueVariant variant = tptQueueVariant(a);

@@ -80,6 +80,11 @@ static_assert(TPT_GROUP_DEAL_ENTRIES >= TPT_GROUP_DEAL_CAP, "the flat variants' 
 #define TPT_Q_ANIM_TABLE_BYTES (TPT_Q_VIEWS_MAX * 2 * 16)
 #define TPT_Q_ANIM_PATHS ((TPT_Q_ANIM_TABLE_BYTES + TPT_Q_NF4 * 16 - 1) / (TPT_Q_NF4 * 16))
 // A camera per frame of a clip (tptCameraClipKernel): both tables, in the place of TPT_Q_VIEW_PATHS + TPT_Q_ANIM_PATHS path records.
+// A clip whose spheres the caller moves (tptKeyframeKernel): the cameras, and each frame's centres of up to TPT_Q_KEYS_MAX moved spheres at
+// a fixed stride of TPT_Q_KEYS_MAX entries per frame (32 x 8 x 16 B = 4096 B) in the place of 64 path records, on top of the cameras' 44.
+#define TPT_Q_KEYS_MAX 8
+#define TPT_Q_KEY_TABLE_BYTES (TPT_Q_VIEWS_MAX * TPT_Q_KEYS_MAX * 16)
+#define TPT_Q_KEY_PATHS ((TPT_Q_KEY_TABLE_BYTES + TPT_Q_NF4 * 16 - 1) / (TPT_Q_NF4 * 16))
 #ifndef TPT_Q_PATHS_GROUPED
 // ... and of the instantiation for GROUPED scenes (no scene staging, no matrix-filter table): 608.  The LDS the smaller pool frees holds
 // the entry areas of the three-stage dealing (640 entries per wave) and the groups' bounding spheres (pair records, 144 B per super-group
@@ -125,6 +130,8 @@ static_assert(2 * (kQueueLdsFixedPart + kDefaultSceneLds + 256) <= 160 * 1024, "
 static_assert(TPT_Q_VIEW_CAM_BYTES <= TPT_Q_NF4 * TPT_Q_VIEW_PATHS * 16, "the views' cameras take no more LDS than the path records they replace");
 static_assert(sizeof(tpt::CameraPOD) == 88 && sizeof(tpt::CameraPOD) % 4 == 0, "cameras are staged in LDS as 22 words");
 static_assert(TPT_Q_ANIM_TABLE_BYTES == TPT_Q_NF4 * TPT_Q_ANIM_PATHS * 16, "the moving centres take exactly the LDS of the path records they replace");
+static_assert(TPT_Q_KEY_TABLE_BYTES == TPT_Q_NF4 * TPT_Q_KEY_PATHS * 16 && TPT_Q_KEY_PATHS == 64, "the keyed centres take exactly the LDS of the 64 path records they replace");
+static_assert(TPT_Q_KEYS_MAX <= 64 && TPT_Q_VIEW_PATHS + TPT_Q_KEY_PATHS < TPT_Q_PATHS_GROUPED, "a keyed sphere's slot is a popcount of the 64-bit mask; path records are left");
 
 // Which pixel a work item of a launch is (both trace kernels).
 // idx -> pixel.  Returns false for padding slots of partially covered tiles.
@@ -149,9 +156,15 @@ TPT_HD int globalRowToLocal(const KernelArgs& a, int gy) { return shardKernelGlo
 
 // Which variant of the path-queue kernel a launch takes: what its argument block holds decides, here and nowhere else.  QV_INVALID: a
 // combination no entry point builds (tptLaunchTraceQueue refuses it).
-enum QueueVariant { QV_FRAME, QV_BATCH, QV_VIEWS, QV_ANIMATION, QV_AOV, QV_MOMENTS, QV_CLIP, QV_ADAPTIVE, QV_CAMERA_CLIP, QV_INVALID };
+enum QueueVariant { QV_FRAME, QV_BATCH, QV_VIEWS, QV_ANIMATION, QV_AOV, QV_MOMENTS, QV_CLIP, QV_ADAPTIVE, QV_KEYFRAME_CLIP, QV_CAMERA_CLIP, QV_INVALID };
 inline QueueVariant tptQueueVariant(const tpt::KernelArgs& a)
 {
+    if (a.keyCentres) { // (tptDrawDeviceKeyframeClip: 1 .. TPT_Q_VIEWS_MAX frames of the batch with their planes, a camera and the keyed centres per frame, a flat scene)
+        if (a.batchFrames < 1 || a.batchFrames > TPT_Q_VIEWS_MAX || a.scene.nGroups > 0 || !a.viewCams || a.moveCentres || a.sampleCounts || !a.aovSums ||
+            !a.momentsOut || a.keyCount < 0 || a.keyCount > TPT_Q_KEYS_MAX)
+            return QV_INVALID;
+        return QV_KEYFRAME_CLIP;
+    }
     if (a.sampleCounts) { // (tptDrawDeviceAdaptive: a single frame with its planes and moments, a sample count per pixel)
         if (a.batchFrames != 1 || a.viewCams || a.moveCentres || !a.aovSums || !a.momentsOut) return QV_INVALID;
         return QV_ADAPTIVE;
@@ -194,9 +207,10 @@ inline size_t tptQueueLdsBytes(const tpt::KernelArgs& a, bool ldsScene)
     using namespace tpt;
     const int nPad = a.scene.nPairs * 2;
     const QueueVariant variant = tptQueueVariant(a);
-    const bool views = variant == QV_VIEWS || variant == QV_CAMERA_CLIP; // (tptTraceViewsKernel: the cameras in LDS, TPT_Q_VIEW_PATHS path records fewer)
+    const bool views = variant == QV_VIEWS || variant == QV_CAMERA_CLIP || variant == QV_KEYFRAME_CLIP; // (tptTraceViewsKernel: the cameras in LDS, TPT_Q_VIEW_PATHS path records fewer)
     const bool moving = variant == QV_ANIMATION || variant == QV_CLIP || variant == QV_CAMERA_CLIP; // (tptTraceAnimationKernel: the centres in LDS, TPT_Q_ANIM_PATHS path records fewer)
-    // (tptCameraClipKernel: both tables, in the place of both shares of path records)
+    // (tptCameraClipKernel: both tables, in the place of both shares of path records; tptKeyframeKernel: the cameras and the keyed centres,
+    //  in the place of TPT_Q_VIEW_PATHS + TPT_Q_KEY_PATHS path records)
     // (tptTraceAovKernel, tptTraceMomentsKernel, tptTraceAdaptiveKernel and tptTraceClipKernel, a.aovSums: the LDS of their twin without
     //  planes -- their sums live in global memory; tptCameraClipKernel likewise)
     size_t bytes = 0;
@@ -205,6 +219,7 @@ inline size_t tptQueueLdsBytes(const tpt::KernelArgs& a, bool ldsScene)
     bytes += (size_t)TPT_Q_NF4 * (ldsScene ? TPT_Q_PATHS : TPT_Q_PATHS_GROUPED) * 16 + (size_t)Q_COUNT * TPT_Q_P * 2 + ((sizeof(QueueCtl) + 63) & ~(size_t)63) + ((sizeof(FrameConsts) + 15) & ~(size_t)15);
     if (views) bytes += (size_t)TPT_Q_VIEW_CAM_BYTES - (size_t)TPT_Q_NF4 * TPT_Q_VIEW_PATHS * 16;
     if (moving) bytes += (size_t)TPT_Q_ANIM_TABLE_BYTES - (size_t)TPT_Q_NF4 * TPT_Q_ANIM_PATHS * 16;
+    if (variant == QV_KEYFRAME_CLIP) bytes += (size_t)TPT_Q_KEY_TABLE_BYTES - (size_t)TPT_Q_NF4 * TPT_Q_KEY_PATHS * 16;
     if (!ldsScene && TPT_GROUP_DEAL) bytes += (size_t)TPT_Q_WAVES * TPT_GROUP_DEAL_WAVE_BYTES;
     if (!ldsScene && a.ldsGroupPairs > 0) bytes += 16 + (size_t)(a.ldsGroupPairs / (TPT_SUPER / 2)) * TPT_GPAIR_LDS_STRIDE * 4; // the groups' bounds for the second filter level (tptQueueGroupPairsInLds), padded stride
 #if TPT_MATRIX_FILTER

@@ -194,6 +194,25 @@ TPT_HD f4 movedSphere(f4 s, int id, LdsMovedPtr moved)
     }
     return s;
 }
+// tptDrawDeviceKeyframeClip (tptKeyframeKernel): the same with a caller-chosen set of up to 8 of the first 64 spheres instead of the pair
+// {1, 8}.  `keys` is launch-uniform and holds sphere i at bit 63 - i -- the candidate mask's layout, so it is OR-ed into the mask where
+// TPT_MOVED_CANDIDATES is --, `moved` points at the path's frame's centres, one per moved sphere in ascending index: a sphere's slot is
+// the number of moved spheres below it, the popcount of the mask above its bit.  The argument above does not ask which spheres move.
+TPT_HD f4 keyedSphere(f4 s, int id, LdsMovedPtr moved, uint64_t keys)
+{
+    if ((unsigned)id < 64u && ((keys << id) >> 63) != 0ull) {
+        const f4 c = moved[__builtin_popcountll((keys >> 1) >> (63 - id))];
+        s.x = c.x;
+        s.y = c.y;
+        s.z = c.z;
+    }
+    return s;
+}
+template <bool KEYS>
+TPT_HD f4 movedOrKeyedSphere(f4 s, int id, LdsMovedPtr moved, uint64_t keys)
+{
+    return KEYS ? keyedSphere(s, id, moved, keys) : movedSphere(s, id, moved);
+}
 
 TPT_HD int hitSpheresSimple(const SceneView& sv, f3 o, f3 d, float tMin, float tMax, float& outT)
 {
@@ -338,9 +357,9 @@ __shared__ unsigned long long g_hsLds[4]; // per-workgroup sums, flushed to g_tp
 #define TPT_HS_TRIP() do { } while (0)
 #define TPT_HS_ADD(a, b, c) do { } while (0)
 #endif
-// MOVED: tptTraceAnimationKernel (movedSphere)
-template <bool MOVED = false>
-TPT_HD int hitSpheresTwoPhase(const SceneView& sv, f3 o, f3 d, float tMin, float tMax, float& outT, LdsMovedPtr moved = nullptr)
+// MOVED: tptTraceAnimationKernel (movedSphere); with KEYS: tptKeyframeKernel (keyedSphere)
+template <bool MOVED = false, bool KEYS = false>
+TPT_HD int hitSpheresTwoPhase(const SceneView& sv, f3 o, f3 d, float tMin, float tMax, float& outT, LdsMovedPtr moved = nullptr, uint64_t keys = 0)
 {
     float hitT = tMax;
     int id = -1;
@@ -354,7 +373,7 @@ TPT_HD int hitSpheresTwoPhase(const SceneView& sv, f3 o, f3 d, float tMin, float
         (void)hsTrips_;
         TPT_HS_STAMP(t0_);
         uint64_t cand = phase1Chunk(pairPtr(sv.pairs + (size_t)pb * 8), cnt, ox, oy, oz, dx, dy, dz);
-        if (MOVED && pb == 0) cand |= TPT_MOVED_CANDIDATES; // (a scene that animates has more than 8 spheres)
+        if (MOVED && pb == 0) cand |= KEYS ? keys : TPT_MOVED_CANDIDATES; // (a scene that animates has more than 8 spheres; a keyed id is one of its scene's)
         TPT_HS_STAMP(t1_);
         while (cand) {
             int k = __builtin_clzll(cand);
@@ -362,7 +381,7 @@ TPT_HD int hitSpheresTwoPhase(const SceneView& sv, f3 o, f3 d, float tMin, float
             int i = pb * 2 + k;
             TPT_STAT(ST_PHASE2);
             TPT_HS_TRIP();
-            testSphere(MOVED ? movedSphere(sv.sph4[i], i, moved) : sv.sph4[i], i, o, d, tMin, hitT, id);
+            testSphere(MOVED ? movedOrKeyedSphere<KEYS>(sv.sph4[i], i, moved, keys) : sv.sph4[i], i, o, d, tMin, hitT, id);
         }
         TPT_HS_STAMP(t2_);
         TPT_HS_ADD(t0_, t1_, t2_);
@@ -634,21 +653,22 @@ __device__ __forceinline__ uint64_t phase1MatrixH(const uint32_t* ldsA, int R1, 
 }
 #endif
 // phase 2 over a candidate mask (sphere p at bit 63 - p): the reference's arithmetic, ascending index
-template <bool MOVED = false> // (tptTraceAnimationKernel: movedSphere)
-TPT_HD int hitSpheresCandidates(const SceneView& sv, uint64_t cand, f3 o, f3 d, float tMin, float tMax, float& outT, LdsMovedPtr moved = nullptr)
+template <bool MOVED = false, bool KEYS = false> // (tptTraceAnimationKernel: movedSphere; tptKeyframeKernel: keyedSphere)
+TPT_HD int hitSpheresCandidates(const SceneView& sv, uint64_t cand, f3 o, f3 d, float tMin, float tMax, float& outT, LdsMovedPtr moved = nullptr,
+                                uint64_t keys = 0)
 {
     float hitT = tMax;
     int id = -1;
     unsigned hsTrips_ = 0;
     (void)hsTrips_;
-    if (MOVED) cand |= TPT_MOVED_CANDIDATES;
+    if (MOVED) cand |= KEYS ? keys : TPT_MOVED_CANDIDATES;
     TPT_HS_STAMP(t1_);
     while (cand) {
         const int i = __builtin_clzll(cand);
         cand &= ~(0x8000000000000000ull >> i);
         TPT_STAT(ST_PHASE2);
         TPT_HS_TRIP();
-        testSphere(MOVED ? movedSphere(sv.sph4[i], i, moved) : sv.sph4[i], i, o, d, tMin, hitT, id);
+        testSphere(MOVED ? movedOrKeyedSphere<KEYS>(sv.sph4[i], i, moved, keys) : sv.sph4[i], i, o, d, tMin, hitT, id);
     }
     TPT_HS_STAMP(t2_);
     TPT_HS_ADD(t1_, t1_, t2_);
@@ -1150,11 +1170,11 @@ TPT_HD void qStackPush(const QStack& s, int level, f3 e, int attId)
     else
         s.spill[(level - 1) * s.stride] = v;
 }
-// hit normal, Maths.cpp:196-197 (MOVED: tptTraceAnimationKernel, movedSphere)
-template <bool MOVED = false>
-TPT_HD f3 qNormal(const SceneView& sv, int id, f3 pos, LdsMovedPtr moved = nullptr)
+// hit normal, Maths.cpp:196-197 (MOVED: tptTraceAnimationKernel, movedSphere; with KEYS: tptKeyframeKernel, keyedSphere)
+template <bool MOVED = false, bool KEYS = false>
+TPT_HD f3 qNormal(const SceneView& sv, int id, f3 pos, LdsMovedPtr moved = nullptr, uint64_t keys = 0)
 {
-    const f4 s = MOVED ? movedSphere(sv.sph4[id], id, moved) : sv.sph4[id];
+    const f4 s = MOVED ? movedOrKeyedSphere<KEYS>(sv.sph4[id], id, moved, keys) : sv.sph4[id];
     return (pos - mk3(s.x, s.y, s.z)) * sv.invR[id];
 }
 // camera ray of the next sample of pixel (x, y), Test.cpp:286-288
@@ -1217,12 +1237,13 @@ TPT_HD f3 qFold(const SceneView& sv, f3 term, int depth, const QStack& s)
     return c;
 }
 // Dielectric, Test.cpp:151-186: always scatters.  e = what this level adds (matE + lightE, lightE = 0), attenuation (1,1,1).
-template <bool MOVED = false>
-TPT_HD f3 qDielectric(const SceneView& sv, const FrameConsts& fc, f3 pos, f3 rdir, int id, bool doMatE, uint32_t& rng, f3& e, LdsMovedPtr moved = nullptr)
+template <bool MOVED = false, bool KEYS = false>
+TPT_HD f3 qDielectric(const SceneView& sv, const FrameConsts& fc, f3 pos, f3 rdir, int id, bool doMatE, uint32_t& rng, f3& e, LdsMovedPtr moved = nullptr,
+                      uint64_t keys = 0)
 {
     TPT_STAT(ST_DIELECTRIC);
     (void)fc;
-    const f3 normal = qNormal<MOVED>(sv, id, pos, moved);
+    const f3 normal = qNormal<MOVED, KEYS>(sv, id, pos, moved, keys);
     const f4 m1 = sv.mats[id * 3 + 1];
     const f4 m2 = sv.mats[id * 3 + 2]; // {ri, 1.0f / ri, r0^2}: the division of Test.cpp:168 and schlick's r0 (Maths.h:329-330) depend on the material only
     const float ri = m2.x;
@@ -1248,12 +1269,12 @@ TPT_HD f3 qDielectric(const SceneView& sv, const FrameConsts& fc, f3 pos, f3 rdi
     return normalize(pick);
 }
 // Metal, Test.cpp:137-150: false = the scattered ray points into the surface (the path ends with the sphere's emission).
-template <bool MOVED = false>
+template <bool MOVED = false, bool KEYS = false>
 TPT_HD bool qMetal(const SceneView& sv, const FrameConsts& fc, f3 pos, f3 rdir, int id, bool doMatE, uint32_t& rng, f3& e, f3& newDir,
-                   LdsMovedPtr moved = nullptr)
+                   LdsMovedPtr moved = nullptr, uint64_t keys = 0)
 {
     TPT_STAT(ST_METAL);
-    const f3 normal = qNormal<MOVED>(sv, id, pos, moved);
+    const f3 normal = qNormal<MOVED, KEYS>(sv, id, pos, moved, keys);
     const f4 m1 = sv.mats[id * 3 + 1];
     const f3 refl = reflect(rdir, normal);
     const float roughness = (fc.config & CFG_MITSUBA_COMPARE) ? 0.0f : m1.w; // Test.cpp:143-145 (the samples are drawn either way)
@@ -1269,11 +1290,11 @@ struct QLambert {
     f3 sdir, nl, albedo, lightE;
     float cosAMax;
 };
-template <bool MOVED = false>
-TPT_HD void qLambertBegin(const SceneView& sv, f3 pos, f3 rdir, int id, uint32_t& rng, QLambert& q, LdsMovedPtr moved = nullptr)
+template <bool MOVED = false, bool KEYS = false>
+TPT_HD void qLambertBegin(const SceneView& sv, f3 pos, f3 rdir, int id, uint32_t& rng, QLambert& q, LdsMovedPtr moved = nullptr, uint64_t keys = 0)
 {
     TPT_STAT(ST_LAMBERT);
-    const f3 normal = qNormal<MOVED>(sv, id, pos, moved);
+    const f3 normal = qNormal<MOVED, KEYS>(sv, id, pos, moved, keys);
     const f4 m0 = sv.mats[id * 3];
     const f3 target = pos + normal + randomUnitVector(rng);
     q.sdir = normalize(target - pos);
