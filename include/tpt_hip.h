@@ -433,6 +433,78 @@ TPT_API int tptTemporalAccumulateObjectsDevice(int screenWidth, int screenHeight
                                                float depthTolerance, float normalTolerance, float coverageTolerance,
                                                const int32_t* deviceObject, const int32_t* devicePrevObject,
                                                const float* deviceObjectMotion, int nObjects);
+/* A CLIP THROUGH THE DENOISING CHAIN: the frames the clip draws leave (tptDrawDeviceAnimationMoments, tptDrawDeviceCameraClip,
+ * tptDrawDeviceKeyframeClip, each without TPT_FLAG_PROGRESSIVE) taken through the temporal pass and the variance-guided filter by one
+ * call.  The temporal pass is a recurrence over frames and stays one launch per frame; the filter's iterations are one launch per
+ * CHUNK of frames each instead of one per frame.
+ * The planes: every deviceFrame* pointer is nFrames consecutive device planes, h*w*4 floats each (deviceFrameObjects: h*w int32 each),
+ * plane j frame j's -- the per-frame outputs of the clip draws as they are laid out.
+ *   deviceFrameImages, deviceFrameMoments   required: the clip draws' deviceFrameImages and deviceFrameMoments
+ *   deviceFrameAlbedo, deviceFrameNormalDepth   required, except in spatial-only mode, where each is optional as in
+ *                                           tptDenoiseDeviceVariance
+ *   cameras              HOST memory, nFrames x 88-byte Camera records (the clip draws' outCameras), read during the call; required
+ *                        except in spatial-only mode, where it is ignored
+ *   deviceFrameObjects   NULL, or the object planes (tptDrawDeviceKeyframeClip's, tptObjectPlaneDevice's): non-NULL selects
+ *                        tptTemporalAccumulateObjectsDevice as the temporal pass
+ *   deviceFrameObjectMotion, nObjects   DEVICE memory, nFrames x nObjects x 4 floats: table j is tptTemporalAccumulateObjectsDevice's
+ *                        table between frame j-1 and frame j (table 0 is read only when the call continues a history); NULL with
+ *                        nObjects == 0 as in that function; allowed only with deviceFrameObjects
+ *   deviceFrameOut       required: the denoised frames
+ *   samples, iterations, sigmaLuminance, sigmaNormal, sigmaDepth, denoiseFlags   tptDenoiseDeviceVariance's, for every frame
+ *   maxHistory, depthTolerance, normalTolerance, coverageTolerance   the temporal pass's, for every frame
+ *   clipFlags            TPT_CLIP_DENOISE_SPATIAL_ONLY or 0
+ *   prevCamera (HOST, 88 bytes), devicePrevNormalDepth, devicePrevObject, deviceHistory   the continuation, below
+ * Every byte of deviceFrameOut is what the existing entry points write:
+ *   spatial-only: plane j is what tptDenoiseDeviceVariance(w, h, images_j, albedo_j, normalDepth_j, moments_j, samples, out_j,
+ *     iterations, the sigmas, denoiseFlags) writes -- nFrames independent jobs (the views of a multi-view clip).
+ *   otherwise: for j = 0 .. nFrames-1, T_j = the four outputs of tptTemporalAccumulateDevice(w, h, cameras_j, cameras_{j-1}, images_j,
+ *     albedo_j, normalDepth_j, moments_j, T_{j-1}.colour, T_{j-1}.albedo, normalDepth_{j-1}, T_{j-1}.moments, ..., the four tolerances)
+ *     -- with deviceFrameObjects of tptTemporalAccumulateObjectsDevice, with objects_j, objects_{j-1}, table j and nObjects -- and plane
+ *     j is what tptDenoiseDeviceVariance(w, h, T_j.colour, T_j.albedo, normalDepth_j, T_j.variance, samples, out_j, ...) writes.
+ * Continuation.  prevCamera NULL: frame 0 is the first frame of a sequence (its prev arguments are NULL); devicePrevNormalDepth and
+ * devicePrevObject must be NULL.  prevCamera given: frame 0 has a predecessor, frame -1, read from prevCamera, devicePrevNormalDepth
+ * (required), devicePrevObject (required exactly when deviceFrameObjects is given) and deviceHistory (required): 3 consecutive planes
+ * of h*w*4 floats, T_{-1}'s colour, albedo and moments.  deviceHistory, whenever it is given, is WRITTEN at the end of the call with
+ * T_{nFrames-1}'s colour, albedo and moments -- in stream order after it was read, so one buffer may be passed call after call, and a
+ * clip cut into calls of any lengths gives the bytes of one call.  In spatial-only mode all four must be NULL.
+ * Chunks and staging.  The call works through the clip in chunks of n frames (the last one shorter), n the largest count <= 32 whose
+ * staging stays within 4096 MiB (the clip draws' limit), in planes of h*w*16 bytes: n in spatial-only mode (the iterations' ping-pong
+ * plane per frame), 4n + 4 otherwise (per frame T_j's colour, albedo and variance and the ping-pong plane; T's moments of two
+ * consecutive frames; and the colour and albedo of the chunk's predecessor, which the last frame of a chunk is copied to before the
+ * next chunk overwrites its staging).  The library owns the staging: allocated for min(n, nFrames) frames by the first call that
+ * needs it (a spatial-only call with iterations == 1 needs none), grown on demand, kept until tptShutdown.
+ * Asynchronous on the context stream, ordered like tptDenoiseDevice; needs tptInitialize only.  The inputs are never written; frames
+ * traced ahead, stream batches, scene and camera are left alone.
+ * Refused (non-zero, tptGetLastError names the function, nothing enqueued, no byte written): args NULL; no context; nFrames outside
+ * 1..4096; w or h outside 1..8192; an unknown clipFlags bit; a required pointer NULL; the mode rules above violated (a camera, an
+ * object, a motion or a continuation field in spatial-only mode; a table without deviceFrameObjects; a prev plane without prevCamera,
+ * or a missing one with it); everything tptDenoiseDeviceVariance refuses of its scalars and flags; everything the temporal passes
+ * refuse of their scalars and of every camera given; nObjects outside 0..65534, or exactly one of table and nObjects set; not even
+ * one frame's staging within 4096 MiB; deviceFrameOut or deviceHistory overlapping any input or each other, each taken at its full
+ * extent (nFrames planes, 3 planes, one plane for the prev planes, nFrames x nObjects x 16 bytes for the tables). */
+enum { TPT_CLIP_DENOISE_SPATIAL_ONLY = 1 << 0 };
+typedef struct tptClipDenoiseArgs {
+    int screenWidth, screenHeight, nFrames;
+    unsigned clipFlags;
+    const float* deviceFrameImages;
+    const float* deviceFrameMoments;
+    const float* deviceFrameAlbedo;
+    const float* deviceFrameNormalDepth;
+    const void* cameras;
+    const int32_t* deviceFrameObjects;
+    const float* deviceFrameObjectMotion;
+    float* deviceFrameOut;
+    const void* prevCamera;
+    const float* devicePrevNormalDepth;
+    const int32_t* devicePrevObject;
+    float* deviceHistory;
+    int nObjects;
+    int iterations;
+    unsigned denoiseFlags;
+    float samples, sigmaLuminance, sigmaNormal, sigmaDepth;
+    float maxHistory, depthTolerance, normalTolerance, coverageTolerance;
+} tptClipDenoiseArgs;
+TPT_API int tptDenoiseClipDevice(const tptClipDenoiseArgs* args);
 /* ADAPTIVE SAMPLING: tptDrawDeviceMoments with a sample count per pixel, so that the moments can steer the next pass (the counts come
  * from tptAdaptiveSamplesDevice below, or from the caller).  deviceSampleCounts (required): h*w int32 in DEVICE memory, row-major like the
  * tile, read by the kernels only.  Per pixel p, n = deviceSampleCounts[p] clamped to 0 .. 2047 (the path record holds 11 bits of sample

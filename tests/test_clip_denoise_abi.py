@@ -1,0 +1,478 @@
+"""tptDenoiseClipDevice without a GPU: the declaration, the layout of tptClipDenoiseArgs against the ctypes mirror, the export and the
+binding; the binding's argument checks; the gfx950 code of the new kernel in the shipped library (tests/test_moments_abi.py's contract
+for the per-frame variance kernel); and the refusals and the launch plan of accepted calls, driven through the host runtime compiled
+against tests/hostemu (a refused call returns before anything is enqueued; the launchers are tests/hostemu_clip_denoise.cpp,
+hostemu_temporal.cpp and hostemu_objects.cpp, which count and run nothing, and show what the host handed them); and the call's data flow
+across chunk seams and calls, with tests/hostemu_clip_chain.cpp's launchers, which run exact elementwise stand-ins on the emulated stream."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from isa_lib import code_object, count, header, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
+from oracle_lib import ROOT
+from test_moments_abi import VARIANCE
+
+FRAMES = "_ZN3tpt21tptFramesAtrousKernelILb%dELb%dELb%dEEEvPKNS_2f4ES3_S3_S3_S3_PS1_iiiffffi"  # <FIRST, LAST, GUIDE>
+# the words other ABI tests count kernels by: the new kernel's name holds none of them
+COUNTED_WORDS = ("Denoise", "Moments", "Variance", "Object", "Adaptive", "Keyframe", "CameraClip", "TraceClip", "Test")
+CTYPES_OF = {"int": C.c_int, "unsigned": C.c_uint, "float": C.c_float}
+
+
+def struct_fields():
+    """tptClipDenoiseArgs as include/tpt_hip.h declares it -> [(name, C type as written)]"""
+    body = re.search(r"typedef\s+struct\s+tptClipDenoiseArgs\s*\{(.*?)\}\s*tptClipDenoiseArgs\s*;", header(), flags=re.S)
+    assert body, "tptClipDenoiseArgs is not declared in include/tpt_hip.h"
+    fields = []
+    for decl in body.group(1).split(";"):
+        decl = " ".join(decl.split())
+        if not decl:
+            continue
+        m = re.match(r"(.*?[\s*])(\w+(?:\s*,\s*\w+)*)$", decl)
+        ctype = m.group(1).strip()
+        fields += [(name.strip(), ctype) for name in m.group(2).split(",")]
+    return fields
+
+
+def test_header_declares_the_entry_point_and_its_struct():
+    assert header_params("tptDenoiseClipDevice") == ["const tptClipDenoiseArgs* args"]
+    m = re.search(r"enum\s*\{\s*TPT_CLIP_DENOISE_SPATIAL_ONLY\s*=\s*1\s*<<\s*0\s*\}", header())
+    from toypathtracer_amd import api
+    assert m and api.CLIP_DENOISE_SPATIAL_ONLY == 1
+    fields = struct_fields()
+    assert [n for n, _ in fields] == [n for n, _ in api.ClipDenoiseArgs._fields_]
+    for (name, ctype), (_, mirror) in zip(fields, api.ClipDenoiseArgs._fields_):
+        assert mirror is (C.c_void_p if ctype.endswith("*") else CTYPES_OF[ctype]), (name, ctype, mirror)
+    for name in ("deviceFrameImages", "deviceFrameMoments", "deviceFrameAlbedo", "deviceFrameNormalDepth", "deviceFrameObjectMotion",
+                 "devicePrevNormalDepth"):
+        assert dict(fields)[name] == "const float*", name  # inputs are never written
+    assert dict(fields)["deviceFrameOut"] == "float*" and dict(fields)["deviceHistory"] == "float*"
+    assert dict(fields)["deviceFrameObjects"] == dict(fields)["devicePrevObject"] == "const int32_t*"
+
+
+def test_struct_layout_matches_the_ctypes_mirror(tmp_path):
+    """sizeof and every offsetof, as the C compiler lays the header's struct out"""
+    from toypathtracer_amd import api
+    names = [n for n, _ in api.ClipDenoiseArgs._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "tpt_hip.h"\nint main(void) {\n'
+                   '    printf("%zu\\n", sizeof(tptClipDenoiseArgs));\n'
+                   + "".join('    printf("%%zu\\n", offsetof(tptClipDenoiseArgs, %s));\n' % n for n in names) + "    return 0;\n}\n")
+    exe = str(tmp_path / "layout")
+    subprocess.check_call([os.environ.get("CC", "gcc"), "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
+    got = [int(v) for v in subprocess.check_output([exe]).decode().split()]
+    assert got == [C.sizeof(api.ClipDenoiseArgs)] + [getattr(api.ClipDenoiseArgs, n).offset for n in names]
+    assert got[0] == 160
+
+
+def test_binding_and_export():
+    from toypathtracer_amd import api
+    name = "tptDenoiseClipDevice"
+    assert name in api.C_ABI_SYMBOLS and callable(api.denoise_clip_device)
+    lib = api.load_library()
+    assert hasattr(lib, name) and lib.tptDenoiseClipDevice.argtypes == [C.POINTER(api.ClipDenoiseArgs)]
+    out = subprocess.check_output(["nm", "-D", "--defined-only", api.library_path()]).decode()
+    assert re.search(r"\bT %s\b" % name, out)
+    import inspect
+    defaults = {k: v.default for k, v in inspect.signature(api.denoise_clip_device).parameters.items()}
+    for k, v in list(api.DENOISE_VARIANCE_DEFAULTS.items()) + list(api.TEMPORAL_DEFAULTS.items()):
+        assert defaults[k] == v, k
+
+
+def no_library():
+    raise AssertionError("the library was called")
+
+
+def cameras(n):
+    from toypathtracer_amd import api
+    return np.zeros(n, api.CAMERA_DT)
+
+
+@pytest.mark.parametrize("args", [
+    dict(w=0), dict(h=-3), dict(w=8.0), dict(h=True), dict(frames=0), dict(frames=4097), dict(frames=2.0), dict(images=0), dict(images=None),
+    dict(moments=0), dict(out=None), dict(out=1.5), dict(albedo=None), dict(nd=None), dict(nd="x"), dict(cameras=None), dict(cameras=2),
+    dict(cameras="x"), dict(cameras=np.zeros((3, 22), np.float32)), dict(objects=-4), dict(motion=4096), dict(n_objects=3),
+    dict(objects=4096, motion=8192, n_objects=-1), dict(objects=4096, motion=8192, n_objects=65535),
+    dict(objects=4096, motion=8192, n_objects=2.0), dict(motion=8192, n_objects=2), dict(prev=()), dict(prev="camera"),
+    dict(prev=(1, 0), history=8192), dict(prev=(1, 4096)), dict(prev=(1, 4096, 8192), history=8192),
+    dict(objects=4096, prev=(1, 4096), history=8192), dict(objects=4096, prev=(1, 4096, None), history=8192), dict(history=-1),
+    dict(spatial_only=True, objects=4096), dict(spatial_only=True, history=4096), dict(spatial_only=True, prev=(1, 4096)),
+    dict(spatial_only=True, n_objects=1), dict(spatial_only=True, albedo=None, demodulate=True),
+    dict(samples=0.5), dict(samples=float("nan")), dict(samples=float("inf")), dict(samples=True), dict(samples="4"),
+    dict(iterations=0), dict(iterations=2.0), dict(sigma_luminance=0.0), dict(sigma_luminance=2e6), dict(sigma_luminance=float("nan")),
+    dict(sigma_normal=-1.0), dict(sigma_depth=float("inf")), dict(max_history=0.5), dict(max_history=float("nan")),
+    dict(depth_tolerance=-0.1), dict(normal_tolerance=float("inf")), dict(coverage_tolerance=float("nan")),
+], ids=lambda a: ",".join("%s=%.20r" % kv for kv in a.items()))
+def test_binding_checks_arguments_before_the_library(monkeypatch, args):
+    from toypathtracer_amd import api
+    monkeypatch.setattr(api, "load_library", no_library)
+    a = dict(w=16, h=8, frames=3, images=1 << 20, moments=2 << 20, out=3 << 20, samples=4.0, albedo=4 << 20, nd=5 << 20, cameras=3,
+             objects=None, motion=None, n_objects=0, prev=None, history=None, spatial_only=False)
+    a.update(args)
+    if isinstance(a["cameras"], int):
+        a["cameras"] = cameras(a["cameras"])
+    if isinstance(a["prev"], tuple) and a["prev"] and a["prev"][0] == 1:
+        a["prev"] = (cameras(1)[0],) + a["prev"][1:]
+    kw = {k: a.pop(k) for k in list(a) if k in api.DENOISE_VARIANCE_DEFAULTS or k in api.TEMPORAL_DEFAULTS or k == "demodulate"}
+    with pytest.raises(ValueError):
+        api.denoise_clip_device(a["w"], a["h"], a["frames"], a["images"], a["moments"], a["out"], a["samples"], albedo_ptr=a["albedo"],
+                                normal_depth_ptr=a["nd"], cameras=a["cameras"], objects_ptr=a["objects"], motion_ptr=a["motion"],
+                                n_objects=a["n_objects"], prev=a["prev"], history_ptr=a["history"], spatial_only=a["spatial_only"], **kw)
+
+
+@pytest.mark.parametrize("first,last,guide", [(f, l, g) for f in (1, 0) for l in (1, 0) for g in (1, 0)], ids=lambda v: str(v))
+def test_frames_kernels_in_the_code_object(code_object, first, last, guide):  # noqa: F811
+    bodies, meta = code_object
+    name, twin = FRAMES % (first, last, guide), VARIANCE % (first, last, guide)
+    assert name in meta and name in bodies, "the frame-stack a-trous kernel is missing from the shipped code object"
+    for word in COUNTED_WORDS:
+        assert word not in name, (name, word)
+    body, m = bodies[name], meta[name]
+    assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0, m
+    assert count(body, r"scratch_") == 0
+    assert count(body, r"flat_") == 0, "a FLAT instruction: a global pointer lost its address space"
+    assert m["group_segment_fixed_size"] == 0 and m["agpr_count"] == 0 and count(body, r"ds_") == 0
+    assert m["max_flat_workgroup_size"] == 256 and m["wavefront_size"] == 64
+    # the per-frame kernel's loads, store and divisions ...
+    assert count(body, r"global_load_dwordx[34]") >= 25 * (1 + guide)
+    assert count(body, r"global_load_dword") >= 25 * (1 + guide) + 8
+    assert count(body, r"global_store_dwordx4") == 1 and count(body, r"global_store") == 1
+    assert count(body, r"global_atomic|buffer_") == 0
+    assert count(body, r"v_rcp_f32") >= 25
+    # ... and its occupancy: no more vector registers than the per-frame kernel of the same instantiation, which stays at eight
+    # waves per SIMD (64 registers)
+    assert m["vgpr_count"] <= meta[twin]["vgpr_count"] <= 64, (m, meta[twin])
+
+
+def test_exactly_the_new_kernels_and_every_count_unchanged(code_object):  # noqa: F811
+    _, meta = code_object
+    assert sorted(n for n in meta if "FramesAtrous" in n) == sorted(FRAMES % (f, l, g) for f in (1, 0) for l in (1, 0) for g in (1, 0))
+    assert sum(1 for n in meta if "Denoise" in n) == 8
+    assert sum(1 for n in meta if "Moments" in n or "Variance" in n) == 10
+    assert sum(1 for n in meta if "Object" in n) == 3
+    assert sum(1 for n in meta if "Adaptive" in n) == 4
+    assert sum(1 for n in meta if "Keyframe" in n) == 2 and sum(1 for n in meta if "CameraClip" in n) == 2
+    assert sum(1 for n in meta if "TraceClip" in n) == 2 and sum(1 for n in meta if "Temporal" in n) == 2
+    for f in (1, 0):
+        for l in (1, 0):
+            for g in (1, 0):
+                assert VARIANCE % (f, l, g) in meta  # (the per-frame kernel keeps its name)
+
+
+REFUSALS = r'''
+import ctypes as C, sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+sys.path.insert(0, sys.argv[1] + "/tests")
+from toypathtracer_amd import api as tpt
+from temporal_lib import look_at_camera
+lib = tpt.load_library()
+F = "tptDenoiseClipDevice"
+w, h, N = 16, 8, 33
+plane_b = w * h * 16
+def msg(): return lib.tptGetLastError().decode()
+def ptr(x): return None if x is None else (x if isinstance(x, int) else x.ctypes.data)
+cams = np.stack([look_at_camera([0.02 * j, 2.0, 3.0], [0.0, 0.0, 0.0], w, h) for j in range(N)])
+pcam = look_at_camera([-0.02, 2.0, 3.0], [0.0, 0.0, 0.0], w, h)
+ins = dict(images=np.full((N, h, w, 4), 0.25, np.float32), moments=np.full((N, h, w, 4), 1.25, np.float32),
+           albedo=np.full((N, h, w, 4), 2.25, np.float32), nd=np.full((N, h, w, 4), 3.25, np.float32),
+           objects=np.full((N, h, w), 3, np.int32), motion=np.full((N, 5, 4), 0.5, np.float32),
+           prev_nd=np.full((h, w, 4), 4.25, np.float32), prev_object=np.full((h, w), 4, np.int32))
+before = {k: v.copy() for k, v in ins.items()}
+out = np.full((N, h, w, 4), np.nan, np.float32)
+history = np.full((3, h, w, 4), np.nan, np.float32)
+big = np.full((2 * N + 3, h, w, 4), np.nan, np.float32)
+FIELDS = dict(w="screenWidth", h="screenHeight", n="nFrames", cf="clipFlags", images="deviceFrameImages", moments="deviceFrameMoments",
+              albedo="deviceFrameAlbedo", nd="deviceFrameNormalDepth", cams="cameras", objects="deviceFrameObjects",
+              motion="deviceFrameObjectMotion", out="deviceFrameOut", pcam="prevCamera", prev_nd="devicePrevNormalDepth",
+              prev_object="devicePrevObject", history="deviceHistory", no="nObjects", it="iterations", fl="denoiseFlags", s="samples",
+              sl="sigmaLuminance", sn="sigmaNormal", sd="sigmaDepth", mh="maxHistory", dt="depthTolerance", nt="normalTolerance",
+              ct="coverageTolerance")
+BASE = dict(w=w, h=h, n=3, cf=0, images=ins["images"], moments=ins["moments"], albedo=ins["albedo"], nd=ins["nd"], cams=cams, objects=None,
+            motion=None, out=out, pcam=None, prev_nd=None, prev_object=None, history=None, no=0, it=3, fl=1, s=4.0, sl=4.0, sn=0.2, sd=0.5,
+            mh=4.0, dt=0.1, nt=0.25, ct=0.0)
+SPATIAL = dict(cf=1, cams=None)
+OBJECTS = dict(objects=ins["objects"], motion=ins["motion"], no=5)
+CONTINUED = dict(pcam=pcam, prev_nd=ins["prev_nd"], history=history)
+def call(**kw):
+    a = dict(BASE); a.update(kw)
+    A = tpt.ClipDenoiseArgs()
+    for k, v in a.items():
+        setattr(A, FIELDS[k], ptr(v) if FIELDS[k].startswith(("device", "cameras", "prevCamera")) else v)
+    keep = list(a.values())
+    return lib.tptDenoiseClipDevice(C.byref(A))
+def refused(what, expect=F, **kw):
+    rc = call(**kw)
+    assert rc != 0 and expect in msg(), (what, rc, msg())
+    print("refused:", what, "--", msg())
+def changed(c, k, v):
+    c = c.copy(); c.reshape(-1)[k] = v; return c
+refused("no context", "not initialised")
+tpt.InitializeTest()
+so = C.CDLL(tpt.library_path())
+class Launch(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("frames", "iterations", "width", "height")] + [(n, C.c_void_p) for n in ("colour", "albedo", "nd", "moments", "out", "scratch")]
+so.hostemuFramesAtrousLaunch.restype = C.POINTER(Launch)
+so.hostemuFramesAtrousLaunch.argtypes = [C.c_int]
+so.hostemuTemporalConsts.restype = C.POINTER(C.c_float * 34)
+so.hostemuObjectPassConsts.restype = C.POINTER(C.c_float * 34)
+def counters(): return (so.hostemuTemporalLaunches(), so.hostemuObjectPassLaunches(), so.hostemuFramesAtrousLaunches())
+def launch(k): return so.hostemuFramesAtrousLaunch(k).contents
+rc = lib.tptDenoiseClipDevice(None)
+assert rc != 0 and F in msg(), msg()
+print("refused: args NULL --", msg())
+for n in (0, -1, 4097):
+    refused("nFrames %d" % n, n=n)
+for ww, hh in ((0, h), (w, 0), (8193, 1), (1, 8193), (-4, -4)):
+    refused("size %dx%d" % (ww, hh), w=ww, h=hh)
+for cf in (2, 3, 0x80000000):
+    refused("clipFlags %#x" % cf, cf=cf)
+for k in ("images", "moments", "out"):
+    refused("%s NULL" % k, **{k: None})
+    refused("%s NULL, spatial-only" % k, **dict(SPATIAL, **{k: None}))
+for k in ("albedo", "nd", "cams"):
+    refused("%s NULL in temporal mode" % k, **{k: None})
+# the mode rules
+for k, v in (("objects", ins["objects"]), ("motion", ins["motion"]), ("no", 5), ("pcam", pcam), ("prev_nd", ins["prev_nd"]),
+             ("prev_object", ins["prev_object"]), ("history", history)):
+    refused("spatial-only with %s" % k, **dict(SPATIAL, **{k: v}))
+refused("prev normal/depth without prevCamera", prev_nd=ins["prev_nd"])
+refused("prev object without prevCamera", **dict(OBJECTS, prev_object=ins["prev_object"]))
+refused("prevCamera without deviceHistory", **dict(CONTINUED, history=None))
+refused("prevCamera without the prev normal/depth", **dict(CONTINUED, prev_nd=None))
+refused("prevCamera and object planes without the prev object plane", **dict(CONTINUED, **OBJECTS))
+refused("prevCamera and a prev object plane without object planes", **dict(CONTINUED, prev_object=ins["prev_object"]))
+refused("a table without object planes", motion=ins["motion"], no=5)
+# what tptDenoiseDeviceVariance refuses of its scalars and flags
+for it in (0, 9, -1):
+    refused("iterations %d" % it, it=it)
+for s in (0.0, 0.999, float("nan"), float("inf")):
+    refused("samples %r" % s, s=s)
+for sl in (0.0, -1.0, 1.000001e6, float("nan")):
+    refused("sigmaLuminance %r" % sl, sl=sl)
+for v in (-1.0, 1e-7, float("nan"), 2e6):
+    refused("sigmaNormal %r" % v, sn=v)
+    refused("sigmaDepth %r" % v, sd=v)
+refused("unknown denoise flag", fl=2)
+refused("spatial-only: a guide sigma without the plane", **dict(SPATIAL, nd=None))
+refused("spatial-only: demodulate without albedo", **dict(SPATIAL, albedo=None))
+# what the temporal passes refuse of their scalars and of every camera given
+for mh in (0.0, 0.999, 65536.5, float("nan")):
+    refused("maxHistory %r" % mh, mh=mh)
+for name in ("dt", "nt", "ct"):
+    for v in (-1e-6, float("nan"), float("inf")):
+        refused("%s %r" % (name, v), **{name: v})
+for j in (0, 1, 2):
+    refused("camera %d field 5 = inf" % j, cams=changed(cams[:3], 22 * j + 5, np.inf))
+    flat = cams[:3].copy(); flat[j, 6:9] = 0
+    refused("camera %d: dot(H, H) == 0" % j, cams=flat)
+refused("prevCamera field 3 = nan", **dict(CONTINUED, pcam=changed(pcam, 3, np.nan)))
+flat = pcam.copy(); flat[9:12] = 0
+refused("prevCamera: dot(V, V) == 0", **dict(CONTINUED, pcam=flat))
+assert call(**dict(SPATIAL, cams=changed(cams[:3], 5, np.inf))) == 0, msg()  # (spatial-only reads no camera)
+print("accepted: spatial-only ignores cameras")
+for no in (-1, 65535, 1 << 30):
+    refused("nObjects %d" % no, **dict(OBJECTS, no=no))
+refused("a table without a count", **dict(OBJECTS, no=0))
+refused("a count without a table", **dict(OBJECTS, motion=None))
+# the staging: 4n + 4 planes within 4096 MiB (fake pointers 64 GiB apart: a refused call follows none)
+fake = {k: (i + 1) << 36 for i, k in enumerate(("images", "moments", "albedo", "nd", "out"))}
+refused("temporal mode at 8192 x 8192: 4 planes of staging at most", w=8192, h=8192, **fake)
+refused("temporal mode at 8192 x 4097: 7 planes", w=8192, h=4097, **fake)
+# overlaps, each buffer at its full extent
+b = big.ctypes.data
+for k in ("images", "moments", "albedo", "nd"):
+    refused("out is %s" % k, out=ins[k])
+    refused("out's last plane holds the head of %s" % k, out=b, **{k: b + 3 * plane_b - 4})
+    refused("the last plane of %s holds out's head" % k, out=b + 3 * plane_b - 16, **{k: b})
+refused("out holds the third object plane", **dict(OBJECTS, out=b, objects=b + 2 * w * h * 4))
+refused("the object planes' tail holds out's head", **dict(OBJECTS, objects=b, out=b + 3 * w * h * 4 - 4))
+refused("out holds the third table's last entry", **dict(OBJECTS, out=b + 16, motion=b + 16 - 3 * 5 * 16 + 12))
+refused("out holds the prev normal/depth plane", **dict(CONTINUED, out=b, prev_nd=b + 3 * plane_b - 4))
+refused("out holds the prev object plane", **dict(CONTINUED, **dict(OBJECTS, out=b + w * h * 4 - 4, prev_object=b)))
+refused("the history's third plane holds the images' head", **dict(CONTINUED, history=b, images=b + 3 * plane_b - 4))
+refused("the history is the prev normal/depth plane", **dict(CONTINUED, history=b, prev_nd=b + 2 * plane_b))
+refused("the history lies in the third moments plane", **dict(CONTINUED, history=b + 2 * plane_b, moments=b))
+refused("out's last plane holds the history's head", **dict(CONTINUED, out=b, history=b + 3 * plane_b - 4))
+refused("the history's last plane holds out's head", **dict(CONTINUED, history=b, out=b + 3 * plane_b - 4))
+refused("a history that is only written overlaps out", history=b + plane_b, out=b)
+assert counters() == (0, 0, 1), "a refused call reached a launcher"
+tpt.synchronize()
+assert np.isnan(out).all() and np.isnan(history).all() and np.isnan(big).all(), "a refused call wrote"
+
+# ---------------------------------------------------------------- the launch plan of accepted calls
+def planes(a, bpt): return (a - bpt) / plane_b
+# 33 frames, temporal mode: 33 temporal launches, and the iterations of two a-trous launches over 32 + 1 frames
+t0, o0, f0 = counters()
+assert call(n=33, it=5, history=history) == 0, msg()
+assert counters() == (t0 + 33, o0, f0 + 2), counters()
+A, B = launch(f0), launch(f0 + 1)
+assert (A.frames, A.iterations, B.frames, B.iterations) == (32, 5, 1, 5) and A.iterations + B.iterations == 2 * 5
+assert (A.width, A.height, B.width, B.height) == (w, h, w, h)
+assert A.out == out.ctypes.data and B.out == out.ctypes.data + 32 * plane_b
+assert A.nd == ins["nd"].ctypes.data and B.nd == ins["nd"].ctypes.data + 32 * plane_b
+# the staging: colour and albedo in stacks of 32 + 1 planes (slot 0 the chunk's predecessor), variance and ping-pong in stacks of 32,
+# the moments in two planes: 4 * 32 + 4 planes, and both chunks start at slot 1
+assert (A.colour, A.albedo, A.moments, A.scratch) == (B.colour, B.albedo, B.moments, B.scratch)
+stage = A.colour - plane_b
+assert [planes(p, stage) for p in (A.colour, A.albedo, A.moments, A.scratch)] == [1, 34, 66, 98]
+tpt.synchronize()
+assert not np.isnan(history).any(), "deviceHistory was not written"  # (the stand-ins run nothing: whatever the staging held)
+assert np.isnan(out).all()
+print("accepted: 33 frames, temporal mode")
+history[:] = np.nan
+# ... with object planes: the other pass, the same plan
+t0, o0, f0 = counters()
+assert call(n=33, it=2, **OBJECTS) == 0, msg()
+assert counters() == (t0, o0 + 33, f0 + 2) and so.hostemuObjectPassObjects() == 5
+assert [(launch(f0 + k).frames, launch(f0 + k).iterations) for k in (0, 1)] == [(32, 2), (1, 2)]
+print("accepted: 33 frames, object-following")
+assert call(n=3, objects=ins["objects"]) == 0 and so.hostemuObjectPassObjects() == 0, msg()
+print("accepted: object planes without a table")
+# spatial-only: no temporal launch, the caller's stacks
+t0, o0, f0 = counters()
+assert call(n=33, it=4, **SPATIAL) == 0, msg()
+assert counters() == (t0, o0, f0 + 2)
+A, B = launch(f0), launch(f0 + 1)
+assert (A.frames, A.iterations, B.frames, B.iterations) == (32, 4, 1, 4)
+for L, at in ((A, 0), (B, 32 * plane_b)):
+    assert (L.colour, L.albedo, L.nd, L.moments, L.out) == tuple(ins[k].ctypes.data + at for k in ("images", "albedo", "nd", "moments")) + (out.ctypes.data + at,)
+assert A.scratch == B.scratch
+assert call(n=5, it=1, albedo=None, nd=None, sn=0.0, sd=0.0, fl=0, **SPATIAL) == 0, msg()
+L = launch(f0 + 2)
+assert (L.frames, L.iterations, L.albedo, L.nd) == (5, 1, None, None)
+print("accepted: spatial-only")
+# the chunk length: the largest count <= 32 whose planes stay within 4096 MiB (one iteration: a spatial-only call then needs no staging)
+for ww, hh, n, want in ((8192, 8192, 5, [4, 1]), (4096, 4096, 17, [16, 1]), (4096, 4095, 17, [16, 1]), (2048, 4097, 70, [31, 31, 8]),
+                        (2048, 4096, 33, [32, 1])):
+    f0 = counters()[2]
+    assert call(w=ww, h=hh, n=n, it=1, **dict(SPATIAL, **fake)) == 0, msg()
+    got = [launch(f0 + k) for k in range(counters()[2] - f0)]
+    assert [L.frames for L in got] == want, (ww, hh, [L.frames for L in got])
+    at = 0
+    for L in got:
+        assert L.colour == fake["images"] + at and L.out == fake["out"] + at and L.nd == fake["nd"] + at
+        at += L.frames * ww * hh * 16
+    print("accepted: chunks of", want, "at %d x %d" % (ww, hh))
+# the temporal constants of frame j are those of the per-frame entry point for (cameras_j, cameras_{j-1})
+tins = [np.full((h, w, 4), 0.5 + k, np.float32) for k in range(8)]
+touts = [np.full((h, w, 4), np.nan, np.float32) for k in range(4)]
+tobj = [np.full((h, w), 3, np.int32) for k in range(2)]
+def per_frame(cam, prev, objects):
+    pl = [ptr(p) for p in tins[:4]] + ([ptr(p) for p in tins[4:]] if prev is not None else [None] * 4) + [ptr(p) for p in touts]
+    if objects:
+        assert lib.tptTemporalAccumulateObjectsDevice(w, h, ptr(cam), ptr(prev), *pl, 2.0, 0.2, 0.3, 0.4, ptr(tobj[0]),
+                                                      ptr(tobj[1]) if prev is not None else None, None, 0) == 0, msg()
+        return np.array(so.hostemuObjectPassConsts().contents, np.float32)
+    assert lib.tptTemporalAccumulateDevice(w, h, ptr(cam), ptr(prev), *pl, 2.0, 0.2, 0.3, 0.4) == 0, msg()
+    return np.array(so.hostemuTemporalConsts().contents, np.float32)
+for objects in (False, True):
+    last = lambda: np.array((so.hostemuObjectPassConsts if objects else so.hostemuTemporalConsts)().contents, np.float32)
+    kw = dict(mh=2.0, dt=0.2, nt=0.3, ct=0.4, objects=ins["objects"] if objects else None)
+    for j in range(4):
+        want = per_frame(cams[j], cams[j - 1] if j else None, objects)
+        assert call(n=j + 1, **kw) == 0, msg()
+        assert last().tobytes() == want.tobytes(), (objects, j)
+    want = per_frame(cams[0], pcam, objects)
+    assert call(n=1, **dict(CONTINUED, prev_object=ins["prev_object"] if objects else None, **kw)) == 0, msg()
+    assert last().tobytes() == want.tobytes(), objects
+    assert want[12:15].tobytes() == pcam[0:3].tobytes() and want[0:3].tobytes() == cams[0, 0:3].tobytes()
+print("accepted: the constants of every frame")
+# deviceHistory in place, call after call
+history[:] = 7.5
+for k in range(2):
+    assert call(n=2, **CONTINUED) == 0, msg()
+tpt.synchronize()
+assert not (history == 7.5).any() and np.isnan(out).all()
+print("accepted: deviceHistory in place")
+assert all((ins[k] == before[k]).all() for k in ins) and np.isnan(big).all(), "a call wrote an input"
+tpt.ShutdownTest()
+print("ok")
+'''
+
+
+def test_refusals_and_the_launch_plan_through_the_host_runtime():
+    out = run_refusals(REFUSALS, "libtpt_hostemu_clip_denoise.so", ["hostemu_clip_denoise.cpp", "hostemu_temporal.cpp", "hostemu_objects.cpp"])
+    head = 2 + 3 + 5 + 3 + 6 + 3
+    modes = 7 + 7
+    filter_ = 3 + 4 + 4 + 8 + 3
+    temporal = 4 + 9 + 6 + 2 + 3 + 2
+    staging, overlaps = 2, 12 + 5 + 6
+    assert out.count("refused:") == head + modes + filter_ + temporal + staging + overlaps, out
+    assert out.count("accepted:") == 1 + 4 + 5 + 2, out
+
+
+DATA_FLOW = r'''
+import ctypes as C, sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+from toypathtracer_amd import api as tpt
+lib = tpt.load_library()
+w, h, N = 16, 8, 70
+rng = np.random.default_rng(5)
+images, albedo, nd, moments = (rng.random((N, h, w, 4), dtype=np.float32) for _ in range(4))
+cams = np.zeros((N, 22), np.float32)
+cams[:, 3:6], cams[:, 6], cams[:, 10], cams[:, 20] = [-1, -1, -1], 2, 2, 1  # (any camera the pass accepts: the stand-ins read none)
+def model(lo, hi, prev=None):
+    """tests/hostemu_clip_chain.cpp's stand-ins, frame after frame -> (outs, (colour, albedo, moments) of the last frame)"""
+    outs = []
+    for j in range(lo, hi):
+        c, a, m = images[j], albedo[j], moments[j]
+        if prev is not None:
+            c, a, m = c + prev[0], a + prev[1], (m + prev[2]) + prev[3]
+        outs.append(((c + a) + nd[j]) + (images[j] + moments[j]))
+        prev = (c, a, m, nd[j])
+    return np.stack(outs), prev[:3]
+def call(lo, hi, out, history=None, continued=False, iterations=2):
+    A = tpt.ClipDenoiseArgs(screenWidth=w, screenHeight=h, nFrames=hi - lo, deviceFrameImages=images[lo:].ctypes.data,
+                            deviceFrameMoments=moments[lo:].ctypes.data, deviceFrameAlbedo=albedo[lo:].ctypes.data,
+                            deviceFrameNormalDepth=nd[lo:].ctypes.data, cameras=cams[lo:].ctypes.data, deviceFrameOut=out.ctypes.data,
+                            deviceHistory=None if history is None else history.ctypes.data, iterations=iterations, denoiseFlags=1, samples=4.0,
+                            sigmaLuminance=4.0, sigmaNormal=0.03, sigmaDepth=0.5, maxHistory=4.0, depthTolerance=0.1, normalTolerance=0.25)
+    if continued:
+        A.prevCamera, A.devicePrevNormalDepth = cams[lo - 1:].ctypes.data, nd[lo - 1].ctypes.data
+    assert lib.tptDenoiseClipDevice(C.byref(A)) == 0, lib.tptGetLastError().decode()
+tpt.InitializeTest()
+want, last = model(0, N)
+for iterations in (1, 2, 5):
+    out = np.full((N + 2, h, w, 4), np.nan, np.float32)
+    history = np.full((5, h, w, 4), np.nan, np.float32)
+    call(0, N, out[1:], history[1:], iterations=iterations)
+    tpt.synchronize()
+    bad = [j for j in range(N) if out[1 + j].tobytes() != want[j].tobytes()]
+    assert not bad, ("frames that differ from the chain", iterations, bad)
+    assert np.isnan(out[0]).all() and np.isnan(out[-1]).all() and np.isnan(history[0]).all() and np.isnan(history[-1]).all()
+    assert all(history[1 + k].tobytes() == last[k].tobytes() for k in range(3)), "deviceHistory is not the last frame's temporal outputs"
+    print("accepted: 70 frames in chunks of 32 + 32 + 6,", iterations, "iterations")
+# the same clip over three calls, deviceHistory in place; a small call first, so that the staging grows between calls of one sequence
+out = np.full((N, h, w, 4), np.nan, np.float32)
+history = np.full((3, h, w, 4), np.nan, np.float32)
+for lo, hi in ((0, 20), (20, 33), (33, N)):
+    call(lo, hi, out[lo:], history, continued=lo > 0)
+tpt.synchronize()
+assert out.tobytes() == want.tobytes(), "20 + 13 + 37 frames differ from the one call"
+assert all(history[k].tobytes() == last[k].tobytes() for k in range(3))
+# ... and with a synchronise and another clip's call in between: the history lives in the caller's buffer alone
+out[:] = np.nan
+call(0, 40, out, history)
+tpt.synchronize()
+other = np.full((N, h, w, 4), np.nan, np.float32)
+call(0, N, other)
+call(40, N, out[40:], history, continued=True)
+tpt.synchronize()
+assert out.tobytes() == want.tobytes() and other.tobytes() == want.tobytes()
+print("accepted: the clip continued over calls")
+tpt.ShutdownTest()
+print("ok")
+'''
+
+
+def test_data_flow_across_chunk_seams_and_calls():
+    """Launchers that run exact stand-ins as stream work (tests/hostemu_clip_chain.cpp): every frame's output depends on its
+    predecessor's temporal outputs, so a chunk whose first frame read clobbered staging, a stack at a wrong offset or a history copied
+    from the wrong slot changes bytes."""
+    out = run_refusals(DATA_FLOW, "libtpt_hostemu_clip_chain.so", ["hostemu_clip_chain.cpp"])
+    assert out.count("accepted:") == 4, out

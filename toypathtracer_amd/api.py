@@ -39,7 +39,7 @@ C_ABI_SYMBOLS = [
     "tptSetSamplesPerPixel", "tptSetConfig", "tptSetSeedMode", "tptSetFoldMode", "tptSetScene", "tptSetCamera", "tptSetStream",
     "tptSetRowShard", "tptLocalRowCount", "tptLocalRowToGlobal", "tptDrawDevice", "tptRayCounterRead", "tptSetRayCounter", "tptSetFrameOverlap", "tptDisplayRGBA8", "tptKernelTimingBegin", "tptKernelTimingEnd",
     "tptSynchronize", "tptTimerBegin", "tptTimerEnd", "tptSetKernelVariant",
-    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceAnimationMoments", "tptDrawDeviceCameraClip", "tptDrawDeviceKeyframeClip", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptObjectPlaneDevice", "tptObjectMotionTable", "tptTemporalAccumulateObjectsDevice", "tptDrawDeviceAdaptive", "tptAdaptiveSamplesDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
+    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceAnimationMoments", "tptDrawDeviceCameraClip", "tptDrawDeviceKeyframeClip", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptObjectPlaneDevice", "tptObjectMotionTable", "tptTemporalAccumulateObjectsDevice", "tptDenoiseClipDevice", "tptDrawDeviceAdaptive", "tptAdaptiveSamplesDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
 ]
 # include/tpt_test_hooks.h: exported by the second build (libtoypathtracer_hip_hooks.so) only
 HOOK_SYMBOLS = ["tptTestMath", "tptTestMathExhaustive", "tptTestHitSpheres", "tptTestMatrixFilter", "tptTestGroupFilter", "tptTestSetDealCapacities", "tptDebugStats", "tptDebugChunkOrder"]
@@ -48,6 +48,17 @@ CXX_ABI_SYMBOLS = [
     "_Z14InitializeTestv", "_Z12ShutdownTestv", "_Z10UpdateTestfiiij", "_Z8DrawTestfiiiPfRij",
     "_Z14GetObjectCountRiS_S_S_", "_Z12GetSceneDescPvS_S_S_Pi",
 ]
+
+
+class ClipDenoiseArgs(C.Structure):
+    """include/tpt_hip.h: tptClipDenoiseArgs (tests/test_clip_denoise_abi.py holds the layout against the header)"""
+    _fields_ = ([("screenWidth", C.c_int), ("screenHeight", C.c_int), ("nFrames", C.c_int), ("clipFlags", C.c_uint)]
+                + [(name, C.c_void_p) for name in ("deviceFrameImages", "deviceFrameMoments", "deviceFrameAlbedo", "deviceFrameNormalDepth",
+                                                   "cameras", "deviceFrameObjects", "deviceFrameObjectMotion", "deviceFrameOut",
+                                                   "prevCamera", "devicePrevNormalDepth", "devicePrevObject", "deviceHistory")]
+                + [("nObjects", C.c_int), ("iterations", C.c_int), ("denoiseFlags", C.c_uint)]
+                + [(name, C.c_float) for name in ("samples", "sigmaLuminance", "sigmaNormal", "sigmaDepth", "maxHistory", "depthTolerance",
+                                                  "normalTolerance", "coverageTolerance")])
 
 
 def _lib_dir():
@@ -78,7 +89,7 @@ def _bind(path, hooks):
         "tptSetRayCounter": [p], "tptSetTileMirror": [p, p], "tptSetFrameOverlap": [i], "tptDisplayRGBA8": [p, i, i, p], "tptKernelTimingBegin": [i],
         "tptKernelTimingEnd": [C.POINTER(f), C.POINTER(i)],
         "tptSynchronize": [], "tptTimerBegin": [], "tptTimerEnd": [C.POINTER(f)], "tptSetKernelVariant": [i, i, i],
-        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDrawDeviceAnimationMoments": [i, i, p, i, i] + [p] * 7 + [u], "tptDrawDeviceCameraClip": [i, i, p, p, i, i] + [p] * 8 + [u], "tptDrawDeviceKeyframeClip": [i, i, p, i, p, p, i, i] + [p] * 9 + [u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptObjectPlaneDevice": [i, p, p, i, i, p, u], "tptObjectMotionTable": [f, f, u, p, i], "tptTemporalAccumulateObjectsDevice": [i, i] + [p] * 14 + [f] * 4 + [p, p, p, i], "tptDrawDeviceAdaptive": [f, i, i, i, p, p, p, p, p, u], "tptAdaptiveSamplesDevice": [i, i, p, f, i, i, p, p, p], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
+        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDrawDeviceAnimationMoments": [i, i, p, i, i] + [p] * 7 + [u], "tptDrawDeviceCameraClip": [i, i, p, p, i, i] + [p] * 8 + [u], "tptDrawDeviceKeyframeClip": [i, i, p, i, p, p, i, i] + [p] * 9 + [u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptObjectPlaneDevice": [i, p, p, i, i, p, u], "tptObjectMotionTable": [f, f, u, p, i], "tptTemporalAccumulateObjectsDevice": [i, i] + [p] * 14 + [f] * 4 + [p, p, p, i], "tptDenoiseClipDevice": [C.POINTER(ClipDenoiseArgs)], "tptDrawDeviceAdaptive": [f, i, i, i, p, p, p, p, p, u], "tptAdaptiveSamplesDevice": [i, i, p, f, i, i, p, p, p], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
     }
     if hooks:
         sigs.update({"tptDebugStats": [p, i], "tptDebugChunkOrder": [p, p, i], "tptTestMath": [i, p, p, p, i], "tptTestMathExhaustive": [i, u, u, p, p],
@@ -807,6 +818,91 @@ def temporal_accumulate_objects_device(w, h, camera, colour_ptr, albedo_ptr, nor
         *prev_ptrs[:4], C.c_void_p(out_colour_ptr), C.c_void_p(out_albedo_ptr), C.c_void_p(out_moments_ptr), C.c_void_p(out_variance_ptr),
         max_history, depth_tolerance, normal_tolerance, coverage_tolerance, C.c_void_p(object_ptr), prev_ptrs[4],
         C.c_void_p(motion_ptr) if motion_ptr else None, n_objects), "tptTemporalAccumulateObjectsDevice")
+
+
+CLIP_DENOISE_SPATIAL_ONLY = 1  # include/tpt_hip.h: TPT_CLIP_DENOISE_SPATIAL_ONLY
+CLIP_DENOISE_MAX_FRAMES = 4096  # include/tpt_hip.h: tptDenoiseClipDevice's nFrames
+
+
+def denoise_clip_device(w, h, frames, images_ptr, moments_ptr, out_ptr, samples, albedo_ptr=None, normal_depth_ptr=None, cameras=None,
+                        objects_ptr=None, motion_ptr=None, n_objects=0, prev=None, history_ptr=None, spatial_only=False,
+                        iterations=DENOISE_VARIANCE_DEFAULTS["iterations"], sigma_luminance=DENOISE_VARIANCE_DEFAULTS["sigma_luminance"],
+                        sigma_normal=DENOISE_VARIANCE_DEFAULTS["sigma_normal"], sigma_depth=DENOISE_VARIANCE_DEFAULTS["sigma_depth"],
+                        demodulate=None, max_history=TEMPORAL_DEFAULTS["max_history"],
+                        depth_tolerance=TEMPORAL_DEFAULTS["depth_tolerance"], normal_tolerance=TEMPORAL_DEFAULTS["normal_tolerance"],
+                        coverage_tolerance=TEMPORAL_DEFAULTS["coverage_tolerance"]):
+    """tptDenoiseClipDevice: `frames` frames of a clip draw (draw_device_animation_moments, draw_device_camera_clip,
+    draw_device_keyframe_clip, each without kFlagProgressive) through temporal_accumulate_[objects_]device and denoise_device_variance,
+    the filter's iterations one launch per chunk of up to 32 frames.  images_ptr, moments_ptr, albedo_ptr, normal_depth_ptr, out_ptr:
+    `frames` consecutive device planes of h*w*4 floats each (the clip draw's images_ptr, frame_moments_ptr, albedo_ptr and
+    normal_depth_ptr; out_ptr receives the denoised frames).  cameras: the clip draw's result, a CAMERA_DT array of `frames` records.
+    objects_ptr: None, or the clip's object planes (h*w int32 each): the temporal pass then follows objects, with motion_ptr / n_objects
+    None / 0 or `frames` tables of n_objects x 4 floats in device memory, table j between frames j-1 and j.  prev: None (frame 0 starts
+    a sequence) or (camera, normal_depth_ptr) -- with objects_ptr (camera, normal_depth_ptr, object_ptr) -- of the frame before frame 0,
+    whose temporal outputs history_ptr holds.  history_ptr: None or 3 device planes {colour, albedo, moments}, read when prev is given
+    and overwritten with the last frame's temporal outputs: pass it call after call.  spatial_only=True: no temporal pass, every frame
+    filtered on its own (albedo_ptr / normal_depth_ptr optional; cameras ignored; objects, prev and history not allowed).  The filter's
+    arguments are denoise_device_variance's, the temporal ones temporal_accumulate_device's.  Ordered on the context's stream."""
+    _positive_ints(("w", w), ("h", h), ("frames", frames), ("iterations", iterations))
+    if frames > CLIP_DENOISE_MAX_FRAMES:
+        raise ValueError("frames: 1..%d expected, got %d" % (CLIP_DENOISE_MAX_FRAMES, frames))
+    named = (("images_ptr", images_ptr), ("moments_ptr", moments_ptr), ("out_ptr", out_ptr), ("albedo_ptr", albedo_ptr),
+             ("normal_depth_ptr", normal_depth_ptr), ("objects_ptr", objects_ptr), ("motion_ptr", motion_ptr), ("history_ptr", history_ptr))
+    _pointers(*named)
+    if not images_ptr or not moments_ptr or not out_ptr:
+        raise ValueError("images_ptr, moments_ptr, out_ptr: device buffers are required")
+    prev_cam, prev_ptrs = None, (None, None)
+    if spatial_only:
+        if objects_ptr or motion_ptr or n_objects or prev is not None or history_ptr:
+            raise ValueError("spatial_only: objects_ptr, motion_ptr, n_objects, prev and history_ptr are not allowed")
+    else:
+        if not albedo_ptr or not normal_depth_ptr:
+            raise ValueError("albedo_ptr, normal_depth_ptr: device buffers are required unless spatial_only")
+        if not isinstance(cameras, np.ndarray) or cameras.dtype != CAMERA_DT or cameras.shape != (frames,):
+            raise ValueError("cameras: a CAMERA_DT array of %d records expected, got %r" % (frames, cameras))
+        cameras = np.ascontiguousarray(cameras)
+        if prev is not None:
+            if not isinstance(prev, (tuple, list)) or len(prev) != (3 if objects_ptr else 2):
+                raise ValueError("prev: None or (camera, normal_depth_ptr%s) expected, got %r" % (", object_ptr" if objects_ptr else "", prev))
+            prev_cam = _camera_bytes("prev camera", prev[0])
+            more = tuple(zip(("prev normal_depth_ptr", "prev object_ptr"), prev[1:]))
+            _pointers(*more)
+            if not all(v for _, v in more):
+                raise ValueError("prev: every device buffer is required")
+            if not history_ptr:
+                raise ValueError("history_ptr: required with prev")
+            prev_ptrs = tuple(prev[1:]) + (None,) * (3 - len(prev))
+    if not isinstance(n_objects, (int, np.integer)) or isinstance(n_objects, bool) or not 0 <= n_objects <= OBJECT_MOTION_MAX_OBJECTS:
+        raise ValueError("n_objects: an int in 0..%d expected, got %r" % (OBJECT_MOTION_MAX_OBJECTS, n_objects))
+    if bool(motion_ptr) != (n_objects > 0):
+        raise ValueError("motion_ptr, n_objects: both or neither expected, got %r and %r" % (motion_ptr, n_objects))
+    if motion_ptr and not objects_ptr:
+        raise ValueError("motion_ptr: needs objects_ptr")
+    if not isinstance(samples, (int, float, np.integer, np.floating)) or isinstance(samples, bool) or not 1 <= samples < float("inf"):
+        raise ValueError("samples: a finite number >= 1 expected, got %r" % (samples,))
+    if not isinstance(sigma_luminance, (int, float, np.integer, np.floating)) or isinstance(sigma_luminance, bool) or not 0 < sigma_luminance <= 1e6:
+        raise ValueError("sigma_luminance: a float in (0, 1e6] expected, got %r" % (sigma_luminance,))
+    _sigmas(("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth))
+    if demodulate is None:
+        demodulate = bool(albedo_ptr)
+    if demodulate and not albedo_ptr:
+        raise ValueError("demodulate: needs albedo_ptr")
+    if not normal_depth_ptr:
+        sigma_normal = sigma_depth = 0.0
+    if not isinstance(max_history, (int, float, np.integer, np.floating)) or isinstance(max_history, bool) or not 1 <= max_history <= 65536:
+        raise ValueError("max_history: a number in 1..65536 expected, got %r" % (max_history,))
+    _sigmas(("depth_tolerance", depth_tolerance), ("normal_tolerance", normal_tolerance), ("coverage_tolerance", coverage_tolerance))
+    a = ClipDenoiseArgs(
+        screenWidth=w, screenHeight=h, nFrames=frames, clipFlags=CLIP_DENOISE_SPATIAL_ONLY if spatial_only else 0,
+        deviceFrameImages=images_ptr, deviceFrameMoments=moments_ptr, deviceFrameAlbedo=albedo_ptr or None,
+        deviceFrameNormalDepth=normal_depth_ptr or None, cameras=None if spatial_only else cameras.ctypes.data,
+        deviceFrameObjects=objects_ptr or None, deviceFrameObjectMotion=motion_ptr or None, deviceFrameOut=out_ptr,
+        prevCamera=C.addressof(prev_cam) if prev_cam is not None else None, devicePrevNormalDepth=prev_ptrs[0],
+        devicePrevObject=prev_ptrs[1], deviceHistory=history_ptr or None, nObjects=n_objects, iterations=iterations,
+        denoiseFlags=DENOISE_DEMODULATE if demodulate else 0, samples=samples, sigmaLuminance=sigma_luminance, sigmaNormal=sigma_normal,
+        sigmaDepth=sigma_depth, maxHistory=max_history, depthTolerance=depth_tolerance, normalTolerance=normal_tolerance,
+        coverageTolerance=coverage_tolerance)
+    _chk(load_library().tptDenoiseClipDevice(C.byref(a)), "tptDenoiseClipDevice")  # (cameras and prev_cam live until here)
 
 
 ADAPTIVE_MAX_SAMPLES = 2047  # one pixel's samples of one launch (include/tpt_hip.h: 11 bits of sample index in the path record)

@@ -266,6 +266,11 @@ struct Context {
     // Only the context stream uses it, so stream order alone keeps one call's iterations from another's.
     f4* dDenoise = nullptr;
     size_t denoiseBytes = 0;
+    // tptDenoiseClipDevice: its staging (include/tpt_hip.h states the layout: per chunk frame the temporal outputs the filter reads and
+    // the ping-pong plane, and the planes that carry the history from frame to frame), made by the first call that needs it, grown when
+    // a later one needs more, freed by tptShutdown.  Only the context stream uses it.
+    f4* dClipStage = nullptr;
+    size_t clipStageBytes = 0;
     long long aheadHits = 0;            // frames that were found traced ahead when their call arrived (tptGetLookaheadHits)
     // per-frame ray counters of the pending launches, one allocation: [kMaxSlots] AHEAD frames (indexed by the frame's sequence number
     // at enqueue), [2][kMaxBatch] ROW_SERIAL batches (two banks, alternating), [kStreamRing][kStreamBatchMax] STREAM batches (a ring)

@@ -114,6 +114,13 @@ __attribute__((weak)) hipError_t tptLaunchDenoiseVariance(const float* colour, c
                                                           const float* moments, float* out, float* scratch, int width, int height,
                                                           int iterations, float samples, float sl2, float in, float id, bool demodulate,
                                                           hipStream_t stream);
+// tptDenoiseClipDevice: tptLaunchDenoiseVariance for `frames` (1..32) frames at once, one launch per iteration.  Every pointer is the
+// first of `frames` consecutive [h][w] f4 planes -- colour, moments, out and scratch always, albedo / normalDepth when given -- and frame
+// j is filtered exactly as tptLaunchDenoiseVariance filters plane j of each.  Weak for the same reason as tptLaunchDenoise.
+__attribute__((weak)) hipError_t tptLaunchFramesAtrous(const float* colour, const float* albedo, const float* normalDepth,
+                                                       const float* moments, float* out, float* scratch, int width, int height, int frames,
+                                                       int iterations, float samples, float sl2, float in, float id, bool demodulate,
+                                                       hipStream_t stream);
 // tptTemporalAccumulateDevice: what the kernel needs of the two cameras and the call, made on the host in the order include/tpt_hip.h
 // states (host and device are built with -ffp-contract=off); by value in the kernel arguments.
 struct tptTemporalConsts {

@@ -447,6 +447,8 @@ int tptShutdown(void)
     }
     (void)hipFree(g.dDenoise); g.dDenoise = nullptr;
     g.denoiseBytes = 0;
+    (void)hipFree(g.dClipStage); g.dClipStage = nullptr;
+    g.clipStageBytes = 0;
     if (g.hViewsStage) (void)hipHostFree(g.hViewsStage);
     g.hViewsStage = nullptr;
     g.inited = false;

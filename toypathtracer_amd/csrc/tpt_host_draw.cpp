@@ -119,31 +119,12 @@ static int ensureDenoisePlane(int w, int h)
     return 0;
 }
 
-// What tptTemporalAccumulateDevice and tptTemporalAccumulateObjectsDevice refuse, in the order they check it (f: the entry point), and
-// what the kernels need of the two cameras, made here in the stated order (k).
-static int checkTemporal(const std::string& f, int w, int h, const void* camera, const void* prevCamera, const float* deviceColour,
-                         const float* deviceAlbedo, const float* deviceNormalDepth, const float* deviceMoments,
-                         const float* devicePrevColour, const float* devicePrevAlbedo, const float* devicePrevNormalDepth,
-                         const float* devicePrevMoments, float* deviceOutColour, float* deviceOutAlbedo, float* deviceOutMoments,
-                         float* deviceOutVariance, float maxHistory, float depthTolerance, float normalTolerance, float coverageTolerance,
-                         tptTemporalConsts& k)
+// What the temporal passes refuse of their scalars and of the two cameras (prevCamera may be null), in the order they check it, and
+// what the kernels need of the cameras, made here in the stated order (k): the second half of checkTemporal, which
+// tptDenoiseClipDevice runs on its own for every frame of its clip.
+static int temporalConsts(const std::string& f, const void* camera, const void* prevCamera, float maxHistory, float depthTolerance,
+                          float normalTolerance, float coverageTolerance, tptTemporalConsts& k)
 {
-    if (w < 1 || w > 8192 || h < 1 || h > 8192) return fail(f + ": w and h must lie in 1..8192");
-    if (!camera) return fail(f + ": camera is required");
-    if (!deviceColour || !deviceAlbedo || !deviceNormalDepth || !deviceMoments) return fail(f + ": the four planes of this frame are required");
-    if (!deviceOutColour || !deviceOutAlbedo || !deviceOutMoments || !deviceOutVariance) return fail(f + ": the four output planes are required");
-    const int nPrev = (prevCamera != nullptr) + (devicePrevColour != nullptr) + (devicePrevAlbedo != nullptr) +
-                      (devicePrevNormalDepth != nullptr) + (devicePrevMoments != nullptr);
-    if (nPrev != 0 && nPrev != 5) return fail(f + ": prevCamera and the four prev planes must be all NULL or all given");
-    const uintptr_t bytes = (uintptr_t)w * (uintptr_t)h * 16u;
-    const float* outs[4] = {deviceOutColour, deviceOutAlbedo, deviceOutMoments, deviceOutVariance};
-    for (int i = 0; i < 4; ++i) {
-        if (overlapsAny(outs[i], {deviceColour, deviceAlbedo, deviceNormalDepth, deviceMoments, devicePrevColour, devicePrevAlbedo,
-                                  devicePrevNormalDepth, devicePrevMoments}, bytes))
-            return fail(f + ": an output overlaps an input");
-        for (int j = 0; j < i; ++j)
-            if (overlapsAny(outs[i], {outs[j]}, bytes)) return fail(f + ": two outputs overlap");
-    }
     if (!(maxHistory >= 1.0f && maxHistory <= 65536.0f)) return fail(f + ": maxHistory must lie in 1..65536"); // (NaN fails)
     auto tolOk = [](float t) { return t >= 0.0f && t <= 3.40282347e38f; };
     if (!tolOk(depthTolerance) || !tolOk(normalTolerance) || !tolOk(coverageTolerance))
@@ -173,6 +154,34 @@ static int checkTemporal(const std::string& f, int w, int h, const void* camera,
     }
     k.maxHistory = maxHistory; k.depthTol = depthTolerance; k.normalTol = normalTolerance; k.coverageTol = coverageTolerance;
     return 0;
+}
+
+// What tptTemporalAccumulateDevice and tptTemporalAccumulateObjectsDevice refuse, in the order they check it (f: the entry point), and
+// what the kernels need of the two cameras, made here in the stated order (k).
+static int checkTemporal(const std::string& f, int w, int h, const void* camera, const void* prevCamera, const float* deviceColour,
+                         const float* deviceAlbedo, const float* deviceNormalDepth, const float* deviceMoments,
+                         const float* devicePrevColour, const float* devicePrevAlbedo, const float* devicePrevNormalDepth,
+                         const float* devicePrevMoments, float* deviceOutColour, float* deviceOutAlbedo, float* deviceOutMoments,
+                         float* deviceOutVariance, float maxHistory, float depthTolerance, float normalTolerance, float coverageTolerance,
+                         tptTemporalConsts& k)
+{
+    if (w < 1 || w > 8192 || h < 1 || h > 8192) return fail(f + ": w and h must lie in 1..8192");
+    if (!camera) return fail(f + ": camera is required");
+    if (!deviceColour || !deviceAlbedo || !deviceNormalDepth || !deviceMoments) return fail(f + ": the four planes of this frame are required");
+    if (!deviceOutColour || !deviceOutAlbedo || !deviceOutMoments || !deviceOutVariance) return fail(f + ": the four output planes are required");
+    const int nPrev = (prevCamera != nullptr) + (devicePrevColour != nullptr) + (devicePrevAlbedo != nullptr) +
+                      (devicePrevNormalDepth != nullptr) + (devicePrevMoments != nullptr);
+    if (nPrev != 0 && nPrev != 5) return fail(f + ": prevCamera and the four prev planes must be all NULL or all given");
+    const uintptr_t bytes = (uintptr_t)w * (uintptr_t)h * 16u;
+    const float* outs[4] = {deviceOutColour, deviceOutAlbedo, deviceOutMoments, deviceOutVariance};
+    for (int i = 0; i < 4; ++i) {
+        if (overlapsAny(outs[i], {deviceColour, deviceAlbedo, deviceNormalDepth, deviceMoments, devicePrevColour, devicePrevAlbedo,
+                                  devicePrevNormalDepth, devicePrevMoments}, bytes))
+            return fail(f + ": an output overlaps an input");
+        for (int j = 0; j < i; ++j)
+            if (overlapsAny(outs[i], {outs[j]}, bytes)) return fail(f + ": two outputs overlap");
+    }
+    return temporalConsts(f, camera, prevCamera, maxHistory, depthTolerance, normalTolerance, coverageTolerance, k);
 }
 
 } // namespace tpth
@@ -483,6 +492,161 @@ int tptTemporalAccumulateObjectsDevice(int w, int h, const void* camera, const v
     HIPCHK(tptLaunchReprojectObjects(deviceColour, deviceAlbedo, deviceNormalDepth, deviceMoments, devicePrevColour, devicePrevAlbedo,
                                      devicePrevNormalDepth, devicePrevMoments, deviceOutColour, deviceOutAlbedo, deviceOutMoments,
                                      deviceOutVariance, deviceObject, devicePrevObject, deviceObjectMotion, nObjects, w, h, k, g.stream));
+    return 0;
+}
+
+// The context's staging of tptDenoiseClipDevice, grown to `bytes` when a call needs more.
+static int ensureClipStage(size_t bytes)
+{
+    if (bytes <= g.clipStageBytes) return 0;
+    // (an earlier call's launches may still be using the staging being replaced; only the context stream uses it)
+    HIPCHK(hipStreamSynchronize(g.stream));
+    (void)hipFree(g.dClipStage);
+    g.dClipStage = nullptr;
+    g.clipStageBytes = 0;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dClipStage), bytes));
+    g.clipStageBytes = bytes;
+    return 0;
+}
+
+// A clip through the denoising chain (include/tpt_hip.h states it, and the staging's layout): per chunk one temporal launch per frame --
+// the per-frame entry points' launchers, writing T_j into the staging's stacks -- then the filter's iterations, one launch each for
+// the whole chunk.  Everything is checked, and every frame's camera constants are made, before the first launch.
+int tptDenoiseClipDevice(const tptClipDenoiseArgs* args)
+{
+    if (requireInit()) return -1;
+    const std::string f("tptDenoiseClipDevice");
+    if (!args) return fail(f + ": args is required");
+    const tptClipDenoiseArgs& A = *args;
+    const int w = A.screenWidth, h = A.screenHeight, nFrames = A.nFrames;
+    if (nFrames < 1 || nFrames > 4096) return fail(f + ": nFrames must lie in 1..4096");
+    if (w < 1 || w > 8192 || h < 1 || h > 8192) return fail(f + ": w and h must lie in 1..8192");
+    if (A.clipFlags & ~(unsigned)TPT_CLIP_DENOISE_SPATIAL_ONLY) return fail(f + ": unknown clipFlags bits");
+    const bool spatial = (A.clipFlags & TPT_CLIP_DENOISE_SPATIAL_ONLY) != 0, objects = A.deviceFrameObjects != nullptr;
+    if (!A.deviceFrameImages || !A.deviceFrameMoments || !A.deviceFrameOut)
+        return fail(f + ": deviceFrameImages, deviceFrameMoments and deviceFrameOut are required");
+    if (spatial) {
+        if (A.deviceFrameObjects || A.deviceFrameObjectMotion || A.nObjects != 0)
+            return fail(f + ": TPT_CLIP_DENOISE_SPATIAL_ONLY takes no object planes and no motion tables");
+        if (A.prevCamera || A.devicePrevNormalDepth || A.devicePrevObject || A.deviceHistory)
+            return fail(f + ": TPT_CLIP_DENOISE_SPATIAL_ONLY takes no continuation (prevCamera, the prev planes, deviceHistory)");
+    } else {
+        if (!A.deviceFrameAlbedo || !A.deviceFrameNormalDepth || !A.cameras)
+            return fail(f + ": deviceFrameAlbedo, deviceFrameNormalDepth and cameras are required without TPT_CLIP_DENOISE_SPATIAL_ONLY");
+        if (A.prevCamera) {
+            if (!A.deviceHistory || !A.devicePrevNormalDepth) return fail(f + ": prevCamera needs deviceHistory and devicePrevNormalDepth");
+            if ((A.devicePrevObject != nullptr) != objects)
+                return fail(f + ": with prevCamera, devicePrevObject must be given exactly when deviceFrameObjects is");
+        } else if (A.devicePrevNormalDepth || A.devicePrevObject) {
+            return fail(f + ": devicePrevNormalDepth and devicePrevObject need prevCamera");
+        }
+    }
+    int rc = checkDenoise(f.c_str(), true, w, h, A.deviceFrameImages, A.deviceFrameAlbedo, A.deviceFrameNormalDepth, A.deviceFrameMoments,
+                          A.deviceFrameOut, A.iterations, A.samples, A.sigmaLuminance, A.sigmaNormal, A.sigmaDepth, A.denoiseFlags);
+    if (rc) return rc;
+    if (A.nObjects < 0 || A.nObjects > 65534) return fail(f + ": nObjects must lie in 0..65534");
+    if ((A.deviceFrameObjectMotion != nullptr) != (A.nObjects > 0)) return fail(f + ": deviceFrameObjectMotion and nObjects must be given together");
+    if (A.deviceFrameObjectMotion && !objects) return fail(f + ": deviceFrameObjectMotion needs deviceFrameObjects");
+    static_assert(sizeof(CameraPOD) == 22 * sizeof(float), "the reference's Camera");
+    std::vector<tptTemporalConsts> consts(spatial ? 0 : (size_t)nFrames);
+    for (int j = 0; !spatial && j < nFrames; ++j) {
+        const char* cam = static_cast<const char*>(A.cameras) + sizeof(CameraPOD) * (size_t)j;
+        if ((rc = temporalConsts(f, cam, j > 0 ? cam - sizeof(CameraPOD) : A.prevCamera, A.maxHistory, A.depthTolerance, A.normalTolerance,
+                                 A.coverageTolerance, consts[j])))
+            return rc;
+    }
+    // the chunk length: the largest count <= 32 whose staging, in planes, stays within 4096 MiB
+    const size_t pixels = (size_t)w * (size_t)h, planeBytes = pixels * 16u, budget = ((size_t)4096 << 20) / planeBytes;
+    const size_t fit = spatial ? budget : (budget >= 4 ? (budget - 4) / 4 : 0);
+    if (fit < 1) return fail(f + ": not even one frame's staging stays within 4096 MiB");
+    const int chunk = fit < 32 ? (int)fit : 32, held = chunk < nFrames ? chunk : nFrames;
+    // no output may share a byte with an input or with the other output, each at its full extent
+    const uintptr_t stack = (uintptr_t)planeBytes * (uintptr_t)nFrames;
+    const struct { const void* p; uintptr_t bytes; } outs[2] = {{A.deviceFrameOut, stack}, {A.deviceHistory, (uintptr_t)planeBytes * 3u}},
+        ins[8] = {{A.deviceFrameImages, stack}, {A.deviceFrameMoments, stack}, {A.deviceFrameAlbedo, stack}, {A.deviceFrameNormalDepth, stack},
+                  {A.deviceFrameObjects, (uintptr_t)pixels * 4u * (uintptr_t)nFrames},
+                  {A.deviceFrameObjectMotion, (uintptr_t)nFrames * (uintptr_t)A.nObjects * 16u}, {A.devicePrevNormalDepth, planeBytes},
+                  {A.devicePrevObject, (uintptr_t)pixels * 4u}};
+    auto overlap = [](const void* p, uintptr_t pn, const void* q, uintptr_t qn) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+        return a && b && a < b + qn && b < a + pn;
+    };
+    for (const auto& o : outs)
+        for (const auto& i : ins)
+            if (overlap(o.p, o.bytes, i.p, i.bytes)) return fail(f + ": deviceFrameOut or deviceHistory overlaps an input");
+    if (overlap(outs[0].p, outs[0].bytes, outs[1].p, outs[1].bytes)) return fail(f + ": deviceFrameOut overlaps deviceHistory");
+    if (!tptLaunchFramesAtrous) return fail(f + ": this build has no frame-stack a-trous kernel");
+    if (!spatial && !(objects ? (bool)tptLaunchReprojectObjects : (bool)tptLaunchTemporal))
+        return fail(f + ": this build has no temporal accumulation kernel");
+    if ((!spatial || A.iterations > 1) && (rc = ensureClipStage(planeBytes * (spatial ? (size_t)held : 4u * (size_t)held + 4u)))) return rc;
+
+    auto inv2 = [](float s) { return s > 0.0f ? 1.0f / (s * s) : 0.0f; };
+    const float sl2 = A.sigmaLuminance * A.sigmaLuminance, in = inv2(A.sigmaNormal), id = inv2(A.sigmaDepth);
+    const bool demod = (A.denoiseFlags & TPT_DENOISE_DEMODULATE) != 0;
+    const size_t plane = pixels * 4u; // (floats)
+    float* const stage = reinterpret_cast<float*>(g.dClipStage);
+    if (spatial) {
+        for (int c0 = 0; c0 < nFrames; c0 += chunk) {
+            const int m = nFrames - c0 < chunk ? nFrames - c0 : chunk;
+            const size_t at = plane * (size_t)c0;
+            HIPCHK(tptLaunchFramesAtrous(A.deviceFrameImages + at, A.deviceFrameAlbedo ? A.deviceFrameAlbedo + at : nullptr,
+                                         A.deviceFrameNormalDepth ? A.deviceFrameNormalDepth + at : nullptr, A.deviceFrameMoments + at,
+                                         A.deviceFrameOut + at, stage, w, h, m, A.iterations, A.samples, sl2, in, id, demod, g.stream));
+        }
+        return 0;
+    }
+    // the staging: T's colour and albedo in stacks of held + 1 planes (slot 0: the chunk's predecessor, slot 1 + i: frame i of the
+    // chunk), its variance and the ping-pong planes in stacks of `held`, its moments in two planes that the frames alternate between
+    float* const tColour = stage;
+    float* const tAlbedo = tColour + plane * (size_t)(held + 1);
+    float* const tVariance = tAlbedo + plane * (size_t)(held + 1);
+    float* const pingPong = tVariance + plane * (size_t)held;
+    float* const tMoments = pingPong + plane * (size_t)held;
+    int last = 0; // the slot of the clip's last frame
+    for (int c0 = 0; c0 < nFrames; c0 += chunk) {
+        const int m = nFrames - c0 < chunk ? nFrames - c0 : chunk;
+        for (int i = 0; i < m; ++i) {
+            const int j = c0 + i;
+            const size_t at = plane * (size_t)j;
+            const bool history = j > 0 || A.prevCamera;
+            const float* pColour = !history ? nullptr : j > 0 ? tColour + plane * (size_t)i : A.deviceHistory;
+            const float* pAlbedo = !history ? nullptr : j > 0 ? tAlbedo + plane * (size_t)i : A.deviceHistory + plane;
+            const float* pMoments = !history ? nullptr : j > 0 ? tMoments + plane * (size_t)((j - 1) & 1) : A.deviceHistory + 2 * plane;
+            const float* pNormalDepth = !history ? nullptr : j > 0 ? A.deviceFrameNormalDepth + at - plane : A.devicePrevNormalDepth;
+            float* oColour = tColour + plane * (size_t)(i + 1);
+            float* oAlbedo = tAlbedo + plane * (size_t)(i + 1);
+            float* oMoments = tMoments + plane * (size_t)(j & 1);
+            float* oVariance = tVariance + plane * (size_t)i;
+            if (objects) {
+                tptReprojectConsts k;
+                k.t = consts[j];
+                const int32_t* pObject = !history ? nullptr : j > 0 ? A.deviceFrameObjects + pixels * (size_t)(j - 1) : A.devicePrevObject;
+                HIPCHK(tptLaunchReprojectObjects(A.deviceFrameImages + at, A.deviceFrameAlbedo + at, A.deviceFrameNormalDepth + at,
+                                                 A.deviceFrameMoments + at, pColour, pAlbedo, pNormalDepth, pMoments, oColour, oAlbedo, oMoments,
+                                                 oVariance, A.deviceFrameObjects + pixels * (size_t)j, pObject,
+                                                 A.deviceFrameObjectMotion ? A.deviceFrameObjectMotion + 4u * (size_t)A.nObjects * (size_t)j : nullptr,
+                                                 A.nObjects, w, h, k, g.stream));
+            } else {
+                HIPCHK(tptLaunchTemporal(A.deviceFrameImages + at, A.deviceFrameAlbedo + at, A.deviceFrameNormalDepth + at,
+                                         A.deviceFrameMoments + at, pColour, pAlbedo, pNormalDepth, pMoments, oColour, oAlbedo, oMoments,
+                                         oVariance, w, h, consts[j], g.stream));
+            }
+        }
+        HIPCHK(tptLaunchFramesAtrous(tColour + plane, tAlbedo + plane, A.deviceFrameNormalDepth + plane * (size_t)c0, tVariance,
+                                     A.deviceFrameOut + plane * (size_t)c0, pingPong, w, h, m, A.iterations, A.samples, sl2, in, id, demod,
+                                     g.stream));
+        last = m;
+        if (c0 + m < nFrames) { // the next chunk overwrites slots 1 ..: its first frame finds this chunk's last in slot 0
+            HIPCHK(hipMemcpyAsync(tColour, tColour + plane * (size_t)m, planeBytes, hipMemcpyDeviceToDevice, g.stream));
+            HIPCHK(hipMemcpyAsync(tAlbedo, tAlbedo + plane * (size_t)m, planeBytes, hipMemcpyDeviceToDevice, g.stream));
+        }
+    }
+    if (A.deviceHistory) {
+        HIPCHK(hipMemcpyAsync(A.deviceHistory, tColour + plane * (size_t)last, planeBytes, hipMemcpyDeviceToDevice, g.stream));
+        HIPCHK(hipMemcpyAsync(A.deviceHistory + plane, tAlbedo + plane * (size_t)last, planeBytes, hipMemcpyDeviceToDevice, g.stream));
+        HIPCHK(hipMemcpyAsync(A.deviceHistory + 2 * plane, tMoments + plane * (size_t)((nFrames - 1) & 1), planeBytes, hipMemcpyDeviceToDevice,
+                              g.stream));
+    }
     return 0;
 }
 

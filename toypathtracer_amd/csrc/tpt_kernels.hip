@@ -394,15 +394,14 @@ __global__ void __launch_bounds__(256) tptDenoiseKernel(const f4* __restrict__ s
 // previous iteration's plane, colour and v.  LAST stores the colour (remodulated when `demod`) with the caller's alpha.  GUIDE: a
 // normal / depth plane is given.  Each lane first takes g, the 3x3 binomial blur of v around it, for its luminance weight; taps
 // outside the image are skipped everywhere.  The weight's division is tdivSafeNum (numerator in [2^-8, 2^-2], as in
-// tptDenoiseKernel), every other quotient a plain IEEE one.
+// tptDenoiseKernel), every other quotient a plain IEEE one.  varianceAtrousPixel is the lane's work for pixel (x, y) inside the image; the
+// per-frame kernel below and tptFramesAtrousKernel (a stack of frames) both are that function behind their own indexing.
 template <bool FIRST, bool LAST, bool GUIDE>
-__global__ void __launch_bounds__(256) tptVarianceAtrousKernel(const f4* __restrict__ src, const f4* __restrict__ colour,
-                                                                const f4* __restrict__ albedo, const f4* __restrict__ nd,
-                                                                const f4* __restrict__ moments, f4* __restrict__ dst, int width, int height,
-                                                                int step, float samples, float sl2, float in, float id, int demod)
+__device__ __forceinline__ void varianceAtrousPixel(const f4* __restrict__ src, const f4* __restrict__ colour, const f4* __restrict__ albedo,
+                                                    const f4* __restrict__ nd, const f4* __restrict__ moments, f4* __restrict__ dst, int x,
+                                                    int y, int width, int height, int step, float samples, float sl2, float in, float id,
+                                                    int demod)
 {
-    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
-    if (x >= width || y >= height) return;
     constexpr float hk[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
     constexpr float gk[3] = {0.25f, 0.5f, 0.25f};
     auto lum = [](float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; };
@@ -478,6 +477,34 @@ __global__ void __launch_bounds__(256) tptVarianceAtrousKernel(const f4* __restr
         o.w = sumV / (sumW * sumW);
     }
     dst[p] = o;
+}
+template <bool FIRST, bool LAST, bool GUIDE>
+__global__ void __launch_bounds__(256) tptVarianceAtrousKernel(const f4* __restrict__ src, const f4* __restrict__ colour,
+                                                                const f4* __restrict__ albedo, const f4* __restrict__ nd,
+                                                                const f4* __restrict__ moments, f4* __restrict__ dst, int width, int height,
+                                                                int step, float samples, float sl2, float in, float id, int demod)
+{
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x >= width || y >= height) return;
+    varianceAtrousPixel<FIRST, LAST, GUIDE>(src, colour, albedo, nd, moments, dst, x, y, width, height, step, samples, sl2, in, id, demod);
+}
+
+// tptDenoiseClipDevice's a-trous iteration: tptVarianceAtrousKernel's pixel for frame blockIdx.z of a stack of planes.  Every pointer is
+// the first plane of its stack, the planes width * height pixels apart (a size_t: 32 planes of 8192 x 8192 pass 2^31 pixels), and each
+// frame is filtered inside its own plane: the pixel function sees the frame's planes and the frame's width and height only, so a tap
+// that leaves the image is skipped and never lands in the neighbouring frame.  (A stack that is not given stays unread, as in the
+// per-frame kernel: its null pointer is offset, never followed.)
+template <bool FIRST, bool LAST, bool GUIDE>
+__global__ void __launch_bounds__(256) tptFramesAtrousKernel(const f4* __restrict__ src, const f4* __restrict__ colour,
+                                                              const f4* __restrict__ albedo, const f4* __restrict__ nd,
+                                                              const f4* __restrict__ moments, f4* __restrict__ dst, int width, int height,
+                                                              int step, float samples, float sl2, float in, float id, int demod)
+{
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x >= width || y >= height) return;
+    const size_t plane = (size_t)blockIdx.z * ((size_t)width * (size_t)height);
+    varianceAtrousPixel<FIRST, LAST, GUIDE>(src + plane, colour + plane, albedo + plane, nd + plane, moments + plane, dst + plane, x, y, width,
+                                            height, step, samples, sl2, in, id, demod);
 }
 
 // tptTemporalAccumulateDevice (include/tpt_hip.h states it; tests/temporal_checker.c restates it): this frame's planes blended with the
@@ -2603,6 +2630,32 @@ hipError_t tptLaunchDenoiseVariance(const float* colour, const float* albedo, co
         (nd ? launchDenoiseVarianceIteration<true> : launchDenoiseVarianceIteration<false>)(i == 0, i == iterations - 1, grid, stream, src, c, a,
                                                                                            nd, m, dst, width, height, 1 << i, samples, sl2,
                                                                                            in, id, demodulate ? 1 : 0);
+    });
+}
+
+template <bool GUIDE>
+static void launchFramesAtrousIteration(bool first, bool last, dim3 grid, hipStream_t stream, const f4* src, const f4* colour, const f4* albedo,
+                                        const f4* nd, const f4* moments, f4* dst, int width, int height, int step, float samples, float sl2,
+                                        float in, float id, int demod)
+{
+    auto k = first ? (last ? tptFramesAtrousKernel<true, true, GUIDE> : tptFramesAtrousKernel<true, false, GUIDE>)
+                   : (last ? tptFramesAtrousKernel<false, true, GUIDE> : tptFramesAtrousKernel<false, false, GUIDE>);
+    hipLaunchKernelGGL(k, grid, dim3(64, 4), 0, stream, src, colour, albedo, nd, moments, dst, width, height, step, samples, sl2, in, id,
+                       demod);
+}
+hipError_t tptLaunchFramesAtrous(const float* colour, const float* albedo, const float* normalDepth, const float* moments, float* out,
+                                 float* scratch, int width, int height, int frames, int iterations, float samples, float sl2, float in,
+                                 float id, bool demodulate, hipStream_t stream)
+{
+    const dim3 grid((unsigned)(width + 63) / 64, (unsigned)(height + 3) / 4, (unsigned)frames);
+    const f4* c = reinterpret_cast<const f4*>(colour);
+    const f4* a = reinterpret_cast<const f4*>(albedo);
+    const f4* nd = reinterpret_cast<const f4*>(normalDepth);
+    const f4* m = reinterpret_cast<const f4*>(moments);
+    return atrousIterations(colour, out, scratch, iterations, [&](int i, const f4* src, f4* dst) {
+        (nd ? launchFramesAtrousIteration<true> : launchFramesAtrousIteration<false>)(i == 0, i == iterations - 1, grid, stream, src, c, a, nd,
+                                                                                     m, dst, width, height, 1 << i, samples, sl2, in, id,
+                                                                                     demodulate ? 1 : 0);
     });
 }
 
