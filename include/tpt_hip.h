@@ -505,6 +505,83 @@ typedef struct tptClipDenoiseArgs {
     float maxHistory, depthTolerance, normalTolerance, coverageTolerance;
 } tptClipDenoiseArgs;
 TPT_API int tptDenoiseClipDevice(const tptClipDenoiseArgs* args);
+/* A CLIP'S MOTION VECTORS: for every pixel of every frame of a clip, where its surface point stood in the previous frame, how far from
+ * that frame's camera, and how much of the bilinear footprint there shows the same surface (0: disoccluded) -- what steps 1-4 of
+ * tptTemporalAccumulateDevice and tptTemporalAccumulateObjectsDevice derive for their own blend, written out: backward optical flow
+ * with an occlusion mask, with the library's own motion tables, snap and surface tests.
+ * The planes: every deviceFrame* pointer is nFrames consecutive device planes, h*w*4 floats each (deviceFrameObjects: h*w int32 each),
+ * plane j frame j's, laid out as the clip draws and tptDenoiseClipDevice lay them out.
+ *   cameras              HOST memory, nFrames x 88-byte Camera records (the clip draws' outCameras), read during the call; required
+ *   deviceFrameAlbedo, deviceFrameNormalDepth   required: the clip draws' planes; albedo.w is the coverage
+ *   deviceFrameObjects   NULL, or the object planes: non-NULL selects the object-following form
+ *   deviceFrameObjectMotion, nObjects   DEVICE memory, nFrames x nObjects x 4 floats: table j is tptTemporalAccumulateObjectsDevice's
+ *                        table between frame j-1 and frame j (table 0 is read only when prevCamera is given); NULL with nObjects == 0
+ *                        as in that function; allowed only with deviceFrameObjects.  The entries' .w, the history cap, is ignored here
+ *   deviceFrameMotion    required: the output, nFrames planes of h*w*4 floats
+ *   prevCamera (HOST, 88 bytes), devicePrevAlbedo, devicePrevNormalDepth, devicePrevObject   frame -1, the predecessor of frame 0: all
+ *                        NULL (frame 0 has no predecessor), or prevCamera and both planes given, and devicePrevObject given exactly
+ *                        when deviceFrameObjects is
+ *   depthTolerance, normalTolerance, coverageTolerance   the temporal pass's, for every frame
+ *   flags                must be 0
+ * Frame j's predecessor is plane j-1 of the same stacks with camera j-1; frame 0's is the prev set.
+ * Binary32, in the order written, no FMA, correctly rounded division and square root, sums from +0;  dot(a, b) = (a.x*b.x + a.y*b.y)
+ * + a.z*b.z;  vectors component by component;  every comparison with a NaN is false.  Camera fields o = origin, ll = lowerLeftCorner,
+ * H = horizontal, V = vertical, w = ww; unprimed: frame j's camera; primed: its predecessor's.  Once per frame, on the host, in this
+ * order:  a = ll' - o';  f = -dot(a, w');  hh = dot(H', H');  vv = dot(V', V').
+ * Per pixel p = (x, y) of a frame with a predecessor, with c = albedo_j[p].w and, in the object form, id = objects_j[p]:
+ *   1. s = (x + 0.5f) / width;  t = (y + 0.5f) / height;  v = ((ll + s*H) + t*V) - o;  dir = v * (1.0f / sqrt(dot(v, v)))
+ *      c > 0:  d = nd_j[p].w / c;  n = nd_j[p].xyz / c;  at = o + dir*d;  in the object form, with the table given and
+ *              0 <= id < nObjects:  at = at + motion_j[id].xyz  (in every other case nothing is added);  rel = at - o'
+ *      otherwise (sky):  rel = dir
+ *   2. z = -dot(rel, w');  k = f / z;  q = rel*k - a;  px = dot(q, H') / hh * width - 0.5f;  py = dot(q, V') / vv * height - 0.5f
+ *      The pixel PROJECTS if z > 0 and px and py are finite.  If it does not, motion_j[p] = {0, 0, 0, 0}.
+ *   3. fx0 = floor(px);  fx = px - fx0;  fx < TPT_TEMPORAL_SNAP: fx = 0;  else fx > 1 - TPT_TEMPORAL_SNAP: fx0 = fx0 + 1, fx = 0;
+ *      likewise fy0, fy.  mv = {(fx0 + fx) - (float)x, (fy0 + fy) - (float)y}  -- the sum is formed after the snap, so a camera and a
+ *      scene that stand still give exactly {0, 0}.  e = sqrt(dot(rel, rel))
+ *   4. W = 0.  Only if px >= -1, px < width, py >= -1 and py < height:  ix = (int)fx0, iy = (int)fy0, and the taps are
+ *      (ix + i, iy + j), i, j in {0, 1}, j outer, with b = (i ? fx : 1 - fx) * (j ? fy : 1 - fy).  A tap counts if b > 0, it lies
+ *      inside the image, in the object form objects'[tap] == id, and, with c' = albedo'[tap].w,  |c - c'| <= coverageTolerance  and
+ *      either
+ *        c == 0 and c' == 0  (sky), or
+ *        c > 0 and c' > 0,  |e - d'| <= depthTolerance * e  with d' = nd'[tap].w / c',  and
+ *        (dx*dx + dy*dy) + dz*dz <= normalTolerance  with (dx, dy, dz) = n - nd'[tap].xyz / c'
+ *      W = the sum of b over the counted taps.
+ *   5. motion_j[p] = {mv.x, mv.y, e, W}:  mv says where, in pixels, the point stood in the previous frame, relative to this pixel;  e is
+ *      its distance from the previous camera;  W in [0, 1] is how much of the bilinear footprint there shows the same surface -- 0 means
+ *      disoccluded, outside the image, or another surface.
+ * A frame 0 without prevCamera has no predecessor: every pixel of plane 0 is {0, 0, 0, 0}.
+ * The taps read the previous frame's OWN albedo and normal / depth planes (primed: plane j-1 as traced), not an accumulated history,
+ * and they do not ask for a history length or a finite colour.  That is the only difference from step 4 of
+ * tptTemporalAccumulate[Objects]Device, and it is what makes the frames independent: this is no recurrence, and a clip cut into calls
+ * (the prev set pointing at the last plane and camera of the call before) gives the bytes of one call.  Where the temporal pass is fed
+ * frame j-1 as a first frame, W > 0 exactly where it finds a history.
+ * Asynchronous on the context stream, ordered like tptDenoiseDevice; needs tptInitialize only.  The inputs are never written; frames
+ * traced ahead, stream batches, scene and camera are left alone.  The cameras' constants travel in a table the library owns (one copy
+ * per call, grown on demand, kept until tptShutdown).
+ * Refused (non-zero, tptGetLastError names the function, nothing enqueued, no byte written): args NULL; no context; nFrames outside
+ * 1..4096; w or h outside 1..8192; flags != 0; a required pointer NULL; the prev set neither all given nor all NULL (devicePrevObject
+ * counts exactly when deviceFrameObjects is given, and is refused without it); a table without deviceFrameObjects; nObjects outside
+ * 0..65534, or exactly one of table and nObjects set; a tolerance negative, NaN or infinite; every camera the temporal passes refuse
+ * (a non-finite field, dot(H, H) == 0, dot(V, V) == 0 or f <= 0), for every record in cameras and for prevCamera; deviceFrameMotion
+ * overlapping any input, each taken at its full extent (nFrames planes, one plane for the prev planes, nFrames x nObjects x 16 bytes
+ * for the tables). */
+typedef struct tptMotionVectorsArgs {
+    int screenWidth, screenHeight, nFrames;
+    unsigned flags;
+    const void* cameras;
+    const float* deviceFrameAlbedo;
+    const float* deviceFrameNormalDepth;
+    const int32_t* deviceFrameObjects;
+    const float* deviceFrameObjectMotion;
+    float* deviceFrameMotion;
+    const void* prevCamera;
+    const float* devicePrevAlbedo;
+    const float* devicePrevNormalDepth;
+    const int32_t* devicePrevObject;
+    int nObjects;
+    float depthTolerance, normalTolerance, coverageTolerance;
+} tptMotionVectorsArgs;
+TPT_API int tptMotionVectorsDevice(const tptMotionVectorsArgs* args);
 /* ADAPTIVE SAMPLING: tptDrawDeviceMoments with a sample count per pixel, so that the moments can steer the next pass (the counts come
  * from tptAdaptiveSamplesDevice below, or from the caller).  deviceSampleCounts (required): h*w int32 in DEVICE memory, row-major like the
  * tile, read by the kernels only.  Per pixel p, n = deviceSampleCounts[p] clamped to 0 .. 2047 (the path record holds 11 bits of sample

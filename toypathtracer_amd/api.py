@@ -39,7 +39,7 @@ C_ABI_SYMBOLS = [
     "tptSetSamplesPerPixel", "tptSetConfig", "tptSetSeedMode", "tptSetFoldMode", "tptSetScene", "tptSetCamera", "tptSetStream",
     "tptSetRowShard", "tptLocalRowCount", "tptLocalRowToGlobal", "tptDrawDevice", "tptRayCounterRead", "tptSetRayCounter", "tptSetFrameOverlap", "tptDisplayRGBA8", "tptKernelTimingBegin", "tptKernelTimingEnd",
     "tptSynchronize", "tptTimerBegin", "tptTimerEnd", "tptSetKernelVariant",
-    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceAnimationMoments", "tptDrawDeviceCameraClip", "tptDrawDeviceKeyframeClip", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptObjectPlaneDevice", "tptObjectMotionTable", "tptTemporalAccumulateObjectsDevice", "tptDenoiseClipDevice", "tptDrawDeviceAdaptive", "tptAdaptiveSamplesDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
+    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceAnimationMoments", "tptDrawDeviceCameraClip", "tptDrawDeviceKeyframeClip", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptObjectPlaneDevice", "tptObjectMotionTable", "tptTemporalAccumulateObjectsDevice", "tptDenoiseClipDevice", "tptMotionVectorsDevice", "tptDrawDeviceAdaptive", "tptAdaptiveSamplesDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
 ]
 # include/tpt_test_hooks.h: exported by the second build (libtoypathtracer_hip_hooks.so) only
 HOOK_SYMBOLS = ["tptTestMath", "tptTestMathExhaustive", "tptTestHitSpheres", "tptTestMatrixFilter", "tptTestGroupFilter", "tptTestSetDealCapacities", "tptDebugStats", "tptDebugChunkOrder"]
@@ -59,6 +59,16 @@ class ClipDenoiseArgs(C.Structure):
                 + [("nObjects", C.c_int), ("iterations", C.c_int), ("denoiseFlags", C.c_uint)]
                 + [(name, C.c_float) for name in ("samples", "sigmaLuminance", "sigmaNormal", "sigmaDepth", "maxHistory", "depthTolerance",
                                                   "normalTolerance", "coverageTolerance")])
+
+
+class MotionVectorsArgs(C.Structure):
+    """include/tpt_hip.h: tptMotionVectorsArgs (tests/test_flow_abi.py holds the layout against the header)"""
+    _fields_ = ([("screenWidth", C.c_int), ("screenHeight", C.c_int), ("nFrames", C.c_int), ("flags", C.c_uint)]
+                + [(name, C.c_void_p) for name in ("cameras", "deviceFrameAlbedo", "deviceFrameNormalDepth", "deviceFrameObjects",
+                                                   "deviceFrameObjectMotion", "deviceFrameMotion", "prevCamera", "devicePrevAlbedo",
+                                                   "devicePrevNormalDepth", "devicePrevObject")]
+                + [("nObjects", C.c_int)]
+                + [(name, C.c_float) for name in ("depthTolerance", "normalTolerance", "coverageTolerance")])
 
 
 def _lib_dir():
@@ -89,7 +99,7 @@ def _bind(path, hooks):
         "tptSetRayCounter": [p], "tptSetTileMirror": [p, p], "tptSetFrameOverlap": [i], "tptDisplayRGBA8": [p, i, i, p], "tptKernelTimingBegin": [i],
         "tptKernelTimingEnd": [C.POINTER(f), C.POINTER(i)],
         "tptSynchronize": [], "tptTimerBegin": [], "tptTimerEnd": [C.POINTER(f)], "tptSetKernelVariant": [i, i, i],
-        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDrawDeviceAnimationMoments": [i, i, p, i, i] + [p] * 7 + [u], "tptDrawDeviceCameraClip": [i, i, p, p, i, i] + [p] * 8 + [u], "tptDrawDeviceKeyframeClip": [i, i, p, i, p, p, i, i] + [p] * 9 + [u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptObjectPlaneDevice": [i, p, p, i, i, p, u], "tptObjectMotionTable": [f, f, u, p, i], "tptTemporalAccumulateObjectsDevice": [i, i] + [p] * 14 + [f] * 4 + [p, p, p, i], "tptDenoiseClipDevice": [C.POINTER(ClipDenoiseArgs)], "tptDrawDeviceAdaptive": [f, i, i, i, p, p, p, p, p, u], "tptAdaptiveSamplesDevice": [i, i, p, f, i, i, p, p, p], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
+        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDrawDeviceAnimationMoments": [i, i, p, i, i] + [p] * 7 + [u], "tptDrawDeviceCameraClip": [i, i, p, p, i, i] + [p] * 8 + [u], "tptDrawDeviceKeyframeClip": [i, i, p, i, p, p, i, i] + [p] * 9 + [u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptObjectPlaneDevice": [i, p, p, i, i, p, u], "tptObjectMotionTable": [f, f, u, p, i], "tptTemporalAccumulateObjectsDevice": [i, i] + [p] * 14 + [f] * 4 + [p, p, p, i], "tptDenoiseClipDevice": [C.POINTER(ClipDenoiseArgs)], "tptMotionVectorsDevice": [C.POINTER(MotionVectorsArgs)], "tptDrawDeviceAdaptive": [f, i, i, i, p, p, p, p, p, u], "tptAdaptiveSamplesDevice": [i, i, p, f, i, i, p, p, p], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
     }
     if hooks:
         sigs.update({"tptDebugStats": [p, i], "tptDebugChunkOrder": [p, p, i], "tptTestMath": [i, p, p, p, i], "tptTestMathExhaustive": [i, u, u, p, p],
@@ -903,6 +913,58 @@ def denoise_clip_device(w, h, frames, images_ptr, moments_ptr, out_ptr, samples,
         sigmaDepth=sigma_depth, maxHistory=max_history, depthTolerance=depth_tolerance, normalTolerance=normal_tolerance,
         coverageTolerance=coverage_tolerance)
     _chk(load_library().tptDenoiseClipDevice(C.byref(a)), "tptDenoiseClipDevice")  # (cameras and prev_cam live until here)
+
+
+def motion_vectors_device(w, h, frames, albedo_ptr, normal_depth_ptr, motion_out_ptr, cameras, objects_ptr=None, motion_ptr=None,
+                          n_objects=0, prev=None, depth_tolerance=TEMPORAL_DEFAULTS["depth_tolerance"],
+                          normal_tolerance=TEMPORAL_DEFAULTS["normal_tolerance"],
+                          coverage_tolerance=TEMPORAL_DEFAULTS["coverage_tolerance"]):
+    """tptMotionVectorsDevice: per pixel of `frames` frames of a clip draw, {mv.x, mv.y, e, W} into motion_out_ptr (`frames` device
+    planes of h*w*4 floats): mv where, in pixels, the pixel's surface point stood in the previous frame relative to this pixel, e its
+    distance from the previous camera, W in [0, 1] how much of the bilinear footprint there shows the same surface (0: disoccluded,
+    outside the image, another surface; all four 0 where the point does not project).  albedo_ptr, normal_depth_ptr: the clip draw's
+    planes, `frames` of h*w*4 floats each.  cameras: the clip draw's result, a CAMERA_DT array of `frames` records.  objects_ptr: None,
+    or the clip's object planes (h*w int32 each): points then move with their object, by motion_ptr / n_objects -- None / 0, or
+    `frames` tables of n_objects x 4 floats in device memory, table j between frames j-1 and j -- and a tap counts only on the same
+    object.  prev: None (frame 0 has no predecessor: its plane is zeroed) or (camera, albedo_ptr, normal_depth_ptr) -- with
+    objects_ptr (camera, albedo_ptr, normal_depth_ptr, object_ptr) -- of the frame before frame 0.  The tolerances are
+    temporal_accumulate_device's.  Ordered on the context's stream."""
+    _positive_ints(("w", w), ("h", h), ("frames", frames))
+    if frames > CLIP_DENOISE_MAX_FRAMES:
+        raise ValueError("frames: 1..%d expected, got %d" % (CLIP_DENOISE_MAX_FRAMES, frames))
+    named = (("albedo_ptr", albedo_ptr), ("normal_depth_ptr", normal_depth_ptr), ("motion_out_ptr", motion_out_ptr),
+             ("objects_ptr", objects_ptr), ("motion_ptr", motion_ptr))
+    _pointers(*named)
+    if not albedo_ptr or not normal_depth_ptr or not motion_out_ptr:
+        raise ValueError("albedo_ptr, normal_depth_ptr, motion_out_ptr: device buffers are required")
+    if not isinstance(cameras, np.ndarray) or cameras.dtype != CAMERA_DT or cameras.shape != (frames,):
+        raise ValueError("cameras: a CAMERA_DT array of %d records expected, got %r" % (frames, cameras))
+    cameras = np.ascontiguousarray(cameras)
+    prev_cam, prev_ptrs = None, (None, None, None)
+    if prev is not None:
+        if not isinstance(prev, (tuple, list)) or len(prev) != (4 if objects_ptr else 3):
+            raise ValueError("prev: None or (camera, albedo_ptr, normal_depth_ptr%s) expected, got %r"
+                             % (", object_ptr" if objects_ptr else "", prev))
+        prev_cam = _camera_bytes("prev camera", prev[0])
+        more = tuple(zip(("prev albedo_ptr", "prev normal_depth_ptr", "prev object_ptr"), prev[1:]))
+        _pointers(*more)
+        if not all(v for _, v in more):
+            raise ValueError("prev: every device buffer is required")
+        prev_ptrs = tuple(prev[1:]) + (None,) * (4 - len(prev))
+    if not isinstance(n_objects, (int, np.integer)) or isinstance(n_objects, bool) or not 0 <= n_objects <= OBJECT_MOTION_MAX_OBJECTS:
+        raise ValueError("n_objects: an int in 0..%d expected, got %r" % (OBJECT_MOTION_MAX_OBJECTS, n_objects))
+    if bool(motion_ptr) != (n_objects > 0):
+        raise ValueError("motion_ptr, n_objects: both or neither expected, got %r and %r" % (motion_ptr, n_objects))
+    if motion_ptr and not objects_ptr:
+        raise ValueError("motion_ptr: needs objects_ptr")
+    _sigmas(("depth_tolerance", depth_tolerance), ("normal_tolerance", normal_tolerance), ("coverage_tolerance", coverage_tolerance))
+    a = MotionVectorsArgs(
+        screenWidth=w, screenHeight=h, nFrames=frames, flags=0, cameras=cameras.ctypes.data, deviceFrameAlbedo=albedo_ptr,
+        deviceFrameNormalDepth=normal_depth_ptr, deviceFrameObjects=objects_ptr or None, deviceFrameObjectMotion=motion_ptr or None,
+        deviceFrameMotion=motion_out_ptr, prevCamera=C.addressof(prev_cam) if prev_cam is not None else None,
+        devicePrevAlbedo=prev_ptrs[0], devicePrevNormalDepth=prev_ptrs[1], devicePrevObject=prev_ptrs[2], nObjects=n_objects,
+        depthTolerance=depth_tolerance, normalTolerance=normal_tolerance, coverageTolerance=coverage_tolerance)
+    _chk(load_library().tptMotionVectorsDevice(C.byref(a)), "tptMotionVectorsDevice")  # (cameras and prev_cam live until here)
 
 
 ADAPTIVE_MAX_SAMPLES = 2047  # one pixel's samples of one launch (include/tpt_hip.h: 11 bits of sample index in the path record)

@@ -271,6 +271,18 @@ struct Context {
     // a later one needs more, freed by tptShutdown.  Only the context stream uses it.
     f4* dClipStage = nullptr;
     size_t clipStageBytes = 0;
+    // tptMotionVectorsDevice: the table of per-frame camera constants its kernel reads (one tptFlowConsts per frame of a call), copied on the
+    // context stream out of a pinned twin.  The device table is single: its copy and the launches that read it are ordered on the
+    // context stream, the only one that uses it.  The pinned twin has two halves of flowConstsBytes each, taken in turn (flowSeq) as
+    // hKeySph's are: a call fills its half while the previous call's copy may still be queued on the other, so that copy reads what its
+    // own call wrote.  evFlow[h]: half h's last copy has left the host (the call after the next waits for it before it refills h).
+    // Grown on demand (after a drain of the context stream), kept until tptShutdown.
+    tptFlowConsts* dFlowConsts = nullptr;
+    tptFlowConsts* hFlowConsts = nullptr;
+    size_t flowConstsBytes = 0;
+    hipEvent_t evFlow[2] = {nullptr, nullptr};
+    bool flowCopied[2] = {false, false};
+    unsigned flowSeq = 0;
     long long aheadHits = 0;            // frames that were found traced ahead when their call arrived (tptGetLookaheadHits)
     // per-frame ray counters of the pending launches, one allocation: [kMaxSlots] AHEAD frames (indexed by the frame's sequence number
     // at enqueue), [2][kMaxBatch] ROW_SERIAL batches (two banks, alternating), [kStreamRing][kStreamBatchMax] STREAM batches (a ring)

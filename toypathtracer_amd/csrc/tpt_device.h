@@ -160,6 +160,24 @@ __attribute__((weak)) hipError_t tptLaunchReprojectObjects(const float* colour, 
                                                            const int32_t* object, const int32_t* prevObject, const float* motion,
                                                            int nObjects, int width, int height, const tptReprojectConsts& k,
                                                            hipStream_t stream);
+// tptMotionVectorsDevice: what the kernel needs of one frame's camera, of its predecessor's and of the call, made on the host like
+// tptTemporalConsts (the same fields in the same order, without the history length).  One record per frame of the clip in a table in
+// device memory: 32 frames of them do not fit in kernel arguments.  (A struct of its own name, for the reason tptReprojectConsts has one.)
+struct tptFlowConsts {
+    float o[3], ll[3], H[3], V[3];
+    float po[3], pa[3], pw[3], pH[3], pV[3];
+    float pf, phh, pvv;
+    float depthTol, normalTol, coverageTol;
+};
+// One launch of the motion-vector kernel over `frames` consecutive frames: every plane pointer is the first of `frames` planes ([h][w]
+// f4, the object planes [h][w] int32), the prev pointers those of the first frame's predecessor (for frames inside a clip the same
+// stacks one plane earlier), `motion` the first frame's table of `frames` tables of nObjects f4 (null with nObjects == 0), deviceConsts
+// the first frame's record of `frames` records in device memory.  object / prevObject both null: the plain form.  Weak for the same
+// reason as tptLaunchDenoise.
+__attribute__((weak)) hipError_t tptLaunchFlow(const float* albedo, const float* normalDepth, const int32_t* object, const float* prevAlbedo,
+                                               const float* prevNormalDepth, const int32_t* prevObject, const float* motion, int nObjects,
+                                               float* out, int width, int height, int frames, const tptFlowConsts* deviceConsts,
+                                               hipStream_t stream);
 // tptDrawDeviceAdaptive's blend: tile.rgb and moments.xyz with lerp = S / (S + n) per pixel, S the running sample count in moments.w
 // (0 unless `progressive`), n the pixel's clamped count; moments.w = S + n; pixels with n == 0 untouched.  Weak for the same reason as
 // tptLaunchDenoise.

@@ -449,6 +449,14 @@ int tptShutdown(void)
     g.denoiseBytes = 0;
     (void)hipFree(g.dClipStage); g.dClipStage = nullptr;
     g.clipStageBytes = 0;
+    (void)hipFree(g.dFlowConsts); g.dFlowConsts = nullptr;
+    if (g.hFlowConsts) (void)hipHostFree(g.hFlowConsts);
+    g.hFlowConsts = nullptr;
+    g.flowConstsBytes = 0;
+    for (int i = 0; i < 2; ++i) {
+        g.flowCopied[i] = false;
+        if (g.evFlow[i]) { (void)hipEventDestroy(g.evFlow[i]); g.evFlow[i] = nullptr; }
+    }
     if (g.hViewsStage) (void)hipHostFree(g.hViewsStage);
     g.hViewsStage = nullptr;
     g.inited = false;

@@ -650,6 +650,116 @@ int tptDenoiseClipDevice(const tptClipDenoiseArgs* args)
     return 0;
 }
 
+// tptMotionVectorsDevice's table (Context::dFlowConsts) and the two halves of its pinned twin, grown to `records` records when a call
+// needs more: the next half is filled with `consts` and copied into the table on the context stream.  `dev`: the table.
+static int uploadFlowConsts(const tptFlowConsts* consts, size_t records, const tptFlowConsts*& dev)
+{
+    const size_t half = sizeof(tptFlowConsts) * records;
+    for (int i = 0; i < 2; ++i)
+        if (!g.evFlow[i]) HIPCHK(hipEventCreateWithFlags(&g.evFlow[i], kOrderingEvent));
+    if (half > g.flowConstsBytes) {
+        // (an earlier call's copy or launches may still be using the table being replaced; only the context stream uses it)
+        HIPCHK(hipStreamSynchronize(g.stream));
+        (void)hipFree(g.dFlowConsts);
+        if (g.hFlowConsts) (void)hipHostFree(g.hFlowConsts);
+        g.dFlowConsts = g.hFlowConsts = nullptr;
+        g.flowConstsBytes = 0;
+        g.flowCopied[0] = g.flowCopied[1] = false;
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dFlowConsts), half));
+        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&g.hFlowConsts), 2 * half, hipHostMallocDefault));
+        g.flowConstsBytes = half;
+    }
+    const int hf = (int)(g.flowSeq++ & 1u);
+    if (g.flowCopied[hf]) HIPCHK(hipEventSynchronize(g.evFlow[hf])); // the half's previous copy has left the pinned twin
+    tptFlowConsts* const host = g.hFlowConsts + (size_t)hf * (g.flowConstsBytes / sizeof(tptFlowConsts));
+    memcpy(host, consts, half);
+    // (one table: its copy and the launches that read it are ordered on the context stream, behind the previous call's launches)
+    HIPCHK(hipMemcpyAsync(g.dFlowConsts, host, half, hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipEventRecord(g.evFlow[hf], g.stream));
+    g.flowCopied[hf] = true;
+    dev = g.dFlowConsts;
+    return 0;
+}
+
+// A clip's motion vectors (include/tpt_hip.h states them): frame j's depend on the planes of frames j and j - 1 as traced and on
+// nothing accumulated, so all frames whose predecessor lies in the stacks go through in one launch (more only where a launch would pass
+// 2^31 lanes), frame 0 in one more on the prev planes, or zeroed where it has no predecessor.  Everything is checked, and every
+// frame's camera constants are made -- by temporalConsts, the temporal passes' own rules and arithmetic -- before the first enqueue; the
+// constants travel in one copy per call.
+int tptMotionVectorsDevice(const tptMotionVectorsArgs* args)
+{
+    if (requireInit()) return -1;
+    const std::string f("tptMotionVectorsDevice");
+    if (!args) return fail(f + ": args is required");
+    const tptMotionVectorsArgs& A = *args;
+    const int w = A.screenWidth, h = A.screenHeight, nFrames = A.nFrames;
+    if (nFrames < 1 || nFrames > 4096) return fail(f + ": nFrames must lie in 1..4096");
+    if (w < 1 || w > 8192 || h < 1 || h > 8192) return fail(f + ": w and h must lie in 1..8192");
+    if (A.flags != 0) return fail(f + ": flags must be 0");
+    if (!A.cameras || !A.deviceFrameAlbedo || !A.deviceFrameNormalDepth || !A.deviceFrameMotion)
+        return fail(f + ": cameras, deviceFrameAlbedo, deviceFrameNormalDepth and deviceFrameMotion are required");
+    const bool objects = A.deviceFrameObjects != nullptr;
+    if (A.prevCamera) {
+        if (!A.devicePrevAlbedo || !A.devicePrevNormalDepth) return fail(f + ": prevCamera needs devicePrevAlbedo and devicePrevNormalDepth");
+        if ((A.devicePrevObject != nullptr) != objects)
+            return fail(f + ": with prevCamera, devicePrevObject must be given exactly when deviceFrameObjects is");
+    } else if (A.devicePrevAlbedo || A.devicePrevNormalDepth || A.devicePrevObject) {
+        return fail(f + ": devicePrevAlbedo, devicePrevNormalDepth and devicePrevObject need prevCamera");
+    }
+    if (A.deviceFrameObjectMotion && !objects) return fail(f + ": deviceFrameObjectMotion needs deviceFrameObjects");
+    if (A.nObjects < 0 || A.nObjects > 65534) return fail(f + ": nObjects must lie in 0..65534");
+    if ((A.deviceFrameObjectMotion != nullptr) != (A.nObjects > 0)) return fail(f + ": deviceFrameObjectMotion and nObjects must be given together");
+    static_assert(sizeof(CameraPOD) == 22 * sizeof(float), "the reference's Camera");
+    std::vector<tptFlowConsts> consts((size_t)nFrames);
+    for (int j = 0; j < nFrames; ++j) {
+        const char* cam = static_cast<const char*>(A.cameras) + sizeof(CameraPOD) * (size_t)j;
+        tptTemporalConsts t; // (a history length the temporal passes accept: this call has none)
+        if (int rc = temporalConsts(f, cam, j > 0 ? cam - sizeof(CameraPOD) : A.prevCamera, 1.0f, A.depthTolerance, A.normalTolerance,
+                                    A.coverageTolerance, t))
+            return rc;
+        tptFlowConsts& k = consts[j];
+        static_assert(offsetof(tptFlowConsts, depthTol) == offsetof(tptTemporalConsts, maxHistory), "tptTemporalConsts' fields, in its order");
+        memcpy(&k, &t, offsetof(tptFlowConsts, depthTol));
+        k.depthTol = t.depthTol; k.normalTol = t.normalTol; k.coverageTol = t.coverageTol;
+    }
+    // the output may not share a byte with an input, each at its full extent
+    const size_t pixels = (size_t)w * (size_t)h, planeBytes = pixels * 16u;
+    const uintptr_t stack = (uintptr_t)planeBytes * (uintptr_t)nFrames;
+    const struct { const void* p; uintptr_t bytes; } ins[7] = {{A.deviceFrameAlbedo, stack}, {A.deviceFrameNormalDepth, stack},
+        {A.deviceFrameObjects, (uintptr_t)pixels * 4u * (uintptr_t)nFrames},
+        {A.deviceFrameObjectMotion, (uintptr_t)nFrames * (uintptr_t)A.nObjects * 16u}, {A.devicePrevAlbedo, planeBytes},
+        {A.devicePrevNormalDepth, planeBytes}, {A.devicePrevObject, (uintptr_t)pixels * 4u}};
+    for (const auto& i : ins) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(A.deviceFrameMotion), b = reinterpret_cast<uintptr_t>(i.p);
+        if (b && a < b + i.bytes && b < a + stack) return fail(f + ": deviceFrameMotion overlaps an input");
+    }
+    if (!tptLaunchFlow) return fail(f + ": this build has no motion-vector kernel");
+
+    const int first = A.prevCamera ? 0 : 1; // the first frame with a predecessor
+    const tptFlowConsts* table = nullptr;   // (its record 0 is frame `first`'s)
+    if (first < nFrames)
+        if (int rc = uploadFlowConsts(consts.data() + first, (size_t)(nFrames - first), table)) return rc;
+    const size_t plane = pixels * 4u; // (floats)
+    if (A.prevCamera)
+        HIPCHK(tptLaunchFlow(A.deviceFrameAlbedo, A.deviceFrameNormalDepth, A.deviceFrameObjects, A.devicePrevAlbedo, A.devicePrevNormalDepth,
+                             A.devicePrevObject, A.deviceFrameObjectMotion, A.nObjects, A.deviceFrameMotion, w, h, 1, table, g.stream));
+    else
+        HIPCHK(hipMemsetAsync(A.deviceFrameMotion, 0, planeBytes, g.stream)); // (no predecessor: four +0 per pixel)
+    // frames 1 .. nFrames-1: the predecessor of each is the plane before it; at most 2^31 lanes a launch (32 frames of 8192 x 8192)
+    const size_t lanes = (size_t)((w + 63) / 64 * 64) * (size_t)((h + 3) / 4 * 4), most = ((size_t)1 << 31) / lanes;
+    for (int j = 1; j < nFrames;) {
+        const int m = (size_t)(nFrames - j) < most ? nFrames - j : (int)most;
+        const size_t at = plane * (size_t)j, ids = pixels * (size_t)j;
+        HIPCHK(tptLaunchFlow(A.deviceFrameAlbedo + at, A.deviceFrameNormalDepth + at, objects ? A.deviceFrameObjects + ids : nullptr,
+                             A.deviceFrameAlbedo + at - plane, A.deviceFrameNormalDepth + at - plane,
+                             objects ? A.deviceFrameObjects + ids - pixels : nullptr,
+                             A.deviceFrameObjectMotion ? A.deviceFrameObjectMotion + 4u * (size_t)A.nObjects * (size_t)j : nullptr, A.nObjects,
+                             A.deviceFrameMotion + at, w, h, m, table + (j - first), g.stream));
+        j += m;
+    }
+    return 0;
+}
+
 // The object plane (include/tpt_hip.h states it): per frame one launch on the context stream over the scene set of the last tptUpdate,
 // with the frame's camera and its centres of spheres 1 and 8 by value.  The host's spheres, camera, the launch queue and every setting
 // stay as they are.  One thing moves: a scene set that tptUpdate staged and no launch has uploaded yet is uploaded here, on the context

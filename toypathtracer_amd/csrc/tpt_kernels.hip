@@ -723,6 +723,115 @@ __global__ void __launch_bounds__(256) tptReprojectObjectsKernel(const f4* __res
     outVariance[p] = r;
 }
 
+// The frame's record of tptMotionVectorsDevice's table is the same for every lane of a workgroup: read through the constant address
+// space (as pairPtr's records are) its fields are scalar loads and sit in scalar registers.
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef const tptFlowConsts __attribute__((address_space(4))) * FlowConstsPtr;
+#else
+typedef const tptFlowConsts* FlowConstsPtr;
+#endif
+TPT_HD FlowConstsPtr flowConstsPtr(const tptFlowConsts* p)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wold-style-cast"
+    return (FlowConstsPtr)(p);
+#pragma clang diagnostic pop
+#else
+    return p;
+#endif
+}
+
+// tptMotionVectorsDevice (include/tpt_hip.h states it; tests/flow_checker.c restates it): steps 1-4 of the temporal kernels for frame
+// blockIdx.z of a stack of planes, with what they find written out instead of blended -- where the pixel's point stood in the previous
+// frame, how far from that frame's camera, and how much of the bilinear footprint there shows the same surface.  The taps read the
+// previous frame's own albedo and normal / depth planes, so no frame waits for another and a clip is one launch.  The layout of the
+// temporal kernels: one lane per pixel, a wave along 64 pixels of a row, every pointer the first plane of its stack, the planes
+// width * height pixels apart (a size_t), each frame's taps tested against its own width and height.  The prev pointers are the
+// predecessor of the launch's first frame: inside a clip the same stacks one plane earlier.  OBJECTS: the object planes are given; a tap
+// of weight 0 is not loaded, and a tap's 4-B id is tested before its 16-B loads.  One 16-B store per pixel.
+template <bool OBJECTS>
+__global__ void __launch_bounds__(256) tptFlowKernel(const f4* __restrict__ albedo, const f4* __restrict__ nd, const int32_t* __restrict__ object,
+                                                     const f4* __restrict__ prevAlbedo, const f4* __restrict__ prevNd,
+                                                     const int32_t* __restrict__ prevObject, const f4* __restrict__ motion, int nObjects,
+                                                     f4* __restrict__ out, int width, int height, const tptFlowConsts* __restrict__ table)
+{
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x >= width || y >= height) return;
+    const FlowConstsPtr k = flowConstsPtr(table + blockIdx.z);
+    auto ldk = [](PairPtr q) { return mk3(q[0], q[1], q[2]); };
+    const size_t plane = (size_t)blockIdx.z * ((size_t)width * (size_t)height);
+    const size_t p = plane + ((size_t)y * width + x);
+    const f4 ca = albedo[p], cn = nd[p];
+    const float c = ca.w;
+    int id = 0;
+    if (OBJECTS) id = object[p];
+    const f3 o = ldk(k->o), po = ldk(k->po), pw = ldk(k->pw), pa = ldk(k->pa);
+    const float s = ((float)x + 0.5f) / (float)width, t = ((float)y + 0.5f) / (float)height;
+    const f3 dir = normalize(((ldk(k->ll) + s * ldk(k->H)) + t * ldk(k->V)) - o);
+    f3 rel = dir, n = mk3(0.0f, 0.0f, 0.0f);
+    if (c > 0.0f) {
+        const float d = cn.w / c;
+        n = mk3(cn.x / c, cn.y / c, cn.z / c);
+        f3 at = o + dir * d;
+        if (OBJECTS && (unsigned)id < (unsigned)nObjects) { // (nObjects is 0 without a table)
+            const f4 m = motion[(size_t)blockIdx.z * (size_t)nObjects + (size_t)id];
+            at = at + mk3(m.x, m.y, m.z);
+        }
+        rel = at - po;
+    }
+    const float z = -dot(rel, pw);
+    const float kz = k->pf / z;
+    const f3 q = rel * kz - pa;
+    const float px = dot(q, ldk(k->pH)) / k->phh * (float)width - 0.5f;
+    const float py = dot(q, ldk(k->pV)) / k->pvv * (float)height - 0.5f;
+    constexpr float snap = TPT_TEMPORAL_SNAP, big = 3.40282347e38f;
+    f4 r;
+    r.x = 0.0f; r.y = 0.0f; r.z = 0.0f; r.w = 0.0f;
+    if (z > 0.0f && __builtin_fabsf(px) <= big && __builtin_fabsf(py) <= big) { // (NaN fails every comparison)
+        float fx0 = __builtin_floorf(px), fy0 = __builtin_floorf(py);
+        float fx = px - fx0, fy = py - fy0;
+        if (fx < snap) fx = 0.0f;
+        else if (fx > 1.0f - snap) { fx0 += 1.0f; fx = 0.0f; }
+        if (fy < snap) fy = 0.0f;
+        else if (fy > 1.0f - snap) { fy0 += 1.0f; fy = 0.0f; }
+        const float e = tsqrt(dot(rel, rel));
+        float W = 0.0f;
+        // (outside [-1, size) no tap lies inside the image; what passes fits an int)
+        if (px >= -1.0f && px < (float)width && py >= -1.0f && py < (float)height) {
+            const int ix = (int)fx0, iy = (int)fy0;
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const float b = (i ? fx : 1.0f - fx) * (j ? fy : 1.0f - fy);
+                    const int qx = ix + i, qy = iy + j;
+                    if (!(b > 0.0f) || qx < 0 || qx >= width || qy < 0 || qy >= height) continue;
+                    const size_t t4 = plane + ((size_t)qy * width + qx);
+                    if (OBJECTS && prevObject[t4] != id) continue; // (the 4-B test first: a tap of another object loads nothing else)
+                    const float c1 = prevAlbedo[t4].w;
+                    if (!(__builtin_fabsf(c - c1) <= k->coverageTol)) continue;
+                    if (c > 0.0f && c1 > 0.0f) {
+                        const f4 pn = prevNd[t4];
+                        const float d1 = pn.w / c1;
+                        if (!(__builtin_fabsf(e - d1) <= k->depthTol * e)) continue;
+                        const float dx = n.x - pn.x / c1, dy = n.y - pn.y / c1, dz = n.z - pn.z / c1;
+                        if (!((dx * dx + dy * dy) + dz * dz <= k->normalTol)) continue;
+                    } else if (!(c == 0.0f && c1 == 0.0f)) {
+                        continue;
+                    }
+                    W += b;
+                }
+            }
+        }
+        r.x = (fx0 + fx) - (float)x;
+        r.y = (fy0 + fy) - (float)y;
+        r.z = e;
+        r.w = W;
+    }
+    out[p] = r;
+}
+
 // tptObjectPlaneDevice (include/tpt_hip.h states it; tests/object_checker.c restates it): the index of the first sphere the ray through
 // each pixel's centre and the lens centre meets.  One lane per pixel, a wave along 64 pixels of a row; the reference's exact test
 // (testSphere) for every sphere in index order, so the nearest hit wins and equal distances go to the lowest index.  The
@@ -2686,6 +2795,18 @@ hipError_t tptLaunchReprojectObjects(const float* colour, const float* albedo, c
                        in(colour), in(albedo), in(normalDepth), in(moments), in(prevColour), in(prevAlbedo), in(prevNormalDepth),
                        in(prevMoments), out(outColour), out(outAlbedo), out(outMoments), out(outVariance), object, prevObject, in(motion),
                        nObjects, width, height, k);
+    return hipGetLastError();
+}
+
+hipError_t tptLaunchFlow(const float* albedo, const float* normalDepth, const int32_t* object, const float* prevAlbedo,
+                         const float* prevNormalDepth, const int32_t* prevObject, const float* motion, int nObjects, float* out, int width,
+                         int height, int frames, const tptFlowConsts* deviceConsts, hipStream_t stream)
+{
+    const dim3 grid((unsigned)(width + 63) / 64, (unsigned)(height + 3) / 4, (unsigned)frames);
+    auto in = [](const float* q) { return reinterpret_cast<const f4*>(q); };
+    hipLaunchKernelGGL(object ? tptFlowKernel<true> : tptFlowKernel<false>, grid, dim3(64, 4), 0, stream, in(albedo), in(normalDepth), object,
+                       in(prevAlbedo), in(prevNormalDepth), prevObject, in(motion), nObjects, reinterpret_cast<f4*>(out), width, height,
+                       deviceConsts);
     return hipGetLastError();
 }
 
