@@ -582,6 +582,49 @@ typedef struct tptMotionVectorsArgs {
     float depthTolerance, normalTolerance, coverageTolerance;
 } tptMotionVectorsArgs;
 TPT_API int tptMotionVectorsDevice(const tptMotionVectorsArgs* args);
+/* HISTORY RECTIFICATION: the accumulated colour of either temporal pass clamped to what this frame's neighbourhood makes plausible,
+ * and the history shortened where it had to be clamped -- the remedy for lighting that changed on a surface that itself passes every
+ * geometric test (a light switched, a moving sphere's shadow or reflection).  A pass of its own behind tptTemporalAccumulateDevice or
+ * tptTemporalAccumulateObjectsDevice.  All seven device buffers are h*w*4 floats, row-major like the tile (row 0 at the bottom).
+ *   deviceColour, deviceMoments         this frame's planes as traced: the ones the temporal pass was given as its current planes
+ *   deviceAccColour, deviceAccMoments   that pass's deviceOutColour and deviceOutMoments (.w = the history length N)
+ *   deviceOutColour, deviceOutMoments, deviceOutVariance   replace the pass's colour, moments and variance planes everywhere
+ *                                       downstream: colour and moments are the next frame's devicePrevColour / devicePrevMoments, colour
+ *                                       and variance go to tptDenoiseDeviceVariance.  The albedo plane is a surface property: untouched
+ *   radius                              1..3: the window is (2*radius + 1)^2 pixels
+ *   gamma                               the window's half-width in standard deviations
+ * Clamping the history hist to [lo, hi] before the blend out = hist*lerp + cur*(1 - lerp) is clamping out to [lo*lerp + cur*(1 - lerp),
+ * hi*lerp + cur*(1 - lerp)] after it, and lerp follows from N: that is why this needs nothing of the pass but its outputs.
+ * Binary32, in the order written, no FMA, correctly rounded division and square root, sums from +0;  rgb component by component;
+ * every comparison with a NaN is false;  finite(v): |v| <= FLT_MAX.  Per pixel p = (x, y), with cur = colour[p].rgb,
+ * acc = accColour[p].rgb, M = accMoments[p], N = M.w:
+ *   0. V = {0, (dd > 0 ? dd : 0) / N, 0, N},  dd = M.y - M.x*M.x  -- the variance the temporal pass writes from those moments.
+ *      PASS-THROUGH unless N is finite, N > 1 and all of cur and acc are finite:  outColour = accColour[p], outMoments = M (all four
+ *      components, byte for byte), outVariance = V.
+ *   1. The window: the pixels q = (x + i, y + j), -radius <= i, j <= radius, that lie inside the image and whose colour[q].rgb are
+ *      all finite (p itself is one).  Per row j, from i = -radius to radius (left to right):  n_j = the number of its pixels,
+ *      s_j = sum of colour[q].rgb,  t_j = sum of colour[q].rgb * colour[q].rgb  (a row without pixels: 0, +0, +0).  Then from
+ *      j = -radius to radius (bottom to top):  n = sum of n_j,  S1 = sum of s_j,  S2 = sum of t_j.
+ *      mean = S1 / n;  var = S2 / n - mean*mean;  var < 0: var = 0;  sd = sqrt(var);  g = gamma*sd
+ *      lo = mean - g;  unless lo < cur: lo = cur.   hi = mean + g;  unless hi > cur: hi = cur   (so lo <= cur <= hi, also with a NaN)
+ *   2. lerp = (N - 1) / N;  one = 1 - lerp  (the passes' own);   L = lo*lerp + cur*one;  U = hi*lerp + cur*one
+ *      out = acc;  out < L: out = L;  out > U: out = U   (in this order)
+ *   3. per channel:  a_c = 0 if out == acc (nothing clipped);  otherwise q = (acc - out) / (acc - cur), and a_c = 1 if q is not finite,
+ *      0 if q < 0, 1 if q > 1, else q.   a = a_r;  a_g > a: a = a_g;  a_b > a: a = a_b
+ *   4. a == 0 (nothing clipped):  the outputs of PASS-THROUGH, byte for byte what the temporal pass wrote.  Otherwise
+ *      k = 1 - a;  N' = 1 + (N - 1)*k;  m.x = M.x*k + moments[p].x*a;  m.y = M.y*k + moments[p].y*a
+ *      outColour = {out.rgb, accColour[p].a};  outMoments = {m.x, m.y, 0, N'};
+ *      outVariance = {0, (dd > 0 ? dd : 0) / N', 0, N'},  dd = m.y - m.x*m.x
+ * 1 <= N' <= N: the filter treats a rectified pixel as the short-history pixel it now is, and the next frame starts it from N'.
+ * A pixel reads no accumulated value but its own, so deviceOutColour == deviceAccColour and deviceOutMoments == deviceAccMoments (exact
+ * equality, either or both) rectify in place.  Asynchronous on the context stream, ordered like tptDenoiseDevice; needs tptInitialize
+ * only and leaves every other state alone.  The inputs are never written (but for the in-place form).
+ * Refused (non-zero, tptGetLastError names the function, nothing enqueued, no byte written): no context; w or h outside 1..8192; any
+ * of the seven pointers NULL; radius outside 1..3; gamma negative, NaN or infinite; an output sharing a byte with an input or with
+ * another output, each plane taken at its full extent, other than the two exact equalities above. */
+TPT_API int tptRectifyHistoryDevice(int w, int h, const float* deviceColour, const float* deviceMoments,
+                                    const float* deviceAccColour, const float* deviceAccMoments, float* deviceOutColour,
+                                    float* deviceOutMoments, float* deviceOutVariance, int radius, float gamma);
 /* ADAPTIVE SAMPLING: tptDrawDeviceMoments with a sample count per pixel, so that the moments can steer the next pass (the counts come
  * from tptAdaptiveSamplesDevice below, or from the caller).  deviceSampleCounts (required): h*w int32 in DEVICE memory, row-major like the
  * tile, read by the kernels only.  Per pixel p, n = deviceSampleCounts[p] clamped to 0 .. 2047 (the path record holds 11 bits of sample

@@ -39,7 +39,7 @@ C_ABI_SYMBOLS = [
     "tptSetSamplesPerPixel", "tptSetConfig", "tptSetSeedMode", "tptSetFoldMode", "tptSetScene", "tptSetCamera", "tptSetStream",
     "tptSetRowShard", "tptLocalRowCount", "tptLocalRowToGlobal", "tptDrawDevice", "tptRayCounterRead", "tptSetRayCounter", "tptSetFrameOverlap", "tptDisplayRGBA8", "tptKernelTimingBegin", "tptKernelTimingEnd",
     "tptSynchronize", "tptTimerBegin", "tptTimerEnd", "tptSetKernelVariant",
-    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceAnimationMoments", "tptDrawDeviceCameraClip", "tptDrawDeviceKeyframeClip", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptObjectPlaneDevice", "tptObjectMotionTable", "tptTemporalAccumulateObjectsDevice", "tptDenoiseClipDevice", "tptMotionVectorsDevice", "tptDrawDeviceAdaptive", "tptAdaptiveSamplesDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
+    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceAnimationMoments", "tptDrawDeviceCameraClip", "tptDrawDeviceKeyframeClip", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptObjectPlaneDevice", "tptObjectMotionTable", "tptTemporalAccumulateObjectsDevice", "tptDenoiseClipDevice", "tptMotionVectorsDevice", "tptRectifyHistoryDevice", "tptDrawDeviceAdaptive", "tptAdaptiveSamplesDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
 ]
 # include/tpt_test_hooks.h: exported by the second build (libtoypathtracer_hip_hooks.so) only
 HOOK_SYMBOLS = ["tptTestMath", "tptTestMathExhaustive", "tptTestHitSpheres", "tptTestMatrixFilter", "tptTestGroupFilter", "tptTestSetDealCapacities", "tptDebugStats", "tptDebugChunkOrder"]
@@ -99,7 +99,7 @@ def _bind(path, hooks):
         "tptSetRayCounter": [p], "tptSetTileMirror": [p, p], "tptSetFrameOverlap": [i], "tptDisplayRGBA8": [p, i, i, p], "tptKernelTimingBegin": [i],
         "tptKernelTimingEnd": [C.POINTER(f), C.POINTER(i)],
         "tptSynchronize": [], "tptTimerBegin": [], "tptTimerEnd": [C.POINTER(f)], "tptSetKernelVariant": [i, i, i],
-        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDrawDeviceAnimationMoments": [i, i, p, i, i] + [p] * 7 + [u], "tptDrawDeviceCameraClip": [i, i, p, p, i, i] + [p] * 8 + [u], "tptDrawDeviceKeyframeClip": [i, i, p, i, p, p, i, i] + [p] * 9 + [u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptObjectPlaneDevice": [i, p, p, i, i, p, u], "tptObjectMotionTable": [f, f, u, p, i], "tptTemporalAccumulateObjectsDevice": [i, i] + [p] * 14 + [f] * 4 + [p, p, p, i], "tptDenoiseClipDevice": [C.POINTER(ClipDenoiseArgs)], "tptMotionVectorsDevice": [C.POINTER(MotionVectorsArgs)], "tptDrawDeviceAdaptive": [f, i, i, i, p, p, p, p, p, u], "tptAdaptiveSamplesDevice": [i, i, p, f, i, i, p, p, p], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
+        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDrawDeviceAnimationMoments": [i, i, p, i, i] + [p] * 7 + [u], "tptDrawDeviceCameraClip": [i, i, p, p, i, i] + [p] * 8 + [u], "tptDrawDeviceKeyframeClip": [i, i, p, i, p, p, i, i] + [p] * 9 + [u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptObjectPlaneDevice": [i, p, p, i, i, p, u], "tptObjectMotionTable": [f, f, u, p, i], "tptTemporalAccumulateObjectsDevice": [i, i] + [p] * 14 + [f] * 4 + [p, p, p, i], "tptDenoiseClipDevice": [C.POINTER(ClipDenoiseArgs)], "tptMotionVectorsDevice": [C.POINTER(MotionVectorsArgs)], "tptRectifyHistoryDevice": [i, i] + [p] * 7 + [i, f], "tptDrawDeviceAdaptive": [f, i, i, i, p, p, p, p, p, u], "tptAdaptiveSamplesDevice": [i, i, p, f, i, i, p, p, p], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
     }
     if hooks:
         sigs.update({"tptDebugStats": [p, i], "tptDebugChunkOrder": [p, p, i], "tptTestMath": [i, p, p, p, i], "tptTestMathExhaustive": [i, u, u, p, p],
@@ -707,6 +707,33 @@ def temporal_accumulate_device(w, h, camera, colour_ptr, albedo_ptr, normal_dept
                                                     C.c_void_p(out_colour_ptr), C.c_void_p(out_albedo_ptr), C.c_void_p(out_moments_ptr),
                                                     C.c_void_p(out_variance_ptr), max_history, depth_tolerance, normal_tolerance,
                                                     coverage_tolerance), "tptTemporalAccumulateDevice")
+
+
+# rectify_history_device's defaults, chosen from tools/rectify_rate.py's table
+RECTIFY_DEFAULTS = dict(radius=1, gamma=2.0)
+RECTIFY_MAX_RADIUS = 3  # include/tpt_hip.h: tptRectifyHistoryDevice's radius
+
+
+def rectify_history_device(w, h, colour_ptr, moments_ptr, acc_colour_ptr, acc_moments_ptr, out_colour_ptr, out_moments_ptr,
+                           out_variance_ptr, radius=RECTIFY_DEFAULTS["radius"], gamma=RECTIFY_DEFAULTS["gamma"]):
+    """tptRectifyHistoryDevice: the accumulated colour of temporal_accumulate_device or temporal_accumulate_objects_device clamped to
+    what this frame's (2*radius + 1)^2 window makes plausible (mean +- gamma standard deviations, widened to hold this frame's own
+    value), and the history shortened where it had to be clamped.  colour_ptr, moments_ptr: this frame's planes as traced (the pass's
+    current planes); acc_colour_ptr, acc_moments_ptr: the pass's out_colour and out_moments.  The three outputs (device buffers of
+    h*w*4 floats) replace the pass's colour, moments and variance planes downstream: colour and moments are the next frame's prev
+    planes, colour and variance go to denoise_device_variance.  out_colour_ptr may be acc_colour_ptr and out_moments_ptr
+    acc_moments_ptr (in place).  Ordered on the context's stream."""
+    _positive_ints(("w", w), ("h", h))
+    named = (("colour_ptr", colour_ptr), ("moments_ptr", moments_ptr), ("acc_colour_ptr", acc_colour_ptr),
+             ("acc_moments_ptr", acc_moments_ptr), ("out_colour_ptr", out_colour_ptr), ("out_moments_ptr", out_moments_ptr),
+             ("out_variance_ptr", out_variance_ptr))
+    _pointers(*named)
+    if not all(v for _, v in named):
+        raise ValueError("%s: device buffers are required" % ", ".join(n for n, v in named if not v))
+    if not isinstance(radius, (int, np.integer)) or isinstance(radius, bool) or not 1 <= radius <= RECTIFY_MAX_RADIUS:
+        raise ValueError("radius: an int in 1..%d expected, got %r" % (RECTIFY_MAX_RADIUS, radius))
+    _sigmas(("gamma", gamma))
+    _chk(load_library().tptRectifyHistoryDevice(w, h, *[C.c_void_p(v) for _, v in named], int(radius), gamma), "tptRectifyHistoryDevice")
 
 
 OBJECT_PLANE_MAX_FRAMES = 4096  # include/tpt_hip.h: tptObjectPlaneDevice's nFrames

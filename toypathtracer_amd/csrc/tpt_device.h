@@ -178,6 +178,15 @@ __attribute__((weak)) hipError_t tptLaunchFlow(const float* albedo, const float*
                                                const float* prevNormalDepth, const int32_t* prevObject, const float* motion, int nObjects,
                                                float* out, int width, int height, int frames, const tptFlowConsts* deviceConsts,
                                                hipStream_t stream);
+// tptRectifyHistoryDevice: one launch over the image.  Every pointer is a plane of [h][w] f4; outColour / outMoments may be accColour /
+// accMoments themselves.  radius 1..3 picks the instantiation.  The tile of the kernel's LDS layout: TPT_RECTIFY_TILE_W x
+// TPT_RECTIFY_TILE_H pixels a workgroup, one lane each.  Weak for the same reason as tptLaunchDenoise.
+#define TPT_RECTIFY_TILE_W 64
+#define TPT_RECTIFY_TILE_H 4
+#define TPT_RECTIFY_MAX_RADIUS 3
+__attribute__((weak)) hipError_t tptLaunchRectify(const float* colour, const float* moments, const float* accColour, const float* accMoments,
+                                                  float* outColour, float* outMoments, float* outVariance, int width, int height,
+                                                  int radius, float gamma, hipStream_t stream);
 // tptDrawDeviceAdaptive's blend: tile.rgb and moments.xyz with lerp = S / (S + n) per pixel, S the running sample count in moments.w
 // (0 unless `progressive`), n the pixel's clamped count; moments.w = S + n; pixels with n == 0 untouched.  Weak for the same reason as
 // tptLaunchDenoise.

@@ -456,6 +456,38 @@ int tptTemporalAccumulateDevice(int w, int h, const void* camera, const void* pr
     return 0;
 }
 
+// History rectification (include/tpt_hip.h states it): a post-process on the context stream behind either temporal pass, one launch,
+// no scratch plane and no constants but the radius and gamma.  A pixel reads no accumulated value but its own, so the colour and
+// moments outputs may BE the accumulated planes; every other shared byte is refused.
+int tptRectifyHistoryDevice(int w, int h, const float* deviceColour, const float* deviceMoments, const float* deviceAccColour,
+                            const float* deviceAccMoments, float* deviceOutColour, float* deviceOutMoments, float* deviceOutVariance,
+                            int radius, float gamma)
+{
+    if (requireInit()) return -1;
+    const std::string f("tptRectifyHistoryDevice");
+    if (w < 1 || w > 8192 || h < 1 || h > 8192) return fail(f + ": w and h must lie in 1..8192");
+    if (!deviceColour || !deviceMoments || !deviceAccColour || !deviceAccMoments)
+        return fail(f + ": this frame's colour and moments planes and the accumulated ones are required");
+    if (!deviceOutColour || !deviceOutMoments || !deviceOutVariance) return fail(f + ": the three output planes are required");
+    if (radius < 1 || radius > TPT_RECTIFY_MAX_RADIUS) return fail(f + ": radius must lie in 1..3");
+    if (!(gamma >= 0.0f && gamma <= 3.40282347e38f)) return fail(f + ": gamma must be finite and at least 0"); // (NaN fails both)
+    const uintptr_t bytes = (uintptr_t)w * (uintptr_t)h * 16u;
+    const float* ins[4] = {deviceColour, deviceMoments, deviceAccColour, deviceAccMoments};
+    const float* outs[3] = {deviceOutColour, deviceOutMoments, deviceOutVariance};
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 4; ++j) {
+            if (i < 2 && j == 2 + i && outs[i] == ins[j]) continue; // in place: the accumulated plane of the output's own kind, exactly
+            if (overlapsAny(outs[i], {ins[j]}, bytes)) return fail(f + ": an output overlaps an input (other than in place)");
+        }
+        for (int j = 0; j < i; ++j)
+            if (overlapsAny(outs[i], {outs[j]}, bytes)) return fail(f + ": two outputs overlap");
+    }
+    if (!tptLaunchRectify) return fail(f + ": this build has no history rectification kernel");
+    HIPCHK(tptLaunchRectify(deviceColour, deviceMoments, deviceAccColour, deviceAccMoments, deviceOutColour, deviceOutMoments,
+                            deviceOutVariance, w, h, radius, gamma, g.stream));
+    return 0;
+}
+
 // The temporal pass that follows objects (include/tpt_hip.h states it): the plain pass's checks, then those of the object planes and
 // the motion table; one launch of its own kernel.
 int tptTemporalAccumulateObjectsDevice(int w, int h, const void* camera, const void* prevCamera, const float* deviceColour,

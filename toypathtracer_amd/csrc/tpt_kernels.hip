@@ -832,6 +832,146 @@ __global__ void __launch_bounds__(256) tptFlowKernel(const f4* __restrict__ albe
     out[p] = r;
 }
 
+// The LDS of tptRectifyKernel<R>, in f4 (16-B slots), one array cut in three:
+//   raw   [kRows][kRawW]  the tile's colours with a halo of R pixels: {rgb, 1}, or {0, 0, 0, 0} for a pixel that does not count
+//   sum1  [kRows][64]     per tile row (halo rows included) and tile column, over the 2R + 1 pixels of the row: {sum of rgb, n}
+//   sum2  [kRows][64]     likewise {sum of rgb*rgb, 0}
+// A wave is 64 lanes along one row in every phase, and every access of a wave-instruction is to 64 consecutive slots (the halo shifts
+// the start, the odd row length of `raw` only moves where a row starts): each 16-lane group of a ds_read_b128 covers one 256-B bank
+// row, each 8-lane group of a ds_write_b128 half of one -- no bank conflicts, no padding or swizzle needed.
+template <int R>
+struct tptRectifyLayout {
+    static constexpr int kRawW = TPT_RECTIFY_TILE_W + 2 * R, kRows = TPT_RECTIFY_TILE_H + 2 * R;
+    static constexpr int kRaw = kRawW * kRows, kSums = kRows * TPT_RECTIFY_TILE_W;
+    static constexpr int kSlots = kRaw + 2 * kSums; // 1164, 1568, 1980 slots = 18624, 25088, 31680 bytes for R = 1, 2, 3
+};
+
+// tptRectifyHistoryDevice (include/tpt_hip.h states it; tests/rectify_checker.c restates it): the accumulated colour clamped to the
+// bounds this frame's window gives, the history shortened by what the clamp took.  The layout of the a-trous and temporal kernels --
+// one lane per pixel, a wave along 64 pixels of a row, 64 x 4 a workgroup.  The window's sums are separable in the order the statement
+// fixes (within a row left to right, then the rows bottom to top), so the tile's raw colours go to LDS once with their halo, the row
+// sums are formed once per tile row and column and shared, and a pixel adds 2R + 1 row sums where the naive form gathers (2R + 1)^2
+// pixels.  A pixel outside the image or with a non-finite channel is staged as zeros: adding +0 to a sum that began at +0 leaves it as
+// it is, so the loops are straight-line.  The pixel's own planes are coalesced 16-B loads issued before the first barrier; lanes
+// outside the image help to stage and leave after the second barrier.  Quotients are plain IEEE divisions, the square root tpt_math.h's.
+template <int R>
+__global__ void __launch_bounds__(256) tptRectifyKernel(const f4* __restrict__ colour, const f4* __restrict__ moments, const f4* accColour,
+                                                        const f4* accMoments, f4* outColour, f4* outMoments, f4* __restrict__ outVariance,
+                                                        int width, int height, float gamma)
+{
+    typedef tptRectifyLayout<R> Lay;
+    __shared__ f4 lds[Lay::kSlots];
+    f4* const raw = lds;
+    f4* const sum1 = lds + Lay::kRaw;
+    f4* const sum2 = sum1 + Lay::kSums;
+    constexpr float big = 3.40282347e38f;
+    const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * TPT_RECTIFY_TILE_W + tx;
+    const int x0 = blockIdx.x * TPT_RECTIFY_TILE_W, y0 = blockIdx.y * TPT_RECTIFY_TILE_H;
+    const int x = x0 + tx, y = y0 + ty;
+    const bool inside = x < width && y < height;
+    const size_t p = (size_t)y * width + x;
+    f4 zero;
+    zero.x = 0.0f; zero.y = 0.0f; zero.z = 0.0f; zero.w = 0.0f;
+    f4 ac = zero, am = zero, cm = zero;
+    if (inside) {
+        ac = accColour[p];
+        am = accMoments[p];
+        cm = moments[p];
+    }
+    // the tile and its halo
+#pragma unroll
+    for (int k = 0; k < (Lay::kRaw + 255) / 256; ++k) {
+        const int item = tid + 256 * k;
+        if (item < Lay::kRaw) {
+            const int row = item / Lay::kRawW, col = item - row * Lay::kRawW;
+            const int gx = x0 - R + col, gy = y0 - R + row;
+            f4 v = zero;
+            if (gx >= 0 && gx < width && gy >= 0 && gy < height) {
+                const f4 c = colour[(size_t)gy * width + gx];
+                if (__builtin_fabsf(c.x) <= big && __builtin_fabsf(c.y) <= big && __builtin_fabsf(c.z) <= big) { // (NaN fails)
+                    v.x = c.x; v.y = c.y; v.z = c.z; v.w = 1.0f;
+                }
+            }
+            raw[item] = v;
+        }
+    }
+    __syncthreads();
+    // the row sums, left to right
+#pragma unroll
+    for (int k = 0; k < (Lay::kSums + 255) / 256; ++k) {
+        const int item = tid + 256 * k;
+        if (item < Lay::kSums) {
+            const f4* q = raw + (item / TPT_RECTIFY_TILE_W) * Lay::kRawW + (item % TPT_RECTIFY_TILE_W);
+            f4 s = zero, t = zero;
+#pragma unroll
+            for (int i = 0; i <= 2 * R; ++i) {
+                const f4 v = q[i];
+                s.w += v.w;
+                s.x += v.x; s.y += v.y; s.z += v.z;
+                t.x += v.x * v.x; t.y += v.y * v.y; t.z += v.z * v.z;
+            }
+            sum1[item] = s;
+            sum2[item] = t;
+        }
+    }
+    __syncthreads();
+    if (!inside) return;
+    const f4 cc = raw[(ty + R) * Lay::kRawW + (tx + R)]; // (.w == 0: a channel of this pixel is not finite)
+    const float N = am.w;
+    f4 oc = ac, om = am;
+    float vm0 = am.x, vm1 = am.y, vN = N;
+    const bool through = !(__builtin_fabsf(N) <= big && N > 1.0f) || cc.w == 0.0f ||
+                         !(__builtin_fabsf(ac.x) <= big && __builtin_fabsf(ac.y) <= big && __builtin_fabsf(ac.z) <= big);
+    if (!through) {
+        // the rows, bottom to top
+        f4 S1 = zero, S2 = zero;
+#pragma unroll
+        for (int j = 0; j <= 2 * R; ++j) {
+            const f4 s = sum1[(ty + j) * TPT_RECTIFY_TILE_W + tx], t = sum2[(ty + j) * TPT_RECTIFY_TILE_W + tx];
+            S1.w += s.w;
+            S1.x += s.x; S1.y += s.y; S1.z += s.z;
+            S2.x += t.x; S2.y += t.y; S2.z += t.z;
+        }
+        const float n = S1.w, lerp = (N - 1.0f) / N, one = 1.0f - lerp;
+        // one channel: the bounds, the clamp, and how far the clamp pulled towards this frame
+        auto channel = [&](float cur, float acc, float s1, float s2, float& out) -> float {
+            const float mean = s1 / n;
+            float var = s2 / n - mean * mean;
+            if (var < 0.0f) var = 0.0f;
+            const float g = gamma * tsqrt(var);
+            float lo = mean - g, hi = mean + g;
+            if (!(lo < cur)) lo = cur;
+            if (!(hi > cur)) hi = cur;
+            const float L = lo * lerp + cur * one, U = hi * lerp + cur * one;
+            out = acc;
+            if (out < L) out = L;
+            if (out > U) out = U;
+            if (out == acc) return 0.0f;
+            const float q = (acc - out) / (acc - cur);
+            return !(__builtin_fabsf(q) <= big) ? 1.0f : q < 0.0f ? 0.0f : q > 1.0f ? 1.0f : q;
+        };
+        float o0, o1, o2;
+        float a = channel(cc.x, ac.x, S1.x, S2.x, o0);
+        const float a1 = channel(cc.y, ac.y, S1.y, S2.y, o1), a2 = channel(cc.z, ac.z, S1.z, S2.z, o2);
+        if (a1 > a) a = a1;
+        if (a2 > a) a = a2;
+        if (!(a == 0.0f)) {
+            const float k = 1.0f - a;
+            vN = 1.0f + (N - 1.0f) * k;
+            vm0 = am.x * k + cm.x * a;
+            vm1 = am.y * k + cm.y * a;
+            oc.x = o0; oc.y = o1; oc.z = o2;
+            om.x = vm0; om.y = vm1; om.z = 0.0f; om.w = vN;
+        }
+    }
+    const float dd = vm1 - vm0 * vm0;
+    f4 ov;
+    ov.x = 0.0f; ov.y = (dd > 0.0f ? dd : 0.0f) / vN; ov.z = 0.0f; ov.w = vN;
+    outColour[p] = oc;
+    outMoments[p] = om;
+    outVariance[p] = ov;
+}
+
 // tptObjectPlaneDevice (include/tpt_hip.h states it; tests/object_checker.c restates it): the index of the first sphere the ray through
 // each pixel's centre and the lens centre meets.  One lane per pixel, a wave along 64 pixels of a row; the reference's exact test
 // (testSphere) for every sphere in index order, so the nearest hit wins and equal distances go to the lowest index.  The
@@ -2807,6 +2947,20 @@ hipError_t tptLaunchFlow(const float* albedo, const float* normalDepth, const in
     hipLaunchKernelGGL(object ? tptFlowKernel<true> : tptFlowKernel<false>, grid, dim3(64, 4), 0, stream, in(albedo), in(normalDepth), object,
                        in(prevAlbedo), in(prevNormalDepth), prevObject, in(motion), nObjects, reinterpret_cast<f4*>(out), width, height,
                        deviceConsts);
+    return hipGetLastError();
+}
+
+hipError_t tptLaunchRectify(const float* colour, const float* moments, const float* accColour, const float* accMoments, float* outColour,
+                            float* outMoments, float* outVariance, int width, int height, int radius, float gamma, hipStream_t stream)
+{
+    static_assert(TPT_RECTIFY_MAX_RADIUS == 3, "one instantiation per radius");
+    if (radius < 1 || radius > TPT_RECTIFY_MAX_RADIUS) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(width + TPT_RECTIFY_TILE_W - 1) / TPT_RECTIFY_TILE_W, (unsigned)(height + TPT_RECTIFY_TILE_H - 1) / TPT_RECTIFY_TILE_H);
+    auto in = [](const float* q) { return reinterpret_cast<const f4*>(q); };
+    auto out = [](float* q) { return reinterpret_cast<f4*>(q); };
+    hipLaunchKernelGGL(radius == 1 ? tptRectifyKernel<1> : radius == 2 ? tptRectifyKernel<2> : tptRectifyKernel<3>, grid,
+                       dim3(TPT_RECTIFY_TILE_W, TPT_RECTIFY_TILE_H), 0, stream, in(colour), in(moments), in(accColour), in(accMoments),
+                       out(outColour), out(outMoments), out(outVariance), width, height, gamma);
     return hipGetLastError();
 }
 
