@@ -107,7 +107,14 @@ TPT_API int tptSetSeedMode(int mode);
 TPT_API int tptSetFoldMode(int mode);
 /* Replace the static scene tables (Test.cpp:13-31, 46-64).  spheres: count x 20 B {center xyz, radius,
  * invRadius(ignored)}; materials: count x 36 B {int type; albedo xyz; emissive xyz; roughness; ri}.
- * count <= 0 or NULL restores the built-in scene. */
+ * count <= 0 or NULL restores the built-in scene.
+ * A scene may have up to TPT_MAX_LIGHTS emissive spheres (a material with a positive emissive channel, Test.cpp:334): every trace kernel
+ * keeps the light table, 32 B a light, in LDS.  tptDrawDevice, tptDraw and tptDrawDeviceAnimation render every such scene -- where the
+ * table does not fit beside the path-queue kernel's path records (about 2860 lights on a grouped scene) they take the lane-refill kernel,
+ * frame by frame, with the same bits.  The launches that exist on the path-queue kernel only (tptDrawDeviceBatch, Views, Aov, Moments,
+ * Adaptive and the clips) refuse such a scene with the number of lights they take beside it; a draw of more than TPT_MAX_LIGHTS
+ * lights is refused by every entry point. */
+#define TPT_MAX_LIGHTS 3072
 TPT_API int tptSetScene(const void* spheres, const void* materials, int count);
 /* Camera ctor arguments (Maths.h:418; defaults Test.cpp:309-319).  NULL lookFrom restores defaults. */
 TPT_API int tptSetCamera(const float* lookFrom, const float* lookAt, float vfovDegrees, float aperture, float focusDist);

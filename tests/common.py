@@ -114,7 +114,7 @@ def matrix_scene(oracle, n, seed=3):
         es["cy"] += rng.uniform(0.5, 3, k).astype(np.float32)
         es["cz"] += rng.uniform(-3, 3, k).astype(np.float32)
         es["radius"] *= rng.uniform(0.3, 1.0, k).astype(np.float32)
-        em["emissive"][:] = 0  # keep the light list short
+        em["emissive"][:] = 0  # (this scene is about the filter: the copies are no lights; light counts and kinds are tests/lights_lib.py's)
         s, m = np.concatenate([s, es]), np.concatenate([m, em])
     s["invRadius"] = np.float32(1.0) / s["radius"]
     return s, m

@@ -16,6 +16,8 @@ struct FramePlan {
     int nOverlap = 1;           // launches that may run side by side (trace streams in use)
     int nSlots = 1, slot = 0;   // frames that may be enqueued ahead / this frame's slot (colour, stack buffers, events)
     int batch = 1;              // frames traced by this launch (tptDrawDeviceBatch)
+    bool plainFrame = true;     // one frame, no planes, no per-frame table: what the lane-refill kernel traces as well
+    const char* entry = "tptDrawDevice"; // (whose launch this is, for a refusal)
 };
 
 // Per-slot device buffers (frame colour, bounce stacks) are allocated for ALL slots of the pipeline at
@@ -114,6 +116,24 @@ static bool pathQueueContext(int spp)
 }
 static bool pathQueueContext() { return pathQueueContext(g.spp); }
 
+// A CU's LDS, and how many path-queue workgroups of `lds` bytes it holds: each is counted with a 256-B margin, except that a workgroup
+// that fits the CU on its own is one workgroup, margin or not (never 0 for lds <= kCuLdsBytes: sizeGrid and maxGridBlocks size the grid
+// by it).
+static const size_t kCuLdsBytes = 160 * 1024;
+static int queueOccupancy(size_t lds)
+{
+    const int n = (int)(kCuLdsBytes / (lds + 256));
+    return n < 1 && lds <= kCuLdsBytes ? 1 : n;
+}
+// Lights whose table (32 B each) the path-queue kernel's LDS holds beside everything else this launch keeps there.
+static int queueLightRoom(KernelArgs a, bool ldsScene)
+{
+    a.scene.nLights = 0;
+    const size_t rest = tptQueueLdsBytes(a, ldsScene);
+    const size_t room = rest < kCuLdsBytes ? (kCuLdsBytes - rest) / 32 : 0;
+    return room < (size_t)TPT_MAX_LIGHTS ? (int)room : TPT_MAX_LIGHTS;
+}
+
 // Which kernel runs this frame, how much LDS it takes, how many workgroups fit on a CU.
 int chooseKernel(FramePlan& P)
 {
@@ -138,30 +158,48 @@ int chooseKernel(FramePlan& P)
     if (P.queued && !P.ldsScene && a.scene.nGroups > 0 && a.scene.gmxTiles == 0 && a.scene.nSuperPairs > 0 && g.useMatrix)
         a.ldsGroupPairs = tptQueueGroupPairsInLds(a.scene.nGroups, a.scene.nSuperPairs);
     P.lds = P.queued ? tptQueueLdsBytes(a, P.ldsScene) : ldsV1;
-    if (P.queued && a.ldsGroupPairs > 0 && 160 * 1024 / (P.lds + 256) < 2) {
+    if (P.queued && a.ldsGroupPairs > 0 && queueOccupancy(P.lds) < 2) {
         // the groups' bounds in LDS would cost the second workgroup per CU (many lights beside them): second level from global memory
         a.ldsGroupPairs = 0;
         P.lds = tptQueueLdsBytes(a, P.ldsScene);
     }
-    if ((size_t)a.scene.nLights * 32 > 96 * 1024)
-        return fail("tptDrawDevice: too many emissive spheres for the LDS light table (3072 at most)");
-    if (P.lds > 160 * 1024) return fail("tptDrawDevice: scene too large for LDS staging; use tptSetKernelVariant(.., .., 0)");
+    if (a.scene.nLights > TPT_MAX_LIGHTS)
+        return fail("tptDrawDevice: too many emissive spheres for the LDS light table (" + std::to_string(TPT_MAX_LIGHTS) + " at most)");
+    if (P.queued && P.lds > kCuLdsBytes && !(P.ldsScene && g.ldsScene > 0)) {
+        // The light table beside the path records is more than a CU's LDS holds.  A single frame without planes or tables is
+        // traced by the lane-refill kernel, whose LDS has room for every light table up to the cap; the launches that exist on the
+        // path-queue kernel only say how many lights they take beside this scene.
+        if (!P.plainFrame || ldsV1 > kCuLdsBytes)
+            return fail(std::string(P.entry) + ": " + std::to_string(a.scene.nLights) + " emissive spheres, and the path-queue kernel's LDS holds the light table of at most " +
+                        std::to_string(queueLightRoom(a, P.ldsScene)) + " beside this scene (tptDrawDevice and tptDraw take up to " + std::to_string(TPT_MAX_LIGHTS) +
+                        " on the lane-refill kernel)");
+        P.queued = false;
+        a.ldsGroupPairs = -1;
+        P.lds = ldsV1;
+    }
+    if (P.lds > kCuLdsBytes) return fail("tptDrawDevice: scene too large for LDS staging; use tptSetKernelVariant(.., .., 0)");
     if (P.queued) {
         a.ldsStackLevels = 1; // level 0 of the bounce stack sits in the path record (LDS), levels 1-9 in global memory
         // two workgroups per CU are worth more than the scene in LDS: a scene that costs the second workgroup its place
         // is read from global memory (L2) instead
-        if (g.ldsScene < 0 && P.ldsScene && 160 * 1024 / (P.lds + 256) < 2 && 160 * 1024 / (tptQueueLdsBytes(a, false) + 256) >= 2) {
+        if (g.ldsScene < 0 && P.ldsScene && queueOccupancy(P.lds) < 2 && queueOccupancy(tptQueueLdsBytes(a, false)) >= 2) {
             P.ldsScene = false;
             P.lds = tptQueueLdsBytes(a, false);
         }
     }
-    const int key = (P.queued ? (1 << 30) : 0) | (g.hs ? 8 : 0) | (g.foldMode ? 4 : 0) | (P.ldsScene ? 1 : 0) | ((int)(P.lds / 256) << 5);
-    auto it = g.occCache.find(key);
-    if (it == g.occCache.end()) {
-        P.occ = P.queued ? (int)(160 * 1024 / (P.lds + 256)) : tptTraceOccupancy(g.hs, g.foldMode, P.ldsScene, P.lds);
-        g.occCache[key] = P.occ;
+    if (P.queued) {
+        P.occ = queueOccupancy(P.lds); // (arithmetic: nothing to remember)
     } else {
-        P.occ = it->second;
+        // (the runtime's answer is remembered per kernel and LDS size, to the 16 bytes the sizes are multiples of: a coarser key once
+        //  handed a launch the occupancy of a neighbour 32 bytes smaller)
+        const int key = (g.hs ? 8 : 0) | (g.foldMode ? 4 : 0) | (P.ldsScene ? 1 : 0) | ((int)(P.lds / 16) << 5);
+        auto it = g.occCache.find(key);
+        if (it == g.occCache.end()) {
+            P.occ = tptTraceOccupancy(g.hs, g.foldMode, P.ldsScene, P.lds);
+            g.occCache[key] = P.occ;
+        } else {
+            P.occ = it->second;
+        }
     }
     P.threadsPerBlock = P.queued ? tptQueueThreadsPerBlock() : TPT_BLOCK;
     return 0;
@@ -273,6 +311,20 @@ int ensureFrameBuffers(FramePlan& P, int w)
     }
     a.pathBuf = nullptr;
     return 0;
+}
+
+// ... and the staged scene's light table fits beside that kernel's path records: what decides whether frames are traced several to a
+// launch (chooseKernel sends a single frame whose lights do not fit to the lane-refill kernel; a batch has no such way out).
+static bool pathQueueTakesScene()
+{
+    if (!pathQueueContext()) return false;
+    if (!activeSet()) return true; // (nothing staged yet: the launch itself decides)
+    FramePlan P;
+    P.a = KernelArgs{};
+    P.a.scene = deviceView();
+    P.a.fc.width = P.a.fc.height = 8;
+    P.a.batchFrames = 1;
+    return chooseKernel(P) == 0 && P.queued;
 }
 
 int syncAllStreams()
@@ -548,6 +600,10 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
         frameRays = g.views[P.slot].rays; // every frame counts its own rays (the blends add them to the running total)
         rayStride = 1;
     }
+    P.plainFrame = batch == 1 && !aov && !viewCams && !centres && !keyCentres;
+    P.entry = keyCentres ? "tptDrawDeviceKeyframeClip" : (viewCams && centres ? "tptDrawDeviceCameraClip" : (viewCams ? "tptDrawDeviceViews" :
+              (centres ? (aov ? "tptDrawDeviceAnimationMoments" : "tptDrawDeviceAnimation") :
+              (aov ? (aov->sampleCounts ? "tptDrawDeviceAdaptive" : (aov->moments ? "tptDrawDeviceMoments" : "tptDrawDeviceAov")) : (batch > 1 ? "tptDrawDeviceBatch" : "tptDrawDevice")))));
     if ((rc = chooseKernel(P))) return rc;
     if (viewCams && !P.queued)
         return refuse("tptDrawDeviceViews: needs the path-queue kernel (per-pixel seeds, recursive fold, two-phase HitSpheres, at most 2047 spp)");
@@ -1069,7 +1125,7 @@ int tptDrawDevice(float time, int frameCount, int w, int h, float* deviceTile, u
             if ((rc = Q.discard())) return rc; // (also closes a stream batch that did not continue as guessed)
             g.streamNext = -1;
             int nBatch = 1;
-            if (g.streamBatch && pipelined && stable && seqStreak >= 2 && pathQueueContext() && w <= 8192 && h <= 8192) {
+            if (g.streamBatch && pipelined && stable && seqStreak >= 2 && pathQueueTakesScene() && w <= 8192 && h <= 8192) {
                 // how many frames make a launch long enough to amortise its fixed cost at this pipeline depth (tpt_stream_batch.h)
                 g.streamRun = continues ? g.streamRun + 1 : 0;
                 nBatch = streamBatchFrames((long long)localRows(h) * w * g.spp, effectiveOverlap(), Context::kMaxOverlap, g.streamRun,
@@ -1186,7 +1242,10 @@ int tptDrawDeviceAnimation(int firstFrame, int nFrames, const float* times, int 
     const bool animate = (testFlags & TPT_FLAG_ANIMATE) && g.spheres.size() > 8;
     // one launch per kMaxBatch frames on the path-queue kernel; the animation kernel also wants a flat scene (its exact tests are
     // those of the flat filters); everything else: one launch per frame, the kernels of tptDrawDevice
-    const int perLaunch = pathQueueContext() && (!animate || g.spheres.size() < TPT_GROUP_MIN_SPHERES) ? kMaxBatch : 1;
+    if (g.updated && (g.sceneDirty || !activeSet())) { // (tptSetScene after the last tptUpdate: what is staged decides the launches below)
+        if (int rc_ = stageScene()) return rc_;
+    }
+    const int perLaunch = pathQueueTakesScene() && (!animate || g.spheres.size() < TPT_GROUP_MIN_SPHERES) ? kMaxBatch : 1;
     int rc = checkPathQueueDraw("tptDrawDeviceAnimation", "animation is", w, h, 0, [&] {
         const size_t colour = (size_t)h * (size_t)w * sizeof(f4) * (size_t)(nFrames < perLaunch ? nFrames : perLaunch);
         return colour > (4ull << 30) ? refuse("tptDrawDeviceAnimation: " + std::to_string(colour >> 20) + " MiB of frame colour per launch: over the 4096 MiB limit") : 0;
