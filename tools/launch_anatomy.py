@@ -15,7 +15,7 @@ rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))
 iv = lambda r: (int(r["Start_Timestamp"]), int(r["End_Timestamp"]))  # noqa: E731
 res = [r for r in rows if "tptResolveKernel" in r["Kernel_Name"]]
 t0, t1 = iv(res[-n - 1])[1], iv(res[-1])[1]
-tr = [r for r in rows if "tptTraceQueueKernel" in r["Kernel_Name"] and iv(r)[0] >= t0]
+tr = [r for r in rows if ("tptTraceQueueKernel" in r["Kernel_Name"] or "tptFramePoolsKernel" in r["Kernel_Name"]) and iv(r)[0] >= t0]
 blends = res[-n:]
 span = t1 - t0
 durs = [iv(r)[1] - iv(r)[0] for r in tr]

@@ -3,6 +3,7 @@
 // variant a launch takes (tptQueueVariant): tpt_queue_layout.h, which includes this header.
 #pragma once
 #include "tpt_trace.h"
+#include "tpt_frame_pools.h"
 
 #ifndef TPT_BLOCK
 #define TPT_BLOCK 64         // threads per workgroup: one wave, so a finished wave frees its LDS/VGPRs at once
@@ -47,7 +48,7 @@ struct KernelArgs {
     const unsigned* chunkOrder;      // may be null: image order
     unsigned* chunkCost;             // may be null
     int chunkShift;                  // log2(chunkSize)
-    unsigned* work;                  // [0] next chunk, [1] finished waves (persistent variants)
+    unsigned* work;                  // [0] next chunk, [1] finished waves (persistent variants), [2] [3] tail helpers, [4..11] next chunk of frame j (framePools)
     unsigned long long* rayCounter;  // monotonic total of rays traced by this context
     int rayCounterStride;            // batched row-serial launch: frame j of the batch counts into rayCounter[j * stride] (0: one counter)
     unsigned gen;                    // tail helpers: serial of this launch (1, 2, ...; 0: takes no helpers)
@@ -90,6 +91,10 @@ struct KernelArgs {
     const f4* keyCentres = nullptr;
     unsigned long long keyMask = 0;
     int keyCount = 0;
+    // A pool of chunks per frame of a plain batched launch (tpt_frame_pools.h): 0 = one shared pool, work[0] counting to numChunks;
+    // n = batchFrames = n pools, work[4 + j] counting frame j's chunks to chunksPerFrame, and workgroup b serves frame
+    // framePoolOfBlock(b, n, grid) alone; the launch takes tptFramePoolsKernel.  0 for every other launch.
+    int framePools = 0;
 };
 
 } // namespace tpt

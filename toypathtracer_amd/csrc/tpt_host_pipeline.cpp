@@ -696,6 +696,8 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
     if ((rc = enqueueChunkOrder(P, ts))) return rc;
     if (frameRays && frameRays != g.dRays) HIPCHK(hipMemsetAsync(frameRays, 0, sizeof(unsigned long long) * (size_t)(rayStride > 0 ? batch : 1), ts));
     const bool helpable = P.queued && pipelined && batch == 1 && !P.rowSerial && !table && !aov; // (single frames of the path-queue kernel)
+    // the plain batched kernel (tptDrawDeviceBatch, STREAM launches) deals its workgroups to the frames, a pool of chunks per frame
+    a.framePools = framePoolsOfLaunch(batch, P.blocks, P.queued && !P.rowSerial && !table && !aov, helpable);
     a.helperBase = 0;
     a.helperPct = 0;
     a.gen = 0u;

@@ -1867,10 +1867,16 @@ __device__ __forceinline__ int hitSpheresGroupedDeal(const SceneView& sv, bool g
 // spheres, named by the launch-uniform mask a.keyMask, at the centres a.keyCentres[TPT_Q_KEYS_MAX j ..] (staged in LDS at that fixed
 // stride) wherever MOVING reads the centres of spheres 1 and 8, and candidates of every ray in their place (tpt_trace.h, keyedSphere).
 // Its own kernel (tptKeyframeKernel) for the same reason.
+// POOLS (with BATCH alone; tptDrawDeviceBatch and STREAM launches of 2 .. 8 frames, tpt_frame_pools.h): a pool of chunks per frame of
+// the batch, a.work[4 + j] counting frame j's chunks to a.chunksPerFrame.  Workgroup b serves frame framePoolOfBlock(b, frames, grid)
+// alone -- it takes no chunk of another frame and leaves when its frame's pool is dry and its paths are done, so the workgroups of a
+// launch run dry frame after frame instead of all at once -- and counts its rays per lane, for that frame's counter.  Its own kernel
+// (tptFramePoolsKernel) for the same reason.
 template <bool LDS_SCENE, bool BATCH, bool VIEWS = false, bool MOVING = false, bool AOV = false, bool MOMENTS = false, bool ADAPTIVE = false,
-          bool CAMERAS = false, bool KEYS = false>
+          bool CAMERAS = false, bool KEYS = false, bool POOLS = false>
 __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
 {
+    static_assert(!POOLS || (BATCH && !VIEWS && !MOVING && !AOV), "a pool per frame belongs to the plain batched launch");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // LDS layout: everything of fixed size first, at compile-time offsets (immediates in the DS instructions instead of base
     // registers): path records, rings, control block, frame constants; then the scene arrays, whose sizes the launch decides
@@ -2010,6 +2016,9 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     int chunkFrame = 0;              // batched launch: the frame of the batch that pool belongs to
     bool noMoreChunks = false;
     unsigned myRays = 0;
+    // POOLS: the frame of the batch this workgroup serves (tpt_frame_pools.h) -- wave-uniform, made where it is used (once per chunk,
+    // in place of the shared pool's division) instead of being held across the loop
+    auto poolFrame = [&]() { return framePoolOfBlock(blockIdx.x, (unsigned)uniformHere(a.batchFrames), (unsigned)uniformHere((int)gridDim.x)); };
 #if defined(TPT_STATS)
     const unsigned long long qT0 = wall_clock64();
     unsigned qSteps = 0, qBatches = 0, qIdle = 0;
@@ -2139,12 +2148,15 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                 if (chunkNext >= chunkEnd) {
                     if (noMoreChunks) break;
                     int c = 0;
+                    [[maybe_unused]] const int myFrame = POOLS ? (int)poolFrame() : 0;
                     if (lane == 0) {
                         atomicAdd(&ctl->poolTotal, 64u); // optimistic: keeps "pixels left" non-zero while the fetch is in flight
-                        c = (int)atomicAdd(&a.work[0], 1u);
+                        // (POOLS: the next chunk of this workgroup's frame.  It takes chunks of that frame only: "exhausted" below then
+                        //  means the frame's own pool, and the workgroup leaves while the other frames' workgroups run on)
+                        c = (int)atomicAdd(POOLS ? &a.work[kFramePoolBase + myFrame] : &a.work[0], 1u);
                     }
                     c = __builtin_amdgcn_readfirstlane(c);
-                    if (c >= a.numChunks) {
+                    if (c >= (POOLS ? a.chunksPerFrame : a.numChunks)) {
                         if (lane == 0) {
                             atomicSub(&ctl->poolTotal, 64u);
                             __hip_atomic_store(&ctl->globalExhausted, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -2153,7 +2165,9 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                         break;
                     }
                     chunkFrame = 0;
-                    if (BATCH) { // batched launch: chunk c belongs to frame c / chunksPerFrame of the batch
+                    if (POOLS) { // ... with a pool per frame: chunk c of this workgroup's frame
+                        chunkFrame = myFrame;
+                    } else if (BATCH) { // batched launch: chunk c belongs to frame c / chunksPerFrame of the batch
                         chunkFrame = c / a.chunksPerFrame;
                         c -= chunkFrame * a.chunksPerFrame;
                     }
@@ -2349,7 +2363,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                         id = hitSpheresTwoPhase<true, KEYS>(sv, ro, d2, TPT_MIN_T, TPT_MAX_T, t, movedLds + movedAt, keyMask);
                     else
                         id = hitSpheres<LDS_SCENE ? HS_TWO_PHASE : HS_TWO_PHASE_GROUPS>(sv, ro, d2, TPT_MIN_T, TPT_MAX_T, t);
-                    if (BATCH) iterRays++; else myRays++;
+                    if (BATCH && !POOLS) iterRays++; else myRays++; // (POOLS: every path of this workgroup belongs to one frame)
                     if (shadow) {
                         if (id == lightId) qLightShade(l1, d2, lam);
                     } else {
@@ -2389,7 +2403,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
             st[1 * kPaths + p] = mk4(rd.x, rd.y, rd.z, u2f(w));
         }
         if (toFree) cls = Q_FREE;
-        if (BATCH && iterRays != 0u) { // (one LDS atomic per lane and iteration)
+        if (BATCH && !POOLS && iterRays != 0u) { // (one LDS atomic per lane and iteration)
             const unsigned fr = f2u(colSum[p].w) >> 26;
             const unsigned old = atomicAdd(&ctl->frameRays[fr], iterRays);
             // a 32-bit counter per workgroup and frame can wrap on a very large frame at high spp on a small grid: the lane whose
@@ -2410,7 +2424,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     }
 
     const unsigned waveRays = waveReduceAdd(myRays);
-    if (BATCH) {
+    if (BATCH && !POOLS) {
         // every frame of the batch has its own counter (rayCounterStride 1: a caller that is served the frames one by one
         // gets each frame's own count; 0: they all add to the context's running total)
         __syncthreads();
@@ -2428,6 +2442,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     }
     if (lane == 0) {
         if (!BATCH) atomicAdd(a.rayCounter, (unsigned long long)waveRays);
+        if (POOLS) atomicAdd(a.rayCounter + (size_t)poolFrame() * a.rayCounterStride, (unsigned long long)waveRays); // (its frame's counter: see the BATCH flush above)
         unsigned done = atomicAdd(&a.work[1], 1u) + 1u;
         if (done == a.totalWaves) {
             if (a.gen != 0u) {
@@ -2444,6 +2459,8 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
             }
             a.work[0] = 0u;
             a.work[1] = 0u;
+            if (POOLS) // (the frames' pools, re-armed like the shared one)
+                for (int j = 0; j < a.batchFrames; ++j) a.work[kFramePoolBase + j] = 0u;
         }
     }
 #if defined(__HIP_DEVICE_COMPILE__) && defined(TPT_STATS) && TPT_STATS >= 2
@@ -2498,21 +2515,21 @@ tptTraceQueueKernel<false, true>(const KernelArgs a)
 // The variants of traceQueueBody beyond <LDS_SCENE, BATCH>, from one list.  Each is a kernel of its own, not another template argument of
 // tptTraceQueueKernel: names and code of the existing kernels stay (tests look them up by name).  <false>: no scene in LDS -- grouped scenes
 // and flat scenes whose arrays stay in global memory (the moving variants take flat scenes only) --, with the grouped register cap.
-enum { QF_BATCH = 1, QF_VIEWS = 2, QF_MOVING = 4, QF_AOV = 8, QF_MOMENTS = 16, QF_ADAPTIVE = 32, QF_CAMERAS = 64, QF_KEYS = 128 };
+enum { QF_BATCH = 1, QF_VIEWS = 2, QF_MOVING = 4, QF_AOV = 8, QF_MOMENTS = 16, QF_ADAPTIVE = 32, QF_CAMERAS = 64, QF_KEYS = 128, QF_POOLS = 256 };
 #define TPT_QUEUE_VARIANT_KERNEL(NAME, F)                                                                                                    \
     template <bool LDS_SCENE>                                                                                                                \
     __global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute__((amdgpu_num_vgpr(TPT_Q_MAX_VGPR)))                    \
     NAME(const KernelArgs a)                                                                                                                 \
     {                                                                                                                                        \
         traceQueueBody<LDS_SCENE, ((F) & QF_BATCH) != 0, ((F) & QF_VIEWS) != 0, ((F) & QF_MOVING) != 0, ((F) & QF_AOV) != 0, ((F) & QF_MOMENTS) != 0, \
-                       ((F) & QF_ADAPTIVE) != 0, ((F) & QF_CAMERAS) != 0, ((F) & QF_KEYS) != 0>(a);                                                             \
+                       ((F) & QF_ADAPTIVE) != 0, ((F) & QF_CAMERAS) != 0, ((F) & QF_KEYS) != 0, ((F) & QF_POOLS) != 0>(a);                                                            \
     }                                                                                                                                        \
     template <>                                                                                                                              \
     __global__ void __launch_bounds__(TPT_Q_T, TPT_Q_MIN_WAVES_PER_SIMD) __attribute__((amdgpu_num_vgpr(TPT_Q_MAX_VGPR_GROUPED)))            \
     NAME<false>(const KernelArgs a)                                                                                                          \
     {                                                                                                                                        \
         traceQueueBody<false, ((F) & QF_BATCH) != 0, ((F) & QF_VIEWS) != 0, ((F) & QF_MOVING) != 0, ((F) & QF_AOV) != 0, ((F) & QF_MOMENTS) != 0, \
-                       ((F) & QF_ADAPTIVE) != 0, ((F) & QF_CAMERAS) != 0, ((F) & QF_KEYS) != 0>(a);                                                             \
+                       ((F) & QF_ADAPTIVE) != 0, ((F) & QF_CAMERAS) != 0, ((F) & QF_KEYS) != 0, ((F) & QF_POOLS) != 0>(a);                                                            \
     }
 TPT_QUEUE_VARIANT_KERNEL(tptTraceViewsKernel, QF_BATCH | QF_VIEWS)                           // tptDrawDeviceViews: several views of one frame, a camera per frame of the batch
 TPT_QUEUE_VARIANT_KERNEL(tptTraceAnimationKernel, QF_BATCH | QF_MOVING)                      // tptDrawDeviceAnimation: frames of an animated scene, spheres 1 and 8 where each frame has them
@@ -2522,6 +2539,7 @@ TPT_QUEUE_VARIANT_KERNEL(tptTraceClipKernel, QF_BATCH | QF_MOVING | QF_AOV | QF_
 TPT_QUEUE_VARIANT_KERNEL(tptTraceAdaptiveKernel, QF_AOV | QF_MOMENTS | QF_ADAPTIVE)             // tptDrawDeviceAdaptive: the moments kernel with each pixel's sample count from a plane
 TPT_QUEUE_VARIANT_KERNEL(tptCameraClipKernel, QF_BATCH | QF_MOVING | QF_AOV | QF_MOMENTS | QF_CAMERAS) // tptDrawDeviceCameraClip: the clip kernel with a camera per frame (not "tptTrace...": tests count those names)
 TPT_QUEUE_VARIANT_KERNEL(tptKeyframeKernel, QF_BATCH | QF_MOVING | QF_AOV | QF_MOMENTS | QF_CAMERAS | QF_KEYS) // tptDrawDeviceKeyframeClip: the camera-clip kernel with the caller's centres per frame (a name without the words tests count kernels by)
+TPT_QUEUE_VARIANT_KERNEL(tptFramePoolsKernel, QF_BATCH | QF_POOLS)                            // tptDrawDeviceBatch and STREAM launches of 2 .. 8 frames: the batched kernel with a pool of chunks per frame (a name without the words tests count kernels by)
 #undef TPT_QUEUE_VARIANT_KERNEL
 
 #if defined(TPT_TEST_HOOKS)
@@ -2791,10 +2809,12 @@ hipError_t tptLaunchTraceQueue(const KernelArgs& a, bool ldsScene, int blocks, s
         /* QV_CLIP      */ {tptTraceClipKernel<false>, tptTraceClipKernel<true>},
         /* QV_ADAPTIVE  */ {tptTraceAdaptiveKernel<false>, tptTraceAdaptiveKernel<true>},
         /* QV_KEYFRAME_CLIP */ {tptKeyframeKernel<false>, tptKeyframeKernel<true>},
+        /* QV_FRAME_POOLS */ {tptFramePoolsKernel<false>, tptFramePoolsKernel<true>},
         /* QV_CAMERA_CLIP */ {tptCameraClipKernel<false>, tptCameraClipKernel<true>},
     };
     const QueueVariant variant = tptQueueVariant(a);
     if (variant == QV_INVALID) return hipErrorInvalidValue;
+    if (variant == QV_FRAME_POOLS && blocks < a.framePools) return hipErrorInvalidValue; // (a workgroup per pool at least)
     return launchQueueKernel(kernel[variant][ldsScene ? 1 : 0], a, blocks, lds, stream);
 }
 #if defined(TPT_TEST_HOOKS)

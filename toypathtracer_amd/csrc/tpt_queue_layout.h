@@ -156,9 +156,15 @@ TPT_HD int globalRowToLocal(const KernelArgs& a, int gy) { return shardKernelGlo
 
 // Which variant of the path-queue kernel a launch takes: what its argument block holds decides, here and nowhere else.  QV_INVALID: a
 // combination no entry point builds (tptLaunchTraceQueue refuses it).
-enum QueueVariant { QV_FRAME, QV_BATCH, QV_VIEWS, QV_ANIMATION, QV_AOV, QV_MOMENTS, QV_CLIP, QV_ADAPTIVE, QV_KEYFRAME_CLIP, QV_CAMERA_CLIP, QV_INVALID };
+enum QueueVariant { QV_FRAME, QV_BATCH, QV_VIEWS, QV_ANIMATION, QV_AOV, QV_MOMENTS, QV_CLIP, QV_ADAPTIVE, QV_KEYFRAME_CLIP, QV_FRAME_POOLS, QV_CAMERA_CLIP, QV_INVALID };
 inline QueueVariant tptQueueVariant(const tpt::KernelArgs& a)
 {
+    if (a.framePools != 0) { // (a pool of chunks per frame, tpt_frame_pools.h: a plain batched launch of 2 .. kFramePoolsMax frames, one pool each, no helper grid)
+        if (a.framePools != a.batchFrames || a.framePools < 2 || a.framePools > tpt::kFramePoolsMax || a.helperBase > 0 || a.viewCams || a.moveCentres ||
+            a.keyCentres || a.sampleCounts || a.aovSums || a.fc.seedMode == tpt::SEED_ROW_SERIAL)
+            return QV_INVALID;
+        return QV_FRAME_POOLS;
+    }
     if (a.keyCentres) { // (tptDrawDeviceKeyframeClip: 1 .. TPT_Q_VIEWS_MAX frames of the batch with their planes, a camera and the keyed centres per frame, a flat scene)
         if (a.batchFrames < 1 || a.batchFrames > TPT_Q_VIEWS_MAX || a.scene.nGroups > 0 || !a.viewCams || a.moveCentres || a.sampleCounts || !a.aovSums ||
             !a.momentsOut || a.keyCount < 0 || a.keyCount > TPT_Q_KEYS_MAX)
