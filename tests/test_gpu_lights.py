@@ -71,14 +71,18 @@ def restore(tpt):
     tpt.set_config(True, 0.9, False)
 
 
-def draw(tpt, oracle, key, s, m, w, h, spp, frames, variant=DEFAULT, fold=FOLD_RECURSIVE, stress=False, light_sampling=True):
-    """the scene through DrawTest with this kernel, held against the oracle -> (launch_info(), scene_info(), per-frame rays)"""
+def draw(tpt, oracle, key, s, m, w, h, spp, frames, variant=DEFAULT, fold=FOLD_RECURSIVE, stress=False, light_sampling=True, camera=None):
+    """the scene through DrawTest with this kernel, held against the oracle -> (launch_info(), scene_info(), per-frame rays); camera: the
+    keyword arguments of tpt.set_camera (stress: STRESS_CAMERA), None for the default camera"""
     cam = None
     try:
         tpt.set_scene(s, m)
         if stress:
             c, cam = stress_camera(oracle, w, h)
             tpt.set_camera(**c)
+        elif camera is not None:
+            cam = oracle.camera(camera["look_from"], camera["look_at"], (0, 1, 0), camera["vfov"], w / h, camera["aperture"], camera["focus_dist"])
+            tpt.set_camera(**camera)
         tpt.set_samples_per_pixel(spp)
         tpt.set_kernel_variant(*variant)
         tpt.set_fold_mode(fold)

@@ -80,11 +80,11 @@ TPT_HD double u2d(uint64_t u)
 #endif
 }
 // Correctly rounded sqrtf.  hipcc's own expansion (-fhip-fp32-correctly-rounded-divide-sqrt, the default) costs 17 VALU
-// instructions, 7 of them for denormal scaling and the inf / nan / zero fix-up.  For 2^-96 <= x <= 2^96 -- everything a
-// path ever feeds it -- five do: y = v_rsq_f32(x), s0 = x y, one fused residual correction s0 + (x - s0^2) (y / 2).
-// PROVEN BY EXHAUSTION, not by argument: tools/exhaustive/exhaustive_math.hip and test_gpu_math.py::test_fast_sqrt_*
-// compare it with the compiler's expansion for every one of the 2^32 binary32 inputs on the device (0 mismatches; outside
-// the guarded range the expansion itself runs).  The guard is two integer instructions.
+// instructions, 7 of them for denormal scaling and the inf / nan / zero fix-up.  For 2^-96 <= x <= 2^96 five do: y =
+// v_rsq_f32(x), s0 = x y, one fused residual correction s0 + (x - s0^2) (y / 2).  PROVEN BY EXHAUSTION, not by argument:
+// tools/exhaustive/exhaustive_math.hip and test_gpu_math.py::test_fast_sqrt_* compare it with the compiler's expansion for
+// every binary32 input on the device (0 mismatches).  Outside the range the expansion itself runs, and frames do get there:
+// a ground of r >= 2^49 has discriminants past 2^96 (tests/test_gpu_scene_kinds.py, ground_2^49 and 2^60).  Guard: 2 int ops.
 #define TPT_SQRT_LO 0x0f800000u /* 2^-96 */
 #define TPT_SQRT_HI 0x6f800000u /* 2^96 */
 TPT_HD float tsqrt(float x)
