@@ -57,7 +57,7 @@ def _variance(mx, my, N):
 
 
 def rectify_numpy(colour, moments, acc_colour, acc_moments, radius=1, gamma=1.0, details=False):
-    """-> (out_colour, out_moments, out_variance); details=True: also a dict of the per-pixel L, U (h, w, 3), a, and the masks"""
+    """-> (out_colour, out_moments, out_variance); details=True: also a dict of the per-pixel L, U (h, w, 3), a, the window variance and the masks"""
     h, w = colour.shape[:2]
     r, gamma = int(radius), f32(gamma)
     cur, acc, M = colour[..., :3], acc_colour[..., :3], acc_moments
@@ -115,7 +115,7 @@ def rectify_numpy(colour, moments, acc_colour, acc_moments, radius=1, gamma=1.0,
         ov = np.where(keep[..., None], _variance(M[..., 0], M[..., 1], N), _variance(mx, my, N1)).astype(f32)
     outs = tuple(np.ascontiguousarray(x) for x in (oc, om, ov))
     if details:
-        return outs, dict(L=L, U=U, a=np.where(through, f32(0), a), through=through, keep=keep, out=out)
+        return outs, dict(L=L, U=U, a=np.where(through, f32(0), a), through=through, keep=keep, out=out, var=var)
     return outs
 
 

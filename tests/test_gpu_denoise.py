@@ -59,16 +59,22 @@ def denoise_gpu(tpt, colour, albedo, nd, iterations, sc, sn, sd, demod):
     return out.cpu().numpy(), [None if t is None else t.cpu().numpy() for t in (dc, da, dn)]
 
 
-def check_all_modes(tpt, checker, colour, albedo, nd, iterations):
+def same_bytes(got, want):
+    return got.tobytes() == want.tobytes()
+
+
+def check_all_modes(tpt, checker, colour, albedo, nd, iterations, same=same_bytes, sigmas=None):
+    """every mode of the call against the checker, compared with `same` (byte equality unless the caller's reference holds NaNs, whose
+    payload is not part of the contract); sigmas: (colour, normal, depth), None for the api's defaults"""
     from toypathtracer_amd.api import DENOISE_DEFAULTS as D
-    sc, sn, sd = D["sigma_colour"], D["sigma_normal"], D["sigma_depth"]
+    sc, sn, sd = (D["sigma_colour"], D["sigma_normal"], D["sigma_depth"]) if sigmas is None else sigmas
     for use_alb, use_nd, demod in ((True, True, True), (True, True, False), (False, True, False), (True, False, True), (False, False, False)):
         a = albedo if use_alb else None
         n = nd if use_nd else None
         for it in iterations:
             got, ins = denoise_gpu(tpt, colour, a, n, it, sc, sn if use_nd else 0.0, sd if use_nd else 0.0, demod)
             want = checker.run(colour, a, n, it, sc, sn if use_nd else 0.0, sd if use_nd else 0.0, DEMODULATE if demod else 0)
-            assert got.tobytes() == want.tobytes(), (use_alb, use_nd, demod, it)
+            assert same(got, want), (use_alb, use_nd, demod, it)
             for x, y in zip(ins, (colour, a, n)):
                 assert (x is None) == (y is None) and (x is None or x.tobytes() == y.tobytes()), "an input was written"
 
