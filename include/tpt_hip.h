@@ -720,8 +720,10 @@ TPT_API int tptSetFrameOverlap(int frames);
  * the sequence (other frame number, size, flags, scene, ...) drops the unserved planes: GPU time only.
  * Larger frames are batched too when the pipeline is shallow (few hardware queues: two launches in flight at 4 queues): enough frames
  * per launch that the launches in flight carry what 16 did, 2 then 4 then 8 at 1280x720x4 as the stream goes on; with the full
- * 16-deep pipeline they keep one frame per launch.  tptSynchronize and tptRayCounterRead drop an open batch's unserved planes, so a
- * frame traced before the caller waited is never served after it; the next call starts a stream afresh. */
+ * 16-deep pipeline they keep one frame per launch.  tptSynchronize, tptTimerEnd and tptRayCounterRead drop an open batch's unserved
+ * planes, so a frame traced before the caller waited is never served after it; the next call starts a stream afresh.  The launch of a
+ * dropped batch is told so while it runs: it stops tracing the frames nobody asked for, and their workgroups that have not started
+ * yet trace the asked frames instead -- same bits, same ray counts, the wait is only shorter. */
 TPT_API int tptSetStreamBatching(int enable);
 /* Display conversion of a device-resident FULL image (w*h float4, row 0 = bottom) into w*h RGBA8 in device memory,
  * top row first: the reference's own conversion for its C++ path, Cpp/Emscripten/main.cpp:63-79
@@ -788,7 +790,10 @@ TPT_API int tptShardedFinish(int64_t* outTotalRays);
 /* hipEvent bracket on the context's stream, for kernel-only timing (as the reference times its
  * Dispatch with timestamp queries, TestWin.cpp:299-302). */
 TPT_API int tptTimerBegin(void);
-TPT_API int tptTimerEnd(float* outMilliseconds); /* synchronises */
+/* tptTimerEnd is a wait like tptSynchronize: it records the end event, closes an open stream batch (tptSetStreamBatching: the
+ * frames traced for calls that have not come yet are dropped, and the next tptDrawDevice starts a launch of its own), then blocks
+ * until the end event has completed. */
+TPT_API int tptTimerEnd(float* outMilliseconds);
 
 /* Per-launch timing of the trace kernel: between Begin and End every tptDrawDevice brackets its trace
  * launch with a hipEvent pair recorded on the stream that launch goes to (the internal trace streams when

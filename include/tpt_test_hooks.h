@@ -35,6 +35,14 @@ TPT_API int tptDebugStats(unsigned long long* out128, int reset);
 /* per-chunk accumulated ray counts and the chunk order table of the last launch (cost-ordered work distribution
  * of the persistent kernel); either pointer may be NULL; returns the number of chunks copied */
 TPT_API int tptDebugChunkOrder(unsigned* outCost, unsigned* outOrder, int capacity);
+/* stream batches (tpt_hip.h, tptSetStreamBatching): the next launch that deals its workgroups to its frames starts with its cut word
+ * already set to "only the first `keep` frames are wanted" (1..7; 0 takes a preset back), as if the caller had waited before the
+ * launch began: every workgroup starts under the cut, so the case is the same on every run.  The caller asks for exactly `keep`
+ * frames of that launch and then waits. */
+TPT_API int tptTestPresetStreamCut(int keep);
+/* the ray counter of every frame of the newest stream-batch launch (after draining the pipeline): what each frame's workgroups
+ * counted, served or not; returns the launch's frames (at most `capacity` copied), 0 when there was none */
+TPT_API int tptTestStreamFrameRays(unsigned long long* outRays, int capacity);
 #ifdef __cplusplus
 }
 #endif

@@ -42,7 +42,7 @@ C_ABI_SYMBOLS = [
     "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceAnimationMoments", "tptDrawDeviceCameraClip", "tptDrawDeviceKeyframeClip", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptObjectPlaneDevice", "tptObjectMotionTable", "tptTemporalAccumulateObjectsDevice", "tptDenoiseClipDevice", "tptMotionVectorsDevice", "tptRectifyHistoryDevice", "tptDrawDeviceAdaptive", "tptAdaptiveSamplesDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
 ]
 # include/tpt_test_hooks.h: exported by the second build (libtoypathtracer_hip_hooks.so) only
-HOOK_SYMBOLS = ["tptTestMath", "tptTestMathExhaustive", "tptTestHitSpheres", "tptTestMatrixFilter", "tptTestGroupFilter", "tptTestSetDealCapacities", "tptDebugStats", "tptDebugChunkOrder"]
+HOOK_SYMBOLS = ["tptTestMath", "tptTestMathExhaustive", "tptTestHitSpheres", "tptTestMatrixFilter", "tptTestGroupFilter", "tptTestSetDealCapacities", "tptDebugStats", "tptDebugChunkOrder", "tptTestPresetStreamCut", "tptTestStreamFrameRays"]
 # the reference's own C++ symbols (nm of the compiled Test.cpp), exported for link-level drop-in
 CXX_ABI_SYMBOLS = [
     "_Z14InitializeTestv", "_Z12ShutdownTestv", "_Z10UpdateTestfiiij", "_Z8DrawTestfiiiPfRij",
@@ -103,7 +103,7 @@ def _bind(path, hooks):
     }
     if hooks:
         sigs.update({"tptDebugStats": [p, i], "tptDebugChunkOrder": [p, p, i], "tptTestMath": [i, p, p, p, i], "tptTestMathExhaustive": [i, u, u, p, p],
-                     "tptTestHitSpheres": [i, p, p, p, i], "tptTestMatrixFilter": [p, p, p, p, i], "tptTestGroupFilter": [p, i, p, p, p], "tptTestSetDealCapacities": [i, i, i]})
+                     "tptTestHitSpheres": [i, p, p, p, i], "tptTestMatrixFilter": [p, p, p, p, i], "tptTestGroupFilter": [p, i, p, p, p], "tptTestSetDealCapacities": [i, i, i], "tptTestPresetStreamCut": [i], "tptTestStreamFrameRays": [p, i]})
     for name, args in sigs.items():
         fn = getattr(lib, name)
         fn.argtypes = args
@@ -1147,3 +1147,17 @@ def test_group_filter(rays):
     v = [C.c_ulonglong(0) for _ in range(3)]
     _chk(_hook("tptTestGroupFilter")(rays.ctypes.data, n, C.byref(v[0]), C.byref(v[1]), C.byref(v[2])), "tptTestGroupFilter")
     return int(v[0].value), v[1].value / n, v[2].value / n
+
+
+def test_preset_stream_cut(keep):
+    """hooks build: the next stream-batch launch with a pool per frame starts cut to its first `keep` frames (0: no preset)"""
+    _chk(_hook("tptTestPresetStreamCut")(int(keep)), "tptTestPresetStreamCut")
+
+
+def test_stream_frame_rays():
+    """hooks build: the per-frame ray counters of the newest stream-batch launch (drains the pipeline first)"""
+    out = np.zeros(8, np.uint64)
+    n = _hook("tptTestStreamFrameRays")(out.ctypes.data, 8)
+    if n < 0:
+        raise TptError(f"tptTestStreamFrameRays: {_lib.tptGetLastError().decode()}")
+    return [int(v) for v in out[:n]]

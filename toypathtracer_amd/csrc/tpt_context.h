@@ -49,6 +49,7 @@ struct TraceTicket {
     int batch = 1;           // frames traced by the launch; their colour planes lie nPixels apart
     tptLerpTable lerp = {};  // batch > 1: each frame's lerp factor
     const f4* moments = nullptr; // a launch with moments: where it staged them (Context::dMoments; a clip launch's half), a plane per frame
+    unsigned cutSerial = 0;      // a launch with a pool per frame: the serial its slot's cut word must carry (tpt_frame_pools.h); 0: none
     TraceTicket plane(int j) const // frame j of the launch, as a ticket of its own (a single-frame launch: plane 0 is itself)
     {
         TraceTicket t = *this;
@@ -100,6 +101,7 @@ struct LaunchQueue {
     int push(const PendingLaunch& L);
     int discard();
     void closeStream();
+    void cutFront(); // (a STREAM entry with unserved frames is about to be dropped: tell its launch, tpt_frame_pools.h)
 };
 
 struct Context {
@@ -212,6 +214,15 @@ struct Context {
     unsigned long long streamBatches = 0;       // stream batches launched (index into their ring of ray counters)
     int streamRun = 0, streamNext = -1;         // stream batches launched back to back before the newest / the frame that continues it (-1: none)
     int streamBatch = 1;                        // on by default since round 4; tptSetStreamBatching(0) / env TPT_STREAM_BATCH=0 turn it off
+    // The cut words of the launches with a pool per frame (tpt_frame_pools.h), one per frame slot, in PINNED HOST memory: the host
+    // writes a word while the launch it is meant for runs, without a stream or a hardware queue -- with few queues a copy or a
+    // one-thread kernel can sit behind the very launch it is meant to cut.  A slot's word is zeroed when a launch is enqueued on it
+    // (stream-ordered behind the slot's previous launch by then: nobody reads the old word any more) and written at most once after.
+    unsigned* hCut = nullptr;
+    unsigned cutSerial = 0;                     // serial of the newest such launch (24 bits, never 0 once used)
+    int cutPreset = 0;                          // hooks build, tptTestPresetStreamCut: the next such launch starts with this `keep` in its word
+    unsigned long long* lastStreamRays = nullptr; // per-frame ray counters of the newest STREAM launch, and its frames (hooks build's read-back)
+    int lastStreamFrames = 0;
     // tptDrawDevice: is the caller synchronous (the previous frame's blend has completed by the time the next call arrives)
     // and are its calls consecutive frames of one configuration?  Then the next frames are traced ahead for it too.
     struct DeviceCaller {

@@ -95,6 +95,11 @@ struct KernelArgs {
     // n = batchFrames = n pools, work[4 + j] counting frame j's chunks to chunksPerFrame, and workgroup b serves frame
     // framePoolOfBlock(b, n, grid) alone; the launch takes tptFramePoolsKernel.  0 for every other launch.
     int framePools = 0;
+    // ... and the launch's cut word (tpt_frame_pools.h): one word of the context's array in pinned host memory, read by the pools kernel
+    // where a workgroup starts, and the serial a word must carry to mean this launch.  Null / 0 for
+    // every other launch.
+    const unsigned* cutWord = nullptr;
+    unsigned cutSerial = 0;
 };
 
 } // namespace tpt

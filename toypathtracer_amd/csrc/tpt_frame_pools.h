@@ -42,4 +42,42 @@ TPT_FP_HD unsigned framePoolOfBlock(unsigned block, unsigned pools, unsigned blo
     return block * pools / blocks;
 }
 
+// A STREAM launch whose caller waited before asking for all of its frames is CUT: frames >= keep of the batch will never be blended,
+// so nobody needs to trace them.  One 32-bit word per launch slot in pinned host memory says so: serial << 8 | keep, the serial (24
+// bits, never 0) naming the launch the word is meant for -- a slot's word left over from an earlier launch, a word not written yet
+// (0) and a word that keeps nothing or everything all read as "not cut".  The host writes it when it drops the launch's unserved
+// frames from its queue (LaunchQueue::closeStream, discard) and never otherwise, so whatever the kernel reads, and whenever, frames
+// < keep are wanted and traced in full.
+// The kernel reads the word ONCE per workgroup, where it starts: a few hundred single reads of host memory per launch.  A workgroup
+// whose own frame is cut by then serves a kept frame instead (frameServedUnderCut); one that is already running finishes its frame's
+// pool as before.  The last launch of a stream mostly starts after the caller's wait -- it queues behind the launches in flight -- so
+// that is where the gain is.  Reading the word again where a wave fetches a chunk was measured and dropped: 50 million fetches a
+// second in the headline run, and every form of it -- the word in host memory, or a copy relayed into the launch's counter block,
+// beside the pool counters or read with a clock-elected poll -- made the steady launches three to five times as long
+// (profiles/stream_cut/README.md).
+TPT_FP_HD unsigned frameCutWord(unsigned serial, unsigned keep)
+{
+    return serial << 8 | (keep & 0xffu);
+}
+// The next launch's serial: 1, 2, ... 2^24 - 1, 1, ...
+TPT_FP_HD unsigned frameCutNextSerial(unsigned serial)
+{
+    return (serial & 0xffffffu) == 0xffffffu ? 1u : (serial & 0xffffffu) + 1u;
+}
+// Frames of a launch of `pools` frames with serial `serial` that are still wanted, given the slot's word: `pools` = not cut.
+TPT_FP_HD unsigned framesKeptUnderCut(unsigned word, unsigned serial, unsigned pools)
+{
+    // (one subtraction and one comparison: word - (serial << 8) lies in 1 .. pools - 1 <= 254 exactly when the word carries this
+    //  serial and such a keep)
+    const unsigned keep = word - (serial << 8);
+    return (serial != 0u && keep - 1u < pools - 1u) ? keep : pools;
+}
+// The frame workgroup `block` serves when only frames < keep are wanted (1 <= keep <= pools): its own while that is wanted, else it
+// helps frame block % keep -- the cut frames' workgroups spread evenly over the kept ones, each of which keeps its own workgroups.
+TPT_FP_HD unsigned frameServedUnderCut(unsigned block, unsigned pools, unsigned blocks, unsigned keep)
+{
+    const unsigned own = framePoolOfBlock(block, pools, blocks);
+    return own < keep ? own : block % keep;
+}
+
 } // namespace tpt

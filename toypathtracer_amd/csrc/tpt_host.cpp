@@ -356,6 +356,9 @@ int tptInitialize(void)
     g.dRaysBatch = g.dRaysAhead + Context::kMaxSlots;
     g.dRaysStream = g.dRaysBatch + 2 * kMaxBatch;
     g.pending.n = 0;
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&g.hCut), sizeof(unsigned) * Context::kMaxSlots, hipHostMallocDefault));
+    memset(g.hCut, 0, sizeof(unsigned) * Context::kMaxSlots);
+    g.cutSerial = 0; g.cutPreset = 0; g.lastStreamRays = nullptr; g.lastStreamFrames = 0;
     if (const char* esb = getenv("TPT_STREAM_BATCH")) g.streamBatch = atoi(esb) != 0; // (default on)
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dRaysOwn), 64));
     HIPCHK(hipMemsetAsync(g.dRaysOwn, 0, 64, g.stream));
@@ -459,6 +462,9 @@ int tptShutdown(void)
     }
     if (g.hViewsStage) (void)hipHostFree(g.hViewsStage);
     g.hViewsStage = nullptr;
+    if (g.hCut) (void)hipHostFree(g.hCut); // (the device is idle: hipDeviceSynchronize above, the streams drained since)
+    g.hCut = nullptr;
+    g.lastStreamRays = nullptr; g.lastStreamFrames = 0;
     g.inited = false;
     g.updated = false;
     g.updatedW = g.updatedH = 0;

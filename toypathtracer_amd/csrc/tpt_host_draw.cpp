@@ -41,8 +41,21 @@ int LaunchQueue::discard()
 {
     if (n > 0 && !holds(PendingLaunch::STREAM))
         for (int k = 0; k < Context::kMaxOverlap; ++k) HIPCHK(hipStreamSynchronize(g.traceStream[k]));
+    cutFront();
     n = 0;
     return 0;
+}
+
+// A STREAM entry is about to be dropped with frames next .. batch - 1 unserved: nobody will blend them, so its launch -- which may
+// still be running, or not even have started -- is told to trace frames < next only (tpt_frame_pools.h: the slot's cut word, a plain
+// store to pinned host memory that the kernel polls; no stream, no queue).  next >= 1: a STREAM batch is served on push.  A launch
+// without a pool per frame (a grid too small for one) has no word and runs to its end as before.
+void LaunchQueue::cutFront()
+{
+    if (!holds(PendingLaunch::STREAM) || !g.hCut) return;
+    const PendingLaunch& F = e[0];
+    if (F.T.valid && F.T.cutSerial != 0u && F.next >= 1 && F.next < F.T.batch)
+        __atomic_store_n(g.hCut + F.T.slot, frameCutWord(F.T.cutSerial, (unsigned)F.next), __ATOMIC_RELEASE);
 }
 
 // The caller waits (tptSynchronize, tptRayCounterRead): an open STREAM batch is dropped, so that no frame traced before the wait is
@@ -50,6 +63,7 @@ int LaunchQueue::discard()
 // served.  AHEAD and ROW_SERIAL launches stay (a synchronous caller's look-ahead).
 void LaunchQueue::closeStream()
 {
+    cutFront();
     if (holds(PendingLaunch::STREAM)) n = 0;
     g.streamNext = -1;
 }

@@ -186,5 +186,27 @@ int tptTestHitSpheres(int hitSpheres, const float* rays, int* outId, float* outT
     return 0;
 }
 
+// The next launch with a pool per frame starts with its cut word already saying "frames < keep only" (tpt_frame_pools.h): every
+// workgroup then starts under the cut, whatever the timing.  The caller asks exactly `keep` frames of that launch.
+int tptTestPresetStreamCut(int keep)
+{
+    if (requireInit()) return -1;
+    if (keep < 0 || keep >= Context::kStreamBatchMax) return fail("tptTestPresetStreamCut: keep must lie in 0..7 (0: no preset)");
+    g.cutPreset = keep;
+    return 0;
+}
+
+// The per-frame ray counters of the newest STREAM launch, after a drain of the pipeline; returns its frames (0: none yet).
+int tptTestStreamFrameRays(unsigned long long* outRays, int capacity)
+{
+    if (requireInit()) return -1;
+    if (int rc = tptSynchronize()) return rc;
+    for (int k = 0; k < Context::kMaxOverlap; ++k) HIPCHK(hipStreamSynchronize(g.traceStream[k]));
+    const int n = g.lastStreamFrames < capacity ? g.lastStreamFrames : capacity;
+    if (n <= 0 || !g.lastStreamRays || !outRays) return 0;
+    HIPCHK(hipMemcpy(outRays, g.lastStreamRays, sizeof(unsigned long long) * (size_t)n, hipMemcpyDeviceToHost));
+    return n;
+}
+
 #endif // TPT_TEST_HOOKS
 } // extern "C"

@@ -698,6 +698,20 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
     const bool helpable = P.queued && pipelined && batch == 1 && !P.rowSerial && !table && !aov; // (single frames of the path-queue kernel)
     // the plain batched kernel (tptDrawDeviceBatch, STREAM launches) deals its workgroups to the frames, a pool of chunks per frame
     a.framePools = framePoolsOfLaunch(batch, P.blocks, P.queued && !P.rowSerial && !table && !aov, helpable);
+    a.cutWord = nullptr;
+    a.cutSerial = 0u;
+    T.cutSerial = 0u;
+    if (a.framePools > 0) {
+        // the launch's cut word (tpt_frame_pools.h): the slot's, not cut.  The slot's previous launch has left the queue that held it
+        // (LaunchQueue: served in full, or cut and dropped), so the host writes that launch's word no more, and whatever serial a late
+        // reader of the old launch finds here is not its own.
+        g.cutSerial = frameCutNextSerial(g.cutSerial);
+        a.cutWord = g.hCut + slot;
+        a.cutSerial = g.cutSerial;
+        T.cutSerial = g.cutSerial;
+        __atomic_store_n(g.hCut + slot, g.cutPreset > 0 ? frameCutWord(g.cutSerial, (unsigned)g.cutPreset) : 0u, __ATOMIC_RELEASE);
+        g.cutPreset = 0;
+    }
     a.helperBase = 0;
     a.helperPct = 0;
     a.gen = 0u;
@@ -1144,6 +1158,8 @@ int tptDrawDevice(float time, int frameCount, int w, int h, float* deviceTile, u
                 } else if (rc) {
                     return rc;
                 } else if (S.T.valid) {
+                    g.lastStreamRays = S.rays;
+                    g.lastStreamFrames = nBatch;
                     g.streamBatches++;
                     g.streamNext = frameCount + nBatch;
                     if ((rc = Q.push(S))) return rc;
@@ -1449,6 +1465,9 @@ int tptTimerEnd(float* outMs)
     if (int rc_ = flushShardDeferred()) return rc_;
     if (requireInit()) return -1;
     HIPCHK(hipEventRecord(g.ev1, g.stream));
+    // a wait like tptSynchronize: the open stream batch is closed FIRST -- its launch is told that its unasked frames are no longer
+    // wanted while it still runs (tpt_frame_pools.h), which after the wait below would be too late
+    g.pending.closeStream();
     if (int rc = launchTailHelpers()) return rc;
     HIPCHK(hipEventSynchronize(g.ev1));
     float ms = 0;

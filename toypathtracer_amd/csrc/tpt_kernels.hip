@@ -1870,8 +1870,10 @@ __device__ __forceinline__ int hitSpheresGroupedDeal(const SceneView& sv, bool g
 // POOLS (with BATCH alone; tptDrawDeviceBatch and STREAM launches of 2 .. 8 frames, tpt_frame_pools.h): a pool of chunks per frame of
 // the batch, a.work[4 + j] counting frame j's chunks to a.chunksPerFrame.  Workgroup b serves frame framePoolOfBlock(b, frames, grid)
 // alone -- it takes no chunk of another frame and leaves when its frame's pool is dry and its paths are done, so the workgroups of a
-// launch run dry frame after frame instead of all at once -- and counts its rays per lane, for that frame's counter.  Its own kernel
-// (tptFramePoolsKernel) for the same reason.
+// launch run dry frame after frame instead of all at once -- and counts its rays per lane, for that frame's counter.  A STREAM launch
+// whose caller waited before asking for all of its frames is cut: a workgroup that starts after that and finds its own frame unasked
+// serves an asked frame instead, for its whole life (tpt_frame_pools.h, frameServedUnderCut).  Its own kernel (tptFramePoolsKernel)
+// for the same reason.
 template <bool LDS_SCENE, bool BATCH, bool VIEWS = false, bool MOVING = false, bool AOV = false, bool MOMENTS = false, bool ADAPTIVE = false,
           bool CAMERAS = false, bool KEYS = false, bool POOLS = false>
 __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
@@ -1998,6 +2000,16 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
         ctl->globalExhausted = 0u;
     }
     if (BATCH && tid < 32) ctl->frameRays[tid] = 0u;
+    if (POOLS && tid == 0) {
+        // the frame this workgroup serves, published in frameRays[0] (the pools kernel counts its rays per lane: the array is free):
+        // its own, or -- the launch was cut before this workgroup started and its own frame is no longer wanted -- one of the kept
+        // frames, for its whole life (tpt_frame_pools.h).  One relaxed system-scope load of the launch's cut word in pinned host
+        // memory per workgroup, through a global pointer; nothing is read again later (tpt_frame_pools.h says why).
+        typedef const __attribute__((address_space(1))) unsigned* GlobalWord;
+        const unsigned pools = (unsigned)a.batchFrames;
+        const unsigned word = __hip_atomic_load((GlobalWord)a.cutWord, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        ctl->frameRays[0] = frameServedUnderCut(blockIdx.x, pools, gridDim.x, framesKeptUnderCut(word, a.cutSerial, pools));
+    }
     __syncthreads();
 
     const FrameConsts& fc = a.fc;
@@ -2016,9 +2028,9 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     int chunkFrame = 0;              // batched launch: the frame of the batch that pool belongs to
     bool noMoreChunks = false;
     unsigned myRays = 0;
-    // POOLS: the frame of the batch this workgroup serves (tpt_frame_pools.h) -- wave-uniform, made where it is used (once per chunk,
-    // in place of the shared pool's division) instead of being held across the loop
-    auto poolFrame = [&]() { return framePoolOfBlock(blockIdx.x, (unsigned)uniformHere(a.batchFrames), (unsigned)uniformHere((int)gridDim.x)); };
+    // POOLS: the frame of the batch this workgroup serves (tpt_frame_pools.h; published above) -- wave-uniform, read where it is used
+    // (once per chunk, in place of the shared pool's division) instead of being held across the loop
+    auto poolFrame = [&]() { return (unsigned)__builtin_amdgcn_readfirstlane((int)ctl->frameRays[0]); };
 #if defined(TPT_STATS)
     const unsigned long long qT0 = wall_clock64();
     unsigned qSteps = 0, qBatches = 0, qIdle = 0;
@@ -2151,8 +2163,8 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
                     [[maybe_unused]] const int myFrame = POOLS ? (int)poolFrame() : 0;
                     if (lane == 0) {
                         atomicAdd(&ctl->poolTotal, 64u); // optimistic: keeps "pixels left" non-zero while the fetch is in flight
-                        // (POOLS: the next chunk of this workgroup's frame.  It takes chunks of that frame only: "exhausted" below then
-                        //  means the frame's own pool, and the workgroup leaves while the other frames' workgroups run on)
+                        // (POOLS: the next chunk of the frame this workgroup serves.  It takes chunks of that frame only: "exhausted"
+                        //  below then means that frame's pool, and the workgroup leaves while the other frames' workgroups run on)
                         c = (int)atomicAdd(POOLS ? &a.work[kFramePoolBase + myFrame] : &a.work[0], 1u);
                     }
                     c = __builtin_amdgcn_readfirstlane(c);
