@@ -209,6 +209,29 @@ TPT_API int tptDenoiseDevice(int screenWidth, int screenHeight, const float* dev
  * refused: deviceMoments NULL, or overlapping the tile or a given plane.  A refused call writes nothing. */
 TPT_API int tptDrawDeviceMoments(float time, int frameCount, int screenWidth, int screenHeight, float* deviceTile,
                                  float* deviceAlbedo, float* deviceNormalDepth, float* deviceMoments, unsigned testFlags);
+/* Progressive frames with averaged guides: nFrames consecutive frames of the scene and camera of the last tptUpdate, up to 32 per
+ * launch, folded into the four planes tptDenoiseDeviceVariance reads.  deviceTile and deviceMoments are required; deviceAlbedo and
+ * deviceNormalDepth may each be NULL; all four are h*w*4 floats in device memory.  For j = 0 .. nFrames-1, in order, the call is byte
+ * for byte, and ray for ray, this sequence:
+ *   tptDrawDeviceMoments(time, firstFrame + j, w, h, deviceTile, A_j, ND_j, deviceMoments, testFlags);
+ *   deviceAlbedo      = deviceAlbedo      * lerp_j + A_j  * (1 - lerp_j)      (all four channels)
+ *   deviceNormalDepth = deviceNormalDepth * lerp_j + ND_j * (1 - lerp_j)      (all four channels)
+ * A_j and ND_j are scratch planes; lerp_j is the factor tptDrawDevice blends frame firstFrame + j's tile with under testFlags
+ * (Test.cpp:272-276).  The blend is the tile's: binary32, in the order written, no FMA, 1 - lerp_j formed in binary32.  The tile's alpha
+ * and the .w of the moments are untouched.  Without TPT_FLAG_PROGRESSIVE lerp is 0 and the planes end as the last frame's.  As for the
+ * tile, the planes must hold finite values before the first call (a caller zeroes them once).  Afterwards the four planes are the
+ * inputs of tptDenoiseDeviceVariance with samples = spp * (firstFrame + nFrames) (progressive; spp otherwise).
+ * The scene and camera are those of the last tptUpdate and are unchanged afterwards; frames traced ahead and stream-batch planes are
+ * dropped first; the ray counter advances by the frames' rays, exactly once.  Asynchronous on the context stream, ordered behind
+ * earlier work there; the launches of one call may overlap as tptDrawDeviceAnimationMoments' do.  Frames per launch: the most, up to
+ * 32, whose staging (colour, moments and each given guide plane, h*w*16 bytes each per frame) stays within 4096 MiB -- a large frame
+ * lowers the count and is never refused for it; scenes of 8 spheres or fewer, or of 256 or more, are traced a frame per launch.
+ * Refused (non-zero, tptGetLastError names the function, nothing enqueued, no byte written): everything tptDrawDeviceMoments refuses;
+ * nFrames < 1; firstFrame < 0 or a last frame number that does not fit an int; any flag bit other than TPT_FLAG_PROGRESSIVE
+ * (TPT_FLAG_ANIMATE belongs to tptDrawDeviceAnimationMoments); any two of the four planes sharing a byte; a scene with more lights
+ * than the path-queue kernel takes. */
+TPT_API int tptDrawDeviceBatchMoments(float time, int firstFrame, int nFrames, int screenWidth, int screenHeight, float* deviceTile,
+                                      float* deviceMoments, float* deviceAlbedo, float* deviceNormalDepth, unsigned testFlags);
 /* The frames of an ANIMATED clip, each with the planes the denoising chain reads (tptTemporalAccumulateDevice, tptDenoiseDeviceVariance),
  * up to 32 per launch: tptDrawDeviceAnimation with tptDrawDeviceMoments' outputs.  Frame j (0 <= j < nFrames) is bit-identical to
  *   tptUpdate(times[j], firstFrame + j, w, h, testFlags);
@@ -327,7 +350,7 @@ TPT_API int tptDrawDeviceKeyframeClip(int firstFrame, int nFrames, const float* 
  * The step in il's numerator makes each iteration twice as strict as the one before; the carried variance alone let 5 iterations blur
  * a 64-frame image past its own noise.  The guides should describe the same samples as the colour: a progressive
  * caller averages the albedo and normal / depth planes over its frames as the tile is averaged (one frame's 4-spp planes beside
- * a 256-sample colour mis-demodulate and mis-guide the edges).  Asynchronous on the context stream; needs
+ * a 256-sample colour mis-demodulate and mis-guide the edges): tptDrawDeviceBatchMoments does that, and states the blend.  Asynchronous on the context stream; needs
  * tptInitialize only and leaves every other state alone.  The inputs are never written.  Refused (non-zero, tptGetLastError, nothing
  * enqueued, deviceOut untouched): tptDenoiseDevice's refusals (sigmaNormal, sigmaDepth, iterations, flags, sizes, overlaps), and
  * deviceMoments NULL or overlapping deviceOut, samples not finite or below 1, sigmaLuminance not in (0, 1e6]. */

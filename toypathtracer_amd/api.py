@@ -39,7 +39,7 @@ C_ABI_SYMBOLS = [
     "tptSetSamplesPerPixel", "tptSetConfig", "tptSetSeedMode", "tptSetFoldMode", "tptSetScene", "tptSetCamera", "tptSetStream",
     "tptSetRowShard", "tptLocalRowCount", "tptLocalRowToGlobal", "tptDrawDevice", "tptRayCounterRead", "tptSetRayCounter", "tptSetFrameOverlap", "tptDisplayRGBA8", "tptKernelTimingBegin", "tptKernelTimingEnd",
     "tptSynchronize", "tptTimerBegin", "tptTimerEnd", "tptSetKernelVariant",
-    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceAnimationMoments", "tptDrawDeviceCameraClip", "tptDrawDeviceKeyframeClip", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptObjectPlaneDevice", "tptObjectMotionTable", "tptTemporalAccumulateObjectsDevice", "tptDenoiseClipDevice", "tptMotionVectorsDevice", "tptRectifyHistoryDevice", "tptDrawDeviceAdaptive", "tptAdaptiveSamplesDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
+    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceBatchMoments", "tptDrawDeviceAnimationMoments", "tptDrawDeviceCameraClip", "tptDrawDeviceKeyframeClip", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptObjectPlaneDevice", "tptObjectMotionTable", "tptTemporalAccumulateObjectsDevice", "tptDenoiseClipDevice", "tptMotionVectorsDevice", "tptRectifyHistoryDevice", "tptDrawDeviceAdaptive", "tptAdaptiveSamplesDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
 ]
 # include/tpt_test_hooks.h: exported by the second build (libtoypathtracer_hip_hooks.so) only
 HOOK_SYMBOLS = ["tptTestMath", "tptTestMathExhaustive", "tptTestHitSpheres", "tptTestMatrixFilter", "tptTestGroupFilter", "tptTestSetDealCapacities", "tptDebugStats", "tptDebugChunkOrder", "tptTestPresetStreamCut", "tptTestStreamFrameRays"]
@@ -99,7 +99,7 @@ def _bind(path, hooks):
         "tptSetRayCounter": [p], "tptSetTileMirror": [p, p], "tptSetFrameOverlap": [i], "tptDisplayRGBA8": [p, i, i, p], "tptKernelTimingBegin": [i],
         "tptKernelTimingEnd": [C.POINTER(f), C.POINTER(i)],
         "tptSynchronize": [], "tptTimerBegin": [], "tptTimerEnd": [C.POINTER(f)], "tptSetKernelVariant": [i, i, i],
-        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDrawDeviceAnimationMoments": [i, i, p, i, i] + [p] * 7 + [u], "tptDrawDeviceCameraClip": [i, i, p, p, i, i] + [p] * 8 + [u], "tptDrawDeviceKeyframeClip": [i, i, p, i, p, p, i, i] + [p] * 9 + [u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptObjectPlaneDevice": [i, p, p, i, i, p, u], "tptObjectMotionTable": [f, f, u, p, i], "tptTemporalAccumulateObjectsDevice": [i, i] + [p] * 14 + [f] * 4 + [p, p, p, i], "tptDenoiseClipDevice": [C.POINTER(ClipDenoiseArgs)], "tptMotionVectorsDevice": [C.POINTER(MotionVectorsArgs)], "tptRectifyHistoryDevice": [i, i] + [p] * 7 + [i, f], "tptDrawDeviceAdaptive": [f, i, i, i, p, p, p, p, p, u], "tptAdaptiveSamplesDevice": [i, i, p, f, i, i, p, p, p], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
+        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDrawDeviceBatchMoments": [f, i, i, i, i, p, p, p, p, u], "tptDrawDeviceAnimationMoments": [i, i, p, i, i] + [p] * 7 + [u], "tptDrawDeviceCameraClip": [i, i, p, p, i, i] + [p] * 8 + [u], "tptDrawDeviceKeyframeClip": [i, i, p, i, p, p, i, i] + [p] * 9 + [u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptObjectPlaneDevice": [i, p, p, i, i, p, u], "tptObjectMotionTable": [f, f, u, p, i], "tptTemporalAccumulateObjectsDevice": [i, i] + [p] * 14 + [f] * 4 + [p, p, p, i], "tptDenoiseClipDevice": [C.POINTER(ClipDenoiseArgs)], "tptMotionVectorsDevice": [C.POINTER(MotionVectorsArgs)], "tptRectifyHistoryDevice": [i, i] + [p] * 7 + [i, f], "tptDrawDeviceAdaptive": [f, i, i, i, p, p, p, p, p, u], "tptAdaptiveSamplesDevice": [i, i, p, f, i, i, p, p, p], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
     }
     if hooks:
         sigs.update({"tptDebugStats": [p, i], "tptDebugChunkOrder": [p, p, i], "tptTestMath": [i, p, p, p, i], "tptTestMathExhaustive": [i, u, u, p, p],
@@ -522,6 +522,24 @@ def draw_device_moments(time, frame, w, h, tile_ptr, moments_ptr, flags, albedo_
     _chk(load_library().tptDrawDeviceMoments(time, frame, w, h, C.c_void_p(tile_ptr), C.c_void_p(albedo_ptr) if albedo_ptr else None,
                                              C.c_void_p(normal_depth_ptr) if normal_depth_ptr else None, C.c_void_p(moments_ptr), flags),
          "tptDrawDeviceMoments")
+
+
+def draw_device_batch_moments(time, first_frame, n_frames, w, h, tile_ptr, moments_ptr, flags, albedo_ptr=None, normal_depth_ptr=None):
+    """n_frames consecutive frames (first_frame ...) of the scene and camera of the last UpdateTest, up to 32 per launch, folded into the
+    four planes denoise_device_variance reads: the same bits and ray counts as n_frames draw_device_moments calls on tile_ptr and
+    moments_ptr, with each frame's guide planes blended into albedo_ptr / normal_depth_ptr (None = not wanted) with the tile's lerp factor,
+    all four channels: a progressive still ends with guides averaged as the tile is.  flags: kFlagProgressive or 0.  Afterwards
+    samples = moment_samples(spp, first_frame + n_frames - 1, flags).  Ordered on the context's stream like the tile."""
+    _positive_ints(("w", w), ("h", h), ("n_frames", n_frames))
+    if not isinstance(first_frame, (int, np.integer)) or isinstance(first_frame, bool) or first_frame < 0 or first_frame + n_frames - 1 > 0x7fffffff:
+        raise ValueError("first_frame: an int >= 0 with first_frame + n_frames - 1 < 2**31 expected, got %r" % (first_frame,))
+    _pointers(("tile_ptr", tile_ptr), ("moments_ptr", moments_ptr), ("albedo_ptr", albedo_ptr), ("normal_depth_ptr", normal_depth_ptr))
+    if not tile_ptr or not moments_ptr:
+        raise ValueError("tile_ptr, moments_ptr: device buffers are required")
+    _chk(load_library().tptDrawDeviceBatchMoments(time, int(first_frame), n_frames, w, h, C.c_void_p(tile_ptr), C.c_void_p(moments_ptr),
+                                                  C.c_void_p(albedo_ptr) if albedo_ptr else None,
+                                                  C.c_void_p(normal_depth_ptr) if normal_depth_ptr else None, int(flags)),
+         "tptDrawDeviceBatchMoments")
 
 
 def draw_device_animation_moments(times, first_frame, w, h, tile_ptr, moments_ptr, flags, images_ptr=None, albedo_ptr=None,

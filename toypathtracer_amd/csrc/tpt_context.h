@@ -261,6 +261,12 @@ struct Context {
     // the previous launch on half h.  The first launch of a call waits for the whole context stream, as every other AOV launch does.
     hipEvent_t evClip[2] = {nullptr, nullptr};
     unsigned clipSeq = 0;
+    // tptDrawDeviceBatchMoments: where a launch's frames leave their albedo and normal / depth planes for the fold behind it (the caller's
+    // planes are running means, not per-frame buffers).  Two halves of guideStageBytes / 2, taken by the launches as they take the halves of
+    // dMoments; in a half the albedo planes of the launch's n frames, then its normal / depth planes (a plane the caller left out takes no
+    // room).  Grown on demand (after a drain), kept until tptShutdown.
+    f4* dGuideStage = nullptr;
+    size_t guideStageBytes = 0;
     // tptDrawDeviceKeyframeClip's object planes: one {centre, r^2} array per frame of a LAUNCH (SceneView::sph4's records, the moved spheres
     // at the frame's centres) for tptObjectPlaneKernel, copied on the context stream out of a pinned twin.  Two halves of keySphBytes each,
     // taken in turn (keySphSeq), so that the host fills one launch's arrays while the previous launch's copy is still queued: at most
@@ -457,6 +463,7 @@ struct AovPlanes {
     bool moments = false; // tptDrawDeviceMoments: tptTraceMomentsKernel, into Context::dMoments
     bool continues = false; // tptDrawDeviceAnimationMoments: a later launch of the call (Context::evClip)
     const int32_t* sampleCounts = nullptr; // tptDrawDeviceAdaptive (with moments): the caller's count per pixel, tptTraceAdaptiveKernel
+    const char* entry = nullptr; // whose launch this is, for a refusal, where the tables and planes do not say it (tptDrawDeviceBatchMoments)
 };
 int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long long* frameRays, TraceTicket& T, int batch = 1, int rayStride = 0,
                  const BatchTable* table = nullptr, const AovPlanes* aov = nullptr);

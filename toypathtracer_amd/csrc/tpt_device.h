@@ -215,6 +215,23 @@ hipError_t tptLaunchResolveBatch(float* tile, const tpt::f4* frameColour, int nP
                                  float* mirror, unsigned long long* rayCounter, unsigned long long* counterOut, hipStream_t stream);
 hipError_t tptLaunchResolve(float* tile, const tpt::f4* frameColour, int nPixels, float lerpFac, float* mirror,
                             unsigned long long* rayCounter, unsigned long long* counterOut, const unsigned long long* frameRays, hipStream_t stream);
+// tptDrawDeviceBatchMoments' blends: one launch folds the nFrames (1..32) staged planes of a trace launch, nPixels f4 apart, into the
+// caller's four running means in frame order with lerp.v[j] -- tile.xyz and moments.xyz (.w kept), all four channels of albedo and
+// normalDepth (either may be null, its staging then unused) -- and adds frameRays[0 .. nFrames - 1] to *totalRays (frameRays null: the
+// trace kernel has counted into the total itself).  TPT_FOLD_BLOCKS_PER_PLANE: the workgroups it stops at per plane, 256 pixels a pass
+// each.  Weak for the same reason as tptLaunchDenoise.
+#define TPT_FOLD_BLOCKS_PER_PLANE 128
+// Frames per launch of tptDrawDeviceBatchMoments: the most, up to 32, whose staging -- `planes` planes of planeBytes per frame: colour,
+// moments and each guide plane that is given -- stays within the clip draws' 4096 MiB per launch; never fewer than one.
+inline int tptFoldFramesPerLaunch(size_t planeBytes, int planes)
+{
+    const size_t perFrame = planeBytes * (size_t)planes, m = perFrame ? (4ull << 30) / perFrame : 32;
+    return m > 32 ? 32 : (m < 1 ? 1 : (int)m);
+}
+__attribute__((weak)) hipError_t tptLaunchFoldBatch(float* tile, float* moments, float* albedo, float* normalDepth, const tpt::f4* stagedColour,
+                                                    const tpt::f4* stagedMoments, const tpt::f4* stagedAlbedo,
+                                                    const tpt::f4* stagedNormalDepth, int nPixels, int nFrames, const tptLerpTable& lerp,
+                                                    const unsigned long long* frameRays, unsigned long long* totalRays, hipStream_t stream);
 hipError_t tptLaunchMathTest(int op, const float* a, const float* b, float* out, int n, hipStream_t stream);
 hipError_t tptLaunchMathExhaustive(int op, unsigned lo, unsigned hi, unsigned long long* nBad, unsigned* firstBad, hipStream_t stream);
 hipError_t tptLaunchMatrixFilterTest(const tpt::KernelArgs& a, const float* rays, unsigned long long* outMask, int* outId, float* outT, int n, hipStream_t stream);

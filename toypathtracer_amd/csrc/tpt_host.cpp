@@ -440,6 +440,8 @@ int tptShutdown(void)
         if (e) { (void)hipEventDestroy(e); e = nullptr; }
     (void)hipFree(g.dMoments); g.dMoments = nullptr;
     g.momentsBytes = 0;
+    (void)hipFree(g.dGuideStage); g.dGuideStage = nullptr;
+    g.guideStageBytes = 0;
     (void)hipFree(g.dKeySph); g.dKeySph = nullptr;
     if (g.hKeySph) (void)hipHostFree(g.hKeySph);
     g.hKeySph = nullptr;

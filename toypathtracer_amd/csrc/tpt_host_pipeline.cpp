@@ -604,6 +604,7 @@ int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long
     P.entry = keyCentres ? "tptDrawDeviceKeyframeClip" : (viewCams && centres ? "tptDrawDeviceCameraClip" : (viewCams ? "tptDrawDeviceViews" :
               (centres ? (aov ? "tptDrawDeviceAnimationMoments" : "tptDrawDeviceAnimation") :
               (aov ? (aov->sampleCounts ? "tptDrawDeviceAdaptive" : (aov->moments ? "tptDrawDeviceMoments" : "tptDrawDeviceAov")) : (batch > 1 ? "tptDrawDeviceBatch" : "tptDrawDevice")))));
+    if (aov && aov->entry) P.entry = aov->entry;
     if ((rc = chooseKernel(P))) return rc;
     if (viewCams && !P.queued)
         return refuse("tptDrawDeviceViews: needs the path-queue kernel (per-pixel seeds, recursive fold, two-phase HitSpheres, at most 2047 spp)");
@@ -1364,6 +1365,93 @@ int tptDrawDeviceMoments(float time, int frameCount, int w, int h, float* device
     if (!T.valid) return 0;
     // (behind the tile's blend, so behind the trace; .xyz blended, .w kept; no ray count: the tile's blend has taken it)
     HIPCHK(tptLaunchResolve(deviceMoments, g.dMoments, T.nPixels, T.lerpFac, nullptr, g.dRays, nullptr, nullptr, g.stream));
+    return 0;
+}
+
+// nFrames tptDrawDeviceMoments calls on the scene and camera of the last tptUpdate, the guide planes averaged as the tile is: the same
+// bits, the same ray counts (include/tpt_hip.h states the sequence).  On a flat scene of more than 8 spheres the camera-clip path traces
+// up to kMaxBatch frames per launch -- the camera table repeats the context's camera, the centres table the scene's own centres, so the
+// kernel reads the numbers tptTraceMomentsKernel reads --; every other scene takes tptDrawDeviceMoments' kernel, a frame per launch.
+// Either way the frames' colour (the slot's buffer), moments (Context::dMoments) and guide planes (Context::dGuideStage) are staged a
+// plane per frame, and ONE launch of the fold kernel behind each trace launch blends them into the caller's four planes; the launches of
+// a call alternate between the halves of the staging as tptDrawDeviceAnimationMoments' do (Context::evClip).
+int tptDrawDeviceBatchMoments(float time, int firstFrame, int nFrames, int w, int h, float* deviceTile, float* deviceMoments,
+                              float* deviceAlbedo, float* deviceNormalDepth, unsigned testFlags)
+{
+    (void)time; // (the scene state is that of the last tptUpdate, as for tptDrawDevice)
+    const std::string fn = "tptDrawDeviceBatchMoments";
+    if (int rc_ = flushShardDeferred()) return rc_; // (see tptDrawDevice)
+    if (requireInit()) return -1;
+    if (nFrames < 1) return fail(fn + ": nFrames must be at least 1");
+    if (firstFrame < 0 || firstFrame > 0x7fffffff - (nFrames - 1)) return fail(fn + ": firstFrame .. firstFrame + nFrames - 1 must be frame numbers 0 .. 2^31 - 1");
+    if (!deviceTile || !deviceMoments || w <= 0 || h <= 0) return fail(fn + ": bad arguments (deviceTile, deviceMoments, size)");
+    if (testFlags & ~(unsigned)TPT_FLAG_PROGRESSIVE)
+        return fail(fn + ": TPT_FLAG_PROGRESSIVE is the only flag (nothing moves between the frames: TPT_FLAG_ANIMATE belongs to tptDrawDeviceAnimationMoments)");
+    int rc = checkPathQueueDraw(fn.c_str(), "moments are", w, h, kQueueKernel | kQueueSpp, [&] {
+        const void* const planes[4] = {deviceTile, deviceMoments, deviceAlbedo, deviceNormalDepth};
+        for (int i = 0; i < 4; ++i)
+            for (int k = i + 1; k < 4; ++k)
+                if (planes[i] && overlapsAny(planes[i], {planes[k]}, (uintptr_t)w * (uintptr_t)h * 16u))
+                    return fail(fn + ": two of the tile, the moments and the guide planes overlap");
+        return 0;
+    });
+    if (rc) return rc;
+    if (!tptLaunchFoldBatch) return fail(fn + ": this build has no fold kernel");
+    if ((rc = g.pending.discard())) return rc;
+    const int nGuides = (deviceAlbedo ? 1 : 0) + (deviceNormalDepth ? 1 : 0);
+    const size_t nPixels = (size_t)h * (size_t)w, planeBytes = nPixels * sizeof(f4);
+    const bool clipPath = g.spheres.size() > 8 && g.spheres.size() < TPT_GROUP_MIN_SPHERES;
+    const int perLaunch = clipPath ? tptFoldFramesPerLaunch(planeBytes, 2 + nGuides) : 1;
+    // the guide staging: two halves of the largest launch's planes
+    const size_t half = planeBytes * (size_t)nGuides * (size_t)(nFrames < perLaunch ? nFrames : perLaunch);
+    if (2 * half > g.guideStageBytes) {
+        if ((rc = syncAllStreams())) return rc; // (an earlier call's launches and folds may still use the old staging)
+        (void)hipFree(g.dGuideStage);
+        g.dGuideStage = nullptr;
+        g.guideStageBytes = 0;
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dGuideStage), 2 * half));
+        g.guideStageBytes = 2 * half;
+    }
+    CameraPOD cams[kMaxBatch];
+    f4 centres[2 * kMaxBatch];
+    BatchTable table;
+    if (clipPath) { // what does not change from frame to frame, as the camera-clip kernel's tables
+        const SpherePOD s1 = g.spheres[1], s8 = g.spheres[8];
+        for (int j = 0; j < kMaxBatch; ++j) {
+            cams[j] = g.cam;
+            centres[2 * j] = f4{s1.cx, s1.cy, s1.cz, 0.0f};
+            centres[2 * j + 1] = f4{s8.cx, s8.cy, s8.cz, 0.0f};
+        }
+        table.cams = cams;
+        table.centres = centres;
+    }
+    for (int f = 0; f < nFrames; f += perLaunch) {
+        const int n = nFrames - f < perLaunch ? nFrames - f : perLaunch;
+        // the launch's half of the guide staging: the one enqueueTrace gives it of the sums and the moments
+        f4* const stage = g.dGuideStage + (clipPath ? (size_t)(g.clipSeq & 1u) * (g.guideStageBytes / (2 * sizeof(f4))) : 0);
+        TraceTicket T;
+        AovPlanes aov;
+        aov.albedo = deviceAlbedo ? stage : nullptr;
+        aov.normalDepth = deviceNormalDepth ? stage + (deviceAlbedo ? (size_t)n * nPixels : 0) : nullptr;
+        aov.moments = true;
+        aov.continues = f > 0;
+        aov.entry = "tptDrawDeviceBatchMoments";
+        if ((rc = clipPath ? enqueueTrace(firstFrame + f, w, h, testFlags, nullptr, T, n, 1, &table, &aov)
+                           : enqueueTrace(firstFrame + f, w, h, testFlags, nullptr, T, 1, 0, nullptr, &aov)))
+            return rc;
+        if (!T.valid) continue;
+        tptLerpTable lerp = {};
+        for (int j = 0; j < n; ++j)
+            lerp.v[j] = makeFrameConsts(g.cam, w, h, g.spp, firstFrame + f + j, testFlags, g.seedMode, g.config, g.animateSmoothing).lerpFac;
+        // the fold, behind the trace on the context stream; the clip path's frames have counted their rays apart (the slot's counters)
+        if (T.pipelined) HIPCHK(hipStreamWaitEvent(g.stream, g.evTrace[T.slot], 0));
+        HIPCHK(tptLaunchFoldBatch(deviceTile, deviceMoments, deviceAlbedo, deviceNormalDepth, T.colour, T.moments, aov.albedo, aov.normalDepth,
+                                  T.nPixels, n, lerp, clipPath ? g.views[T.slot].rays : nullptr, g.dRays, g.stream));
+        if (T.pipelined) { // (what enqueueResolve records: the slot's colour plane and counters are free again behind this fold)
+            HIPCHK(hipEventRecord(g.evResolve[T.slot], g.stream));
+            g.resolveRecorded[T.slot] = true;
+        }
+    }
     return 0;
 }
 

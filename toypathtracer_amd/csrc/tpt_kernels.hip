@@ -114,6 +114,72 @@ __global__ void __launch_bounds__(256) tptResolveBatchKernel(float* __restrict__
     }
 }
 
+// The blends of tptDrawDeviceBatchMoments (include/tpt_hip.h states them): what tptResolveBatchKernel does for the tile, for four running
+// means at once -- the tile, the moments (.xyz blended, .w kept) and the two guide planes (all four channels) -- nFrames blendPixel steps
+// per value in frame order over the launch's staged planes, nPixels apart.  HBM-bound: (4 nFrames + 4) x 16 B read and 64 B written per
+// pixel.  blockIdx.y is the plane, so a lane folds ONE plane of a pixel: the four planes' independence is spread over workgroups, the
+// frames' over the unrolled loads (4 staged values and the running value in flight before the first blend, 5 x 16 B a lane), and the
+// kernel stays within the 32 VGPRs a SIMD has left beside four 120-VGPR trace waves -- it lands on CUs full of them (see
+// tptResolveKernel).  Addresses are a uniform base and a 32-bit lane offset.  A plane the caller left out (null) costs its workgroups
+// one branch.  The launch's per-frame ray counts (null: the trace kernel has counted into the total itself) are added to the total once.
+// (one plane of the fold: KEEP_W, the tile and the moments, blends .xyz and leaves .w as it is; the guides blend all four channels)
+template <bool KEEP_W>
+__device__ __forceinline__ f4 blendPlane(f4 prev, f4 col, float lerpFac)
+{
+    const f3 r = blendPixel(mk3(prev.x, prev.y, prev.z), mk3(col.x, col.y, col.z), lerpFac);
+    f4 v;
+    v.x = r.x; v.y = r.y; v.z = r.z;
+    v.w = KEEP_W ? prev.w : prev.w * lerpFac + col.w * (1 - lerpFac); // (blendPixel's arithmetic for the fourth channel)
+    return v;
+}
+template <bool KEEP_W>
+__device__ __forceinline__ void foldPlane(f4* __restrict__ dstPlane, const char* __restrict__ src, unsigned nPixels, int nFrames, const tptLerpTable& lerp)
+{
+    char* const dst = reinterpret_cast<char*>(dstPlane);
+    const size_t plane = (size_t)nPixels * sizeof(f4);
+    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < nPixels; i += gridDim.x * 256u) {
+        const unsigned at = i * (unsigned)sizeof(f4); // (nPixels <= 2^26: the launcher)
+        f4 r = *reinterpret_cast<const f4*>(dst + at);
+        const char* s = src;
+        int j = 0;
+        for (; j + 4 <= nFrames; j += 4) {
+            const f4 c0 = *reinterpret_cast<const f4*>(s + at), c1 = *reinterpret_cast<const f4*>(s + plane + at);
+            const f4 c2 = *reinterpret_cast<const f4*>(s + 2 * plane + at), c3 = *reinterpret_cast<const f4*>(s + 3 * plane + at);
+            s += 4 * plane;
+            r = blendPlane<KEEP_W>(r, c0, lerp.v[j]);
+            r = blendPlane<KEEP_W>(r, c1, lerp.v[j + 1]);
+            r = blendPlane<KEEP_W>(r, c2, lerp.v[j + 2]);
+            r = blendPlane<KEEP_W>(r, c3, lerp.v[j + 3]);
+        }
+        for (; j < nFrames; ++j) {
+            const f4 c = *reinterpret_cast<const f4*>(s + at);
+            s += plane;
+            r = blendPlane<KEEP_W>(r, c, lerp.v[j]);
+        }
+        *reinterpret_cast<f4*>(dst + at) = r;
+    }
+}
+__global__ void __launch_bounds__(256) tptFoldBatchKernel(f4* __restrict__ tile, f4* __restrict__ moments, f4* __restrict__ albedo,
+                                                          f4* __restrict__ normalDepth, const f4* __restrict__ sColour,
+                                                          const f4* __restrict__ sMoments, const f4* __restrict__ sAlbedo,
+                                                          const f4* __restrict__ sNormalDepth, int nPixels, int nFrames, tptLerpTable lerp,
+                                                          const unsigned long long* __restrict__ frameRays, int nRays,
+                                                          unsigned long long* totalRays)
+{
+    __builtin_amdgcn_s_setprio(3); // see tptResolveKernel
+    const unsigned p = blockIdx.y;
+    if (blockIdx.x == 0 && p == 0 && threadIdx.x == 0 && frameRays) {
+        unsigned long long rays = 0;
+        for (int j = 0; j < nRays; ++j) rays += frameRays[j];
+        atomicAdd(totalRays, rays);
+    }
+    f4* const dst = p == 0 ? tile : (p == 1 ? moments : (p == 2 ? albedo : normalDepth));
+    const char* const src = reinterpret_cast<const char*>(p == 0 ? sColour : (p == 1 ? sMoments : (p == 2 ? sAlbedo : sNormalDepth)));
+    if (!dst) return;
+    if (p < 2) foldPlane<true>(dst, src, (unsigned)nPixels, nFrames, lerp);
+    else foldPlane<false>(dst, src, (unsigned)nPixels, nFrames, lerp);
+}
+
 // The blend of tptDrawDeviceAdaptive (include/tpt_hip.h states it): weighted by samples, not by frame number.  The pixel's running
 // sample count S travels in moments.w; this frame's n comes from the caller's plane, clamped as the trace kernel clamps it.  A pixel
 // with n == 0 was not traced -- its entries of `colour` and `staged` were never written -- and is left alone.  lerp = S / (S + n), an
@@ -3047,6 +3113,23 @@ hipError_t tptLaunchResolveBatch(float* tile, const f4* frameColour, int nPixels
     if (nPixels <= 0) return hipSuccess;
     hipLaunchKernelGGL(tptResolveBatchKernel, dim3(tptResolveBlocks(nPixels)), dim3(256), 0, stream, tile, frameColour, nPixels, planeStride, nFrames, lerp,
                        reinterpret_cast<f4*>(mirror), rayCounter, counterOut);
+    return hipGetLastError();
+}
+
+// Workgroups of a fold launch per plane: one per 256 pixels up to TPT_FOLD_BLOCKS_PER_PLANE, grid-stride beyond -- with the four planes
+// the 512 workgroups the blend launches stop at (tptResolveBlocks).
+hipError_t tptLaunchFoldBatch(float* tile, float* moments, float* albedo, float* normalDepth, const f4* stagedColour, const f4* stagedMoments,
+                              const f4* stagedAlbedo, const f4* stagedNormalDepth, int nPixels, int nFrames, const tptLerpTable& lerp,
+                              const unsigned long long* frameRays, unsigned long long* totalRays, hipStream_t stream)
+{
+    if (nPixels <= 0) return hipSuccess;
+    if (nFrames < 1 || nFrames > 32 || nPixels > (1 << 26) || !tile || !moments || !stagedColour || !stagedMoments || (albedo && !stagedAlbedo) ||
+        (normalDepth && !stagedNormalDepth))
+        return hipErrorInvalidValue;
+    const int need = (nPixels + 255) / 256, perPlane = need < TPT_FOLD_BLOCKS_PER_PLANE ? need : TPT_FOLD_BLOCKS_PER_PLANE;
+    hipLaunchKernelGGL(tptFoldBatchKernel, dim3(perPlane, 4), dim3(256), 0, stream, reinterpret_cast<f4*>(tile), reinterpret_cast<f4*>(moments),
+                       reinterpret_cast<f4*>(albedo), reinterpret_cast<f4*>(normalDepth), stagedColour, stagedMoments, stagedAlbedo,
+                       stagedNormalDepth, nPixels, nFrames, lerp, frameRays, frameRays ? nFrames : 0, totalRays);
     return hipGetLastError();
 }
 
