@@ -655,6 +655,49 @@ TPT_API int tptMotionVectorsDevice(const tptMotionVectorsArgs* args);
 TPT_API int tptRectifyHistoryDevice(int w, int h, const float* deviceColour, const float* deviceMoments,
                                     const float* deviceAccColour, const float* deviceAccMoments, float* deviceOutColour,
                                     float* deviceOutMoments, float* deviceOutVariance, int radius, float gamma);
+/* SPATIAL VARIANCE ESTIMATE: the luminance variance of a pixel that has too few samples for its own moments to mean anything, taken
+ * from its neighbours' first and second moments -- SVGF's fallback.  At 1 spp a frame's moments are {l, l*l}, so m.y - m.x*m.x is
+ * exactly 0 and tptDenoiseDeviceVariance's luminance weights collapse; the same holds wherever a temporal pass wrote N = 1 at 1 spp
+ * (every pixel of frame 0 and after a cut, every view of a 1-spp multi-view stack).  This call sits between the planes the chain has
+ * and the filter it has and changes neither.  Every pointer is nFrames consecutive device planes of h*w*4 floats, plane j frame j's,
+ * row-major like the tile (row 0 at the bottom), laid out as the clip draws and tptDenoiseClipDevice lay them out; nFrames == 1 is the
+ * per-frame form.
+ *   deviceFrameMoments      any moments plane of the chain: tptDrawDeviceMoments' own (or a stack of them from the clip draws; .w is
+ *                           whatever the caller left there), or the deviceOutMoments of either temporal pass or of
+ *                           tptRectifyHistoryDevice (.w = the history length N)
+ *   deviceFrameNormalDepth  the normal / depth planes (normal in .xyz, depth in .w), or NULL: then both sigmas must be 0
+ *   deviceFrameOutVariance  a variance plane in the temporal pass's form, {0, v/N, 0, N}: tptDenoiseDeviceVariance's deviceMoments with
+ *                           samples = samplesPerFrame, or (spatial-only mode) tptDenoiseClipDevice's deviceFrameMoments
+ *   samplesPerFrame         the samples per pixel of one traced frame;  minSamples: a pixel is estimated while samplesPerFrame * N is
+ *                           below it (+infinity: every pixel);  radius 1..3: the window is (2*radius + 1)^2 pixels
+ *   sigmaNormal, sigmaDepth tptDenoiseDevice's: a tap's weight falls with the guides' distance to the pixel's own
+ * Binary32, in the order written, no FMA, correctly rounded division, sums from +0;  every comparison with a NaN is false;
+ * finite(v): |v| <= FLT_MAX;  in, id = 1 / sigma^2 (0 for a sigma of 0), formed on the host as tptDenoiseDevice's.  Per pixel p of a
+ * frame, with M = moments[p]:
+ *   0. N = M.w;  unless N is finite and N >= 1: N = 1.   dd = M.y - M.x*M.x;   Vt = {0, (dd > 0 ? dd : 0) / N, 0, N}  -- step 6 of the
+ *      temporal pass, byte for byte wherever that pass wrote N.
+ *      PASS-THROUGH, out = Vt, unless samplesPerFrame * N < minSamples (the product formed in binary32).
+ *   1. The window: q = p + (i, j), -radius <= i, j <= radius, j outer (bottom to top), i left to right; a window never leaves its own
+ *      frame's plane.  A tap counts if it lies inside the image, moments[q].x and .y are finite, and den is finite, where
+ *        without a normal / depth plane  den = 1
+ *        with one                        dn = nd[q].xyz - nd[p].xyz;  den = 1 + ((dn.x*dn.x + dn.y*dn.y) + dn.z*dn.z) * in;
+ *                                        dz = nd[q].w - nd[p].w;  den = den * (1 + (dz*dz) * id)
+ *      (the raw plane values: the same factors as tptDenoiseDevice's).  w = 1 / den;  W = sum of w;  S1 = sum of w*moments[q].x;
+ *      S2 = sum of w*moments[q].y.  p itself is a tap with w = 1, and it can fail to count like any other.
+ *   2. No tap counted: out = Vt.  Otherwise e1 = S1 / W;  e2 = S2 / W;  ds = e2 - e1*e1;  out = {0, (ds > 0 ? ds : 0) / N, 0, N}.
+ * Two consequences.  A raw moments plane whose pixels all pass through comes back as {0, max(dd, 0), 0, 1}, which the filter reads to
+ * the very same v_0 as the raw plane: its output is byte for byte the one on the raw plane.  Behind a temporal pass, every pixel with
+ * samplesPerFrame * N >= minSamples carries that pass's own variance bytes.
+ * Asynchronous on the context stream, ordered like tptDenoiseDevice; needs tptInitialize only; frames traced ahead, stream batches,
+ * scene and camera are left alone.  The inputs are never written.
+ * Refused (non-zero, tptGetLastError names the function, nothing enqueued, no byte written): no context; w or h outside 1..8192;
+ * nFrames outside 1..4096; moments or output NULL; radius outside 1..3; samplesPerFrame not finite or below 1; minSamples NaN or below
+ * 1; a sigma that tptDenoiseDevice refuses; a non-zero sigma without the normal / depth plane; the output sharing a byte with an
+ * input, each taken at its full extent of nFrames planes. */
+TPT_API int tptSpatialVarianceDevice(int screenWidth, int screenHeight, int nFrames,
+                                     const float* deviceFrameMoments, const float* deviceFrameNormalDepth,
+                                     float* deviceFrameOutVariance, float samplesPerFrame, float minSamples,
+                                     int radius, float sigmaNormal, float sigmaDepth);
 /* ADAPTIVE SAMPLING: tptDrawDeviceMoments with a sample count per pixel, so that the moments can steer the next pass (the counts come
  * from tptAdaptiveSamplesDevice below, or from the caller).  deviceSampleCounts (required): h*w int32 in DEVICE memory, row-major like the
  * tile, read by the kernels only.  Per pixel p, n = deviceSampleCounts[p] clamped to 0 .. 2047 (the path record holds 11 bits of sample

@@ -39,7 +39,7 @@ C_ABI_SYMBOLS = [
     "tptSetSamplesPerPixel", "tptSetConfig", "tptSetSeedMode", "tptSetFoldMode", "tptSetScene", "tptSetCamera", "tptSetStream",
     "tptSetRowShard", "tptLocalRowCount", "tptLocalRowToGlobal", "tptDrawDevice", "tptRayCounterRead", "tptSetRayCounter", "tptSetFrameOverlap", "tptDisplayRGBA8", "tptKernelTimingBegin", "tptKernelTimingEnd",
     "tptSynchronize", "tptTimerBegin", "tptTimerEnd", "tptSetKernelVariant",
-    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceBatchMoments", "tptDrawDeviceAnimationMoments", "tptDrawDeviceCameraClip", "tptDrawDeviceKeyframeClip", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptObjectPlaneDevice", "tptObjectMotionTable", "tptTemporalAccumulateObjectsDevice", "tptDenoiseClipDevice", "tptMotionVectorsDevice", "tptRectifyHistoryDevice", "tptDrawDeviceAdaptive", "tptAdaptiveSamplesDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
+    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceBatchMoments", "tptDrawDeviceAnimationMoments", "tptDrawDeviceCameraClip", "tptDrawDeviceKeyframeClip", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptObjectPlaneDevice", "tptObjectMotionTable", "tptTemporalAccumulateObjectsDevice", "tptDenoiseClipDevice", "tptMotionVectorsDevice", "tptRectifyHistoryDevice", "tptSpatialVarianceDevice", "tptDrawDeviceAdaptive", "tptAdaptiveSamplesDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
 ]
 # include/tpt_test_hooks.h: exported by the second build (libtoypathtracer_hip_hooks.so) only
 HOOK_SYMBOLS = ["tptTestMath", "tptTestMathExhaustive", "tptTestHitSpheres", "tptTestMatrixFilter", "tptTestGroupFilter", "tptTestSetDealCapacities", "tptDebugStats", "tptDebugChunkOrder", "tptTestPresetStreamCut", "tptTestStreamFrameRays"]
@@ -99,7 +99,7 @@ def _bind(path, hooks):
         "tptSetRayCounter": [p], "tptSetTileMirror": [p, p], "tptSetFrameOverlap": [i], "tptDisplayRGBA8": [p, i, i, p], "tptKernelTimingBegin": [i],
         "tptKernelTimingEnd": [C.POINTER(f), C.POINTER(i)],
         "tptSynchronize": [], "tptTimerBegin": [], "tptTimerEnd": [C.POINTER(f)], "tptSetKernelVariant": [i, i, i],
-        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDrawDeviceBatchMoments": [f, i, i, i, i, p, p, p, p, u], "tptDrawDeviceAnimationMoments": [i, i, p, i, i] + [p] * 7 + [u], "tptDrawDeviceCameraClip": [i, i, p, p, i, i] + [p] * 8 + [u], "tptDrawDeviceKeyframeClip": [i, i, p, i, p, p, i, i] + [p] * 9 + [u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptObjectPlaneDevice": [i, p, p, i, i, p, u], "tptObjectMotionTable": [f, f, u, p, i], "tptTemporalAccumulateObjectsDevice": [i, i] + [p] * 14 + [f] * 4 + [p, p, p, i], "tptDenoiseClipDevice": [C.POINTER(ClipDenoiseArgs)], "tptMotionVectorsDevice": [C.POINTER(MotionVectorsArgs)], "tptRectifyHistoryDevice": [i, i] + [p] * 7 + [i, f], "tptDrawDeviceAdaptive": [f, i, i, i, p, p, p, p, p, u], "tptAdaptiveSamplesDevice": [i, i, p, f, i, i, p, p, p], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
+        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDrawDeviceBatchMoments": [f, i, i, i, i, p, p, p, p, u], "tptDrawDeviceAnimationMoments": [i, i, p, i, i] + [p] * 7 + [u], "tptDrawDeviceCameraClip": [i, i, p, p, i, i] + [p] * 8 + [u], "tptDrawDeviceKeyframeClip": [i, i, p, i, p, p, i, i] + [p] * 9 + [u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptObjectPlaneDevice": [i, p, p, i, i, p, u], "tptObjectMotionTable": [f, f, u, p, i], "tptTemporalAccumulateObjectsDevice": [i, i] + [p] * 14 + [f] * 4 + [p, p, p, i], "tptDenoiseClipDevice": [C.POINTER(ClipDenoiseArgs)], "tptMotionVectorsDevice": [C.POINTER(MotionVectorsArgs)], "tptRectifyHistoryDevice": [i, i] + [p] * 7 + [i, f], "tptSpatialVarianceDevice": [i, i, i, p, p, p, f, f, i, f, f], "tptDrawDeviceAdaptive": [f, i, i, i, p, p, p, p, p, u], "tptAdaptiveSamplesDevice": [i, i, p, f, i, i, p, p, p], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
     }
     if hooks:
         sigs.update({"tptDebugStats": [p, i], "tptDebugChunkOrder": [p, p, i], "tptTestMath": [i, p, p, p, i], "tptTestMathExhaustive": [i, u, u, p, p],
@@ -752,6 +752,42 @@ def rectify_history_device(w, h, colour_ptr, moments_ptr, acc_colour_ptr, acc_mo
         raise ValueError("radius: an int in 1..%d expected, got %r" % (RECTIFY_MAX_RADIUS, radius))
     _sigmas(("gamma", gamma))
     _chk(load_library().tptRectifyHistoryDevice(w, h, *[C.c_void_p(v) for _, v in named], int(radius), gamma), "tptRectifyHistoryDevice")
+
+
+# spatial_variance_device's defaults, confirmed by tools/spatial_variance_rate.py's table
+SPATIAL_VARIANCE_DEFAULTS = dict(min_samples=2.0, radius=1, sigma_normal=0.03, sigma_depth=0.5)
+SPATIAL_VARIANCE_MAX_RADIUS = 3  # include/tpt_hip.h: tptSpatialVarianceDevice's radius
+SPATIAL_VARIANCE_MAX_FRAMES = 4096  # ... and its nFrames
+
+
+def spatial_variance_device(w, h, moments_ptr, out_variance_ptr, normal_depth_ptr=None, frames=1, samples_per_frame=1.0,
+                            min_samples=SPATIAL_VARIANCE_DEFAULTS["min_samples"], radius=SPATIAL_VARIANCE_DEFAULTS["radius"],
+                            sigma_normal=SPATIAL_VARIANCE_DEFAULTS["sigma_normal"], sigma_depth=SPATIAL_VARIANCE_DEFAULTS["sigma_depth"]):
+    """tptSpatialVarianceDevice: a variance plane {0, v/N, 0, N} for denoise_device_variance (as its moments_ptr, with samples =
+    samples_per_frame) or for denoise_clip_device in spatial-only mode, from any moments plane of the chain: draw_device_moments' own,
+    a clip draw's stack, or the out_moments of a temporal pass or of rectify_history_device (.w = N).  A pixel with
+    samples_per_frame * N < min_samples takes its variance from the (2*radius + 1)^2 window's weighted moments, every other pixel its
+    own (the temporal pass's variance bytes).  moments_ptr, out_variance_ptr, normal_depth_ptr: `frames` consecutive device planes of
+    h*w*4 floats.  A guide's sigma is ignored (passed as 0) when normal_depth_ptr is not given.  min_samples may be float("inf"):
+    every pixel is estimated.  Ordered on the context's stream."""
+    _positive_ints(("w", w), ("h", h), ("frames", frames))
+    if frames > SPATIAL_VARIANCE_MAX_FRAMES:
+        raise ValueError("frames: at most %d, got %r" % (SPATIAL_VARIANCE_MAX_FRAMES, frames))
+    _pointers(("moments_ptr", moments_ptr), ("out_variance_ptr", out_variance_ptr), ("normal_depth_ptr", normal_depth_ptr))
+    if not moments_ptr or not out_variance_ptr:
+        raise ValueError("moments_ptr, out_variance_ptr: device buffers are required")
+    _sigmas(("samples_per_frame", samples_per_frame), ("sigma_normal", sigma_normal), ("sigma_depth", sigma_depth))
+    if not samples_per_frame >= 1:
+        raise ValueError("samples_per_frame: a finite float >= 1 expected, got %r" % (samples_per_frame,))
+    if not isinstance(min_samples, (int, float, np.integer, np.floating)) or isinstance(min_samples, bool) or not min_samples >= 1:
+        raise ValueError("min_samples: a float >= 1 (or +inf) expected, got %r" % (min_samples,))
+    if not isinstance(radius, (int, np.integer)) or isinstance(radius, bool) or not 1 <= radius <= SPATIAL_VARIANCE_MAX_RADIUS:
+        raise ValueError("radius: an int in 1..%d expected, got %r" % (SPATIAL_VARIANCE_MAX_RADIUS, radius))
+    if not normal_depth_ptr:
+        sigma_normal = sigma_depth = 0.0
+    _chk(load_library().tptSpatialVarianceDevice(w, h, frames, C.c_void_p(moments_ptr), C.c_void_p(normal_depth_ptr or None),
+                                                 C.c_void_p(out_variance_ptr), samples_per_frame, min_samples, int(radius), sigma_normal,
+                                                 sigma_depth), "tptSpatialVarianceDevice")
 
 
 OBJECT_PLANE_MAX_FRAMES = 4096  # include/tpt_hip.h: tptObjectPlaneDevice's nFrames

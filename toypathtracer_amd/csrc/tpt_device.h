@@ -197,6 +197,14 @@ __attribute__((weak)) hipError_t tptLaunchFlow(const float* albedo, const float*
 __attribute__((weak)) hipError_t tptLaunchRectify(const float* colour, const float* moments, const float* accColour, const float* accMoments,
                                                   float* outColour, float* outMoments, float* outVariance, int width, int height,
                                                   int radius, float gamma, hipStream_t stream);
+// tptSpatialVarianceDevice: one launch over `frames` consecutive planes of [h][w] f4 each (grid.z is the frame).  normalDepth may be
+// null (then in and id are 0 and the taps' weights are 1); in, id: the inverse squared sigmas, as tptLaunchDenoise takes them.
+// radius 1..3 and the presence of normalDepth pick the instantiation.  The tile is the rectification kernel's.  Weak for the same
+// reason as tptLaunchDenoise.
+#define TPT_SPREAD_MAX_RADIUS 3
+__attribute__((weak)) hipError_t tptLaunchSpread(const float* moments, const float* normalDepth, float* out, int width, int height,
+                                                 int frames, float samplesPerFrame, float minSamples, int radius, float in, float id,
+                                                 hipStream_t stream);
 // tptDrawDeviceAdaptive's blend: tile.rgb and moments.xyz with lerp = S / (S + n) per pixel, S the running sample count in moments.w
 // (0 unless `progressive`), n the pixel's clamped count; moments.w = S + n; pixels with n == 0 untouched.  Weak for the same reason as
 // tptLaunchDenoise.

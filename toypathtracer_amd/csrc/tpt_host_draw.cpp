@@ -502,6 +502,37 @@ int tptRectifyHistoryDevice(int w, int h, const float* deviceColour, const float
     return 0;
 }
 
+// The spatial variance estimate (include/tpt_hip.h states it): a post-process on the context stream between the chain's moments planes
+// and its filter, one launch over the whole stack of frames, no scratch plane.  The sigmas are checked and inverted as
+// tptDenoiseDevice's are.
+int tptSpatialVarianceDevice(int screenWidth, int screenHeight, int nFrames, const float* deviceFrameMoments,
+                             const float* deviceFrameNormalDepth, float* deviceFrameOutVariance, float samplesPerFrame, float minSamples,
+                             int radius, float sigmaNormal, float sigmaDepth)
+{
+    if (requireInit()) return -1;
+    const std::string f("tptSpatialVarianceDevice");
+    const int w = screenWidth, h = screenHeight;
+    if (w < 1 || w > 8192 || h < 1 || h > 8192) return fail(f + ": screenWidth and screenHeight must lie in 1..8192");
+    if (nFrames < 1 || nFrames > 4096) return fail(f + ": nFrames must lie in 1..4096");
+    if (!deviceFrameMoments || !deviceFrameOutVariance) return fail(f + ": deviceFrameMoments and deviceFrameOutVariance are required");
+    if (radius < 1 || radius > TPT_SPREAD_MAX_RADIUS) return fail(f + ": radius must lie in 1..3");
+    if (!(samplesPerFrame >= 1.0f && samplesPerFrame <= 3.40282347e38f))
+        return fail(f + ": samplesPerFrame must be finite and at least 1"); // (NaN and +inf fail)
+    if (!(minSamples >= 1.0f)) return fail(f + ": minSamples must be at least 1 (+infinity: every pixel is estimated)"); // (NaN fails)
+    auto sigmaOk = [](float s) { return s == 0.0f || (s >= 1e-6f && s <= 1e6f); }; // (NaN fails both comparisons)
+    if (!sigmaOk(sigmaNormal) || !sigmaOk(sigmaDepth)) return fail(f + ": sigmaNormal and sigmaDepth must be 0 or lie in [1e-6, 1e6]");
+    if ((sigmaNormal != 0.0f || sigmaDepth != 0.0f) && !deviceFrameNormalDepth)
+        return fail(f + ": sigmaNormal and sigmaDepth need deviceFrameNormalDepth");
+    const uintptr_t bytes = (uintptr_t)w * (uintptr_t)h * 16u * (uintptr_t)nFrames;
+    if (overlapsAny(deviceFrameOutVariance, {deviceFrameMoments, deviceFrameNormalDepth}, bytes))
+        return fail(f + ": deviceFrameOutVariance overlaps an input");
+    if (!tptLaunchSpread) return fail(f + ": this build has no spatial variance kernel");
+    auto inv2 = [](float s) { return s > 0.0f ? 1.0f / (s * s) : 0.0f; };
+    HIPCHK(tptLaunchSpread(deviceFrameMoments, deviceFrameNormalDepth, deviceFrameOutVariance, w, h, nFrames, samplesPerFrame, minSamples,
+                           radius, inv2(sigmaNormal), inv2(sigmaDepth), g.stream));
+    return 0;
+}
+
 // The temporal pass that follows objects (include/tpt_hip.h states it): the plain pass's checks, then those of the object planes and
 // the motion table; one launch of its own kernel.
 int tptTemporalAccumulateObjectsDevice(int w, int h, const void* camera, const void* prevCamera, const float* deviceColour,

@@ -1038,6 +1038,126 @@ __global__ void __launch_bounds__(256) tptRectifyKernel(const f4* __restrict__ c
     outVariance[p] = ov;
 }
 
+// The LDS of tptSpreadKernel<R, GUIDE>, in f4 (16-B slots), one array cut in two:
+//   mom  [kRows][kW]  the tile's moments with a halo of R pixels: {m.x, m.y, 1, 0}, or {0, 0, 0, 0} for a pixel that does not count
+//                     (outside the image, or m.x or m.y not finite)
+//   nd   [kRows][kW]  with GUIDE, the normal / depth pixel as it is in the plane ({0, 0, 0, 0} outside the image)
+// 22 400 bytes at R = 3 with the guide.  The first four slots of `mom` carry the workgroup's vote before anything is staged.  As in
+// tptRectifyLayout, a wave is 64 lanes along one row and every access of a wave-instruction is to 64 consecutive slots: no bank
+// conflicts, no padding or swizzle needed.
+template <int R, int GUIDE>
+struct tptSpreadLayout {
+    static constexpr int kW = TPT_RECTIFY_TILE_W + 2 * R, kRows = TPT_RECTIFY_TILE_H + 2 * R;
+    static constexpr int kTile = kW * kRows;         // 396, 544, 700 slots for R = 1, 2, 3
+    static constexpr int kSlots = kTile * (1 + GUIDE); // 6336, 8704, 11200 bytes without the guide, twice that with it
+};
+
+// tptSpatialVarianceDevice (include/tpt_hip.h states it; tests/spatial_variance_checker.c restates it): the variance of a pixel with too
+// few samples from its window's weighted first and second moments.  The layout of the rectification kernel -- one lane per pixel, a
+// wave along 64 pixels of a row, 64 x 4 a workgroup -- with the frame in grid.z.  The weights depend on the pixel, so nothing of the
+// sums is shared: the tile goes to LDS once with its halo and every estimating lane gathers its (2R + 1)^2 taps from there.  Whether
+// a pixel is estimated follows from its own coalesced load; the waves vote through the LDS, and a workgroup none of whose pixels
+// qualifies -- nearly all of them behind a temporal pass -- stages nothing and stores step 0's plane: 16 B in, 16 B out a pixel.  A tap
+// that does not count is staged as zeros and takes the weight 0: adding +0 (or w*m = +-0) to a sum that began at +0 leaves it as it
+// is, so the tap loop is straight-line.  Lanes outside the image vote no, help to stage and leave after the last barrier.  Quotients
+// are plain IEEE divisions.
+template <int R, int GUIDE>
+__global__ void __launch_bounds__(256) tptSpreadKernel(const f4* __restrict__ moments, const f4* __restrict__ nd, f4* __restrict__ out,
+                                                       int width, int height, float samplesPerFrame, float minSamples, float in, float id)
+{
+    typedef tptSpreadLayout<R, GUIDE> Lay;
+    __shared__ f4 lds[Lay::kSlots];
+    f4* const mom = lds;
+    f4* const gd = lds + Lay::kTile;
+    constexpr float big = 3.40282347e38f;
+    const int tx = threadIdx.x, ty = threadIdx.y, tid = ty * TPT_RECTIFY_TILE_W + tx;
+    const int x0 = blockIdx.x * TPT_RECTIFY_TILE_W, y0 = blockIdx.y * TPT_RECTIFY_TILE_H;
+    const int x = x0 + tx, y = y0 + ty;
+    const bool inside = x < width && y < height;
+    const size_t plane = (size_t)blockIdx.z * (size_t)width * (size_t)height; // (a window never leaves its frame's plane)
+    const size_t p = plane + (size_t)y * width + x;
+    f4 zero;
+    zero.x = 0.0f; zero.y = 0.0f; zero.z = 0.0f; zero.w = 0.0f;
+    f4 M = zero;
+    if (inside) M = moments[p];
+    float N = M.w;
+    if (!(__builtin_fabsf(N) <= big && N >= 1.0f)) N = 1.0f;
+    const float dd = M.y - M.x * M.x;
+    float v = dd > 0.0f ? dd : 0.0f;
+    const bool mine = inside && samplesPerFrame * N < minSamples;
+    // the vote: a wave is a row of the tile
+    const unsigned long long wave = __ballot(mine); // (by all 64 lanes: not inside the branch below)
+    if (tx == 0) {
+        f4 b = zero;
+        b.x = wave != 0ull ? 1.0f : 0.0f;
+        mom[ty] = b;
+    }
+    __syncthreads();
+    const float votes = (mom[0].x + mom[1].x) + (mom[2].x + mom[3].x);
+    if (__builtin_amdgcn_readfirstlane(votes != 0.0f ? 1 : 0)) {
+        __syncthreads(); // (every wave has read the votes before their slots are staged over)
+        // the tile and its halo
+#pragma unroll
+        for (int k = 0; k < (Lay::kTile + 255) / 256; ++k) {
+            const int item = tid + 256 * k;
+            if (item < Lay::kTile) {
+                const int row = item / Lay::kW, col = item - row * Lay::kW;
+                const int gx = x0 - R + col, gy = y0 - R + row;
+                f4 s = zero, n = zero;
+                if (gx >= 0 && gx < width && gy >= 0 && gy < height) {
+                    const size_t q = plane + (size_t)gy * width + gx;
+                    const f4 m = moments[q];
+                    if (__builtin_fabsf(m.x) <= big && __builtin_fabsf(m.y) <= big) { // (NaN fails)
+                        s.x = m.x; s.y = m.y; s.z = 1.0f;
+                    }
+                    if (GUIDE) n = nd[q];
+                }
+                mom[item] = s;
+                if (GUIDE) gd[item] = n;
+            }
+        }
+        __syncthreads();
+        if (mine) {
+            f4 np = zero;
+            if (GUIDE) np = gd[(ty + R) * Lay::kW + (tx + R)];
+            float W = 0.0f, S1 = 0.0f, S2 = 0.0f;
+            int any = 0;
+#pragma unroll 1 // (a row of taps in flight at a time: the registers of 2R + 1 taps, not of (2R + 1)^2)
+            for (int j = 0; j <= 2 * R; ++j) {
+#pragma unroll
+                for (int i = 0; i <= 2 * R; ++i) {
+                    const f4 s = mom[(ty + j) * Lay::kW + (tx + i)];
+                    float w = s.z; // (without the guide den == 1, and 1 / 1 == 1)
+                    if (GUIDE) {
+                        const f4 nq = gd[(ty + j) * Lay::kW + (tx + i)];
+                        const float dx = nq.x - np.x, dy = nq.y - np.y, dz = nq.z - np.z;
+                        float den = 1.0f + ((dx * dx + dy * dy) + dz * dz) * in;
+                        const float dw = nq.w - np.w;
+                        den = den * (1.0f + (dw * dw) * id);
+                        const int counts = s.z != 0.0f && __builtin_fabsf(den) <= big;
+                        w = counts ? 1.0f / den : 0.0f;
+                        any |= counts;
+                    } else {
+                        any |= s.z != 0.0f;
+                    }
+                    W += w;
+                    S1 += w * s.x;
+                    S2 += w * s.y;
+                }
+            }
+            if (any) {
+                const float e1 = S1 / W, e2 = S2 / W;
+                const float ds = e2 - e1 * e1;
+                v = ds > 0.0f ? ds : 0.0f;
+            }
+        }
+    }
+    if (!inside) return;
+    f4 o;
+    o.x = 0.0f; o.y = v / N; o.z = 0.0f; o.w = N;
+    out[p] = o;
+}
+
 // tptObjectPlaneDevice (include/tpt_hip.h states it; tests/object_checker.c restates it): the index of the first sphere the ray through
 // each pixel's centre and the lens centre meets.  One lane per pixel, a wave along 64 pixels of a row; the reference's exact test
 // (testSphere) for every sphere in index order, so the nearest hit wins and equal distances go to the lowest index.  The
@@ -3059,6 +3179,21 @@ hipError_t tptLaunchRectify(const float* colour, const float* moments, const flo
     hipLaunchKernelGGL(radius == 1 ? tptRectifyKernel<1> : radius == 2 ? tptRectifyKernel<2> : tptRectifyKernel<3>, grid,
                        dim3(TPT_RECTIFY_TILE_W, TPT_RECTIFY_TILE_H), 0, stream, in(colour), in(moments), in(accColour), in(accMoments),
                        out(outColour), out(outMoments), out(outVariance), width, height, gamma);
+    return hipGetLastError();
+}
+
+hipError_t tptLaunchSpread(const float* moments, const float* normalDepth, float* out, int width, int height, int frames,
+                           float samplesPerFrame, float minSamples, int radius, float in, float id, hipStream_t stream)
+{
+    static_assert(TPT_SPREAD_MAX_RADIUS == 3, "one instantiation per radius and guide");
+    if (radius < 1 || radius > TPT_SPREAD_MAX_RADIUS || frames < 1) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(width + TPT_RECTIFY_TILE_W - 1) / TPT_RECTIFY_TILE_W, (unsigned)(height + TPT_RECTIFY_TILE_H - 1) / TPT_RECTIFY_TILE_H,
+                    (unsigned)frames);
+    auto k = normalDepth ? (radius == 1 ? tptSpreadKernel<1, 1> : radius == 2 ? tptSpreadKernel<2, 1> : tptSpreadKernel<3, 1>)
+                         : (radius == 1 ? tptSpreadKernel<1, 0> : radius == 2 ? tptSpreadKernel<2, 0> : tptSpreadKernel<3, 0>);
+    hipLaunchKernelGGL(k, grid, dim3(TPT_RECTIFY_TILE_W, TPT_RECTIFY_TILE_H), 0, stream, reinterpret_cast<const f4*>(moments),
+                       reinterpret_cast<const f4*>(normalDepth), reinterpret_cast<f4*>(out), width, height, samplesPerFrame, minSamples, in,
+                       id);
     return hipGetLastError();
 }
 
