@@ -7,7 +7,8 @@ import os
 
 import numpy as np
 
-from moments_lib import GK, _build
+from aov_lib import build_checker
+from moments_lib import GK
 from oracle_lib import FLAG_ANIMATE, FLAG_PROGRESSIVE, FOLD_RECURSIVE, MATH_TPT, ROOT, SEED_PER_PIXEL, Params
 
 ADAPTIVE_SOURCE = os.path.join(ROOT, "tests", "adaptive_checker.c")
@@ -17,7 +18,7 @@ MAX_COUNT = 2047
 
 class AdaptiveChecker:
     def __init__(self, out_dir):
-        self.lib = lib = _build(ADAPTIVE_SOURCE, out_dir, "libadaptive_checker.so")
+        self.lib = lib = build_checker(ADAPTIVE_SOURCE, out_dir, "libadaptive_checker.so")
         lib.adaptive_render.restype = C.c_int64
         lib.adaptive_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(Params)] + [C.c_void_p] * 5
         lib.adaptive_plan.restype = C.c_int64

@@ -20,12 +20,17 @@ def oracle_cflags():
     return m.group(1).split()
 
 
+def build_checker(source, out_dir, name):
+    """`source` (a tests/*_checker.c) compiled with the oracle's flags as `out_dir`/`name`, loaded"""
+    so = os.path.join(str(out_dir), name)
+    cc = os.environ.get("CC", "gcc")
+    subprocess.check_call([cc] + oracle_cflags() + ["-shared", "-o", so, source, "-lm"])
+    return C.CDLL(so)
+
+
 class AovChecker:
     def __init__(self, out_dir):
-        so = os.path.join(str(out_dir), "libaov_checker.so")
-        cc = os.environ.get("CC", "gcc")
-        subprocess.check_call([cc] + oracle_cflags() + ["-shared", "-o", so, SOURCE, "-lm"])
-        self.lib = lib = C.CDLL(so)
+        self.lib = lib = build_checker(SOURCE, out_dir, "libaov_checker.so")
         lib.aov_render.restype = C.c_int64
         lib.aov_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p]
         lib.tpto_render.restype = C.c_int64

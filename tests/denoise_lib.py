@@ -3,11 +3,10 @@ oracle/Makefile's CFLAGS into a directory the caller gives (a pytest temp direct
 of the same formula -- one array operation per step, in the order written, so every rounding is the checker's."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-from aov_lib import oracle_cflags
+from aov_lib import build_checker
 from oracle_lib import ROOT
 
 SOURCE = os.path.join(ROOT, "tests", "denoise_checker.c")
@@ -17,10 +16,7 @@ HK = np.array([0.0625, 0.25, 0.375, 0.25, 0.0625], np.float32)
 
 class DenoiseChecker:
     def __init__(self, out_dir):
-        so = os.path.join(str(out_dir), "libdenoise_checker.so")
-        cc = os.environ.get("CC", "gcc")
-        subprocess.check_call([cc] + oracle_cflags() + ["-shared", "-o", so, SOURCE, "-lm"])
-        self.lib = lib = C.CDLL(so)
+        self.lib = lib = build_checker(SOURCE, out_dir, "libdenoise_checker.so")
         lib.denoise.restype = C.c_int
         lib.denoise.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float,
                                 C.c_float, C.c_uint]

@@ -4,11 +4,10 @@ array operation per step, in the order written, so every rounding is the C state
 and the GPU."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-from aov_lib import oracle_cflags
+from aov_lib import build_checker
 from object_lib import cameras_floats
 from oracle_lib import ROOT
 from temporal_lib import FLT_MAX, SNAP, _dot, _finite, axis_camera, camera_floats, look_at_camera, plane_frame, random_frame
@@ -38,10 +37,7 @@ def _check(clip):
 
 class FlowChecker:
     def __init__(self, out_dir):
-        so = os.path.join(str(out_dir), "libflow_checker.so")
-        cc = os.environ.get("CC", "gcc")
-        subprocess.check_call([cc] + oracle_cflags() + ["-shared", "-o", so, SOURCE, "-lm"])
-        self.lib = lib = C.CDLL(so)
+        self.lib = lib = build_checker(SOURCE, out_dir, "libflow_checker.so")
         lib.flow_motion.restype = C.c_int
         lib.flow_motion.argtypes = [C.c_int] * 3 + [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 4 + [C.c_float] * 3 + [C.c_void_p]
 

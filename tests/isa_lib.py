@@ -1,12 +1,15 @@
 """What the ABI and ISA tests share (a plain module they import, not a conftest): the gfx950 code object inside the shipped library,
-disassembled (the `code_object` fixture, count()); the parameters of an entry point as include/tpt_hip.h declares it; and the run of a
-refusal script against the host runtime compiled for tests/hostemu (a refused call returns before anything is enqueued).  No GPU needed:
-the fat binary is unbundled and disassembled with the ROCm LLVM tools."""
+disassembled (the `code_object` fixture, count()); the library's exported symbols; the parameters of an entry point as include/tpt_hip.h
+declares it; and the run of a refusal script against the host runtime compiled for tests/hostemu (a refused call returns before anything
+is enqueued).  No GPU needed: the fat binary is unbundled and disassembled with the ROCm LLVM tools.  The kernels' names are
+tests/kernel_manifest.py's."""
+import functools
 import os
 import re
 import shutil
 import subprocess
 import sys
+import tempfile
 
 import pytest
 
@@ -18,31 +21,24 @@ OBJDUMP = os.path.join(LLVM, "llvm-objdump")
 READELF = os.path.join(LLVM, "llvm-readelf")
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
 HAVE_TOOLS = all(os.path.exists(p) for p in (BUNDLER, OBJDUMP, READELF)) and shutil.which("objcopy") is not None
-# the path-queue kernel and its variants by their mangled names
-QUEUE = "_ZN3tpt19tptTraceQueueKernelILb%dELb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE, BATCH>
-VIEWS = "_ZN3tpt19tptTraceViewsKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
-ANIM = "_ZN3tpt23tptTraceAnimationKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
-AOV = "_ZN3tpt17tptTraceAovKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
-MOMENTS = "_ZN3tpt21tptTraceMomentsKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
-# (not "tptTraceAnimationMomentsKernel": tests/test_moments_abi.py counts the kernels whose names hold "Moments")
-CLIP = "_ZN3tpt18tptTraceClipKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
 
 
-@pytest.fixture(scope="module")
-def code_object(tmp_path_factory):
-    """(bodies, meta) of the shipped library's gfx950 code object: each kernel's instructions as [mnemonic, operands...] and its
-    metadata (register counts, spills, LDS, scratch) as ints"""
-    if not HAVE_TOOLS:
-        pytest.skip("ROCm LLVM tools not installed")
-    from toypathtracer_amd import api
-    d = tmp_path_factory.mktemp("isa")
-    fat, co = str(d / "fat.bin"), str(d / "kernels.co")
-    subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", api.library_path(), fat])
-    targets = subprocess.check_output([BUNDLER, "--list", "--type=o", "--input=" + fat]).decode().split()
-    assert [t for t in targets if t.startswith("hipv4-amdgcn")] == [TARGET], "the library carries gfx950 code only: %r" % targets
-    subprocess.check_call([BUNDLER, "--unbundle", "--type=o", "--targets=" + TARGET, "--input=" + fat, "--output=" + co])
-    dis = subprocess.check_output([OBJDUMP, "-d", co]).decode()
-    notes = subprocess.check_output([READELF, "--notes", co]).decode()
+def _stamp(path):
+    """what a cached reading of the file at `path` is keyed by: a rebuilt library is read again"""
+    st = os.stat(path)
+    return path, st.st_mtime_ns, st.st_size
+
+
+@functools.lru_cache(maxsize=None)
+def _extract(path, mtime, size):
+    with tempfile.TemporaryDirectory() as d:
+        fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "kernels.co")
+        subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", path, fat])
+        targets = subprocess.check_output([BUNDLER, "--list", "--type=o", "--input=" + fat]).decode().split()
+        assert [t for t in targets if t.startswith("hipv4-amdgcn")] == [TARGET], "the library carries gfx950 code only: %r" % targets
+        subprocess.check_call([BUNDLER, "--unbundle", "--type=o", "--targets=" + TARGET, "--input=" + fat, "--output=" + co])
+        dis = subprocess.check_output([OBJDUMP, "-d", co]).decode()
+        notes = subprocess.check_output([READELF, "--notes", co]).decode()
     bodies = {}
     for m in re.finditer(r"^[0-9a-f]+ <(\w+)>:\n(.*?)(?=^[0-9a-f]+ <\w+>:|\Z)", dis, flags=re.S | re.M):
         # one instruction per line: "\t<mnemonic> operands  // address: encoding"
@@ -52,6 +48,32 @@ def code_object(tmp_path_factory):
         name = re.search(r"\.name:\s+(\S+)", blk).group(1)
         meta[name] = {k: int(v) for k, v in re.findall(r"\.(\w+):\s+(\d+)\s*$", blk, flags=re.M)}
     return bodies, meta
+
+
+@pytest.fixture(scope="module")
+def code_object():
+    """(bodies, meta) of the shipped library's gfx950 code object: each kernel's instructions as [mnemonic, operands...] and its
+    metadata (register counts, spills, LDS, scratch) as ints.  Extracted once per process and library file; the modules share it and
+    leave it as it is."""
+    if not HAVE_TOOLS:
+        pytest.skip("ROCm LLVM tools not installed")
+    from toypathtracer_amd import api
+    return _extract(*_stamp(api.library_path()))
+
+
+@functools.lru_cache(maxsize=None)
+def _nm(path, mtime, size):
+    return subprocess.check_output(["nm", "-D", "--defined-only", path]).decode()
+
+
+def exported_symbols(path):
+    """`nm -D --defined-only` of the library at `path`, as text: an entry point NAME is exported where "T NAME" stands in it"""
+    return _nm(*_stamp(path))
+
+
+def no_library():
+    """stands in for api.load_library where a binding must refuse its arguments before it reaches the library"""
+    raise AssertionError("the library was called")
 
 
 def count(body, pattern):

@@ -4,11 +4,10 @@ compiled with oracle/Makefile's CFLAGS into a directory the caller gives (a pyte
 float32 statement of the filter -- one array operation per step, in the order written, so every rounding is the C statement's."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-from aov_lib import oracle_cflags
+from aov_lib import build_checker
 from denoise_lib import DEMODULATE, HK, random_planes  # noqa: F401  (re-exported for the tests)
 from oracle_lib import FLAG_ANIMATE, FLAG_PROGRESSIVE, FOLD_RECURSIVE, MATH_TPT, ROOT, SEED_PER_PIXEL, Params
 
@@ -18,16 +17,9 @@ GK = np.array([0.25, 0.5, 0.25], np.float32)
 EPS = np.float32(1e-4)  # include/tpt_hip.h: TPT_DENOISE_VARIANCE_EPS
 
 
-def _build(src, out_dir, name):
-    so = os.path.join(str(out_dir), name)
-    cc = os.environ.get("CC", "gcc")
-    subprocess.check_call([cc] + oracle_cflags() + ["-shared", "-o", so, src, "-lm"])
-    return C.CDLL(so)
-
-
 class MomentsChecker:
     def __init__(self, out_dir):
-        self.lib = lib = _build(MOMENTS_SOURCE, out_dir, "libmoments_checker.so")
+        self.lib = lib = build_checker(MOMENTS_SOURCE, out_dir, "libmoments_checker.so")
         lib.moments_render.restype = C.c_int64
         lib.moments_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(Params)] + [C.c_void_p] * 4
         lib.tpto_render.restype = C.c_int64
@@ -73,7 +65,7 @@ class MomentsChecker:
 
 class VarianceChecker:
     def __init__(self, out_dir):
-        self.lib = lib = _build(VARIANCE_SOURCE, out_dir, "libvariance_checker.so")
+        self.lib = lib = build_checker(VARIANCE_SOURCE, out_dir, "libvariance_checker.so")
         lib.denoise_variance.restype = C.c_int
         lib.denoise_variance.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_float, C.c_void_p, C.c_int, C.c_float, C.c_float,
                                                                                  C.c_float, C.c_uint]

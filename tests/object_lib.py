@@ -4,11 +4,10 @@ twins -- one float32 array operation per step, in the order written, so every ro
 tests feed both."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-from aov_lib import oracle_cflags
+from aov_lib import build_checker
 from oracle_lib import FLAG_ANIMATE, ROOT, SPHERE_DT
 from temporal_lib import FLT_MAX, KINDS, SNAP, _dot, _finite, camera_floats, look_at_camera, synthetic_case
 
@@ -25,10 +24,7 @@ def cameras_floats(cams):
 
 class ObjectChecker:
     def __init__(self, out_dir):
-        so = os.path.join(str(out_dir), "libobject_checker.so")
-        cc = os.environ.get("CC", "gcc")
-        subprocess.check_call([cc] + oracle_cflags() + ["-shared", "-o", so, SOURCE, "-lm"])
-        self.lib = lib = C.CDLL(so)
+        self.lib = lib = build_checker(SOURCE, out_dir, "libobject_checker.so")
         lib.object_plane.restype = C.c_int
         lib.object_plane.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_uint, C.c_void_p]
         lib.object_accumulate.restype = C.c_int

@@ -4,11 +4,10 @@ statement -- one array operation per step, in the order written, so every roundi
 tests feed both."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-from aov_lib import oracle_cflags
+from aov_lib import build_checker
 from oracle_lib import ROOT
 
 SOURCE = os.path.join(ROOT, "tests", "rectify_checker.c")
@@ -20,10 +19,7 @@ f32 = np.float32
 
 class RectifyChecker:
     def __init__(self, out_dir):
-        so = os.path.join(str(out_dir), "librectify_checker.so")
-        cc = os.environ.get("CC", "gcc")
-        subprocess.check_call([cc] + oracle_cflags() + ["-shared", "-o", so, SOURCE, "-lm"])
-        self.lib = lib = C.CDLL(so)
+        self.lib = lib = build_checker(SOURCE, out_dir, "librectify_checker.so")
         lib.rectify_history.restype = C.c_int
         lib.rectify_history.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_float]
 

@@ -4,11 +4,10 @@ vectorised float32 statement -- one array operation per step and per tap, in the
 statement's -- and the seeded planes the tests feed both."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-from aov_lib import oracle_cflags
+from aov_lib import build_checker
 from oracle_lib import ROOT
 
 SOURCE = os.path.join(ROOT, "tests", "spatial_variance_checker.c")
@@ -21,10 +20,7 @@ f32 = np.float32
 
 class SpatialVarianceChecker:
     def __init__(self, out_dir):
-        so = os.path.join(str(out_dir), "libspatial_variance_checker.so")
-        cc = os.environ.get("CC", "gcc")
-        subprocess.check_call([cc] + oracle_cflags() + ["-shared", "-o", so, SOURCE, "-lm"])
-        self.lib = lib = C.CDLL(so)
+        self.lib = lib = build_checker(SOURCE, out_dir, "libspatial_variance_checker.so")
         lib.spatial_variance.restype = C.c_int
         lib.spatial_variance.argtypes = [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_float, C.c_float, C.c_int, C.c_float, C.c_float]
 

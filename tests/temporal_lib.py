@@ -4,11 +4,10 @@ float32 statement -- one array operation per step, in the order written, so ever
 planes the tests feed both."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-from aov_lib import oracle_cflags
+from aov_lib import build_checker
 from oracle_lib import ROOT
 
 SOURCE = os.path.join(ROOT, "tests", "temporal_checker.c")
@@ -27,10 +26,7 @@ def camera_floats(cam):
 
 class TemporalChecker:
     def __init__(self, out_dir):
-        so = os.path.join(str(out_dir), "libtemporal_checker.so")
-        cc = os.environ.get("CC", "gcc")
-        subprocess.check_call([cc] + oracle_cflags() + ["-shared", "-o", so, SOURCE, "-lm"])
-        self.lib = lib = C.CDLL(so)
+        self.lib = lib = build_checker(SOURCE, out_dir, "libtemporal_checker.so")
         lib.temporal_accumulate.restype = C.c_int
         lib.temporal_accumulate.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 14 + [C.c_float] * 4
 

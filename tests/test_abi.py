@@ -6,6 +6,7 @@ import subprocess
 
 import pytest
 
+from isa_lib import exported_symbols, header
 from oracle_lib import ROOT
 
 
@@ -16,8 +17,7 @@ def header_symbols(name="tpt_hip.h"):
 
 
 def exported(path):
-    out = subprocess.check_output(["nm", "-D", "--defined-only", path]).decode()
-    return sorted(line.split()[-1] for line in out.splitlines() if line.strip())
+    return sorted(line.split()[-1] for line in exported_symbols(path).splitlines() if line.strip())
 
 
 def test_library_exports_every_declared_symbol():
@@ -26,6 +26,7 @@ def test_library_exports_every_declared_symbol():
     declared = header_symbols()
     assert len(declared) >= 25
     assert sorted(api.C_ABI_SYMBOLS) == declared, "api.C_ABI_SYMBOLS out of sync with include/tpt_hip.h"
+    assert sorted(set(re.findall(r"TPT_API\s+[\w\s*]+?\b(tpt\w+)\s*\(", header()))) == declared, "a declared function is not TPT_API"
     for name in declared:
         assert hasattr(lib, name), name
 
@@ -44,7 +45,7 @@ def test_library_exports_exactly_its_abi():
 def test_library_exports_reference_cxx_symbols():
     """Link-level drop-in: the mangled names `nm` shows for the reference's compiled Test.cpp."""
     from toypathtracer_amd import api
-    out = subprocess.check_output(["nm", "-D", "--defined-only", api.library_path()]).decode()
+    out = exported_symbols(api.library_path())
     for sym in api.CXX_ABI_SYMBOLS:
         assert re.search(r"\bT %s\b" % re.escape(sym), out), sym
 

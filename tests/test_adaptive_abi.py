@@ -4,16 +4,11 @@ and the existing instantiations of the path-queue kernel held to the register, s
 compiled beside them --; and the refusals, driven through the host runtime compiled against tests/hostemu (a refused call returns
 before anything is enqueued; the new launchers are tests/hostemu_adaptive.cpp, which counts and runs nothing)."""
 import re
-import subprocess
 
 import pytest
 
-from isa_lib import MOMENTS, QUEUE, code_object, count, header, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
-
-ADAPTIVE = "_ZN3tpt22tptTraceAdaptiveKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
-RESOLVE = "_ZN3tpt24tptAdaptiveResolveKernelEPfS0_PKNS_2f4ES3_PKiii"
-PLAN = "_ZN3tpt21tptAdaptivePlanKernelEPKNS_2f4EPiPS0_Pyiifii"
-COUNTED_WORDS = ("tptTraceKernel", "Test", "Moments", "Variance", "Denoise", "Temporal")  # what existing ABI / ISA tests count in names
+from isa_lib import code_object, count, exported_symbols, header, header_params, no_library, run_refusals  # noqa: F401  (code_object: a module fixture)
+from kernel_manifest import ADAPTIVE, ADAPTIVE_PLAN as PLAN, ADAPTIVE_RESOLVE as RESOLVE, MOMENTS, QUEUE, family
 
 # The path-queue kernel's instantiations as the parent commit's build has them (the same compiler, the same flags):
 # (vgpr_count, group_segment_fixed_size, vgpr_spill_count, sgpr_spill_count, private_segment_fixed_size).  The adaptive variant is one
@@ -57,12 +52,7 @@ def test_binding_and_export(name, fn):
     assert callable(getattr(api, fn))
     lib = api.load_library()
     assert hasattr(lib, name)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", api.library_path()]).decode()
-    assert re.search(r"\bT %s\b" % name, out)
-
-
-def no_library():
-    raise AssertionError("the library was called")
+    assert re.search(r"\bT %s\b" % name, exported_symbols(api.library_path()))
 
 
 @pytest.mark.parametrize("args", [
@@ -129,12 +119,9 @@ def test_helper_kernels_in_the_code_object(code_object):  # noqa: F811
 
 
 def test_new_kernel_names_hold_no_counted_word(code_object):  # noqa: F811
+    """(no test counts kernels by the words in their names any more: tests/test_isa_contract.py holds the library to the manifest)"""
     _, meta = code_object
-    new = [n for n in meta if "Adaptive" in n]
-    assert sorted(new) == sorted([ADAPTIVE % 0, ADAPTIVE % 1, RESOLVE, PLAN]), new
-    for n in new:
-        for word in COUNTED_WORDS:
-            assert word not in n, (n, word)
+    assert sorted(n for n in meta if "Adaptive" in n) == sorted(family(ADAPTIVE) + [RESOLVE, PLAN])
 
 
 def test_existing_instantiations_are_what_the_parent_built(code_object):  # noqa: F811
@@ -143,7 +130,6 @@ def test_existing_instantiations_are_what_the_parent_built(code_object):  # noqa
         m = meta[name]
         got = (m["vgpr_count"], m["group_segment_fixed_size"], m["vgpr_spill_count"], m["sgpr_spill_count"], m["private_segment_fixed_size"])
         assert got == want, (name, got, want)
-    assert len([n for n in meta if "tptTrace" in n and "tptTraceKernel" not in n]) == len(PARENT) + 2
 
 
 # ---------------------------------------------------------------- refusals, through the host runtime

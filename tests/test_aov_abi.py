@@ -3,11 +3,11 @@ gfx950 code of the AOV kernels in the shipped library against their plain single
 the refusals, driven through the host runtime compiled against tests/hostemu (a refused call returns before anything is enqueued, so no
 kernel is emulated)."""
 import re
-import subprocess
 
 import pytest
 
-from isa_lib import AOV, QUEUE, code_object, count, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
+from isa_lib import code_object, count, exported_symbols, header_params, no_library, run_refusals  # noqa: F401  (code_object: a module fixture)
+from kernel_manifest import AOV, QUEUE
 
 
 def test_header_declares_the_entry_point():
@@ -22,8 +22,7 @@ def test_binding_and_export():
     assert callable(api.draw_device_aov)
     lib = api.load_library()
     assert hasattr(lib, "tptDrawDeviceAov")
-    out = subprocess.check_output(["nm", "-D", "--defined-only", api.library_path()]).decode()
-    assert re.search(r"\bT tptDrawDeviceAov\b", out)
+    assert re.search(r"\bT tptDrawDeviceAov\b", exported_symbols(api.library_path()))
 
 
 @pytest.mark.parametrize("args", [
@@ -34,10 +33,6 @@ def test_binding_and_export():
 def test_binding_checks_arguments_before_the_library(monkeypatch, args):
     """every bad argument raises ValueError in Python: the library is never reached (load_library would fail the test)"""
     from toypathtracer_amd import api
-
-    def no_library():
-        raise AssertionError("the library was called")
-
     monkeypatch.setattr(api, "load_library", no_library)
     a = dict(w=16, h=8, tile=4096, albedo=8192, nd=16384)
     a.update(args)

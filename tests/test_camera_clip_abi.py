@@ -9,13 +9,11 @@ import subprocess
 
 import pytest
 
-from isa_lib import CLIP, QUEUE, code_object, count, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
+from isa_lib import code_object, count, exported_symbols, header_params, no_library, run_refusals  # noqa: F401  (code_object: a module fixture)
+from kernel_manifest import CAMERA_CLIP, CLIP, QUEUE, family
 from oracle_lib import ROOT
 
 NAME = "tptDrawDeviceCameraClip"
-CAMERA_CLIP = "_ZN3tpt19tptCameraClipKernelILb%dEEEvNS_10KernelArgsE"  # <LDS_SCENE>
-# what existing ABI / ISA tests count in kernel names
-COUNTED_WORDS = ("tptTrace", "Test", "Moments", "Variance", "Denoise", "Temporal", "Adaptive")
 
 
 def test_header_declares_the_entry_point():
@@ -31,12 +29,7 @@ def test_binding_and_export():
     assert callable(api.draw_device_camera_clip)
     lib = api.load_library()
     assert hasattr(lib, NAME)
-    out = subprocess.check_output(["nm", "-D", "--defined-only", api.library_path()]).decode()
-    assert re.search(r"\bT %s\b" % NAME, out)
-
-
-def no_library():
-    raise AssertionError("the library was called")
+    assert re.search(r"\bT %s\b" % NAME, exported_symbols(api.library_path()))
 
 
 VIEW = [0.0, 2.0, 3.0, 0.0, 0.0, 0.0, 60.0, 0.02, 3.0]
@@ -69,8 +62,6 @@ def test_camera_clip_kernels_keep_the_queue_kernel_contract(code_object, lds):  
     bodies, meta = code_object
     name = CAMERA_CLIP % lds
     assert name in meta and name in bodies, "the camera-clip kernel is missing from the shipped code object"
-    for word in COUNTED_WORDS:
-        assert word not in name, word
     body, m = bodies[name], meta[name]
     assert count(body, r"flat_") == 0, "a FLAT instruction: an LDS pointer lost its address space"
     assert count(body, r"buffer_(load|store|atomic)") == 0
@@ -91,7 +82,7 @@ def test_camera_clip_kernels_keep_the_queue_kernel_contract(code_object, lds):  
 
 def test_exactly_one_new_kernel_pair(code_object):  # noqa: F811
     _, meta = code_object
-    assert sorted(n for n in meta if "CameraClip" in n) == [CAMERA_CLIP % 0, CAMERA_CLIP % 1]
+    assert sorted(n for n in meta if "CameraClip" in n) == sorted(family(CAMERA_CLIP))
 
 
 # ---------------------------------------------------------------- the variant decision and the LDS of a launch, on the host

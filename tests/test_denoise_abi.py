@@ -2,13 +2,11 @@
 gfx950 code of the a-trous kernels in the shipped library; and every refusal of the ABI, driven through the host runtime compiled
 against tests/hostemu (a refused call returns before anything is enqueued, so no kernel is emulated)."""
 import re
-import subprocess
 
 import pytest
 
-from isa_lib import code_object, count, header, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
-
-DENOISE = "_ZN3tpt16tptDenoiseKernelILb%dELb%dELb%dEEEvPKNS_2f4ES3_S3_PS1_iiifffi"  # <FIRST, LAST, GUIDE>
+from isa_lib import code_object, count, exported_symbols, header, header_params, no_library, run_refusals  # noqa: F401  (code_object: a module fixture)
+from kernel_manifest import DENOISE, family
 
 
 def test_header_declares_the_entry_point():
@@ -25,8 +23,7 @@ def test_binding_and_export():
     assert callable(api.denoise_device) and api.DENOISE_DEMODULATE == 1
     lib = api.load_library()
     assert hasattr(lib, "tptDenoiseDevice")
-    out = subprocess.check_output(["nm", "-D", "--defined-only", api.library_path()]).decode()
-    assert re.search(r"\bT tptDenoiseDevice\b", out)
+    assert re.search(r"\bT tptDenoiseDevice\b", exported_symbols(api.library_path()))
 
 
 @pytest.mark.parametrize("args", [
@@ -39,10 +36,6 @@ def test_binding_and_export():
 def test_binding_checks_arguments_before_the_library(monkeypatch, args):
     """every bad argument raises ValueError in Python: the library is never reached (load_library would fail the test)"""
     from toypathtracer_amd import api
-
-    def no_library():
-        raise AssertionError("the library was called")
-
     monkeypatch.setattr(api, "load_library", no_library)
     a = dict(w=16, h=8, colour=4096, out=8192, albedo=16384, nd=32768, iterations=5, sigma_colour=1.0, sigma_normal=0.2,
              sigma_depth=0.5, demodulate=None)
@@ -79,7 +72,6 @@ def test_denoise_kernels_in_the_code_object(code_object, first, last, guide):
     bodies, meta = code_object
     name = DENOISE % (first, last, guide)
     assert name in meta and name in bodies, "the a-trous kernel is missing from the shipped code object"
-    assert "Test" not in name
     body, m = bodies[name], meta[name]
     assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0, m
     assert count(body, r"scratch_") == 0
@@ -94,9 +86,9 @@ def test_denoise_kernels_in_the_code_object(code_object, first, last, guide):
 
 
 def test_no_kernel_name_contains_test(code_object):
-    bodies, meta = code_object
-    names = [n for n in meta if "Denoise" in n]
-    assert len(names) == 8 and not [n for n in names if "Test" in n], names
+    """(that no kernel of the library is a unit-test kernel: tests/test_isa_contract.py)"""
+    _, meta = code_object
+    assert sorted(n for n in meta if "Denoise" in n) == sorted(family(DENOISE))
 
 
 REFUSALS = r'''

@@ -11,13 +11,10 @@ import subprocess
 import numpy as np
 import pytest
 
-from isa_lib import code_object, count, header, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
+from isa_lib import code_object, count, exported_symbols, header, header_params, no_library, run_refusals  # noqa: F401  (code_object: a module fixture)
+from kernel_manifest import FLOW, family
 from oracle_lib import ROOT
 
-FLOW = "_ZN3tpt13tptFlowKernelILb%dEEEvPKNS_2f4ES3_PKiS3_S3_S5_S3_iPS1_iiPK13tptFlowConsts"  # <OBJECTS>
-# the words other ABI tests count kernels by: the new kernels' names, parameter types included, hold none of them
-COUNTED_WORDS = ("Denoise", "Moments", "Variance", "Object", "Adaptive", "Keyframe", "CameraClip", "TraceClip", "Temporal", "FramesAtrous",
-                 "tptTrace", "Test")
 CTYPES_OF = {"int": C.c_int, "unsigned": C.c_uint, "float": C.c_float}
 
 
@@ -76,20 +73,12 @@ def test_binding_and_export():
     assert name in api.C_ABI_SYMBOLS and callable(api.motion_vectors_device)
     lib = api.load_library()
     assert hasattr(lib, name) and lib.tptMotionVectorsDevice.argtypes == [C.POINTER(api.MotionVectorsArgs)]
-    out = subprocess.check_output(["nm", "-D", "--defined-only", api.library_path()]).decode()
-    assert re.search(r"\bT %s\b" % name, out)
-    # nm -D shows exactly the header's symbols
-    exported = {ln.split()[-1] for ln in out.splitlines() if ln.split()[-1].startswith("tpt")}
-    assert exported == set(re.findall(r"TPT_API\s+[\w\s*]+?\b(tpt\w+)\s*\(", header())) == set(api.C_ABI_SYMBOLS)
+    assert re.search(r"\bT %s\b" % name, exported_symbols(api.library_path()))
     import inspect
     defaults = {k: v.default for k, v in inspect.signature(api.motion_vectors_device).parameters.items()}
     for k in ("depth_tolerance", "normal_tolerance", "coverage_tolerance"):
         assert defaults[k] == api.TEMPORAL_DEFAULTS[k], k
     assert "max_history" not in defaults
-
-
-def no_library():
-    raise AssertionError("the library was called")
 
 
 def cameras(n):
@@ -127,8 +116,6 @@ def test_flow_kernels_in_the_code_object(code_object, objects):  # noqa: F811
     bodies, meta = code_object
     name = FLOW % objects
     assert name in meta and name in bodies, "the motion-vector kernel is missing from the shipped code object"
-    for word in COUNTED_WORDS:
-        assert word not in name, (name, word)
     body, m = bodies[name], meta[name]
     assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0, m
     assert count(body, r"scratch_") == 0
@@ -146,15 +133,9 @@ def test_flow_kernels_in_the_code_object(code_object, objects):  # noqa: F811
 
 
 def test_exactly_the_new_kernels_and_every_count_unchanged(code_object):  # noqa: F811
+    """(every other family: tests/test_isa_contract.py holds the library to exactly tests/kernel_manifest.py)"""
     _, meta = code_object
-    assert sorted(n for n in meta if "Flow" in n) == sorted(FLOW % o for o in (0, 1))
-    assert sum(1 for n in meta if "Denoise" in n) == 8
-    assert sum(1 for n in meta if "Moments" in n or "Variance" in n) == 10
-    assert sum(1 for n in meta if "Object" in n) == 3
-    assert sum(1 for n in meta if "Adaptive" in n) == 4
-    assert sum(1 for n in meta if "Keyframe" in n) == 2 and sum(1 for n in meta if "CameraClip" in n) == 2
-    assert sum(1 for n in meta if "TraceClip" in n) == 2 and sum(1 for n in meta if "Temporal" in n) == 2
-    assert sum(1 for n in meta if "FramesAtrous" in n) == 8
+    assert sorted(n for n in meta if "Flow" in n) == sorted(family(FLOW))
 
 
 REFUSALS = r'''

@@ -12,20 +12,20 @@ a profiling session to find when it was lost:
 """
 import pytest
 
-from isa_lib import HAVE_TOOLS, QUEUE, code_object, count  # noqa: F401  (code_object: a module fixture)
+import kernel_manifest
+from isa_lib import HAVE_TOOLS, code_object, count  # noqa: F401  (code_object: a module fixture)
+from kernel_manifest import QUEUE
 
 pytestmark = pytest.mark.skipif(not HAVE_TOOLS, reason="ROCm LLVM tools not installed")
 
 
 def test_every_kernel_of_the_library_is_there(code_object):
+    """the inventory: the library ships exactly the kernels of tests/kernel_manifest.py, no more and no fewer"""
     bodies, meta = code_object
     names = set(meta)
-    for lds in (0, 1):
-        for batch in (0, 1):
-            assert QUEUE % (lds, batch) in names
-    assert sum(1 for n in names if "tptTraceKernel" in n) == 8      # the lane-refill fallback: HS x PERSIST x LDS
-    for n in ("tptResolveKernel", "tptResolveMirrorKernel", "tptResolveBatchKernel", "tptAssembleKernel", "tptDisplayKernel", "tptChunkOrderKernel"):
-        assert any(n in k for k in names), n
+    unexpected, missing = sorted(names - kernel_manifest.ALL), sorted(kernel_manifest.ALL - names)
+    assert names == kernel_manifest.ALL, ("in the library but not in the manifest: %s\nin the manifest but not in the library: %s"
+                                          % (unexpected or "none", missing or "none"))
     assert not any("Test" in k for k in names), "unit-test kernels belong to the hooks build only"
     assert set(bodies) >= names
 

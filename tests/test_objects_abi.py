@@ -3,17 +3,13 @@ exports; the bindings' argument checks; the gfx950 code of the new kernels in th
 table, driven through the host runtime compiled against tests/hostemu (a refused call returns before anything is enqueued; the
 launchers are tests/hostemu_objects.cpp, which count and run nothing, and show what the host made of cameras, times and scene)."""
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from isa_lib import code_object, count, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
-from test_temporal_abi import TEMPORAL
+from isa_lib import code_object, count, exported_symbols, header_params, no_library, run_refusals  # noqa: F401  (code_object: a module fixture)
+from kernel_manifest import OBJECT_PLANE as PLANE, REPROJECT, TEMPORAL, family
 
-PLANE = "_ZN3tpt20tptObjectPlaneKernelEPKNS_2f4EiPiii20tptObjectPlaneConsts"
-REPROJECT = "_ZN3tpt25tptReprojectObjectsKernelILb%dEEEvPKNS_2f4ES3_S3_S3_S3_S3_S3_S3_PS1_S4_S4_S4_PKiS6_S3_iii18tptReprojectConsts"  # <HISTORY>
-COUNTED_WORDS = ("tptTrace", "Test", "Moments", "Variance", "Denoise", "Temporal", "Adaptive", "CameraClip")  # other ABI tests count by these
 TEMPORAL_PARAMS = [
     "int screenWidth", "int screenHeight", "const void* camera", "const void* prevCamera", "const float* deviceColour",
     "const float* deviceAlbedo", "const float* deviceNormalDepth", "const float* deviceMoments", "const float* devicePrevColour",
@@ -36,16 +32,12 @@ def test_header_declares_the_entry_points():
 def test_bindings_and_exports():
     from toypathtracer_amd import api
     lib = api.load_library()
-    out = subprocess.check_output(["nm", "-D", "--defined-only", api.library_path()]).decode()
+    out = exported_symbols(api.library_path())
     for name in NEW:
         assert name in api.C_ABI_SYMBOLS and hasattr(lib, name)
         assert re.search(r"\bT %s\b" % name, out), name
     for fn in (api.object_plane_device, api.object_motion_table, api.motion_table, api.temporal_accumulate_objects_device):
         assert callable(fn)
-
-
-def no_library():
-    raise AssertionError("the library was called")
 
 
 def camera(n=1):
@@ -124,13 +116,10 @@ def test_motion_table_helpers(monkeypatch):
 
 
 def test_exactly_the_new_kernels_are_in_the_code_object(code_object):  # noqa: F811
+    """(every other family, the plain pass's among them: tests/test_isa_contract.py holds the library to exactly
+    tests/kernel_manifest.py)"""
     _, meta = code_object
-    new = sorted(n for n in meta if "Object" in n)
-    assert new == sorted([PLANE, REPROJECT % 0, REPROJECT % 1]), new
-    for n in new:
-        for word in COUNTED_WORDS:
-            assert word not in n, (n, word)
-    assert TEMPORAL % 0 in meta and TEMPORAL % 1 in meta  # (the plain pass's kernel keeps its name)
+    assert sorted(n for n in meta if "Object" in n) == sorted([PLANE] + family(REPROJECT))
 
 
 @pytest.mark.parametrize("history", [1, 0], ids=["history", "first-frame"])

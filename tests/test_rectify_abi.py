@@ -5,17 +5,13 @@ nothing, and shows what the host handed it)."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import pytest
 
-from isa_lib import code_object, count, header, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
+from isa_lib import code_object, count, exported_symbols, header_params, no_library, run_refusals  # noqa: F401  (code_object: a module fixture)
+from kernel_manifest import RECTIFY, family
 from oracle_lib import ROOT
 
-RECTIFY = "_ZN3tpt16tptRectifyKernelILi%dEEEvPKNS_2f4ES3_S3_S3_PS1_S4_S4_iif"  # <R>
-# the words other ABI tests count kernels by: the new kernels' names, parameter types included, hold none of them
-COUNTED_WORDS = ("Denoise", "Moments", "Variance", "Object", "Adaptive", "Keyframe", "CameraClip", "TraceClip", "Temporal", "FramesAtrous",
-                 "tptTrace", "Flow", "Test")
 # the kernel's LDS in 16-byte slots: (64 + 2R) x (4 + 2R) raw pixels and twice (4 + 2R) x 64 row sums (tptRectifyLayout)
 LDS_BYTES = {r: 16 * ((64 + 2 * r) * (4 + 2 * r) + 2 * (4 + 2 * r) * 64) for r in (1, 2, 3)}
 # DESIGN.md 3.16 records these from the code object's notes: radius -> (vgpr_count, sgpr_count)
@@ -43,18 +39,10 @@ def test_binding_and_export():
     lib = api.load_library()
     assert hasattr(lib, name)
     assert lib.tptRectifyHistoryDevice.argtypes == [C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_float]
-    out = subprocess.check_output(["nm", "-D", "--defined-only", api.library_path()]).decode()
-    assert re.search(r"\bT %s\b" % name, out)
-    # nm -D shows exactly the header's symbols
-    exported = {ln.split()[-1] for ln in out.splitlines() if ln.split()[-1].startswith("tpt")}
-    assert exported == set(re.findall(r"TPT_API\s+[\w\s*]+?\b(tpt\w+)\s*\(", header())) == set(api.C_ABI_SYMBOLS)
+    assert re.search(r"\bT %s\b" % name, exported_symbols(api.library_path()))
     import inspect
     defaults = {k: v.default for k, v in inspect.signature(api.rectify_history_device).parameters.items()}
     assert {k: defaults[k] for k in api.RECTIFY_DEFAULTS} == api.RECTIFY_DEFAULTS
-
-
-def no_library():
-    raise AssertionError("the library was called")
 
 
 @pytest.mark.parametrize("args", [
@@ -79,8 +67,6 @@ def test_rectify_kernels_in_the_code_object(code_object, radius):  # noqa: F811
     bodies, meta = code_object
     name = RECTIFY % radius
     assert name in meta and name in bodies, "the rectification kernel is missing from the shipped code object"
-    for word in COUNTED_WORDS:
-        assert word not in name, (name, word)
     body, m = bodies[name], meta[name]
     assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0, m
     assert count(body, r"scratch_") == 0
@@ -104,15 +90,9 @@ def test_rectify_kernels_in_the_code_object(code_object, radius):  # noqa: F811
 
 
 def test_exactly_the_new_kernels_and_every_count_unchanged(code_object):  # noqa: F811
+    """(every other family: tests/test_isa_contract.py holds the library to exactly tests/kernel_manifest.py)"""
     _, meta = code_object
-    assert sorted(n for n in meta if "Rectify" in n) == sorted(RECTIFY % r for r in (1, 2, 3))
-    assert sum(1 for n in meta if "Denoise" in n) == 8
-    assert sum(1 for n in meta if "Moments" in n or "Variance" in n) == 10
-    assert sum(1 for n in meta if "Object" in n) == 3
-    assert sum(1 for n in meta if "Adaptive" in n) == 4
-    assert sum(1 for n in meta if "Keyframe" in n) == 2 and sum(1 for n in meta if "CameraClip" in n) == 2
-    assert sum(1 for n in meta if "TraceClip" in n) == 2 and sum(1 for n in meta if "Temporal" in n) == 2
-    assert sum(1 for n in meta if "FramesAtrous" in n) == 8 and sum(1 for n in meta if "Flow" in n) == 2
+    assert sorted(n for n in meta if "Rectify" in n) == sorted(family(RECTIFY))
 
 
 REFUSALS = r'''

@@ -6,18 +6,14 @@ import ctypes as C
 import inspect
 import os
 import re
-import subprocess
 
 import pytest
 
-from isa_lib import code_object, count, header, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
+from isa_lib import code_object, count, exported_symbols, header_params, no_library, run_refusals  # noqa: F401  (code_object: a module fixture)
+from kernel_manifest import SPREAD, family
 from oracle_lib import ROOT
 
 NAME = "tptSpatialVarianceDevice"
-SPREAD = "_ZN3tpt15tptSpreadKernelILi%dELi%dEEEvPKNS_2f4ES3_PS1_iiffff"  # <R, GUIDE>
-# the words other ABI tests count kernels by: the new kernels' names, parameter types included, hold none of them
-COUNTED_WORDS = ("Denoise", "Moments", "Variance", "Object", "Adaptive", "Keyframe", "CameraClip", "TraceClip", "Temporal", "FramesAtrous",
-                 "tptTrace", "Flow", "Rectify", "FramePools", "Test", "Fold")
 # the kernel's LDS in 16-byte slots: (64 + 2R) x (4 + 2R) moments pixels and, with the guide, as many normal / depth pixels
 # (tptSpreadLayout)
 LDS_BYTES = {(r, g): 16 * (64 + 2 * r) * (4 + 2 * r) * (1 + g) for r in (1, 2, 3) for g in (0, 1)}
@@ -47,20 +43,12 @@ def test_binding_and_export():
     lib = api.load_library()
     assert hasattr(lib, NAME)
     assert lib.tptSpatialVarianceDevice.argtypes == [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_float, C.c_float, C.c_int, C.c_float, C.c_float]
-    out = subprocess.check_output(["nm", "-D", "--defined-only", api.library_path()]).decode()
-    assert re.search(r"\bT %s\b" % NAME, out)
-    # nm -D shows exactly the header's symbols
-    exported = {ln.split()[-1] for ln in out.splitlines() if ln.split()[-1].startswith("tpt")}
-    assert exported == set(re.findall(r"TPT_API\s+[\w\s*]+?\b(tpt\w+)\s*\(", header())) == set(api.C_ABI_SYMBOLS)
+    assert re.search(r"\bT %s\b" % NAME, exported_symbols(api.library_path()))
     sig = inspect.signature(api.spatial_variance_device)
     assert list(sig.parameters)[:7] == ["w", "h", "moments_ptr", "out_variance_ptr", "normal_depth_ptr", "frames", "samples_per_frame"]
     defaults = {k: v.default for k, v in sig.parameters.items()}
     assert {k: defaults[k] for k in api.SPATIAL_VARIANCE_DEFAULTS} == api.SPATIAL_VARIANCE_DEFAULTS
     assert (defaults["normal_depth_ptr"], defaults["frames"], defaults["samples_per_frame"]) == (None, 1, 1.0)
-
-
-def no_library():
-    raise AssertionError("the library was called")
 
 
 @pytest.mark.parametrize("args", [
@@ -87,8 +75,6 @@ def test_spread_kernels_in_the_code_object(code_object, variant):  # noqa: F811
     radius, guide = variant
     name = SPREAD % variant
     assert name in meta and name in bodies, "the kernel is missing from the shipped code object"
-    for word in COUNTED_WORDS:
-        assert word not in name, (name, word)
     body, m = bodies[name], meta[name]
     assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0, m
     assert count(body, r"scratch_") == 0
@@ -115,17 +101,10 @@ def test_spread_kernels_in_the_code_object(code_object, variant):  # noqa: F811
 
 
 def test_exactly_the_new_kernels_and_every_count_unchanged(code_object):  # noqa: F811
+    """(every other family, and how many kernels there are: tests/test_isa_contract.py holds the library to exactly
+    tests/kernel_manifest.py)"""
     _, meta = code_object
-    assert sorted(n for n in meta if "Spread" in n) == sorted(SPREAD % v for v in VARIANTS)
-    assert len(meta) == 74 + 6
-    assert sum(1 for n in meta if "Denoise" in n) == 8
-    assert sum(1 for n in meta if "Moments" in n or "Variance" in n) == 10
-    assert sum(1 for n in meta if "Object" in n) == 3
-    assert sum(1 for n in meta if "Adaptive" in n) == 4
-    assert sum(1 for n in meta if "Keyframe" in n) == 2 and sum(1 for n in meta if "CameraClip" in n) == 2
-    assert sum(1 for n in meta if "TraceClip" in n) == 2 and sum(1 for n in meta if "Temporal" in n) == 2
-    assert sum(1 for n in meta if "FramesAtrous" in n) == 8 and sum(1 for n in meta if "Flow" in n) == 2
-    assert sum(1 for n in meta if "Rectify" in n) == 3 and sum(1 for n in meta if "Fold" in n) == 1
+    assert sorted(n for n in meta if "Spread" in n) == sorted(family(SPREAD)) == sorted(SPREAD % v for v in VARIANTS)
 
 
 REFUSALS = r'''

@@ -3,14 +3,12 @@ the two instantiations of the kernel in the shipped library; and the refusals, d
 tests/hostemu (a refused call returns before anything is enqueued; the launcher is tests/hostemu_temporal.cpp, which counts and runs
 nothing, and shows what the host made of the cameras)."""
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from isa_lib import code_object, count, header, header_params, run_refusals  # noqa: F401  (code_object: a module fixture)
-
-TEMPORAL = "_ZN3tpt17tptTemporalKernelILb%dEEEvPKNS_2f4ES3_S3_S3_S3_S3_S3_S3_PS1_S4_S4_S4_ii17tptTemporalConsts"  # <HISTORY>
+from isa_lib import code_object, count, exported_symbols, header, header_params, no_library, run_refusals  # noqa: F401  (code_object: a module fixture)
+from kernel_manifest import TEMPORAL
 
 
 def test_header_declares_the_entry_point():
@@ -32,12 +30,7 @@ def test_binding_and_export():
     assert api.TEMPORAL_DEFAULTS.keys() == {"max_history", "depth_tolerance", "normal_tolerance", "coverage_tolerance"}
     lib = api.load_library()
     assert hasattr(lib, "tptTemporalAccumulateDevice")
-    out = subprocess.check_output(["nm", "-D", "--defined-only", api.library_path()]).decode()
-    assert re.search(r"\bT tptTemporalAccumulateDevice\b", out)
-
-
-def no_library():
-    raise AssertionError("the library was called")
+    assert re.search(r"\bT tptTemporalAccumulateDevice\b", exported_symbols(api.library_path()))
 
 
 def camera():
@@ -71,7 +64,6 @@ def test_temporal_kernels_in_the_code_object(code_object, history):
     bodies, meta = code_object
     name = TEMPORAL % history
     assert name in meta and name in bodies, "the temporal kernel is missing from the shipped code object"
-    assert not [word for word in ("Denoise", "Moments", "Variance", "Test") if word in name]  # (other ABI tests count kernels by these)
     body, m = bodies[name], meta[name]
     assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0, m
     assert count(body, r"scratch_") == 0

@@ -156,8 +156,8 @@ struct tptObjectPlaneConsts {
 // centre meets, -1 for none; sph4 = SceneView::sph4 of nSpheres records in device memory.  Weak for the same reason as tptLaunchDenoise.
 __attribute__((weak)) hipError_t tptLaunchObjectPlane(const tpt::f4* sph4, int nSpheres, int32_t* out, int width, int height,
                                                       const tptObjectPlaneConsts& k, hipStream_t stream);
-// tptTemporalAccumulateObjectsDevice: the plain pass's constants, made the same way.  (A struct of its own name: the kernel's mangled
-// name carries its parameter types, and tests count kernels by the words in their names.)
+// tptTemporalAccumulateObjectsDevice: the plain pass's constants, made the same way.  (A struct of its own name: it is part of the two
+// kernels' shipped symbols, which tests/kernel_manifest.py and profiles/ look them up by; folding it into tptTemporalConsts renames both.)
 struct tptReprojectConsts {
     tptTemporalConsts t;
 };
@@ -172,7 +172,7 @@ __attribute__((weak)) hipError_t tptLaunchReprojectObjects(const float* colour, 
                                                            hipStream_t stream);
 // tptMotionVectorsDevice: what the kernel needs of one frame's camera, of its predecessor's and of the call, made on the host like
 // tptTemporalConsts (the same fields in the same order, without the history length).  One record per frame of the clip in a table in
-// device memory: 32 frames of them do not fit in kernel arguments.  (A struct of its own name, for the reason tptReprojectConsts has one.)
+// device memory: 32 frames of them do not fit in kernel arguments.  (Its name is part of the kernels' shipped symbols, like tptReprojectConsts.)
 struct tptFlowConsts {
     float o[3], ll[3], H[3], V[3];
     float po[3], pa[3], pw[3], pH[3], pV[3];

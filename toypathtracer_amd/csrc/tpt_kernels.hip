@@ -2711,7 +2711,7 @@ tptTraceQueueKernel<false, true>(const KernelArgs a)
     traceQueueBody<false, true>(a);
 }
 // The variants of traceQueueBody beyond <LDS_SCENE, BATCH>, from one list.  Each is a kernel of its own, not another template argument of
-// tptTraceQueueKernel: names and code of the existing kernels stay (tests look them up by name).  <false>: no scene in LDS -- grouped scenes
+// tptTraceQueueKernel: names and code of the existing kernels stay (the shipped symbols: tests/kernel_manifest.py and profiles/ look them up).  <false>: no scene in LDS -- grouped scenes
 // and flat scenes whose arrays stay in global memory (the moving variants take flat scenes only) --, with the grouped register cap.
 enum { QF_BATCH = 1, QF_VIEWS = 2, QF_MOVING = 4, QF_AOV = 8, QF_MOMENTS = 16, QF_ADAPTIVE = 32, QF_CAMERAS = 64, QF_KEYS = 128, QF_POOLS = 256 };
 #define TPT_QUEUE_VARIANT_KERNEL(NAME, F)                                                                                                    \
@@ -2735,9 +2735,9 @@ TPT_QUEUE_VARIANT_KERNEL(tptTraceAovKernel, QF_AOV)                             
 TPT_QUEUE_VARIANT_KERNEL(tptTraceMomentsKernel, QF_AOV | QF_MOMENTS)                         // tptDrawDeviceMoments: the AOV kernel plus a third f4 of sums per path, the luminance moments
 TPT_QUEUE_VARIANT_KERNEL(tptTraceClipKernel, QF_BATCH | QF_MOVING | QF_AOV | QF_MOMENTS)     // tptDrawDeviceAnimationMoments: the animation kernel plus the moments kernel's per-path sums
 TPT_QUEUE_VARIANT_KERNEL(tptTraceAdaptiveKernel, QF_AOV | QF_MOMENTS | QF_ADAPTIVE)             // tptDrawDeviceAdaptive: the moments kernel with each pixel's sample count from a plane
-TPT_QUEUE_VARIANT_KERNEL(tptCameraClipKernel, QF_BATCH | QF_MOVING | QF_AOV | QF_MOMENTS | QF_CAMERAS) // tptDrawDeviceCameraClip: the clip kernel with a camera per frame (not "tptTrace...": tests count those names)
-TPT_QUEUE_VARIANT_KERNEL(tptKeyframeKernel, QF_BATCH | QF_MOVING | QF_AOV | QF_MOMENTS | QF_CAMERAS | QF_KEYS) // tptDrawDeviceKeyframeClip: the camera-clip kernel with the caller's centres per frame (a name without the words tests count kernels by)
-TPT_QUEUE_VARIANT_KERNEL(tptFramePoolsKernel, QF_BATCH | QF_POOLS)                            // tptDrawDeviceBatch and STREAM launches of 2 .. 8 frames: the batched kernel with a pool of chunks per frame (a name without the words tests count kernels by)
+TPT_QUEUE_VARIANT_KERNEL(tptCameraClipKernel, QF_BATCH | QF_MOVING | QF_AOV | QF_MOMENTS | QF_CAMERAS) // tptDrawDeviceCameraClip: the clip kernel with a camera per frame (the name is kept as shipped, like the two below: tests/kernel_manifest.py and profiles/ look kernels up by it)
+TPT_QUEUE_VARIANT_KERNEL(tptKeyframeKernel, QF_BATCH | QF_MOVING | QF_AOV | QF_MOMENTS | QF_CAMERAS | QF_KEYS) // tptDrawDeviceKeyframeClip: the camera-clip kernel with the caller's centres per frame
+TPT_QUEUE_VARIANT_KERNEL(tptFramePoolsKernel, QF_BATCH | QF_POOLS)                            // tptDrawDeviceBatch and STREAM launches of 2 .. 8 frames: the batched kernel with a pool of chunks per frame
 #undef TPT_QUEUE_VARIANT_KERNEL
 
 #if defined(TPT_TEST_HOOKS)
