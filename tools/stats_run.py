@@ -27,15 +27,15 @@ for (w, h, spp, persist) in [(1280, 720, 4, 3), (3840, 2160, 16, 3)]:
     if waves:
         span = (int(st[26]) - int(st[25])) * 10e-9
         print("  waves %d  kernel span %.3f ms  mean wave lifetime %.3f ms  longest %.3f ms" % (waves, span * 1e3, int(st[24]) / waves * 10e-6, int(st[28]) * 10e-6))
-    QN = ["FREE", "INT", "END", "DIEL", "METAL", "LAMBERT"]
+    QN = ["FREE", "INT", "END", "DIEL", "METAL", "LAMBERT", "LAST"]  # (LAST: tptFramePoolsKernel<true> alone; its timing slots lie behind those of the idle polls)
     for c, n in enumerate(QN):
         if st[16 + c]:
             print("  queue %-8s batches %9d  paths %11d  fill %.1f / 64" % (n, st[16 + c], st[48 + c], st[48 + c] / st[16 + c]))
-    tot = float(sum(int(st[64 + k]) for k in range(25))) or 1.0
+    tot = float(sum(int(st[64 + k]) for k in range(32))) or 1.0
     if tot > 1:
         print("  wave time by section (s_memtime ticks, share of all wave time): idle polls %.1f %%" % (100.0 * int(st[64 + 24]) / tot))
         for c, n in enumerate(QN):
-            v = [int(st[64 + c * 4 + k]) for k in range(4)]
+            v = [int(st[64 + (c if c < 6 else c + 1) * 4 + k]) for k in range(4)]
             print("    %-8s pick+pop %5.1f %%  class code %5.1f %%  intersect+classify %5.1f %%  push %5.1f %%" % ((n,) + tuple(100.0 * x / tot for x in v)))
     for i, n in enumerate(NAMES):
         if st[i]:

@@ -1357,6 +1357,11 @@ __device__ __forceinline__ f4 mk4(float x, float y, float z, float w)
 //   LAMBERT -> [Scatter: lambert + the whole light loop: every    /   (or FREE when its pixel is done)
 //               shadow ray is intersected and shaded in place]
 //   INT     -> overflow only: rays of batches that kept fewer than TPT_Q_FUSE_MIN lanes are re-batched here first
+// The frame-pools kernel for scenes staged in LDS (POOLS below, LAST_CLASS) splits END by the sample number, known where the path is
+// pushed, and owns 32 paths fewer for the seventh ring (tpt_queue_layout.h):
+//   END     -> [sky / emission, fold, next sample's camera ray]        every lane: the pixel has a further sample
+//   LAST    -> [sky / emission, fold, store the pixel; then FREE's     the pixel's last sample: the lane that finished a pixel
+//               code: assign a pixel, camera ray]                      starts the next one, or goes to FREE when none is left
 // A batch holds paths that all need the same code, so Scatter and the intersections that follow run at (nearly)
 // full lane utilisation instead of ~40 %, a lane never idles because "its" pixel ended (any wave picks up any path),
 // and a path crosses a queue once per bounce (not once per ray: the shadow rays of a Lambert hit stay in registers).
@@ -1400,7 +1405,7 @@ __device__ __forceinline__ unsigned dependentZero(unsigned v)
     asm volatile("v_and_b32_e32 %0, 0, %1" : "=v"(z) : "v"(v));
     return z;
 }
-// Push every lane's path id to the queue of its class `cls` (Q_FREE..Q_LAMBERT, or -1 for none): one returning LDS atomic
+// Push every lane's path id to the queue of its class `cls` (Q_FREE..Q_LAMBERT, the pools kernel's Q_LAST, or -1 for none): one returning LDS atomic
 // per lane reserves the slot (the LDS unit serialises the lanes that hit the same tail word -- its time, not the VALU's:
 // the ballot / popcount / readlane version of this cost ~35 VALU instructions per batch).
 __device__ __forceinline__ void qPushByClass(LdsRing q, QueueCtl* ctl, int cls, int pathId, int lane)
@@ -2059,12 +2064,14 @@ __device__ __forceinline__ int hitSpheresGroupedDeal(const SceneView& sv, bool g
 // launch run dry frame after frame instead of all at once -- and counts its rays per lane, for that frame's counter.  A STREAM launch
 // whose caller waited before asking for all of its frames is cut: a workgroup that starts after that and finds its own frame unasked
 // serves an asked frame instead, for its whole life (tpt_frame_pools.h, frameServedUnderCut).  Its own kernel (tptFramePoolsKernel)
-// for the same reason.
+// for the same reason.  With the scene in LDS it has seven classes, END and LAST for an ended sample (LAST_CLASS below), in a class
+// chain of its own; every other instantiation's statements stay where and what they were.
 template <bool LDS_SCENE, bool BATCH, bool VIEWS = false, bool MOVING = false, bool AOV = false, bool MOMENTS = false, bool ADAPTIVE = false,
           bool CAMERAS = false, bool KEYS = false, bool POOLS = false>
 __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
 {
     static_assert(!POOLS || (BATCH && !VIEWS && !MOVING && !AOV), "a pool per frame belongs to the plain batched launch");
+    static_assert(!POOLS || (!MOMENTS && !ADAPTIVE && !CAMERAS && !KEYS), "the pools kernel's own FREE / END / LAST code below knows the plain batched launch only");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // LDS layout: everything of fixed size first, at compile-time offsets (immediates in the DS instructions instead of base
     // registers): path records, rings, control block, frame constants; then the scene arrays, whose sizes the launch decides
@@ -2079,11 +2086,16 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     static_assert(!KEYS || CAMERAS, "the caller's centres per frame belong to the frames of a clip with their cameras and planes");
     constexpr bool CAM_TABLE = VIEWS || CAMERAS; // (the cameras of the batch's frames in LDS)
     constexpr int kMovedPerFrame = KEYS ? TPT_Q_KEYS_MAX : 2; // (MOVING: centres per frame in the table)
+    // The pools kernel for scenes staged in LDS splits the END class in two (tpt_queue_layout.h, Q_LAST).  Its grouped twin keeps one END
+    // class: with the split its launches of 2 frames at 8 spp measured 1 % slower (profiles/last_sample_class/README.md).
+    constexpr bool LAST_CLASS = POOLS && LDS_SCENE;
+    constexpr int kRings = LAST_CLASS ? Q_COUNT_POOLS : Q_COUNT; // (the LAST ring, in the place of TPT_Q_LAST_PATHS path records)
     constexpr int kPaths = (LDS_SCENE ? TPT_Q_PATHS : TPT_Q_PATHS_GROUPED) - (CAM_TABLE ? TPT_Q_VIEW_PATHS : 0) -
-                           (MOVING ? (KEYS ? TPT_Q_KEY_PATHS : TPT_Q_ANIM_PATHS) : 0); // paths this workgroup owns
+                           (MOVING ? (KEYS ? TPT_Q_KEY_PATHS : TPT_Q_ANIM_PATHS) : 0) - (LAST_CLASS ? TPT_Q_LAST_PATHS : 0); // paths this workgroup owns
     constexpr int kOffSt = LDS_SCENE ? TPT_Q_SPH_FIXED : 0;
     constexpr int kOffQ = kOffSt + TPT_Q_NF4 * kPaths * 16;
-    constexpr int kOffCtl = kOffQ + Q_COUNT * TPT_Q_P * 2;
+    constexpr int kOffCtl = kOffQ + kRings * TPT_Q_P * 2;
+    static_assert(kRings <= (int)(sizeof(QueueCtl::head) / 4) && kPaths <= TPT_Q_P, "a head and a tail per ring; a ring holds every path");
     constexpr int kOffDeal = kOffCtl + (((int)sizeof(QueueCtl) + 63) & ~63);
     constexpr int kDealBytes = (!LDS_SCENE && TPT_GROUP_DEAL) ? TPT_Q_WAVES * TPT_GROUP_DEAL_WAVE_BYTES : 0; // pair lists of the grouped traversal
     constexpr int kOffFc = kOffDeal + kDealBytes;
@@ -2176,7 +2188,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
         for (int i = tid; i < a.batchFrames * kMovedPerFrame; i += TPT_Q_T) ldsMoved[i] = KEYS ? a.keyCentres[i] : a.moveCentres[i];
     const uint64_t keyMask = KEYS ? (uint64_t)a.keyMask : 0ull; // (KEYS: the moved spheres, sphere i at bit 63 - i)
     // every path starts in the FREE queue; all other queues empty (sentinel everywhere)
-    for (int i = tid; i < Q_COUNT * TPT_Q_P; i += TPT_Q_T) q[i] = (unsigned short)(i < kPaths ? i : 0xFFFF);
+    for (int i = tid; i < kRings * TPT_Q_P; i += TPT_Q_T) q[i] = (unsigned short)(i < kPaths ? i : 0xFFFF);
     if (tid < 8) {
         ctl->head[tid] = 0u;
         ctl->tail[tid] = tid == Q_FREE ? (unsigned)kPaths : 0u;
@@ -2223,6 +2235,8 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
     unsigned long long qSec[5] = {0, 0, 0, 0, 0}; // s_memtime ticks: pick+pop, class code, intersect, push, idle
 #endif
 
+// timing slots of class `pick`: four at 64 + 4 pick; the idle polls have 64 + 24 .. 27, so the pools kernel's seventh class takes 64 + 28 .. 31
+#define TPT_TSLOT(pick) (64 + ((pick) < Q_COUNT ? (pick) : (pick) + 1) * 4)
 #if defined(TPT_STATS)
 #define TPT_TSTAMP(v)                      \
     __builtin_amdgcn_sched_barrier(0);     \
@@ -2240,16 +2254,16 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
 #endif
     for (;;) {
         TPT_TSTAMP(tsTop);
-        // ---- what is waiting?  lanes 0..5 read one queue each, broadcast through readlane
+        // ---- what is waiting?  lanes 0..5 (LAST_CLASS: 0..6) read one queue each, broadcast through readlane
         unsigned myAvail = 0, myHead = 0, myTail = 0;
-        if (lane < Q_COUNT) {
+        if (lane < kRings) {
             myTail = __hip_atomic_load(&ctl->tail[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             myHead = __hip_atomic_load(&ctl->head[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             myAvail = myTail - myHead;
         }
-        unsigned avail[Q_COUNT];
+        unsigned avail[kRings];
 #pragma unroll
-        for (int c = 0; c < Q_COUNT; ++c) avail[c] = (unsigned)__builtin_amdgcn_readlane((int)myAvail, c);
+        for (int c = 0; c < kRings; ++c) avail[c] = (unsigned)__builtin_amdgcn_readlane((int)myAvail, c);
         const bool canStart = (chunkEnd > chunkNext) || !noMoreChunks;
         int pick = -1;
         unsigned best = 0;
@@ -2257,7 +2271,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
         if (canStart && avail[Q_FREE] >= 64u) pick = Q_FREE;
         if (pick < 0) {
 #pragma unroll
-            for (int c = 1; c < Q_COUNT; ++c)
+            for (int c = 1; c < kRings; ++c)
                 if (avail[c] >= 64u && avail[c] > best) {
                     best = avail[c];
                     pick = c;
@@ -2265,7 +2279,7 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
         }
         if (pick < 0) { // no full batch anywhere: take the largest partial one
 #pragma unroll
-            for (int c = 0; c < Q_COUNT; ++c)
+            for (int c = 0; c < kRings; ++c)
                 if ((c != Q_FREE || canStart) && avail[c] > best) {
                     best = avail[c];
                     pick = c;
@@ -2295,10 +2309,16 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
 #endif
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         TPT_TSTAMP(tsPop);
-        TPT_TADD(64 + pick * 4 + 0, tsTop, tsPop);
+        TPT_TADD(TPT_TSLOT(pick) + 0, tsTop, tsPop);
         const bool mine = lane < n;
 #if defined(TPT_STATS)
         if (mine) { TPT_STAT(16 + pick); } // [16+pick] batches popped per queue, [48+pick] paths in them
+#if TPT_STATS >= 2
+        if (lane == 0) { // (the light build counts them too, once per wave)
+            TPT_COUNT(16 + pick, 1);
+            TPT_COUNT(48 + pick, n);
+        }
+#endif
 #endif
 
         // ---- this iteration's path state, in registers: the ray the batch produces (or, from a class queue, the hit
@@ -2335,7 +2355,125 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
             recId = (w >> 16) == 0xffffu ? -1 : (int)(w >> 16);
         }
 
-        if (pick == Q_FREE) {
+        if constexpr (LAST_CLASS) {
+            // ---- The pools kernel's own class chain (tpt_queue_layout.h, Q_LAST): an ended sample was pushed to END when its pixel
+            //      has a further sample and to LAST when it was the pixel's last one, so both batches stay full -- END makes 64
+            //      camera rays of 64 paths, LAST stores its pixels and starts the next ones in the same lanes.  What the chain below
+            //      does for a plain batched launch (BATCH alone: no views, planes, counts or moving spheres), the same arithmetic in
+            //      the same order; it is written out here, not shared, because the other instantiations' code must stay what it is to
+            //      the instruction (tests/test_adaptive_abi.py pins their registers and spills).  Every condition on pick is wave-uniform.
+            if ((pick == Q_END || pick == Q_LAST) && mine) {
+                // a path ended (sky / emission): fold, add the sample to the pixel's sum
+                const f3 c = qFold(sv, qEndTerm(sv, fc, rd, recId), depth, stack);
+                const f4 c3 = colSum[p];
+                const f3 col = mk3(c3.x, c3.y, c3.z) + c; // same order of additions as Test.cpp:289
+                const int px = (int)(f2u(c3.w) & 0x1fffu), py = (int)((f2u(c3.w) >> 13) & 0x1fffu);
+                if (pick == Q_END) { // the pixel's next sample
+                    sample++;
+                    colSum[p] = mk4(col.x, col.y, col.z, c3.w);
+                    qCamera(*ldsFc, px, py, rng, ro, rd);
+                    depth = 0;
+                    doMatE = true;
+                    ray = true;
+                } else { // the pixel is done
+                    const int plane = (int)(f2u(c3.w) >> 26) * a.framePlane;
+                    const f3 out = col * fc.invSpp; // Test.cpp:291
+                    a.frameColour[plane + globalRowToLocal(a, py) * fc.width + px] = mk4(out.x, out.y, out.z, 0.0f); // one 16-B store per pixel
+                }
+            }
+            if (pick == Q_FREE || pick == Q_LAST) {
+                // ---- start pixels on free paths, or on the paths whose pixel has just been stored (this wave's chunk pool, refilled
+                //      from the pool of the frame this workgroup serves)
+                bool need = mine, got = false;
+                int px = 0, py = 0;
+                for (;;) {
+                    const unsigned long long needMask = __ballot(need);
+                    if (needMask == 0ull) break;
+                    if (chunkNext >= chunkEnd) {
+                        if (noMoreChunks) break;
+                        int c = 0;
+                        const int myFrame = (int)poolFrame();
+                        if (lane == 0) {
+                            atomicAdd(&ctl->poolTotal, 64u); // optimistic: keeps "pixels left" non-zero while the fetch is in flight
+                            // (the next chunk of the frame this workgroup serves.  It takes chunks of that frame only: "exhausted" below
+                            //  then means that frame's pool, and the workgroup leaves while the other frames' workgroups run on)
+                            c = (int)atomicAdd(&a.work[kFramePoolBase + myFrame], 1u);
+                        }
+                        c = __builtin_amdgcn_readfirstlane(c);
+                        if (c >= a.chunksPerFrame) {
+                            if (lane == 0) {
+                                atomicSub(&ctl->poolTotal, 64u);
+                                __hip_atomic_store(&ctl->globalExhausted, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                            }
+                            noMoreChunks = true;
+                            break;
+                        }
+                        chunkFrame = myFrame;
+                        chunkNext = c * a.chunkSize;
+                        chunkEnd = chunkNext + a.chunkSize;
+                        if (chunkEnd > a.numItems) chunkEnd = a.numItems;
+                        if (lane == 0 && chunkEnd - chunkNext != 64) atomicSub(&ctl->poolTotal, (unsigned)(64 - (chunkEnd - chunkNext)));
+                    }
+                    const int rank = __popcll(needMask & laneBelow);
+                    const int want = __popcll(needMask);
+                    const int availPx = chunkEnd - chunkNext;
+                    const int take = want < availPx ? want : availPx;
+                    if (need && rank < take) {
+                        int x, ly;
+                        if (mapItem(a, chunkNext + rank, x, ly)) {
+                            px = x;
+                            py = localRowToGlobal(a, ly);
+                            got = true;
+                            need = false;
+                        }
+                    }
+                    chunkNext += take;
+                    if (lane == 0) atomicSub(&ctl->poolTotal, (unsigned)take);
+                }
+                if (got) {
+                    rng = pixelSeed(fc.seedMode, px, py, fc.frame + chunkFrame);
+                    // colour sum = 0; the pixel: x | y << 13 | frame << 26
+                    colSum[p] = mk4(0.0f, 0.0f, 0.0f, u2f((uint32_t)px | ((uint32_t)py << 13) | ((uint32_t)chunkFrame << 26)));
+                    qCamera(*ldsFc, px, py, rng, ro, rd);
+                    sample = 0; // (a LAST lane: the record it loaded was the stored pixel's)
+                    depth = 0;
+                    doMatE = true;
+                    recId = -1;
+                    ray = true;
+                } else if (mine) {
+                    toFree = true; // no pixel left for this path
+                }
+            } else if (pick == Q_INT) {
+                ray = mine; // overflow: rays of sparse batches, re-batched
+            } else if (pick == Q_DIEL) {
+                if (mine) {
+                    f3 e;
+                    rd = qDielectric<MOVING, KEYS>(sv, fc, ro, rd, recId, doMatE, rng, e, movedLds + movedAt, keyMask);
+                    qStackPush(stack, depth, e, -1);
+                    depth++;
+                    doMatE = true; // Test.cpp:214
+                    ray = true;
+                }
+            } else if (pick == Q_METAL) {
+                if (mine) {
+                    f3 e, nd;
+                    if (qMetal<MOVING, KEYS>(sv, fc, ro, rd, recId, doMatE, rng, e, nd, movedLds + movedAt, keyMask)) {
+                        qStackPush(stack, depth, e, recId);
+                        depth++;
+                        doMatE = true;
+                        rd = nd;
+                        ray = true;
+                    } else {
+                        toEnd = true; // Test.cpp:218-221: return matE -- the END / LAST class does that from the record as it stands
+                    }
+                }
+            } else if (pick == Q_LAMBERT) {
+                if (mine) {
+                    qLambertBegin<MOVING, KEYS>(sv, ro, rd, recId, rng, lam, movedLds + movedAt, keyMask);
+                    ray = true;
+                }
+            }
+        } else if (pick == Q_FREE) {
             // ---- start pixels on free paths (this wave's chunk pool, refilled from the global counter)
             bool need = mine, got = false;
             int px = 0, py = 0, laneFrame = 0;
@@ -2495,12 +2633,20 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
         }
 
         TPT_TSTAMP(tsClass);
-        TPT_TADD(64 + pick * 4 + 1, tsPop, tsClass);
+        TPT_TADD(TPT_TSLOT(pick) + 1, tsPop, tsClass);
         // ---- HitWorld for the rays this batch produced.  A Lambert batch first runs its light loop (Test.cpp:96-133), wave-
         //      uniform in j: shadow ray, intersection, shading, all in registers; its last trip intersects the bounce ray.
         int cls = -1;
         unsigned iterRays = 0; // (batched launch: this lane's rays of this iteration, counted for the frame its path belongs to)
         const int nRay = __popcll(__ballot(ray));
+#if defined(TPT_STATS)
+        // [56] rays made by END batches, [57] END batches that intersect their own rays, [58] rays of the others, which cross INT
+        if (lane == 0 && pick == Q_END) {
+            TPT_COUNT(56, nRay);
+            TPT_COUNT(57, nRay >= TPT_Q_FUSE_MIN ? 1 : 0);
+            TPT_COUNT(58, nRay >= TPT_Q_FUSE_MIN ? 0 : nRay);
+        }
+#endif
         if (pick == Q_FREE || pick == Q_INT || pick == Q_LAMBERT || nRay >= TPT_Q_FUSE_MIN) {
             const int nShadow = (pick == Q_LAMBERT && (fc.config & CFG_LIGHT_SAMPLING)) ? sv.nLights : 0;
             int hitId = -1;
@@ -2595,6 +2741,9 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
             cls = Q_INT;
         }
         if (toEnd) cls = Q_END;
+        if constexpr (LAST_CLASS) { // (the ended sample is its pixel's last one: the class that stores the pixel and starts the next)
+            if (cls == Q_END && sample + 1 >= fc.spp) cls = Q_LAST;
+        }
         if (ray || toEnd) {
             const uint32_t w = ((uint32_t)sample & 0x7ffu) | (((uint32_t)depth & 15u) << 11) | ((uint32_t)doMatE << 15) | (((uint32_t)recId & 0xffffu) << 16);
             st[0 * kPaths + p] = mk4(ro.x, ro.y, ro.z, u2f(rng));
@@ -2612,13 +2761,13 @@ __device__ __forceinline__ void traceQueueBody(const KernelArgs& a)
             }
         }
         TPT_TSTAMP(tsInt);
-        TPT_TADD(64 + pick * 4 + 2, tsClass, tsInt);
+        TPT_TADD(TPT_TSLOT(pick) + 2, tsClass, tsInt);
         // (the cold state is global memory, but every wave that can pop this path runs on this CU and shares its L1:
         //  the workgroup-scope release orders the stores before the queue entry becomes visible)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         qPushByClass(q, ctl, mine ? cls : -1, p, lane);
         TPT_TSTAMP(tsPush);
-        TPT_TADD(64 + pick * 4 + 3, tsInt, tsPush);
+        TPT_TADD(TPT_TSLOT(pick) + 3, tsInt, tsPush);
     }
 
     const unsigned waveRays = waveReduceAdd(myRays);

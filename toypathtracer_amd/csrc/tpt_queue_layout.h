@@ -107,6 +107,17 @@ static_assert(TPT_GROUP_DEAL_ENTRIES >= TPT_GROUP_DEAL_CAP, "the flat variants' 
 namespace tpt {
 
 enum { Q_FREE = 0, Q_INT = 1, Q_END = 2, Q_DIEL = 3, Q_METAL = 4, Q_LAMBERT = 5, Q_COUNT = 6 };
+// The frame-pools kernel for scenes staged in LDS (tptFramePoolsKernel<true>: the headline's steady state) alone has a seventh ring:
+// Q_LAST, the ended samples that are their pixel's LAST one.  (Its grouped twin keeps the six: there the split measured slower.)
+// There a path's next class is decided by its sample number where it is pushed, so a popped END batch holds only paths with a
+// further sample -- every lane makes a camera ray, the batch intersects 64 rays of 64 -- and a LAST batch stores its pixels and
+// starts the next pixels in the same lanes (the FREE code), which fills it again.  With one END class a quarter of a batch's lanes
+// at 4 spp went to FREE, and a batch left with fewer than TPT_Q_FUSE_MIN rays sent them all through INT.
+// The ring (TPT_Q_P x 2 B) takes the LDS of TPT_Q_LAST_PATHS path records, which that instantiation gives up: a launch's LDS is its
+// twin's, byte for byte (tptQueueLdsBytes below knows no difference).
+enum { Q_LAST = Q_COUNT, Q_COUNT_POOLS = Q_COUNT + 1 };
+#define TPT_Q_LAST_PATHS ((TPT_Q_P * 2) / (TPT_Q_NF4 * 16))
+static_assert(TPT_Q_LAST_PATHS * TPT_Q_NF4 * 16 == TPT_Q_P * 2, "the seventh ring takes exactly the LDS of the path records it replaces");
 struct QueueCtl {
     unsigned head[8];
     unsigned tail[8];
