@@ -134,14 +134,20 @@ TPT_API int tptLocalRowCount(int screenHeight);
 TPT_API int tptLocalRowToGlobal(int localRow);
 /* Asynchronous draw into a DEVICE buffer holding this rank's tile: localRows*w*4 floats, the
  * accumulation buffer stays resident in HBM across frames.  Enqueued on the context's stream;
- * returns immediately.  Ray counts accumulate in a device counter (tptRayCounterRead). */
+ * returns immediately.  Ray counts accumulate in a device counter (tptRayCounterRead).
+ * Any positive size, sample count and sphere count: with the default configuration the path-queue kernel traces the frame up to
+ * 65535 columns and rows, 2047 samples per pixel and 65534 spheres (what its packed path and pixel records hold); a frame past any
+ * of these is traced by the lane-refill kernel, without a word and with the same bits and ray count (tptGetLaunchInfo shows which
+ * one ran).  tptDraw takes the same route. */
 TPT_API int tptDrawDevice(float time, int frameCount, int screenWidth, int screenHeight, float* deviceTile, unsigned testFlags);
 /* Several frames per launch: frames firstFrame .. firstFrame + nFrames - 1 of the scene and camera as of the last tptUpdate
  * (what the reference's main loop renders while nothing moves: TestWin.cpp:313-316 with kFlagAnimate off), traced by ONE
  * kernel launch and blended into the tile in frame order by one more.  Bit-identical to nFrames tptDrawDevice calls; a
  * launch's fixed costs (pool ramp-up and drain, no launch shorter than its longest pixel, queue latencies) are paid once
  * per batch instead of once per frame -- what bounds small frames and tiles of a sharded frame.  Path-queue kernel only
- * (the default); frames up to 8192 x 8192; kFlagAnimate is refused (the scene changes every frame: tptDrawDeviceAnimation). */
+ * (the default; so at most 2047 samples per pixel and 65534 spheres, unless the seeds are row-serial); frames up to 8192 x 8192, 32
+ * to a launch (a longer call is several launches); kFlagAnimate is refused (the scene changes every frame: tptDrawDeviceAnimation).
+ * nFrames = 1 is tptDrawDevice, with everything it accepts. */
 TPT_API int tptDrawDeviceBatch(float time, int firstFrame, int nFrames, int screenWidth, int screenHeight, float* deviceTile, unsigned testFlags);
 /* Frames of an ANIMATED scene at times the caller knows (a clip at a fixed frame rate, a video export, a dataset), up to 32 per
  * launch.  Frame j (0 <= j < nFrames) is bit-identical to tptUpdate(times[j], firstFrame + j, w, h, testFlags) followed by
@@ -174,8 +180,8 @@ TPT_API int tptDrawDeviceAnimation(int firstFrame, int nFrames, const float* tim
  * there before the call finishes before the planes are written, work enqueued after it sees them.  Frames traced ahead and
  * stream-batch planes are dropped (the call does not continue a sequence); the camera and the scene are unchanged.
  * Refused (non-zero, tptGetLastError, no tile or plane written): deviceTile NULL or both planes NULL, no tptUpdate at this size, w or h
- * over 8192, row-serial seeds, the forward fold, a kernel variant other than the path-queue kernel, spp over 2047, row sharding or a
- * communicator, a tile mirror. */
+ * over 8192, row-serial seeds, the forward fold, a kernel variant other than the path-queue kernel, spp over 2047, more than 65534
+ * spheres, row sharding or a communicator, a tile mirror. */
 TPT_API int tptDrawDeviceAov(float time, int frameCount, int screenWidth, int screenHeight, float* deviceTile,
                              float* deviceAlbedo, float* deviceNormalDepth, unsigned testFlags);
 /* An edge-avoiding a-trous wavelet filter (Dammertz et al., HPG 2010) of a tile, guided by the planes of tptDrawDeviceAov.  All five
@@ -762,7 +768,7 @@ TPT_API int tptAdaptiveSamplesDevice(int screenWidth, int screenHeight, const fl
  * own camera is not changed; frames traced ahead and stream-batch planes are dropped (the call does not continue a sequence).
  * Refused (non-zero, tptGetLastError, no tile written): nViews outside 1..32, views or deviceTiles NULL, no tptUpdate at this size,
  * w or h over 8192, colour planes over 4096 MiB, row-serial seeds, the forward fold, a kernel variant other than the path-queue
- * kernel, row sharding or a communicator, a tile mirror. */
+ * kernel, spp over 2047, more than 65534 spheres, row sharding or a communicator, a tile mirror. */
 TPT_API int tptDrawDeviceViews(float time, int frameCount, int screenWidth, int screenHeight, int nViews, const float* views,
                                float* deviceTiles, int64_t* deviceViewRays, unsigned testFlags);
 /* Frame pipelining of the asynchronous path: the trace kernels of up to `frames` consecutive tptDrawDevice

@@ -52,8 +52,9 @@ def golden_scene():
     return z["spheres"], z["materials"], z["camera_640x360"], z["emissives"]
 
 
-def oracle_frames(o, w, h, spp, frames, flags=FLAG_PROGRESSIVE, time=0.0, spheres=None, mats=None, cam=None, **kw):
-    """frames 0..frames-1 with the oracle on a zeroed buffer; applies kFlagAnimate like UpdateTest does."""
+def oracle_frames(o, w, h, spp, frames, flags=FLAG_PROGRESSIVE, time=0.0, spheres=None, mats=None, cam=None, first=0, bb=None, **kw):
+    """frames first..first+frames-1 (first: 0) with the oracle on a zeroed buffer (bb: on a copy of this tile); applies kFlagAnimate like
+    UpdateTest does."""
     if spheres is None:
         spheres, mats = o.default_scene()
     else:
@@ -62,10 +63,10 @@ def oracle_frames(o, w, h, spp, frames, flags=FLAG_PROGRESSIVE, time=0.0, sphere
         o.animate(spheres, time)
     if cam is None:
         cam = o.default_camera(w, h)
-    bb = np.zeros((h, w, 4), np.float32)
+    bb = np.zeros((h, w, 4), np.float32) if bb is None else np.ascontiguousarray(bb, np.float32).copy()
     total = 0
     per_frame = []
-    for f in range(frames):
+    for f in range(first, first + frames):
         r, _ = o.render(spheres, mats, cam, w, h, spp, f, flags, backbuffer=bb, **kw)
         total += r
         per_frame.append(r)

@@ -50,12 +50,14 @@ def stress_camera(oracle, w, h):
     return c, oracle.camera(c["look_from"], c["look_at"], (0, 1, 0), c["vfov"], w / h, c["aperture"], c["focus_dist"])
 
 
-def wanted(oracle, key, s, m, w, h, spp, frames, cam=None, fold=FOLD_RECURSIVE, light_sampling=True):
-    """the oracle's frames of a scene, rendered once per module and shared between the kernels that draw it -> (image, per-frame rays)"""
-    key = (key, w, h, spp, frames, fold, light_sampling)
+def wanted(oracle, key, s, m, w, h, spp, frames, cam=None, fold=FOLD_RECURSIVE, light_sampling=True, first_frame=0, prev=None):
+    """the oracle's frames of a scene (first_frame .. first_frame + frames - 1, blended into a copy of `prev`: a zeroed tile when None),
+    rendered once per module and shared between the kernels that draw it -> (image, per-frame rays).  The caller's key tells two `prev`
+    apart."""
+    key = (key, w, h, spp, frames, fold, light_sampling, first_frame, prev is not None)
     if key not in _wanted:
         _, bo, pero = oracle_frames(oracle, w, h, spp, frames, spheres=s, mats=m, cam=cam, seed_mode=SEED_PER_PIXEL, fold_mode=fold,
-                                    light_sampling=light_sampling)
+                                    light_sampling=light_sampling, first=first_frame, bb=prev)
         assert np.isfinite(bo).all(), "the oracle's own image is not finite: the scene is no fair test (tests/lights_lib.py)"
         bo.setflags(write=False)
         _wanted[key] = (bo, pero)
@@ -71,9 +73,11 @@ def restore(tpt):
     tpt.set_config(True, 0.9, False)
 
 
-def draw(tpt, oracle, key, s, m, w, h, spp, frames, variant=DEFAULT, fold=FOLD_RECURSIVE, stress=False, light_sampling=True, camera=None):
+def draw(tpt, oracle, key, s, m, w, h, spp, frames, variant=DEFAULT, fold=FOLD_RECURSIVE, stress=False, light_sampling=True, camera=None,
+         first_frame=0, prev=None):
     """the scene through DrawTest with this kernel, held against the oracle -> (launch_info(), scene_info(), per-frame rays); camera: the
-    keyword arguments of tpt.set_camera (stress: STRESS_CAMERA), None for the default camera"""
+    keyword arguments of tpt.set_camera (stress: STRESS_CAMERA), None for the default camera; the frames are first_frame ..
+    first_frame + frames - 1, blended into a copy of the tile `prev` (a zeroed one when None)"""
     cam = None
     try:
         tpt.set_scene(s, m)
@@ -87,11 +91,11 @@ def draw(tpt, oracle, key, s, m, w, h, spp, frames, variant=DEFAULT, fold=FOLD_R
         tpt.set_kernel_variant(*variant)
         tpt.set_fold_mode(fold)
         tpt.set_config(light_sampling, 0.9, False)
-        _, bb, per = gpu_frames(tpt, w, h, frames)
+        _, bb, per = gpu_frames(tpt, w, h, frames, bb=None if prev is None else np.ascontiguousarray(prev, np.float32).copy(), first=first_frame)
         info, scene = tpt.launch_info(), tpt.scene_info()
     finally:
         restore(tpt)
-    bo, pero = wanted(oracle, key, s, m, w, h, spp, frames, cam, fold, light_sampling)
+    bo, pero = wanted(oracle, key, s, m, w, h, spp, frames, cam, fold, light_sampling, first_frame, prev)
     assert per == pero, (key, variant, per, pero)
     assert bb.tobytes() == bo.tobytes(), describe_image_mismatch(bb, bo)
     return info, scene, per

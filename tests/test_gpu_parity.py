@@ -14,11 +14,12 @@ from oracle_lib import (FLAG_ANIMATE, FLAG_PROGRESSIVE, FOLD_FORWARD, FOLD_RECUR
 pytestmark = pytest.mark.gpu
 
 
-def gpu_frames(tpt, w, h, frames, flags=FLAG_PROGRESSIVE, time=0.0, bb=None):
+def gpu_frames(tpt, w, h, frames, flags=FLAG_PROGRESSIVE, time=0.0, bb=None, first=0):
+    """frames first .. first + frames - 1 through DrawTest into bb (zeroed when not given) -> (rays, bb, per-frame rays)"""
     if bb is None:
         bb = np.zeros((h, w, 4), np.float32)
     total, per = 0, []
-    for f in range(frames):
+    for f in range(first, first + frames):
         tpt.UpdateTest(time, f, w, h, flags)
         r = tpt.DrawTest(time, f, w, h, bb, flags)
         total += r
@@ -814,14 +815,16 @@ def test_config_switches_on_the_gpu(tpt_defaults, oracle, case):
 
 
 # ---- several frames per launch (tptDrawDeviceBatch): the same bits as one tptDrawDevice per frame
-def _batched(tpt, w, h, sizes, flags=FLAG_PROGRESSIVE, spp=4):
+def _batched(tpt, w, h, sizes, flags=FLAG_PROGRESSIVE, spp=4, first=0, prev=None):
+    """tptDrawDeviceBatch once per entry of `sizes`, consecutive frames from `first`, on a zeroed tile (prev: on a copy of this one) ->
+    (rays, tile)"""
     import torch
-    tile = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda")
+    tile = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda") if prev is None else torch.from_numpy(np.ascontiguousarray(prev)).cuda()
     torch.cuda.synchronize()
     tpt.set_samples_per_pixel(spp)
     r0 = tpt.ray_counter_read()
-    tpt.UpdateTest(0.0, 0, w, h, flags)
-    f = 0
+    tpt.UpdateTest(0.0, first, w, h, flags)
+    f = first
     for n in sizes:
         tpt.draw_device_batch(0.0, f, n, w, h, tile.data_ptr(), flags)
         f += n
