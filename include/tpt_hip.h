@@ -138,7 +138,13 @@ TPT_API int tptLocalRowToGlobal(int localRow);
  * Any positive size, sample count and sphere count: with the default configuration the path-queue kernel traces the frame up to
  * 65535 columns and rows, 2047 samples per pixel and 65534 spheres (what its packed path and pixel records hold); a frame past any
  * of these is traced by the lane-refill kernel, without a word and with the same bits and ray count (tptGetLaunchInfo shows which
- * one ran).  tptDraw takes the same route. */
+ * one ran).  tptDraw takes the same route.
+ * The blend is the reference's (Test.cpp:293-295), tile.rgb = tile.rgb * lerp + colour * (1 - lerp) in binary32, and it READS the tile
+ * even where lerp is 0 (frame 0, or no kFlagProgressive): a NaN or an infinity the caller left in the tile comes out as NaN
+ * (inf * 0) also there, while every finite previous value, -0 and subnormals included, leaves frame 0's colour as it is.  The
+ * tile's alpha is returned bit for bit -- a NaN's payload included; no arithmetic touches it.  The same holds for tptDrawDeviceBatch,
+ * tptDrawDeviceBatchMoments (also for its moments' .w, and for all four channels of its guide planes' previous values) and
+ * tptDrawDeviceAdaptive (with its own lerp factor), and a tile mirror (tptSetTileMirror) receives the blended pixel with that alpha. */
 TPT_API int tptDrawDevice(float time, int frameCount, int screenWidth, int screenHeight, float* deviceTile, unsigned testFlags);
 /* Several frames per launch: frames firstFrame .. firstFrame + nFrames - 1 of the scene and camera as of the last tptUpdate
  * (what the reference's main loop renders while nothing moves: TestWin.cpp:313-316 with kFlagAnimate off), traced by ONE
@@ -800,7 +806,10 @@ TPT_API int tptSetStreamBatching(int enable);
 /* Display conversion of a device-resident FULL image (w*h float4, row 0 = bottom) into w*h RGBA8 in device memory,
  * top row first: the reference's own conversion for its C++ path, Cpp/Emscripten/main.cpp:63-79
  * (c8 = min(sqrtf(c)*255, 255), alpha 255).  Enqueued on the context's stream; 4x less data to download than
- * the float buffer. */
+ * the float buffer.  Per colour channel, in binary32: s = sqrt(c) * 255 (a correctly rounded root); a channel whose s is NaN -- c a
+ * NaN or negative, which the reference converts with undefined behaviour -- or not > 0 (c either zero) is 0: a poisoned pixel shows
+ * black, never white; every other channel is min(s, 255) truncated, so +infinity is 255.  The tile's alpha is ignored whatever it
+ * holds (NaN included): every output alpha is 255.  The tile is not written, and nothing is written past w*h*4 bytes. */
 TPT_API int tptDisplayRGBA8(const float* deviceTile, int screenWidth, int screenHeight, unsigned char* deviceRGBA);
 /* Synchronise the stream and return the monotonic total of rays traced by this context. */
 TPT_API int tptRayCounterRead(int64_t* outTotalRays);

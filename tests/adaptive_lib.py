@@ -78,8 +78,9 @@ class AdaptiveChecker:
         return counts, var, total
 
 
-def plan_numpy(moments, target_error, min_samples, max_samples):
-    """the plan function of include/tpt_hip.h on whole arrays -> (counts, variance plane, total)"""
+def plan_numpy(moments, target_error, min_samples, max_samples, details=False):
+    """the plan function of include/tpt_hip.h on whole arrays -> (counts, variance plane, total); details: also a dict of the
+    intermediates b*b, r, R, need and extra (every pixel's, counted or not) and of `counted` (valid and gw > 0)"""
     f32 = np.float32
     h, w = moments.shape[:2]
     with np.errstate(all="ignore"):
@@ -116,6 +117,9 @@ def plan_numpy(moments, target_error, min_samples, max_samples):
         out = np.zeros((h, w, 4), f32)
         out[..., 1] = np.where(valid, var / np.where(valid, S, f32(1)), f32(0))
         out[..., 3] = np.where(valid, S, f32(0))
+        inner = dict(bb=(b * b).astype(f32), r=r, R=R, need=need, extra=extra, counted=valid & (gw > 0))
+    if details:
+        return n, out, int(n.astype(np.int64).sum()), inner
     return n, out, int(n.astype(np.int64).sum())
 
 

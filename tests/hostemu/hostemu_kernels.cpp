@@ -276,9 +276,9 @@ void runDisplay(void* p)
 {
     const DisplayJob& J = *static_cast<const DisplayJob*>(p);
     auto to8 = [](float v) -> uint32_t {
-        float s = tsqrt(v) * 255.0f;
-        s = s < 255.0f ? s : 255.0f;
-        return s > 0.0f ? (uint32_t)s : 0u;
+        const float s = tsqrt(v) * 255.0f;
+        if (!(s > 0.0f)) return 0u; // (first: tptDisplayKernel says why)
+        return (uint32_t)(s < 255.0f ? s : 255.0f);
     };
     for (int i = 0; i < J.width * J.height; ++i) {
         const int y = i / J.width, x = i - y * J.width;

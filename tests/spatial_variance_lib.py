@@ -68,15 +68,17 @@ def estimated(moments, samples_per_frame=1.0, min_samples=2.0):
 
 
 def spatial_variance_numpy(moments, normal_depth=None, samples_per_frame=1.0, min_samples=2.0, radius=1, sigma_normal=0.0,
-                           sigma_depth=0.0):
-    """the shapes of SpatialVarianceChecker.run"""
+                           sigma_depth=0.0, details=False):
+    """the shapes of SpatialVarianceChecker.run; details: (the output, a dict of the intermediates est, any (a tap counted), W, S1, S2,
+    e1 -- the last four of every pixel, estimated or not).  It takes any sigma and any counts, also those the call refuses"""
     if moments.ndim == 3:
-        return spatial_variance_numpy(moments[None], None if normal_depth is None else normal_depth[None], samples_per_frame, min_samples,
-                                      radius, sigma_normal, sigma_depth)[0]
+        out = spatial_variance_numpy(moments[None], None if normal_depth is None else normal_depth[None], samples_per_frame, min_samples,
+                                     radius, sigma_normal, sigma_depth, details)
+        return (out[0][0], {k: v[0] for k, v in out[1].items()}) if details else out[0]
     F, h, w = moments.shape[:3]
     r = int(radius)
-    in_, id_ = inv2(sigma_normal), inv2(sigma_depth)
     with np.errstate(all="ignore"):
+        in_, id_ = inv2(sigma_normal), inv2(sigma_depth)
         Vt, N = own_variance(moments)
         est = estimated(moments, samples_per_frame, min_samples)
         mx, my = moments[..., 0], moments[..., 1]
@@ -109,7 +111,8 @@ def spatial_variance_numpy(moments, normal_depth=None, samples_per_frame=1.0, mi
         v = np.where(ds > 0, ds, f32(0)).astype(f32)
         zero = np.zeros_like(N)
         Ve = np.stack([zero, v / N, zero, N], axis=-1).astype(f32)
-        return np.ascontiguousarray(np.where((est & any_tap)[..., None], Ve, Vt).astype(f32))
+        out = np.ascontiguousarray(np.where((est & any_tap)[..., None], Ve, Vt).astype(f32))
+        return (out, dict(est=est, any=any_tap, W=W, S1=S1, S2=S2, e1=e1)) if details else out
 
 
 def synthetic_case(w, h, frames=1, kind="mixed", seed=0):

@@ -82,9 +82,8 @@ def test_display_conversion_matches_reference_formula(tpt_defaults, tmp_path):
     tpt.display_rgba8(tile.data_ptr(), w, h, out.data_ptr())
     tpt.synchronize()
     bb = tile.cpu().numpy()
-    want = np.empty((h, w, 4), np.uint8)
-    want[..., :3] = np.minimum(np.sqrt(bb[::-1, :, :3]) * np.float32(255), np.float32(255.0)).astype(np.uint8)
-    want[..., 3] = 255
+    from resolve_ranges_lib import display_numpy  # (the formula with its branches written out: tests/test_resolve_ranges.py)
+    want = display_numpy(bb)
     got = out.cpu().numpy()
     assert np.array_equal(got, want)
     assert got[..., :3].max() > 200 and got[..., :3].min() < 80  # a real image, not a constant

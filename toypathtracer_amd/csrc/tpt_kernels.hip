@@ -357,7 +357,9 @@ __global__ void __launch_bounds__(1024) tptChunkOrderKernel(const unsigned* __re
 // Display conversion of the linear float accumulation buffer, the way the reference's C++ path shows it in the
 // browser (Cpp/Emscripten/main.cpp:63-79): rows flipped (row 0 of the buffer is the bottom of the image), cheap sRGB
 // approximation c8 = (uint8) min(sqrtf(c) * 255, 255), alpha 255.  HBM-bound: 16 B read + 4 B written per pixel,
-// one uchar4 per lane, fully coalesced.  Negative / NaN inputs (which the reference would convert with UB) give 0.
+// one uchar4 per lane, fully coalesced.  Negative / NaN inputs (which the reference would convert with UB) give 0, as do both zeros
+// (include/tpt_hip.h states it): the test for them comes FIRST -- `s < 255 ? s : 255` is 255 for a NaN, so the minimum taken first
+// turned a poisoned channel white.  The input's alpha is not read into the result.
 __global__ void __launch_bounds__(256) tptDisplayKernel(const f4* __restrict__ tile, uint32_t* __restrict__ rgba, int width, int height)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -365,9 +367,9 @@ __global__ void __launch_bounds__(256) tptDisplayKernel(const f4* __restrict__ t
     const int y = i / width, x = i - y * width;
     const f4 c = tile[(height - 1 - y) * width + x];
     auto to8 = [](float v) -> uint32_t {
-        float s = tsqrt(v) * 255.0f;
-        s = s < 255.0f ? s : 255.0f; // std::min(s, 255.0f)
-        return s > 0.0f ? (uint32_t)s : 0u;
+        const float s = tsqrt(v) * 255.0f;
+        if (!(s > 0.0f)) return 0u;                 // NaN (the root of a NaN or of a negative), -0, +0
+        return (uint32_t)(s < 255.0f ? s : 255.0f); // std::min(s, 255.0f), truncated
     };
     rgba[i] = to8(c.x) | (to8(c.y) << 8) | (to8(c.z) << 16) | 0xff000000u;
 }
