@@ -710,6 +710,46 @@ TPT_API int tptSpatialVarianceDevice(int screenWidth, int screenHeight, int nFra
                                      const float* deviceFrameMoments, const float* deviceFrameNormalDepth,
                                      float* deviceFrameOutVariance, float samplesPerFrame, float minSamples,
                                      int radius, float sigmaNormal, float sigmaDepth);
+/* THE CALLER'S RAYS: what comes back along ray i, and what it meets first -- the tracer without its camera, for panorama, fisheye,
+ * orthographic and stereo cameras, light and irradiance probes, picking and visibility queries, re-tracing chosen pixels, a cost map.
+ * Every pointer is DEVICE memory, 16-byte aligned (deviceRayCount: 8), read or written by the kernel only:
+ *   deviceRays      nRays records of 8 floats, r0 = {ox, oy, oz, seed bits}, r1 = {dx, dy, dz, unused}
+ *   deviceRadiance  nRays x 4 floats {c.x, c.y, c.z, (float)k}, or NULL: first hits only
+ *   deviceHits      nRays records of 8 floats {pos.x, pos.y, pos.z, t}, {normal.x, normal.y, normal.z, bits(id)}, or NULL
+ *   deviceRayCount  a u64 the call ADDS the sum of its k to, or NULL
+ * The scene is what the context last staged for a launch, as for tptObjectPlaneDevice with times == NULL; light sampling and the
+ * mitsuba switch are tptSetConfig's, the fold tptSetFoldMode's, the HitSpheres variant tptSetKernelVariant's (the lane-refill kernel
+ * traces the rays whatever `persistent` says; all variants give the same bits).  Samples per pixel and the seed mode play no part.
+ * Binary32, in the order written, no FMA, correctly rounded division and square root.  Per ray i:
+ *   state = bits(r0.w), or 1 where that is 0 (an xorshift32 state of 0 never leaves 0, and the reference never has one)
+ *   o = r0.xyz;  d = r1.xyz, taken as given: it is NOT normalised.  Defined for finite o and finite non-zero d; any other record
+ *   affects its own outputs only.
+ *   hits:     id = HitWorld({o, d}, 0.001f, 1e7f) in the reference's arithmetic and order (Maths.cpp:165-202): every sphere in index
+ *             order, the nearest hit wins and equal distances go to the lowest index.  A hit: pos = o + d*t, normal = (pos - centre) *
+ *             invRadius, hits[i] = {pos, t}, {normal, bits(id)}.  A miss: {0, 0, 0, 0}, {0, 0, 0, bits(-1)}.
+ *   radiance: c = 0.0f + Trace({o, d}, depth 0, state, doMaterialE = true) (Test.cpp:195-234; a -0 becomes +0, as in a pixel's
+ *             sample sum); with tptSetFoldMode(1) Trace is the forward fold of the same path.  k = the HitWorld calls of this path,
+ *             shadow rays included (what Test.cpp:122,199 count).  radiance[i] = {c, (float)k}.
+ *   deviceRadiance == NULL: the path ends after its first HitWorld: k = 1, no random number drawn, nothing scattered.
+ *   *deviceRayCount += the sum of k over the call.  The context's own counter (tptRayCounterRead) is not touched.
+ * A ray made as the camera makes pixel (x, y)'s first sample of frame f -- the pixel's seed, two jitter draws, Camera::GetRay, the
+ * state left behind as the seed word -- gives tptDrawDevice's colour of that pixel at 1 spp with per-pixel seeds, frame f, on a
+ * zeroed tile.
+ * Asynchronous on the context stream, ordered like tptDenoiseDevice.  Camera, scene, frames traced ahead, stream batches and row
+ * sharding are left alone; a tptSetScene or tptUpdate that follows does not reach the scene the running call reads.
+ * Refused (non-zero, tptGetLastError names the function, nothing enqueued, no byte written): args NULL; no context; no tptUpdate yet;
+ * nRays outside 1..16777216; flags != 0; deviceRays NULL; deviceRadiance and deviceHits both NULL; an output sharing a byte with
+ * deviceRays or with another output, each taken at its full extent; more than TPT_MAX_LIGHTS emissive spheres; a scene whose LDS
+ * does not fit a compute unit (tptSetKernelVariant(.., .., 0) reads it from global memory). */
+typedef struct tptTraceRaysArgs {
+    int nRays;                          /* 1 .. 16777216 */
+    unsigned flags;                     /* 0 */
+    const float* deviceRays;            /* nRays x 8 floats: {ox, oy, oz, seed bits}, {dx, dy, dz, unused} */
+    float* deviceRadiance;              /* nRays x 4 floats, or NULL: first hits only */
+    float* deviceHits;                  /* nRays x 8 floats, or NULL */
+    unsigned long long* deviceRayCount; /* device u64 the call ADDS its HitWorld calls to, or NULL */
+} tptTraceRaysArgs;
+TPT_API int tptTraceRaysDevice(const tptTraceRaysArgs* args);
 /* ADAPTIVE SAMPLING: tptDrawDeviceMoments with a sample count per pixel, so that the moments can steer the next pass (the counts come
  * from tptAdaptiveSamplesDevice below, or from the caller).  deviceSampleCounts (required): h*w int32 in DEVICE memory, row-major like the
  * tile, read by the kernels only.  Per pixel p, n = deviceSampleCounts[p] clamped to 0 .. 2047 (the path record holds 11 bits of sample

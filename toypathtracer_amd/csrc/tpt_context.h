@@ -300,6 +300,13 @@ struct Context {
     hipEvent_t evFlow[2] = {nullptr, nullptr};
     bool flowCopied[2] = {false, false};
     unsigned flowSeq = 0;
+    // tptTraceRaysDevice: the launch's own bounce-stack spill (KernelArgs::stackBuf, a column per thread of the largest grid seen) and
+    // its own counter block -- 16 words as KernelArgs::work, then the u64 the rays are counted into when the caller gives no word.
+    // Made by the first call, the spill grown on demand (after a drain of the context stream), zeroed when allocated, kept until
+    // tptShutdown.  Only the context stream uses them.
+    f4* dRayStack = nullptr;
+    size_t rayStackBytes = 0;
+    unsigned* dRayWork = nullptr;
     long long aheadHits = 0;            // frames that were found traced ahead when their call arrived (tptGetLookaheadHits)
     // per-frame ray counters of the pending launches, one allocation: [kMaxSlots] AHEAD frames (indexed by the frame's sequence number
     // at enqueue), [2][kMaxBatch] ROW_SERIAL batches (two banks, alternating), [kStreamRing][kStreamBatchMax] STREAM batches (a ring)
@@ -468,6 +475,9 @@ struct AovPlanes {
 int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long long* frameRays, TraceTicket& T, int batch = 1, int rayStride = 0,
                  const BatchTable* table = nullptr, const AovPlanes* aov = nullptr);
 int enqueueResolve(const TraceTicket& T, float* deviceTile, const unsigned long long* frameRays);
+size_t laneRefillLds(KernelArgs& a, bool& ldsScene); // (the lane-refill kernel's plan: chooseKernel, tptTraceRaysDevice)
+bool fitsCuLds(size_t lds);
+int laneRefillOccupancy(bool ldsScene, size_t lds);
 int syncAllStreams();
 int launchTailHelpers();
 int flushShardDeferred(); // tpt_host_shard.cpp: issue the sharded frames tptDrawSharded has accepted but deferred (none: nothing happens)

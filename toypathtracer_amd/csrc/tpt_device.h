@@ -100,12 +100,24 @@ struct KernelArgs {
     // every other launch.
     const unsigned* cutWord = nullptr;
     unsigned cutSerial = 0;
+    // The caller's rays instead of a camera's (tptTraceRaysDevice; the lane-refill kernel through tptLaunchTraceRays): numItems records of
+    // two f4 in device memory, {origin, seed bits} {direction, -}; work item i is ray i, one path each (fc: spp 1, per-pixel seeds,
+    // width 1).  rayRadiance ([numItems] f4, may be null: the paths end after their first HitWorld) receives {colour, HitWorld calls of
+    // the path}, rayHits ([numItems][2] f4, may be null) the first hit {pos, t} {normal, bits(id)}.  No frameColour, no chunk order or
+    // cost, one frame.  Null for every other launch.
+    const f4* rays = nullptr;
+    f4* rayRadiance = nullptr;
+    f4* rayHits = nullptr;
 };
 
 } // namespace tpt
 
 hipError_t tptLaunchTrace(const tpt::KernelArgs& a, int hs, int fold, bool ldsScene, int blocks, size_t lds, hipStream_t stream);
 int tptTraceOccupancy(int hs, int fold, bool ldsScene, size_t lds);
+// tptTraceRaysDevice: tptLaunchTrace's kernels with a.rays given (the ray source of the lane-refill kernel; no kernel of its own).  Weak
+// for the same reason as tptLaunchDenoise below.
+__attribute__((weak)) hipError_t tptLaunchTraceRays(const tpt::KernelArgs& a, int hs, int fold, bool ldsScene, int blocks, size_t lds,
+                                                    hipStream_t stream);
 hipError_t tptLaunchTraceQueue(const tpt::KernelArgs& a, bool ldsScene, int blocks, size_t lds, hipStream_t stream);
 int tptQueueMatrixFilter();
 int tptQueueGroupMatrixBounds(); // 1: this build carries the groups' bounds on the matrix cores (hooks build only)

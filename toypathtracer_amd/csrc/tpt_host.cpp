@@ -462,6 +462,9 @@ int tptShutdown(void)
         g.flowCopied[i] = false;
         if (g.evFlow[i]) { (void)hipEventDestroy(g.evFlow[i]); g.evFlow[i] = nullptr; }
     }
+    (void)hipFree(g.dRayStack); g.dRayStack = nullptr;
+    g.rayStackBytes = 0;
+    (void)hipFree(g.dRayWork); g.dRayWork = nullptr;
     if (g.hViewsStage) (void)hipHostFree(g.hViewsStage);
     g.hViewsStage = nullptr;
     if (g.hCut) (void)hipHostFree(g.hCut); // (the device is idle: hipDeviceSynchronize above, the streams drained since)

@@ -886,6 +886,94 @@ int tptObjectPlaneDevice(int nFrames, const float* times, const void* cameras, i
     return 0;
 }
 
+// Radiance and first hits along the caller's rays (include/tpt_hip.h states them): one launch of the lane-refill kernel on the context
+// stream with the rays as its work items (KernelArgs::rays), planned as chooseKernel plans that kernel for a frame -- LDS scene, bounce
+// stack levels, occupancy -- and sized as sizeGrid sizes it, without the frame pipeline: no colour slot, no trace stream, no blend, no
+// chunk order.  The scene set is the object plane's: what the context last staged, uploaded here if no launch has yet, and from then on
+// the current set, which a later tptUpdate does not touch -- it stages into the ring's next set, as it does under a draw's launch.
+// The launch has a spill buffer and a counter block of its own (Context::dRayStack, dRayWork).  The kernel's last wave re-arms the
+// counters, and two ray calls cannot share the block in flight: both launches are on the context stream, so the second starts after
+// the first has ended.
+int tptTraceRaysDevice(const tptTraceRaysArgs* args)
+{
+    if (requireInit()) return -1;
+    const std::string f("tptTraceRaysDevice");
+    if (!args) return fail(f + ": args is required");
+    const tptTraceRaysArgs& A = *args;
+    if (!g.updated) return fail(f + ": call tptUpdate first");
+    if (A.nRays < 1 || A.nRays > 16777216) return fail(f + ": nRays must lie in 1..16777216");
+    if (A.flags != 0) return fail(f + ": flags must be 0");
+    if (!A.deviceRays) return fail(f + ": deviceRays is required");
+    if (!A.deviceRadiance && !A.deviceHits) return fail(f + ": deviceRadiance or deviceHits is required");
+    // the input and the three outputs, each at its own extent: no output may share a byte with the input or with another output
+    const uintptr_t n = (uintptr_t)A.nRays;
+    const struct { const void* p; uintptr_t bytes; } bufs[4] = {{A.deviceRays, n * 32u}, {A.deviceRadiance, n * 16u}, {A.deviceHits, n * 32u},
+                                                                {A.deviceRayCount, sizeof(unsigned long long)}};
+    for (int i = 0; i < 4; ++i)
+        for (int k = i + 1; k < 4; ++k) {
+            const uintptr_t a = reinterpret_cast<uintptr_t>(bufs[i].p), b = reinterpret_cast<uintptr_t>(bufs[k].p);
+            if (a && b && a < b + bufs[k].bytes && b < a + bufs[i].bytes)
+                return fail(f + (i == 0 ? ": an output overlaps deviceRays" : ": two outputs overlap"));
+        }
+    Context::SceneSet* S = activeSet();
+    if (!S || !S->dev || S->nSpheres < 1) return fail(f + ": no scene staged (call tptUpdate first)");
+    if (S->nLights > TPT_MAX_LIGHTS)
+        return fail(f + ": too many emissive spheres for the LDS light table (" + std::to_string(TPT_MAX_LIGHTS) + " at most)");
+    KernelArgs a = KernelArgs{};
+    a.scene = deviceView();
+    bool ldsScene = false;
+    const size_t lds = laneRefillLds(a, ldsScene);
+    if (!fitsCuLds(lds)) return fail(f + ": scene too large for LDS staging; use tptSetKernelVariant(.., .., 0)");
+    if (!tptLaunchTraceRays) return fail(f + ": this build has no ray launcher");
+
+    memset(&a.fc, 0, sizeof a.fc); // (the camera plays no part)
+    a.fc.width = a.fc.height = 1;
+    a.fc.spp = 1; // with per-pixel seeds and one sample lanePost ends a lane after one path
+    a.fc.invWidth = a.fc.invHeight = a.fc.invSpp = 1.0f;
+    a.fc.seedMode = SEED_PER_PIXEL;
+    a.fc.config = g.config;
+    a.nLocalRows = 1; a.stripeRows = 1; a.stripeStride = 1; a.tilesX = 1;
+    a.numItems = A.nRays;
+    a.batchFrames = 1;
+    a.laneCap = 64;
+    // sizeGrid's chunks: 256 rays a chunk, 64 when that leaves a resident wave fewer than eight
+    const int occ = laneRefillOccupancy(ldsScene, lds), resident = g.traceCUs * occ;
+    a.chunkSize = a.numItems / TPT_CHUNK_PIXELS < 8 * resident ? 64 : TPT_CHUNK_PIXELS;
+    a.chunkShift = a.chunkSize == 64 ? 6 : 8;
+    a.numChunks = (a.numItems + a.chunkSize - 1) / a.chunkSize;
+    a.chunksPerFrame = a.numChunks;
+    int blocks = a.numChunks < resident ? a.numChunks : resident;
+    if (blocks < 1) blocks = 1;
+    a.totalWaves = (unsigned)blocks;
+
+    if (!g.dRayWork) {
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dRayWork), 16 * sizeof(unsigned) + sizeof(unsigned long long)));
+        HIPCHK(hipMemsetAsync(g.dRayWork, 0, 16 * sizeof(unsigned) + sizeof(unsigned long long), g.stream));
+    }
+    const bool needStack = g.foldMode == FOLD_RECURSIVE && a.ldsStackLevels < TPT_MAX_DEPTH;
+    const size_t stackBytes = needStack ? (size_t)blocks * TPT_BLOCK * (size_t)(TPT_MAX_DEPTH - a.ldsStackLevels) * sizeof(f4) : 0;
+    if (stackBytes > g.rayStackBytes) {
+        HIPCHK(hipStreamSynchronize(g.stream)); // (an earlier ray call may still spill into the buffer that goes)
+        (void)hipFree(g.dRayStack);
+        g.dRayStack = nullptr;
+        g.rayStackBytes = 0;
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dRayStack), stackBytes));
+        g.rayStackBytes = stackBytes;
+        HIPCHK(hipMemsetAsync(g.dRayStack, 0, stackBytes, g.stream));
+    }
+    a.stackBuf = needStack ? g.dRayStack : nullptr;
+    a.stackStride = needStack ? blocks * TPT_BLOCK : 0;
+    a.work = g.dRayWork;
+    a.rayCounter = A.deviceRayCount ? A.deviceRayCount : reinterpret_cast<unsigned long long*>(g.dRayWork + 16);
+    a.rays = reinterpret_cast<const f4*>(A.deviceRays);
+    a.rayRadiance = reinterpret_cast<f4*>(A.deviceRadiance);
+    a.rayHits = reinterpret_cast<f4*>(A.deviceHits);
+    int rc = enqueueSceneUpload(g.stream);
+    if (rc) return rc;
+    HIPCHK(tptLaunchTraceRays(a, g.hs, g.foldMode, ldsScene, blocks, lds, g.stream));
+    return 0;
+}
+
 // The animated scene's displacement per sphere between two times (include/tpt_hip.h states it): host arithmetic only.
 int tptObjectMotionTable(float time, float prevTime, unsigned testFlags, float* outTable, int capacity)
 {

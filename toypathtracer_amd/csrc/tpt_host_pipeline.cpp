@@ -134,19 +134,39 @@ static int queueLightRoom(KernelArgs a, bool ldsScene)
     return room < (size_t)TPT_MAX_LIGHTS ? (int)room : TPT_MAX_LIGHTS;
 }
 
+// The lane-refill kernel's share of the plan (chooseKernel for a launch that is not queued; tptTraceRaysDevice): whether the scene is
+// staged in LDS, the bounce-stack levels kept there (a.ldsStackLevels), and the bytes both take.
+size_t laneRefillLds(KernelArgs& a, bool& ldsScene)
+{
+    // LDS scene staging: default when {centre, r^2} + 1/r (20 B per padded sphere) + 48 B of material per sphere fit in
+    // 40 KB (46 spheres: 3.2 KB; up to ~600 spheres)
+    const int nPad = a.scene.nPairs * 2;
+    ldsScene = g.ldsScene < 0 ? ((size_t)nPad * 20 + (size_t)a.scene.nSpheres * 48 <= 40960) : (g.ldsScene != 0);
+    if (a.scene.nGroups > 0) ldsScene = false; // the LDS-staging kernels are built without the grouped traversal
+    // bounce stack: the lane-refill kernel keeps the first levels in LDS and spills the rare deep ones to global memory
+    a.ldsStackLevels = g.foldMode == FOLD_RECURSIVE ? g.ldsStackLevels : TPT_MAX_DEPTH;
+    return tptLdsBytes(a, g.foldMode, ldsScene);
+}
+bool fitsCuLds(size_t lds) { return lds <= kCuLdsBytes; }
+// ... and its workgroups per CU at that size, as the runtime answers for the context's instantiation
+// (the runtime's answer is remembered per kernel and LDS size, to the 16 bytes the sizes are multiples of: a coarser key once
+//  handed a launch the occupancy of a neighbour 32 bytes smaller)
+int laneRefillOccupancy(bool ldsScene, size_t lds)
+{
+    const int key = (g.hs ? 8 : 0) | (g.foldMode ? 4 : 0) | (ldsScene ? 1 : 0) | ((int)(lds / 16) << 5);
+    auto it = g.occCache.find(key);
+    if (it != g.occCache.end()) return it->second;
+    const int occ = tptTraceOccupancy(g.hs, g.foldMode, ldsScene, lds);
+    g.occCache[key] = occ;
+    return occ;
+}
+
 // Which kernel runs this frame, how much LDS it takes, how many workgroups fit on a CU.
 int chooseKernel(FramePlan& P)
 {
     KernelArgs& a = P.a;
     P.rowSerial = g.seedMode == SEED_ROW_SERIAL;
-    // LDS scene staging: default when {centre, r^2} + 1/r (20 B per padded sphere) + 48 B of material per sphere fit in
-    // 40 KB (46 spheres: 3.2 KB; up to ~600 spheres)
-    const int nPad = a.scene.nPairs * 2;
-    P.ldsScene = g.ldsScene < 0 ? ((size_t)nPad * 20 + (size_t)a.scene.nSpheres * 48 <= 40960) : (g.ldsScene != 0);
-    if (a.scene.nGroups > 0) P.ldsScene = false; // the LDS-staging kernels are built without the grouped traversal
-    // bounce stack: the lane-refill kernel keeps the first levels in LDS and spills the rare deep ones to global memory
-    a.ldsStackLevels = g.foldMode == FOLD_RECURSIVE ? g.ldsStackLevels : TPT_MAX_DEPTH;
-    const size_t ldsV1 = tptLdsBytes(a, g.foldMode, P.ldsScene);
+    const size_t ldsV1 = laneRefillLds(a, P.ldsScene);
     // path-queue kernel: it packs a pixel as x | y << 16 and a path id as 16 bits (larger frames take the lane-refill kernel), and its
     // path record 16 bits of sphere id
     // (a launch with a sample count per pixel, tptDrawDeviceAdaptive: the context's spp plays no part)
@@ -190,16 +210,7 @@ int chooseKernel(FramePlan& P)
     if (P.queued) {
         P.occ = queueOccupancy(P.lds); // (arithmetic: nothing to remember)
     } else {
-        // (the runtime's answer is remembered per kernel and LDS size, to the 16 bytes the sizes are multiples of: a coarser key once
-        //  handed a launch the occupancy of a neighbour 32 bytes smaller)
-        const int key = (g.hs ? 8 : 0) | (g.foldMode ? 4 : 0) | (P.ldsScene ? 1 : 0) | ((int)(P.lds / 16) << 5);
-        auto it = g.occCache.find(key);
-        if (it == g.occCache.end()) {
-            P.occ = tptTraceOccupancy(g.hs, g.foldMode, P.ldsScene, P.lds);
-            g.occCache[key] = P.occ;
-        } else {
-            P.occ = it->second;
-        }
+        P.occ = laneRefillOccupancy(P.ldsScene, P.lds);
     }
     P.threadsPerBlock = P.queued ? tptQueueThreadsPerBlock() : TPT_BLOCK;
     return 0;

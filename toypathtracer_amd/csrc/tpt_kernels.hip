@@ -1279,7 +1279,15 @@ tptTraceKernel(const KernelArgs a)
                 int want = __popcll(needMask);
                 int avail = chunkEnd - chunkNext;
                 int take = want < avail ? want : avail;
-                if (need && rank < take) {
+                if (a.rays) { // (launch-uniform: a scalar branch)
+                    // tptTraceRaysDevice: item i is the caller's ray i, two 16-B records a lane, consecutive lanes consecutive rays
+                    if (need && rank < take) {
+                        const size_t i = (size_t)(chunkNext + rank);
+                        laneBeginRay(L, a.rays[2 * i], a.rays[2 * i + 1], chunkNext + rank);
+                        L.rays0 = L.rays;
+                        need = false;
+                    }
+                } else if (need && rank < take) {
                     int x, ly;
                     if (mapItem(a, chunkNext + rank, x, ly)) {
                         laneBeginPixel(L, fc, x, localRowToGlobal(a, ly), chunkFrame * a.framePlane + ly * fc.width + x, true);
@@ -1294,7 +1302,33 @@ tptTraceKernel(const KernelArgs a)
             }
             if (__ballot(L.active) == 0ull) break;
             if (L.active) {
-                if (laneStep<HSX, FOLD>(L, sv, fc, stack)) {
+                // laneStep's two halves, so that a caller's ray (tptTraceRaysDevice) can store its first hit between them
+                TPT_STAT(ST_STEP);
+                if (L.needCamera) laneCamera<FOLD>(L, fc);
+                const bool firstOfRay = a.rays != nullptr && L.depth == 0 && L.kind == KIND_MAIN;
+                float t;
+                int id;
+                if (HSX != HS_SIMPLE && firstOfRay && !rayDirFitsFilter(L.dir))
+                    id = hitSpheres<HS_SIMPLE>(sv, L.orig, L.dir, TPT_MIN_T, TPT_MAX_T, t); // (a direction the filter is not made for)
+                else
+                    id = hitSpheres<HSX>(sv, L.orig, L.dir, TPT_MIN_T, TPT_MAX_T, t);
+                L.rays++;
+                if (firstOfRay && a.rayHits) {
+                    f4 h0, h1;
+                    rayHitRecord(sv, L.orig, L.dir, id, t, h0, h1);
+                    a.rayHits[2 * (size_t)L.pix] = h0;
+                    a.rayHits[2 * (size_t)L.pix + 1] = h1;
+                }
+                // (without a radiance buffer the path ends after its first HitWorld: nothing drawn, nothing scattered)
+                const bool done = (firstOfRay && !a.rayRadiance) || lanePost<FOLD>(L, id, t, sv, fc, stack);
+                if (done && a.rays) {
+                    if (a.rayRadiance) {
+                        f4 v;
+                        v.x = L.col.x; v.y = L.col.y; v.z = L.col.z; v.w = (float)(L.rays - L.rays0);
+                        a.rayRadiance[L.pix] = v; // one 16-B store per ray: {0.0f + Trace, the path's HitWorld calls}
+                    }
+                    L.active = false;
+                } else if (done) {
                     storeColour(a, L);
                     if (rowSerial && L.x + 1 < fc.width) {
                         laneBeginPixel(L, fc, L.x + 1, L.y, L.pix + 1, false);
@@ -3136,6 +3170,12 @@ hipError_t tptLaunchTrace(const KernelArgs& a, int hs, int fold, bool ldsScene, 
 int tptTraceOccupancy(int hs, int fold, bool ldsScene, size_t lds)
 {
     TPT_DISPATCH(occupancyOne, lds);
+}
+// tptTraceRaysDevice: the same eight instantiations, fed from a.rays
+hipError_t tptLaunchTraceRays(const KernelArgs& a, int hs, int fold, bool ldsScene, int blocks, size_t lds, hipStream_t stream)
+{
+    if (!a.rays || (!a.rayRadiance && !a.rayHits)) return hipErrorInvalidValue;
+    TPT_DISPATCH(launchOne, a, blocks, lds, stream);
 }
 
 // One launch of a path-queue kernel: its dynamic LDS, then the grid.

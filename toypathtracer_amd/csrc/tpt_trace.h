@@ -919,6 +919,52 @@ TPT_HD void laneCamera(Lane& L, const FrameConsts& fc)
     }
 }
 
+// Start a caller's ray (tptTraceRaysDevice) instead of a pixel: r0 = {origin, seed bits}, r1 = {direction, -}, `index` the ray's
+// place in the caller's buffers.  One path from this ray as given -- no camera, no jitter, the direction not normalised -- so the lane
+// is left where laneCamera leaves it, with the fold's state of both fold modes (the unused one is dead code in either instantiation).
+// An xorshift32 state of 0 never leaves 0 and the reference never has one: such a seed word counts as 1.
+TPT_HD void laneBeginRay(Lane& L, f4 r0, f4 r1, int index)
+{
+    const uint32_t seed = f2u(r0.w);
+    L.rng = seed ? seed : 1u;
+    L.orig = mk3(r0.x, r0.y, r0.z);
+    L.dir = mk3(r1.x, r1.y, r1.z);
+    L.x = 0; L.y = 0; L.pix = index;
+    L.sample = 0;
+    L.col = mk3(0, 0, 0);
+    L.depth = 0;
+    L.doMatE = true;
+    L.kind = KIND_MAIN;
+    L.needCamera = false;
+    L.active = true;
+    L.radiance = mk3(0, 0, 0);
+    L.throughput = mk3(1, 1, 1);
+    L.sp = 0;
+}
+// The two-phase filter's argument (phase1Pair, the group bounds, the matrix table) is made for directions of unit length, which every
+// ray the tracer generates itself has.  A caller's direction that is not (|d|^2 outside 1 -+ 1e-5, NaN included) takes the exact test
+// for every sphere on its first HitWorld; whatever the path does from there has a direction of the tracer's own.
+TPT_HD bool rayDirFitsFilter(f3 d)
+{
+    const float dd = d.x * d.x + d.y * d.y + d.z * d.z;
+    return dd >= 0.99999f && dd <= 1.00001f;
+}
+// A caller's ray's first-hit record (tptTraceRaysDevice): {pos, t} {normal, bits(id)} as HitSpheres finishes them (Maths.cpp:195-197),
+// all zero with bits(-1) for a miss.
+TPT_HD void rayHitRecord(const SceneView& sv, f3 o, f3 d, int id, float t, f4& h0, f4& h1)
+{
+    h0.x = h0.y = h0.z = h0.w = 0.0f;
+    h1.x = h1.y = h1.z = 0.0f;
+    h1.w = u2f((uint32_t)id);
+    if (id >= 0) {
+        const f4 s = sv.sph4[id];
+        const f3 pos = o + d * t;
+        const f3 normal = (pos - mk3(s.x, s.y, s.z)) * sv.invR[id];
+        h0.x = pos.x; h0.y = pos.y; h0.z = pos.z; h0.w = t;
+        h1.x = normal.x; h1.y = normal.y; h1.z = normal.z;
+    }
+}
+
 // Everything after HitWorld for one ray of this lane: Scatter / light sampling / bounce / fold.
 // Returns true when the lane's pixel is complete (L.col then holds the sum over spp samples).
 // POS_GIVEN: L.orig already holds the hit position orig + dir * t (the path-queue kernel computes it right after the
