@@ -723,7 +723,9 @@ TPT_API int tptSpatialVarianceDevice(int screenWidth, int screenHeight, int nFra
  * Binary32, in the order written, no FMA, correctly rounded division and square root.  Per ray i:
  *   state = bits(r0.w), or 1 where that is 0 (an xorshift32 state of 0 never leaves 0, and the reference never has one)
  *   o = r0.xyz;  d = r1.xyz, taken as given: it is NOT normalised.  Defined for finite o and finite non-zero d; any other record
- *   affects its own outputs only.
+ *   affects its own outputs only: its records are written, its k is counted, its path ends within the depth limit.  A defined ray
+ *   whose arithmetic leaves binary32's range (|d|^2 overflows for a component near 3e38, underflows to 0 below 1e-23) gets what that
+ *   arithmetic gives, Inf and NaN included; the bit pattern of a NaN in an output is not specified.
  *   hits:     id = HitWorld({o, d}, 0.001f, 1e7f) in the reference's arithmetic and order (Maths.cpp:165-202): every sphere in index
  *             order, the nearest hit wins and equal distances go to the lowest index.  A hit: pos = o + d*t, normal = (pos - centre) *
  *             invRadius, hits[i] = {pos, t}, {normal, bits(id)}.  A miss: {0, 0, 0, 0}, {0, 0, 0, bits(-1)}.
