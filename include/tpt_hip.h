@@ -752,6 +752,63 @@ typedef struct tptTraceRaysArgs {
     unsigned long long* deviceRayCount; /* device u64 the call ADDS its HitWorld calls to, or NULL */
 } tptTraceRaysArgs;
 TPT_API int tptTraceRaysDevice(const tptTraceRaysArgs* args);
+/* OTHER LENSES: tptDrawDevice's contract with a panorama (equirectangular), fisheye (equidistant) or orthographic lens in the
+ * camera's place.  All tptSetSamplesPerPixel samples of a pixel come from the pixel's own random stream in one launch and are blended
+ * into the caller's tile; nothing is made on the host and no ray record is uploaded.  deviceTile: h*w*4 floats in DEVICE memory, row 0
+ * at the bottom, 16-byte aligned; deviceRayCount: a device u64 (8-byte aligned) the call ADDS its HitWorld calls to, or NULL.
+ * The scene is what the context last staged for a launch, as for tptTraceRaysDevice; light sampling and the mitsuba switch are
+ * tptSetConfig's, the fold tptSetFoldMode's, the HitSpheres variant tptSetKernelVariant's (the lane-refill kernel traces the draw
+ * whatever `persistent` says; all variants give the same bits).  The seeds are per pixel whatever tptSetSeedMode says.
+ * Binary32, in the order written, no FMA, correctly rounded division and square root.  Per pixel (x, y), w = screenWidth,
+ * h = screenHeight:
+ *   state = (x*1973 + y*9277 + frameCount*26699) | 1;  invWidth = 1.0f / (float)w;  invHeight = 1.0f / (float)h;  colour = 0
+ *   for each of the spp samples, in sequence from that one stream:
+ *     u = ((float)x + RandomFloat01(state)) * invWidth;  v = ((float)y + RandomFloat01(state)) * invHeight   (Test.cpp:286-287)
+ *     a = (u - 0.5f) * sx;  b = (v - 0.5f) * sy
+ *     EQUIRECT: (sa, ca) = sincosf(a); (sb, cb) = sincosf(b);
+ *               q = right*(cb*sa) + up*sb + forward*(cb*ca);  o = origin
+ *     FISHEYE:  r = sqrtf(a*a + b*b); (st, ct) = sincosf(r * maxAngle); k = r > 0 ? st / r : 0.0f;
+ *               q = right*(a*k) + up*(b*k) + forward*ct;      o = origin
+ *     ORTHO:    q = forward;                                  o = (origin + right*a) + up*b
+ *     d = normalize(q)  (the reference's normalize, Maths.h:301, as Camera::GetRay applies it)
+ *     colour += Trace({o, d}, depth 0, state, doMaterialE = true)  (Test.cpp:195-234; with tptSetFoldMode(1) the forward fold)
+ *   colour *= 1.0f / (float)spp
+ *   lerp = (float)frameCount / (float)(frameCount + 1) under TPT_FLAG_PROGRESSIVE, else 0  (Test.cpp:272-276)
+ *   tile.rgb = prev * lerp + colour * (1 - lerp); the alpha is untouched; prev is always read
+ * Each vector*scalar is three multiplies, sums go left to right.  sincosf is glibc's sinf / cosf.  No lens draws a further random
+ * number: these lenses have no aperture.
+ *   *deviceRayCount += the HitWorld calls of the call, shadow rays included.  The context's own counter (tptRayCounterRead) is not
+ *   touched.
+ * A 1-spp draw of frame f on a zeroed tile equals tptTraceRaysDevice's colours on the rays made as above with the state left behind as
+ * the seed word.
+ * Asynchronous on the context stream, ordered like tptDenoiseDevice.  Camera, scene, frames traced ahead, stream batches and row
+ * sharding are left alone.
+ * Refused (non-zero, tptGetLastError names the function, nothing enqueued, no byte written): args NULL; no context; no tptUpdate yet;
+ * screenWidth or screenHeight outside 1..8192; frameCount < 0; flags other than 0 or TPT_FLAG_PROGRESSIVE; deviceTile NULL; the tile
+ * sharing a byte with the counter; an unknown kind; any non-finite field; a basis vector whose squared length lies outside
+ * 0.99..1.01; a pair of basis vectors whose dot product lies outside -0.01..0.01; sx or sy not positive; EQUIRECT with
+ * sx > 6.2831855f or sy > 3.1415927f; FISHEYE with sx or sy > 4 or maxAngle outside (0, 3.1415927f]; maxAngle != 0 for the other
+ * kinds; more than TPT_MAX_LIGHTS emissive spheres; a scene whose LDS does not fit a compute unit.  The basis check keeps |q| near 1,
+ * so normalize yields the unit direction the HitSpheres filters are made for; the angle bounds keep every sincosf argument below 9. */
+enum { TPT_LENS_EQUIRECT = 1, TPT_LENS_FISHEYE = 2, TPT_LENS_ORTHO = 3 };
+typedef struct tptLens {
+    int   kind;
+    float origin[3];
+    float right[3], up[3], forward[3];  /* the caller's basis, used as given */
+    float sx, sy;                       /* EQUIRECT: longitude / latitude span in radians; FISHEYE: scale of the image
+                                           plane (2, 2 on a square image: the image circle touches the edges); ORTHO:
+                                           width / height of the window in world units */
+    float maxAngle;                     /* FISHEYE: the angle from `forward` at r = 1 (equidistant projection); else 0 */
+} tptLens;
+typedef struct tptDrawLensArgs {
+    int screenWidth, screenHeight;      /* 1 .. 8192 each */
+    int frameCount;                     /* >= 0: seeds and blend, as tptDrawDevice */
+    unsigned flags;                     /* 0 or TPT_FLAG_PROGRESSIVE */
+    tptLens lens;
+    float* deviceTile;                  /* h*w*4 floats, row 0 at the bottom, 16-byte aligned */
+    unsigned long long* deviceRayCount; /* device u64 the call ADDS its HitWorld calls to, or NULL */
+} tptDrawLensArgs;
+TPT_API int tptDrawDeviceLens(const tptDrawLensArgs* args);
 /* ADAPTIVE SAMPLING: tptDrawDeviceMoments with a sample count per pixel, so that the moments can steer the next pass (the counts come
  * from tptAdaptiveSamplesDevice below, or from the caller).  deviceSampleCounts (required): h*w int32 in DEVICE memory, row-major like the
  * tile, read by the kernels only.  Per pixel p, n = deviceSampleCounts[p] clamped to 0 .. 2047 (the path record holds 11 bits of sample

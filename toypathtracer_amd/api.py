@@ -17,6 +17,7 @@ kFlagAnimate = 1 << 0      # Test.h:6
 kFlagProgressive = 1 << 1  # Test.h:7
 SEED_ROW_SERIAL, SEED_PER_PIXEL = 0, 1
 FOLD_RECURSIVE, FOLD_FORWARD = 0, 1
+FLAG_ANIMATE, FLAG_PROGRESSIVE = 1, 2  # include/tpt_hip.h: TPT_FLAG_*
 
 # layout contract of the reference (TestWin.cpp:132-134): 20 / 36 / 88 bytes
 SPHERE_DT = np.dtype([("cx", "<f4"), ("cy", "<f4"), ("cz", "<f4"), ("radius", "<f4"), ("invRadius", "<f4")])
@@ -39,7 +40,7 @@ C_ABI_SYMBOLS = [
     "tptSetSamplesPerPixel", "tptSetConfig", "tptSetSeedMode", "tptSetFoldMode", "tptSetScene", "tptSetCamera", "tptSetStream",
     "tptSetRowShard", "tptLocalRowCount", "tptLocalRowToGlobal", "tptDrawDevice", "tptRayCounterRead", "tptSetRayCounter", "tptSetFrameOverlap", "tptDisplayRGBA8", "tptKernelTimingBegin", "tptKernelTimingEnd",
     "tptSynchronize", "tptTimerBegin", "tptTimerEnd", "tptSetKernelVariant",
-    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceBatchMoments", "tptDrawDeviceAnimationMoments", "tptDrawDeviceCameraClip", "tptDrawDeviceKeyframeClip", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptObjectPlaneDevice", "tptObjectMotionTable", "tptTemporalAccumulateObjectsDevice", "tptDenoiseClipDevice", "tptMotionVectorsDevice", "tptRectifyHistoryDevice", "tptSpatialVarianceDevice", "tptTraceRaysDevice", "tptDrawDeviceAdaptive", "tptAdaptiveSamplesDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
+    "tptDrawDeviceBatch", "tptDrawDeviceViews", "tptDrawDeviceAnimation", "tptDrawDeviceAov", "tptDenoiseDevice", "tptDrawDeviceMoments", "tptDrawDeviceBatchMoments", "tptDrawDeviceAnimationMoments", "tptDrawDeviceCameraClip", "tptDrawDeviceKeyframeClip", "tptDenoiseDeviceVariance", "tptTemporalAccumulateDevice", "tptObjectPlaneDevice", "tptObjectMotionTable", "tptTemporalAccumulateObjectsDevice", "tptDenoiseClipDevice", "tptMotionVectorsDevice", "tptRectifyHistoryDevice", "tptSpatialVarianceDevice", "tptTraceRaysDevice", "tptDrawDeviceLens", "tptDrawDeviceAdaptive", "tptAdaptiveSamplesDevice", "tptDrawShardedBatch", "tptGetLookaheadHits", "tptCommGetUniqueId", "tptCommInit", "tptCommInitLoopback", "tptCommInfo", "tptCommDestroy", "tptDrawSharded", "tptSetShardExchangeInterval", "tptShardedFinish", "tptGetLaunchInfo", "tptGetPipelineInfo", "tptGetSceneInfo", "tptSetHostBufferMode", "tptSetHostLookahead", "tptSetStreamBatching", "tptSetTileMirror", "tptGetLastError", "tptSetErrorHandler", "tptGetDeviceName",
 ]
 # include/tpt_test_hooks.h: exported by the second build (libtoypathtracer_hip_hooks.so) only
 HOOK_SYMBOLS = ["tptTestMath", "tptTestMathExhaustive", "tptTestHitSpheres", "tptTestMatrixFilter", "tptTestGroupFilter", "tptTestSetDealCapacities", "tptDebugStats", "tptDebugChunkOrder", "tptTestPresetStreamCut", "tptTestStreamFrameRays"]
@@ -77,6 +78,18 @@ class TraceRaysArgs(C.Structure):
                 ("deviceHits", C.c_void_p), ("deviceRayCount", C.c_void_p)]
 
 
+class Lens(C.Structure):
+    """include/tpt_hip.h: tptLens (tests/test_lens_abi.py holds the layout against the header)"""
+    _fields_ = [("kind", C.c_int), ("origin", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3),
+                ("forward", C.c_float * 3), ("sx", C.c_float), ("sy", C.c_float), ("maxAngle", C.c_float)]
+
+
+class DrawLensArgs(C.Structure):
+    """include/tpt_hip.h: tptDrawLensArgs"""
+    _fields_ = [("screenWidth", C.c_int), ("screenHeight", C.c_int), ("frameCount", C.c_int), ("flags", C.c_uint), ("lens", Lens),
+                ("deviceTile", C.c_void_p), ("deviceRayCount", C.c_void_p)]
+
+
 def _lib_dir():
     # TPT_LIB_DIR: a directory holding another build of BOTH libraries (csrc/build.sh with TPT_OUT_DIR / TPT_EXTRA_FLAGS)
     return os.environ.get("TPT_LIB_DIR") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib")
@@ -105,7 +118,7 @@ def _bind(path, hooks):
         "tptSetRayCounter": [p], "tptSetTileMirror": [p, p], "tptSetFrameOverlap": [i], "tptDisplayRGBA8": [p, i, i, p], "tptKernelTimingBegin": [i],
         "tptKernelTimingEnd": [C.POINTER(f), C.POINTER(i)],
         "tptSynchronize": [], "tptTimerBegin": [], "tptTimerEnd": [C.POINTER(f)], "tptSetKernelVariant": [i, i, i],
-        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDrawDeviceBatchMoments": [f, i, i, i, i, p, p, p, p, u], "tptDrawDeviceAnimationMoments": [i, i, p, i, i] + [p] * 7 + [u], "tptDrawDeviceCameraClip": [i, i, p, p, i, i] + [p] * 8 + [u], "tptDrawDeviceKeyframeClip": [i, i, p, i, p, p, i, i] + [p] * 9 + [u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptObjectPlaneDevice": [i, p, p, i, i, p, u], "tptObjectMotionTable": [f, f, u, p, i], "tptTemporalAccumulateObjectsDevice": [i, i] + [p] * 14 + [f] * 4 + [p, p, p, i], "tptDenoiseClipDevice": [C.POINTER(ClipDenoiseArgs)], "tptMotionVectorsDevice": [C.POINTER(MotionVectorsArgs)], "tptRectifyHistoryDevice": [i, i] + [p] * 7 + [i, f], "tptSpatialVarianceDevice": [i, i, i, p, p, p, f, f, i, f, f], "tptTraceRaysDevice": [C.POINTER(TraceRaysArgs)], "tptDrawDeviceAdaptive": [f, i, i, i, p, p, p, p, p, u], "tptAdaptiveSamplesDevice": [i, i, p, f, i, i, p, p, p], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
+        "tptGetLaunchInfo": [C.POINTER(i)] * 4, "tptGetPipelineInfo": [C.POINTER(i)] * 4, "tptGetSceneInfo": [C.POINTER(i)] * 3, "tptCommGetUniqueId": [p], "tptCommInit": [p, i, i, i], "tptCommInitLoopback": [i, i], "tptCommInfo": [C.POINTER(i)] * 3, "tptCommDestroy": [], "tptDrawSharded": [f, i, i, i, p, u], "tptSetShardExchangeInterval": [i], "tptDrawShardedBatch": [f, i, i, i, i, p, u], "tptDrawDeviceBatch": [f, i, i, i, i, p, u], "tptDrawDeviceViews": [f, i, i, i, i, p, p, p, u], "tptDrawDeviceAnimation": [i, i, p, i, i, p, p, p, u], "tptDrawDeviceAov": [f, i, i, i, p, p, p, u], "tptDenoiseDevice": [i, i, p, p, p, p, i, f, f, f, u], "tptDrawDeviceMoments": [f, i, i, i, p, p, p, p, u], "tptDrawDeviceBatchMoments": [f, i, i, i, i, p, p, p, p, u], "tptDrawDeviceAnimationMoments": [i, i, p, i, i] + [p] * 7 + [u], "tptDrawDeviceCameraClip": [i, i, p, p, i, i] + [p] * 8 + [u], "tptDrawDeviceKeyframeClip": [i, i, p, i, p, p, i, i] + [p] * 9 + [u], "tptDenoiseDeviceVariance": [i, i, p, p, p, p, f, p, i, f, f, f, u], "tptTemporalAccumulateDevice": [i, i] + [p] * 14 + [f] * 4, "tptObjectPlaneDevice": [i, p, p, i, i, p, u], "tptObjectMotionTable": [f, f, u, p, i], "tptTemporalAccumulateObjectsDevice": [i, i] + [p] * 14 + [f] * 4 + [p, p, p, i], "tptDenoiseClipDevice": [C.POINTER(ClipDenoiseArgs)], "tptMotionVectorsDevice": [C.POINTER(MotionVectorsArgs)], "tptRectifyHistoryDevice": [i, i] + [p] * 7 + [i, f], "tptSpatialVarianceDevice": [i, i, i, p, p, p, f, f, i, f, f], "tptTraceRaysDevice": [C.POINTER(TraceRaysArgs)], "tptDrawDeviceLens": [C.POINTER(DrawLensArgs)], "tptDrawDeviceAdaptive": [f, i, i, i, p, p, p, p, p, u], "tptAdaptiveSamplesDevice": [i, i, p, f, i, i, p, p, p], "tptShardedFinish": [C.POINTER(C.c_int64)], "tptSetHostBufferMode": [i], "tptGetLookaheadHits": [C.POINTER(C.c_longlong)], "tptSetHostLookahead": [i], "tptSetStreamBatching": [i],
     }
     if hooks:
         sigs.update({"tptDebugStats": [p, i], "tptDebugChunkOrder": [p, p, i], "tptTestMath": [i, p, p, p, i], "tptTestMathExhaustive": [i, u, u, p, p],
@@ -816,6 +829,104 @@ def trace_rays_device(n, rays_ptr, radiance_ptr=None, hits_ptr=None, ray_count_p
     a = TraceRaysArgs(nRays=int(n), flags=0, deviceRays=rays_ptr, deviceRadiance=radiance_ptr or None, deviceHits=hits_ptr or None,
                       deviceRayCount=ray_count_ptr or None)
     _chk(load_library().tptTraceRaysDevice(C.byref(a)), "tptTraceRaysDevice")
+
+
+LENS_EQUIRECT, LENS_FISHEYE, LENS_ORTHO = 1, 2, 3  # include/tpt_hip.h: TPT_LENS_*
+LENS_MAX_SIDE = 8192  # include/tpt_hip.h: tptDrawDeviceLens's screenWidth / screenHeight
+_LENS_TWO_PI, _LENS_PI = float(np.float32(6.2831855)), float(np.float32(3.1415927))
+
+
+def _lens_basis(origin, forward, up):
+    """an orthonormal basis from a viewing direction and an up hint, made in float64 and rounded to binary32: (origin, right, up, forward)"""
+    o, f, u = (np.asarray(v, np.float64).reshape(-1) for v in (origin, forward, up))
+    if o.shape != (3,) or f.shape != (3,) or u.shape != (3,) or not (np.isfinite(o).all() and np.isfinite(f).all() and np.isfinite(u).all()):
+        raise ValueError("origin, forward, up: three finite numbers each expected")
+    if not np.linalg.norm(f) > 0:
+        raise ValueError("forward: a direction of non-zero length expected")
+    f = f / np.linalg.norm(f)
+    r = np.cross(f, u)
+    if not np.linalg.norm(r) > 1e-6 * max(np.linalg.norm(u), 1e-300):
+        raise ValueError("up: must not be parallel to forward (or zero)")
+    r = r / np.linalg.norm(r)
+    u = np.cross(r, f)
+    return tuple(tuple(float(x) for x in v.astype(np.float32)) for v in (o, r, u, f))
+
+
+def _lens(kind, origin, forward, up, sx, sy, max_angle):
+    o, r, u, f = _lens_basis(origin, forward, up)
+    lens = Lens(kind=kind, sx=sx, sy=sy, maxAngle=max_angle)
+    lens.origin[:], lens.right[:], lens.up[:], lens.forward[:] = o, r, u, f
+    _check_lens(lens)
+    return lens
+
+
+def lens_equirect(origin=(0.0, 1.0, 0.0), forward=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), lon_span=_LENS_TWO_PI, lat_span=_LENS_PI):
+    """a tptLens for a panorama: longitude (about `up`, 0 at `forward`, growing towards the right) across the image's width, latitude
+    across its height; the spans in radians, at most 2 pi by pi (the defaults: the whole sphere)"""
+    return _lens(LENS_EQUIRECT, origin, forward, up, lon_span, lat_span, 0.0)
+
+
+def lens_fisheye(origin=(0.0, 1.0, 0.0), forward=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), max_angle=_LENS_PI / 2, sx=2.0, sy=2.0):
+    """a tptLens for an equidistant fisheye: the angle from `forward` grows linearly with the distance r from the image centre and is
+    max_angle (radians, at most pi) at r = 1; sx, sy scale the image plane (2, 2 on a square image: the circle touches the edges; for a
+    wide image 2 * w / h, 2)"""
+    return _lens(LENS_FISHEYE, origin, forward, up, sx, sy, max_angle)
+
+
+def lens_ortho(origin=(0.0, 1.0, 3.0), forward=(0.0, 0.0, -1.0), up=(0.0, 1.0, 0.0), width=4.0, height=4.0):
+    """a tptLens for an orthographic view: parallel rays along `forward` from a window of width x height world units centred on origin"""
+    return _lens(LENS_ORTHO, origin, forward, up, width, height, 0.0)
+
+
+def _check_lens(lens):
+    """include/tpt_hip.h's rules for a tptLens, before the library is reached: ValueError for the first one broken"""
+    if not isinstance(lens, Lens):
+        raise ValueError("lens: a Lens expected (lens_equirect, lens_fisheye, lens_ortho), got %r" % (lens,))
+    if lens.kind not in (LENS_EQUIRECT, LENS_FISHEYE, LENS_ORTHO):
+        raise ValueError("lens.kind: LENS_EQUIRECT, LENS_FISHEYE or LENS_ORTHO expected, got %r" % lens.kind)
+    vecs = [np.array(v[:], np.float64) for v in (lens.origin, lens.right, lens.up, lens.forward)]
+    scalars = (lens.sx, lens.sy, lens.maxAngle)
+    if not all(np.isfinite(v).all() for v in vecs) or not np.isfinite(scalars).all():
+        raise ValueError("lens: every field must be finite")
+    for i in range(1, 4):
+        if not 0.99 <= float(vecs[i] @ vecs[i]) <= 1.01:
+            raise ValueError("lens: a basis vector is not of unit length")
+        for k in range(i + 1, 4):
+            if not -0.01 <= float(vecs[i] @ vecs[k]) <= 0.01:
+                raise ValueError("lens: two basis vectors are not orthogonal")
+    if not (lens.sx > 0 and lens.sy > 0):
+        raise ValueError("lens.sx, lens.sy: positive numbers expected")
+    if lens.kind == LENS_EQUIRECT and (lens.sx > _LENS_TWO_PI or lens.sy > _LENS_PI):
+        raise ValueError("lens: an equirectangular span of at most 2 pi x pi expected")
+    if lens.kind == LENS_FISHEYE and (lens.sx > 4 or lens.sy > 4 or not 0 < lens.maxAngle <= _LENS_PI):
+        raise ValueError("lens: a fisheye scale of at most 4 and a maxAngle in (0, pi] expected")
+    if lens.kind != LENS_FISHEYE and lens.maxAngle != 0:
+        raise ValueError("lens.maxAngle: 0 expected for this kind")
+
+
+def draw_device_lens(frame, w, h, tile_ptr, lens, flags=0, ray_count_ptr=None):
+    """tptDrawDeviceLens: draw_device's contract through `lens` (lens_equirect, lens_fisheye, lens_ortho) instead of the camera.  All
+    set_samples_per_pixel samples of a pixel are traced in one launch from the pixel's own random stream (per-pixel seeds) and blended
+    into tile_ptr (a device buffer of h*w*4 floats, row 0 at the bottom): lerp = frame / (frame + 1) under FLAG_PROGRESSIVE (flags 2),
+    else 0.  ray_count_ptr: None, or a device u64 the call adds its HitWorld calls to; the context's counter is not touched.  The
+    scene is the last UpdateTest's; light sampling, fold mode and the hitSpheres variant are the context's.  Ordered on the context's
+    stream."""
+    for name, v in (("w", w), ("h", h)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 1 <= v <= LENS_MAX_SIDE:
+            raise ValueError("%s: an int in 1..%d expected, got %r" % (name, LENS_MAX_SIDE, v))
+    if not isinstance(frame, (int, np.integer)) or isinstance(frame, bool) or not 0 <= frame < 2 ** 31:
+        raise ValueError("frame: an int >= 0 expected, got %r" % (frame,))
+    if isinstance(flags, bool) or flags not in (0, FLAG_PROGRESSIVE):
+        raise ValueError("flags: 0 or FLAG_PROGRESSIVE (2) expected, got %r" % (flags,))
+    _pointers(("tile_ptr", tile_ptr), ("ray_count_ptr", ray_count_ptr))
+    if not tile_ptr:
+        raise ValueError("tile_ptr: a device buffer is required")
+    if ray_count_ptr and tile_ptr - 8 < ray_count_ptr < tile_ptr + 16 * int(w) * int(h):
+        raise ValueError("ray_count_ptr: lies inside the tile")
+    _check_lens(lens)
+    a = DrawLensArgs(screenWidth=int(w), screenHeight=int(h), frameCount=int(frame), flags=int(flags), lens=lens, deviceTile=tile_ptr,
+                     deviceRayCount=ray_count_ptr or None)
+    _chk(load_library().tptDrawDeviceLens(C.byref(a)), "tptDrawDeviceLens")
 
 
 OBJECT_PLANE_MAX_FRAMES = 4096  # include/tpt_hip.h: tptObjectPlaneDevice's nFrames

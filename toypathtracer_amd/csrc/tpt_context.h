@@ -307,6 +307,10 @@ struct Context {
     f4* dRayStack = nullptr;
     size_t rayStackBytes = 0;
     unsigned* dRayWork = nullptr;
+    // tptDrawDeviceLens: the draw's own colour plane (KernelArgs::frameColour, [h][w] f4 of the largest image seen), grown like the
+    // spill above; the launch shares that spill and counter block with the ray calls -- all of them run on the context stream.
+    f4* dLensColour = nullptr;
+    size_t lensColourBytes = 0;
     long long aheadHits = 0;            // frames that were found traced ahead when their call arrived (tptGetLookaheadHits)
     // per-frame ray counters of the pending launches, one allocation: [kMaxSlots] AHEAD frames (indexed by the frame's sequence number
     // at enqueue), [2][kMaxBatch] ROW_SERIAL batches (two banks, alternating), [kStreamRing][kStreamBatchMax] STREAM batches (a ring)

@@ -108,6 +108,10 @@ struct KernelArgs {
     const f4* rays = nullptr;
     f4* rayRadiance = nullptr;
     f4* rayHits = nullptr;
+    // A lens instead of the camera (tptDrawDeviceLens; the lane-refill kernel through tptLaunchTraceLens): every sample of the launch
+    // starts at lensGetRay(lens, u, v) where it would start at cameraGetRay(fc.cam, ..); everything else is the pixel mode.  At the
+    // tail, so that no other field moves; read by the kernel only where a sample starts.  kind 0 for every other launch.
+    LensPOD lens = LensPOD{};
 };
 
 } // namespace tpt
@@ -117,6 +121,10 @@ int tptTraceOccupancy(int hs, int fold, bool ldsScene, size_t lds);
 // tptTraceRaysDevice: tptLaunchTrace's kernels with a.rays given (the ray source of the lane-refill kernel; no kernel of its own).  Weak
 // for the same reason as tptLaunchDenoise below.
 __attribute__((weak)) hipError_t tptLaunchTraceRays(const tpt::KernelArgs& a, int hs, int fold, bool ldsScene, int blocks, size_t lds,
+                                                    hipStream_t stream);
+// tptDrawDeviceLens: tptLaunchTrace's kernels with a.lens given (a mode of the lane-refill kernel; no kernel of its own).  Weak for the
+// same reason as tptLaunchDenoise below.
+__attribute__((weak)) hipError_t tptLaunchTraceLens(const tpt::KernelArgs& a, int hs, int fold, bool ldsScene, int blocks, size_t lds,
                                                     hipStream_t stream);
 hipError_t tptLaunchTraceQueue(const tpt::KernelArgs& a, bool ldsScene, int blocks, size_t lds, hipStream_t stream);
 int tptQueueMatrixFilter();

@@ -465,6 +465,8 @@ int tptShutdown(void)
     (void)hipFree(g.dRayStack); g.dRayStack = nullptr;
     g.rayStackBytes = 0;
     (void)hipFree(g.dRayWork); g.dRayWork = nullptr;
+    (void)hipFree(g.dLensColour); g.dLensColour = nullptr;
+    g.lensColourBytes = 0;
     if (g.hViewsStage) (void)hipHostFree(g.hViewsStage);
     g.hViewsStage = nullptr;
     if (g.hCut) (void)hipHostFree(g.hCut); // (the device is idle: hipDeviceSynchronize above, the streams drained since)

@@ -886,6 +886,33 @@ int tptObjectPlaneDevice(int nFrames, const float* times, const void* cameras, i
     return 0;
 }
 
+// The buffers of a lane-refill launch outside the frame pipeline (tptTraceRaysDevice, tptDrawDeviceLens; tpt_context.h: dRayStack,
+// dRayWork): the bounce-stack spill for `blocks` workgroups, grown on demand, the counter block, and the word the rays are counted into
+// -- the caller's, or the block's own.
+static int rayLaunchBuffers(KernelArgs& a, int blocks, unsigned long long* deviceRayCount)
+{
+    if (!g.dRayWork) {
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dRayWork), 16 * sizeof(unsigned) + sizeof(unsigned long long)));
+        HIPCHK(hipMemsetAsync(g.dRayWork, 0, 16 * sizeof(unsigned) + sizeof(unsigned long long), g.stream));
+    }
+    const bool needStack = g.foldMode == FOLD_RECURSIVE && a.ldsStackLevels < TPT_MAX_DEPTH;
+    const size_t stackBytes = needStack ? (size_t)blocks * TPT_BLOCK * (size_t)(TPT_MAX_DEPTH - a.ldsStackLevels) * sizeof(f4) : 0;
+    if (stackBytes > g.rayStackBytes) {
+        HIPCHK(hipStreamSynchronize(g.stream)); // (an earlier ray call may still spill into the buffer that goes)
+        (void)hipFree(g.dRayStack);
+        g.dRayStack = nullptr;
+        g.rayStackBytes = 0;
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dRayStack), stackBytes));
+        g.rayStackBytes = stackBytes;
+        HIPCHK(hipMemsetAsync(g.dRayStack, 0, stackBytes, g.stream));
+    }
+    a.stackBuf = needStack ? g.dRayStack : nullptr;
+    a.stackStride = needStack ? blocks * TPT_BLOCK : 0;
+    a.work = g.dRayWork;
+    a.rayCounter = deviceRayCount ? deviceRayCount : reinterpret_cast<unsigned long long*>(g.dRayWork + 16);
+    return 0;
+}
+
 // Radiance and first hits along the caller's rays (include/tpt_hip.h states them): one launch of the lane-refill kernel on the context
 // stream with the rays as its work items (KernelArgs::rays), planned as chooseKernel plans that kernel for a frame -- LDS scene, bounce
 // stack levels, occupancy -- and sized as sizeGrid sizes it, without the frame pipeline: no colour slot, no trace stream, no blend, no
@@ -946,31 +973,109 @@ int tptTraceRaysDevice(const tptTraceRaysArgs* args)
     if (blocks < 1) blocks = 1;
     a.totalWaves = (unsigned)blocks;
 
-    if (!g.dRayWork) {
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dRayWork), 16 * sizeof(unsigned) + sizeof(unsigned long long)));
-        HIPCHK(hipMemsetAsync(g.dRayWork, 0, 16 * sizeof(unsigned) + sizeof(unsigned long long), g.stream));
-    }
-    const bool needStack = g.foldMode == FOLD_RECURSIVE && a.ldsStackLevels < TPT_MAX_DEPTH;
-    const size_t stackBytes = needStack ? (size_t)blocks * TPT_BLOCK * (size_t)(TPT_MAX_DEPTH - a.ldsStackLevels) * sizeof(f4) : 0;
-    if (stackBytes > g.rayStackBytes) {
-        HIPCHK(hipStreamSynchronize(g.stream)); // (an earlier ray call may still spill into the buffer that goes)
-        (void)hipFree(g.dRayStack);
-        g.dRayStack = nullptr;
-        g.rayStackBytes = 0;
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dRayStack), stackBytes));
-        g.rayStackBytes = stackBytes;
-        HIPCHK(hipMemsetAsync(g.dRayStack, 0, stackBytes, g.stream));
-    }
-    a.stackBuf = needStack ? g.dRayStack : nullptr;
-    a.stackStride = needStack ? blocks * TPT_BLOCK : 0;
-    a.work = g.dRayWork;
-    a.rayCounter = A.deviceRayCount ? A.deviceRayCount : reinterpret_cast<unsigned long long*>(g.dRayWork + 16);
+    int rc = rayLaunchBuffers(a, blocks, A.deviceRayCount);
+    if (rc) return rc;
     a.rays = reinterpret_cast<const f4*>(A.deviceRays);
     a.rayRadiance = reinterpret_cast<f4*>(A.deviceRadiance);
     a.rayHits = reinterpret_cast<f4*>(A.deviceHits);
-    int rc = enqueueSceneUpload(g.stream);
-    if (rc) return rc;
+    if ((rc = enqueueSceneUpload(g.stream))) return rc;
     HIPCHK(tptLaunchTraceRays(a, g.hs, g.foldMode, ldsScene, blocks, lds, g.stream));
+    return 0;
+}
+
+// Why a lens record is refused, or null (include/tpt_hip.h lists the rules; the Python binding states them again before the call).
+static const char* lensFault(const tptLens& L)
+{
+    if (L.kind != TPT_LENS_EQUIRECT && L.kind != TPT_LENS_FISHEYE && L.kind != TPT_LENS_ORTHO) return "unknown lens kind";
+    const float* vecs[4] = {L.origin, L.right, L.up, L.forward};
+    for (const float* v : vecs)
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(v[k])) return "a non-finite lens field";
+    if (!std::isfinite(L.sx) || !std::isfinite(L.sy) || !std::isfinite(L.maxAngle)) return "a non-finite lens field";
+    for (int i = 1; i < 4; ++i) {
+        const double dd = (double)vecs[i][0] * vecs[i][0] + (double)vecs[i][1] * vecs[i][1] + (double)vecs[i][2] * vecs[i][2];
+        if (!(dd >= 0.99 && dd <= 1.01)) return "a basis vector is not of unit length (its squared length must lie in 0.99..1.01)";
+        for (int k = i + 1; k < 4; ++k) {
+            const double d = (double)vecs[i][0] * vecs[k][0] + (double)vecs[i][1] * vecs[k][1] + (double)vecs[i][2] * vecs[k][2];
+            if (!(d >= -0.01 && d <= 0.01)) return "two basis vectors are not orthogonal (their dot product must lie in -0.01..0.01)";
+        }
+    }
+    if (!(L.sx > 0.0f) || !(L.sy > 0.0f)) return "sx and sy must be positive";
+    if (L.kind == TPT_LENS_EQUIRECT && (L.sx > 6.2831855f || L.sy > 3.1415927f)) return "an equirectangular span beyond 2 pi x pi";
+    if (L.kind == TPT_LENS_FISHEYE && (L.sx > 4.0f || L.sy > 4.0f)) return "a fisheye scale beyond 4";
+    if (L.kind == TPT_LENS_FISHEYE && !(L.maxAngle > 0.0f && L.maxAngle <= 3.1415927f)) return "a fisheye maxAngle outside (0, pi]";
+    if (L.kind != TPT_LENS_FISHEYE && L.maxAngle != 0.0f) return "maxAngle must be 0 for this lens kind";
+    return nullptr;
+}
+
+// tptDrawDevice's contract through another lens (include/tpt_hip.h states it): one launch of the lane-refill kernel in its pixel mode
+// on the context stream, its samples started at KernelArgs::lens, then the blend of the context's own colour plane into the caller's
+// tile.  Planned as tptTraceRaysDevice plans its launch, whose scene set, spill buffer and counter block it shares, outside the frame
+// pipeline: no colour slot, no trace stream, no chunk order, no frame traced ahead.
+int tptDrawDeviceLens(const tptDrawLensArgs* args)
+{
+    if (requireInit()) return -1;
+    const std::string f("tptDrawDeviceLens");
+    if (!args) return fail(f + ": args is required");
+    const tptDrawLensArgs& A = *args;
+    if (!g.updated) return fail(f + ": call tptUpdate first");
+    const int w = A.screenWidth, h = A.screenHeight;
+    if (w < 1 || w > 8192 || h < 1 || h > 8192) return fail(f + ": screenWidth and screenHeight must lie in 1..8192");
+    if (A.frameCount < 0) return fail(f + ": frameCount must not be negative");
+    if (A.flags != 0 && A.flags != (unsigned)TPT_FLAG_PROGRESSIVE) return fail(f + ": flags must be 0 or TPT_FLAG_PROGRESSIVE");
+    if (!A.deviceTile) return fail(f + ": deviceTile is required");
+    const size_t nPixels = (size_t)w * (size_t)h;
+    {
+        const uintptr_t t = reinterpret_cast<uintptr_t>(A.deviceTile), c = reinterpret_cast<uintptr_t>(A.deviceRayCount);
+        if (c && c < t + nPixels * sizeof(f4) && t < c + sizeof(unsigned long long)) return fail(f + ": deviceRayCount lies inside the tile");
+    }
+    if (const char* why = lensFault(A.lens)) return fail(f + ": " + why);
+    Context::SceneSet* S = activeSet();
+    if (!S || !S->dev || S->nSpheres < 1) return fail(f + ": no scene staged (call tptUpdate first)");
+    if (S->nLights > TPT_MAX_LIGHTS)
+        return fail(f + ": too many emissive spheres for the LDS light table (" + std::to_string(TPT_MAX_LIGHTS) + " at most)");
+    KernelArgs a = KernelArgs{};
+    a.scene = deviceView();
+    bool ldsScene = false;
+    const size_t lds = laneRefillLds(a, ldsScene);
+    if (!fitsCuLds(lds)) return fail(f + ": scene too large for LDS staging; use tptSetKernelVariant(.., .., 0)");
+    if (!tptLaunchTraceLens) return fail(f + ": this build has no lens launcher");
+
+    // (the camera plays no part; seeds per pixel, the flags' blend)
+    a.fc = makeFrameConsts(g.cam, w, h, g.spp, A.frameCount, A.flags, SEED_PER_PIXEL, g.config, g.animateSmoothing);
+    static_assert(sizeof(LensPOD) == sizeof(tptLens) && sizeof(tptLens) == 64, "the kernel reads the caller's record as it is");
+    memcpy(&a.lens, &A.lens, sizeof a.lens);
+    a.nLocalRows = h; a.stripeRows = h; a.stripeStride = h; a.stripeOffset = 0;
+    a.tilesX = (w + 7) / 8;
+    a.numItems = a.tilesX * ((h + 7) / 8) * 64;
+    a.batchFrames = 1;
+    a.framePlane = h * w;
+    a.laneCap = 64;
+    // sizeGrid's chunks: 256 pixels a chunk, single 8x8 tiles when that leaves a resident wave fewer than eight
+    const int occ = laneRefillOccupancy(ldsScene, lds), resident = g.traceCUs * occ;
+    a.chunkSize = a.numItems / TPT_CHUNK_PIXELS < 8 * resident ? 64 : TPT_CHUNK_PIXELS;
+    a.chunkShift = a.chunkSize == 64 ? 6 : 8;
+    a.numChunks = (a.numItems + a.chunkSize - 1) / a.chunkSize;
+    a.chunksPerFrame = a.numChunks;
+    int blocks = a.numChunks < resident ? a.numChunks : resident;
+    if (blocks < 1) blocks = 1;
+    a.totalWaves = (unsigned)blocks;
+
+    int rc = rayLaunchBuffers(a, blocks, A.deviceRayCount);
+    if (rc) return rc;
+    const size_t colourBytes = nPixels * sizeof(f4);
+    if (colourBytes > g.lensColourBytes) {
+        HIPCHK(hipStreamSynchronize(g.stream)); // (an earlier lens draw may still read the plane that goes)
+        (void)hipFree(g.dLensColour);
+        g.dLensColour = nullptr;
+        g.lensColourBytes = 0;
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dLensColour), colourBytes));
+        g.lensColourBytes = colourBytes;
+    }
+    a.frameColour = g.dLensColour;
+    if ((rc = enqueueSceneUpload(g.stream))) return rc;
+    HIPCHK(tptLaunchTraceLens(a, g.hs, g.foldMode, ldsScene, blocks, lds, g.stream));
+    HIPCHK(tptLaunchResolve(A.deviceTile, g.dLensColour, (int)nPixels, a.fc.lerpFac, nullptr, g.dRays, nullptr, nullptr, g.stream));
     return 0;
 }
 

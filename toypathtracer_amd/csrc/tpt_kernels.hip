@@ -1189,6 +1189,27 @@ __global__ void __launch_bounds__(256) tptObjectPlaneKernel(const f4* __restrict
     out[(size_t)y * width + x] = id;
 }
 
+// tptDrawDeviceLens: the lens record of the lane-refill kernel's argument block, found where a sample starts.  Its sixteen words are
+// needed there and nowhere else; read as fields of `a` they are loaded once at the kernel's start and carried in scalar registers
+// through the step (the ray mode's loop-carried pointers cost the existing draws 4.9 % that way).  The address of the
+// kernel's argument segment (KernelArgs is its only argument, at offset 0) goes through an empty asm here, so the loads that depend
+// on it are made here: scalar loads from the constant address space, into registers that are free again after the sample's start.
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef const LensPOD __attribute__((address_space(4))) * LensArgsPtr;
+__device__ __forceinline__ LensArgsPtr lensArgsHere()
+{
+    typedef const unsigned char __attribute__((address_space(4))) * ArgBytes;
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wold-style-cast"
+    ArgBytes p = (ArgBytes)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return (LensArgsPtr)(p + offsetof(KernelArgs, lens));
+#pragma clang diagnostic pop
+}
+#else
+__device__ inline const LensPOD* lensArgsHere() { return nullptr; } // (the host pass of the compiler: never run)
+#endif
+
 template <int HS, int FOLD, bool LDS_SCENE>
 // 112 VGPRs x 4 waves/SIMD leaves 64 registers per SIMD lane for the resolve kernel's waves (see tptTraceQueueKernel;
 // amdgpu_num_vgpr counts half of the unified file on gfx90a+, so 56 means 112)
@@ -1304,7 +1325,10 @@ tptTraceKernel(const KernelArgs a)
             if (L.active) {
                 // laneStep's two halves, so that a caller's ray (tptTraceRaysDevice) can store its first hit between them
                 TPT_STAT(ST_STEP);
-                if (L.needCamera) laneCamera<FOLD>(L, fc);
+                if (L.needCamera) {
+                    if (a.lens.kind != LENS_NONE) laneLens<FOLD>(L, fc, lensArgsHere()); // (launch-uniform: a scalar branch)
+                    else laneCamera<FOLD>(L, fc);
+                }
                 const bool firstOfRay = a.rays != nullptr && L.depth == 0 && L.kind == KIND_MAIN;
                 float t;
                 int id;
@@ -3175,6 +3199,12 @@ int tptTraceOccupancy(int hs, int fold, bool ldsScene, size_t lds)
 hipError_t tptLaunchTraceRays(const KernelArgs& a, int hs, int fold, bool ldsScene, int blocks, size_t lds, hipStream_t stream)
 {
     if (!a.rays || (!a.rayRadiance && !a.rayHits)) return hipErrorInvalidValue;
+    TPT_DISPATCH(launchOne, a, blocks, lds, stream);
+}
+// tptDrawDeviceLens: the same eight instantiations in their pixel mode, every sample started at a.lens
+hipError_t tptLaunchTraceLens(const KernelArgs& a, int hs, int fold, bool ldsScene, int blocks, size_t lds, hipStream_t stream)
+{
+    if (a.lens.kind < LENS_EQUIRECT || a.lens.kind > LENS_ORTHO || a.rays || !a.frameColour) return hipErrorInvalidValue;
     TPT_DISPATCH(launchOne, a, blocks, lds, stream);
 }
 

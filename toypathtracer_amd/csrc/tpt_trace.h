@@ -47,6 +47,14 @@ struct CameraPOD {
     float origin[3], lowerLeftCorner[3], horizontal[3], vertical[3], uu[3], vv[3], ww[3];
     float lensRadius;
 };
+// A lens other than the camera's (tptDrawDeviceLens): word for word tptLens of include/tpt_hip.h (64 B), so the host copies the
+// caller's record.  kind 0: none, the launch starts its samples at the camera.
+enum { LENS_NONE = 0, LENS_EQUIRECT = 1, LENS_FISHEYE = 2, LENS_ORTHO = 3 };
+struct LensPOD {
+    int kind;
+    float origin[3], right[3], up[3], forward[3];
+    float sx, sy, maxAngle;
+};
 
 // Device-side view of the scene (all arrays built on the host by tptUpdate, see tpt_host.cpp).
 //   pairs  : phase-1 stream, one 32-B record per sphere PAIR {cx0,cx1, cy0,cy1, cz0,cz1, sq0,sq1};
@@ -828,6 +836,48 @@ TPT_HD void cameraGetRay(const CameraPOD& c, float s, float t, uint32_t& state, 
     orig = ld3(c.origin) + offset;
     dir = normalize(ld3(c.lowerLeftCorner) + s * ld3(c.horizontal) + t * ld3(c.vertical) - ld3(c.origin) - offset);
 }
+// A sample's ray through a lens (tptDrawDeviceLens; include/tpt_hip.h states the three projections): binary32 in the order written,
+// each vector * scalar three multiplies, the sums left to right, sin and cos glibc's (tsincosf), then the reference's normalize as
+// cameraGetRay applies it.  No random number is drawn: these lenses have no aperture.  The angles (a, b: EQUIRECT; r * maxAngle:
+// FISHEYE) go through ONE expansion of tsincosf, a loop the kind gives 2, 1 or 0 turns (the kind is launch-uniform).
+// (LensPtr: a pointer to the record in whatever address space it lies -- the kernel reads it from its argument segment)
+template <class LensPtr>
+TPT_HD void lensGetRayAt(LensPtr l, float u, float v, f3& orig, f3& dir)
+{
+    const float a = (u - 0.5f) * l->sx, b = (v - 0.5f) * l->sy;
+    const int kind = l->kind;
+    float r = 0.0f, angle = a;
+    if (kind == LENS_FISHEYE) {
+        r = tsqrt(a * a + b * b);
+        angle = r * l->maxAngle;
+    }
+    // after the loop: EQUIRECT (sa, ca) = sincos(a), (sb, cb) = sincos(b); FISHEYE (sb, cb) = sincos(r * maxAngle)
+    float sa = 0.0f, ca = 0.0f, sb = 0.0f, cb = 0.0f;
+    const int turns = kind == LENS_EQUIRECT ? 2 : (kind == LENS_FISHEYE ? 1 : 0);
+#if defined(__clang__)
+#pragma clang loop unroll(disable)
+#endif
+    for (int i = 0; i < turns; ++i) {
+        sa = sb;
+        ca = cb;
+        tsincosf(angle, sb, cb);
+        angle = b;
+    }
+    const f3 org = mk3(l->origin[0], l->origin[1], l->origin[2]), rgt = mk3(l->right[0], l->right[1], l->right[2]);
+    const f3 upw = mk3(l->up[0], l->up[1], l->up[2]), fwd = mk3(l->forward[0], l->forward[1], l->forward[2]);
+    orig = org;
+    f3 q = fwd;
+    if (kind == LENS_EQUIRECT) {
+        q = rgt * (cb * sa) + upw * sb + fwd * (cb * ca);
+    } else if (kind == LENS_FISHEYE) {
+        const float k = r > 0.0f ? sb / r : 0.0f;
+        q = rgt * (a * k) + upw * (b * k) + fwd * cb;
+    } else {
+        orig = (orig + rgt * a) + upw * b;
+    }
+    dir = normalize(q);
+}
+TPT_HD void lensGetRay(const LensPOD& l, float u, float v, f3& orig, f3& dir) { lensGetRayAt(&l, u, v, orig, dir); }
 TPT_HD f3 sky(f3 dir)
 {
     float t = 0.5f * (dir.y + 1.0f);
@@ -907,6 +957,26 @@ TPT_HD void laneCamera(Lane& L, const FrameConsts& fc)
     float u = ((float)L.x + rnd01(L.rng)) * fc.invWidth;
     float v = ((float)L.y + rnd01(L.rng)) * fc.invHeight;
     cameraGetRay(fc.cam, u, v, L.rng, L.orig, L.dir);
+    L.depth = 0;
+    L.doMatE = true;
+    L.kind = KIND_MAIN;
+    L.needCamera = false;
+    if (FOLD == FOLD_FORWARD) {
+        L.radiance = mk3(0, 0, 0);
+        L.throughput = mk3(1, 1, 1);
+    } else {
+        L.sp = 0;
+    }
+}
+
+// New sample through a lens (tptDrawDeviceLens): laneCamera with lensGetRay in cameraGetRay's place.
+template <int FOLD, class LensPtr>
+TPT_HD void laneLens(Lane& L, const FrameConsts& fc, LensPtr lens)
+{
+    TPT_STAT(ST_CAMERA);
+    float u = ((float)L.x + rnd01(L.rng)) * fc.invWidth;
+    float v = ((float)L.y + rnd01(L.rng)) * fc.invHeight;
+    lensGetRayAt(lens, u, v, L.orig, L.dir);
     L.depth = 0;
     L.doMatE = true;
     L.kind = KIND_MAIN;
