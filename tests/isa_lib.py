@@ -3,6 +3,7 @@ disassembled (the `code_object` fixture, count()); the library's exported symbol
 declares it; and the run of a refusal script against the host runtime compiled for tests/hostemu (a refused call returns before anything
 is enqueued).  No GPU needed: the fat binary is unbundled and disassembled with the ROCm LLVM tools.  The kernels' names are
 tests/kernel_manifest.py's."""
+import collections
 import functools
 import os
 import re
@@ -105,3 +106,20 @@ def run_refusals(script, lib="libtpt_hostemu.so", extra_sources=()):
     out = p.stdout.decode()
     assert p.returncode == 0 and out.rstrip().endswith("ok"), out[-3000:]
     return out
+
+
+def refusal_messages(out):
+    """what a refusal script's "refused: <case> -- <message>" lines report: {message: how many cases reported it}.  A test holds this
+    against the messages written out character for character, so a message that changes, or a case that reports another rule than it
+    did (two rules violated: the order of the checks), fails."""
+    return dict(collections.Counter(ln.split(" -- ", 1)[1] for ln in out.splitlines() if ln.startswith("refused:") and " -- " in ln))
+
+
+def refused_without_its_launcher(body, message, lib="libtpt_hostemu.so", extra_sources=()):
+    """The host runtime with the emulated kernels alone (the launcher is a weak symbol nobody defines; `lib` and `extra_sources`: a
+    build that has some launchers and lacks others): after InitializeTest, `body` -- Python source with tpt (the binding), lib, C and
+    np in scope -- makes calls and leaves the last one's return value in `rc`; that call is refused with exactly `message`."""
+    script = ("import ctypes as C, sys\nimport numpy as np\nsys.path.insert(0, sys.argv[1])\nfrom toypathtracer_amd import api as tpt\n"
+              "lib = tpt.load_library()\nmsg = lambda: lib.tptGetLastError().decode()\ntpt.InitializeTest()\n" + body +
+              "\nassert rc != 0 and msg() == %r, (rc, msg())\ntpt.ShutdownTest()\nprint('ok')\n" % message)
+    return run_refusals(script, lib, extra_sources)

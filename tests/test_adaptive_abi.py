@@ -7,7 +7,7 @@ import re
 
 import pytest
 
-from isa_lib import code_object, count, exported_symbols, header, header_params, no_library, run_refusals  # noqa: F401  (code_object: a module fixture)
+from isa_lib import code_object, count, exported_symbols, header, header_params, no_library, refusal_messages, refused_without_its_launcher, run_refusals  # noqa: F401  (code_object: a module fixture)
 from kernel_manifest import ADAPTIVE, ADAPTIVE_PLAN as PLAN, ADAPTIVE_RESOLVE as RESOLVE, MOMENTS, QUEUE, family
 
 # The path-queue kernel's instantiations as the parent commit's build has them (the same compiler, the same flags):
@@ -227,6 +227,17 @@ refused("total in the moments", plan, P, t=mo.ctypes.data + 8)
 refused("variance overlaps the counts", plan, P, c=big.ctypes.data + plane - 4, v=big)
 refused("total in the counts", plan, P, t=cnt.ctypes.data + 8)
 refused("total in the variance", plan, P, t=var.ctypes.data + plane - 8)
+# two rules broken at once: the one that is checked first is the one reported
+def order(expect, **kw):
+    rc = plan(**kw)
+    msg = lib.tptGetLastError().decode()
+    assert rc != 0 and msg == P + ": " + expect, (expect, sorted(kw), rc, msg)
+    print("order:", sorted(kw), "--", expect)
+order("deviceMoments and deviceSampleCounts are required", c=None, te=0.0)
+order("targetError must lie in (0, 1e6]", te=0.0, lo=-1)
+order("0 <= minSamples <= maxSamples <= 2047 expected", lo=-1, v=mo)
+order("an output overlaps deviceMoments", c=mo.ctypes.data + plane - 4, t=var.ctypes.data + 8)  # (the input's pairs before the outputs')
+order("an output overlaps deviceMoments", v=big, c=big.ctypes.data + plane - 4, t=mo.ctypes.data + 8)  # (... the last of them too)
 assert emu.hostemuAdaptivePlans() == 0, "a refused plan reached the launcher"
 for kw in (dict(), dict(v=None), dict(t=None), dict(v=None, t=None), dict(te=1e6), dict(te=1e-30), dict(lo=0, hi=0), dict(lo=2047, hi=2047),
            dict(ww=1, hh=1), dict(v=big, c=big.ctypes.data + plane)):
@@ -244,3 +255,33 @@ def test_refusals_through_the_host_runtime():
     out = run_refusals(REFUSALS, "libtpt_hostemu_adaptive.so", ["hostemu_adaptive.cpp"])
     assert out.count("refused:") == 2 + 16 + 5 + 4 + 2 + 6 + 3 + 6, out
     assert out.count("accepted:") == 2 + 10, out
+    assert out.count("order:") == 5, out
+    D, P = "tptDrawDeviceAdaptive: ", "tptAdaptiveSamplesDevice: "
+    assert refusal_messages(out) == {
+        "tpt: not initialised (call tptInitialize / InitializeTest first)": 2,
+        D + "call tptUpdate (UpdateTest) at this size first": 2,
+        D + "bad arguments (deviceTile, deviceMoments, deviceSampleCounts, size)": 3,
+        D + "deviceMoments overlaps the tile or a plane": 4,
+        D + "frames of at most 8192 x 8192": 1,
+        D + "needs per-pixel seeds (tptSetSeedMode(1)); row-serial sample counts are not supported": 1,
+        D + "needs the recursive fold (tptSetFoldMode(0))": 1,
+        D + "needs the path-queue kernel (tptSetKernelVariant(0, 3, ..))": 2,
+        D + "not with row sharding or a communicator (sharded sample counts are not supported)": 2,
+        D + "not with a tile mirror (tptSetTileMirror)": 1,
+        D + "deviceSampleCounts overlaps the tile, the moments or a plane": 4,
+        P + "w and h must lie in 1..8192": 4,
+        P + "deviceMoments and deviceSampleCounts are required": 2,
+        P + "targetError must lie in (0, 1e6]": 6,
+        P + "0 <= minSamples <= maxSamples <= 2047 expected": 3,
+        P + "an output overlaps deviceMoments": 3,
+        P + "two outputs overlap": 3,
+    }
+
+
+def test_a_build_without_the_plan_launcher_refuses():
+    refused_without_its_launcher('''
+mo, cnt = np.full((8, 16, 4), 0.5, np.float32), np.full((8, 16), 4, np.int32)
+rc = lib.tptAdaptiveSamplesDevice(16, 8, mo.ctypes.data, 0.05, 0, 64, cnt.ctypes.data, None, None)
+tpt.synchronize()
+assert (cnt == 4).all()
+''', "tptAdaptiveSamplesDevice: this build has no adaptive plan kernel")

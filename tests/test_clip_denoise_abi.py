@@ -12,7 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from isa_lib import code_object, count, exported_symbols, header, header_params, no_library, run_refusals  # noqa: F401  (code_object: a module fixture)
+from isa_lib import code_object, count, exported_symbols, header, header_params, no_library, refusal_messages, refused_without_its_launcher, run_refusals  # noqa: F401  (code_object: a module fixture)
 from kernel_manifest import FRAMES, VARIANCE, family
 from oracle_lib import ROOT
 
@@ -281,6 +281,19 @@ refused("the history lies in the third moments plane", **dict(CONTINUED, history
 refused("out's last plane holds the history's head", **dict(CONTINUED, out=b, history=b + 3 * plane_b - 4))
 refused("the history's last plane holds out's head", **dict(CONTINUED, history=b, out=b + 3 * plane_b - 4))
 refused("a history that is only written overlaps out", history=b + plane_b, out=b)
+# two rules broken at once: the one that is checked first is the one reported
+def order(expect, **kw):
+    rc = call(**kw)
+    assert rc != 0 and msg() == F + ": " + expect, (expect, sorted(kw), rc, msg())
+    print("order:", sorted(kw), "--", expect)
+order("samples must be finite and at least 1", s=0.0, sl=0.0)
+order("sigmaLuminance must lie in (0, 1e6]", sl=0.0, sn=float("nan"))
+order("unknown flag bits", fl=2, no=-1)
+order("nObjects must lie in 0..65534", no=-1, motion=ins["motion"])
+order("deviceFrameObjectMotion and nObjects must be given together", motion=ins["motion"], no=0)
+order("nObjects must lie in 0..65534", **dict(OBJECTS, no=65535, mh=0.0))
+order("maxHistory must lie in 1..65536", **dict(OBJECTS, mh=0.0, out=b, objects=b))
+order("deviceFrameOut or deviceHistory overlaps an input", **dict(CONTINUED, history=b + plane_b, out=b, prev_nd=b))
 assert counters() == (0, 0, 1), "a refused call reached a launcher"
 tpt.synchronize()
 assert np.isnan(out).all() and np.isnan(history).all() and np.isnan(big).all(), "a refused call wrote"
@@ -385,6 +398,61 @@ def test_refusals_and_the_launch_plan_through_the_host_runtime():
     staging, overlaps = 2, 12 + 5 + 6
     assert out.count("refused:") == head + modes + filter_ + temporal + staging + overlaps, out
     assert out.count("accepted:") == 1 + 4 + 5 + 2, out
+    assert out.count("order:") == 8, out
+    F = "tptDenoiseClipDevice: "
+    assert refusal_messages(out) == {
+        "tpt: not initialised (call tptInitialize / InitializeTest first)": 1,
+        F + "args is required": 1,
+        F + "nFrames must lie in 1..4096": 3,
+        F + "w and h must lie in 1..8192": 5,
+        F + "unknown clipFlags bits": 3,
+        F + "deviceFrameImages, deviceFrameMoments and deviceFrameOut are required": 6,
+        F + "deviceFrameAlbedo, deviceFrameNormalDepth and cameras are required without TPT_CLIP_DENOISE_SPATIAL_ONLY": 3,
+        F + "TPT_CLIP_DENOISE_SPATIAL_ONLY takes no object planes and no motion tables": 3,
+        F + "TPT_CLIP_DENOISE_SPATIAL_ONLY takes no continuation (prevCamera, the prev planes, deviceHistory)": 4,
+        F + "devicePrevNormalDepth and devicePrevObject need prevCamera": 2,
+        F + "prevCamera needs deviceHistory and devicePrevNormalDepth": 2,
+        F + "with prevCamera, devicePrevObject must be given exactly when deviceFrameObjects is": 2,
+        F + "deviceFrameObjectMotion needs deviceFrameObjects": 1,
+        F + "iterations must lie in 1..8": 3,
+        F + "samples must be finite and at least 1": 4,
+        F + "sigmaLuminance must lie in (0, 1e6]": 4,
+        F + "sigmaNormal and sigmaDepth must be 0 or lie in [1e-6, 1e6]": 8,
+        F + "unknown flag bits": 1,
+        F + "sigmaNormal and sigmaDepth need deviceNormalDepth": 1,
+        F + "TPT_DENOISE_DEMODULATE needs deviceAlbedo": 1,
+        F + "maxHistory must lie in 1..65536": 4,
+        F + "every tolerance must be finite and at least 0": 9,
+        F + "camera has a non-finite field, a degenerate frame or its frame behind its origin": 6,
+        F + "prevCamera has a non-finite field, a degenerate frame or its frame behind its origin": 2,
+        F + "nObjects must lie in 0..65534": 3,
+        F + "deviceFrameObjectMotion and nObjects must be given together": 2,
+        F + "not even one frame's staging stays within 4096 MiB": 2,
+        F + "deviceOut overlaps an input": 4,
+        F + "deviceFrameOut or deviceHistory overlaps an input": 16,
+        F + "deviceFrameOut overlaps deviceHistory": 3,
+    }
+
+
+NO_LAUNCHER = '''
+sys.path.insert(0, sys.argv[1] + "/tests")
+from temporal_lib import look_at_camera
+planes = [np.full((2, 8, 16, 4), 0.25, np.float32) for _ in range(4)] + [np.full((2, 8, 16, 4), np.nan, np.float32)]
+cams = np.stack([look_at_camera([0.02 * j, 2.0, 3.0], [0.0, 0.0, 0.0], 16, 8) for j in range(2)])
+A = tpt.ClipDenoiseArgs(screenWidth=16, screenHeight=8, nFrames=2, deviceFrameImages=planes[0].ctypes.data, deviceFrameMoments=planes[1].ctypes.data,
+                        deviceFrameAlbedo=planes[2].ctypes.data, deviceFrameNormalDepth=planes[3].ctypes.data, cameras=cams.ctypes.data,
+                        deviceFrameOut=planes[4].ctypes.data, iterations=2, samples=4.0, sigmaLuminance=4.0, maxHistory=4.0)
+rc = lib.tptDenoiseClipDevice(C.byref(A))
+tpt.synchronize()
+assert np.isnan(planes[4]).all()
+'''
+
+
+def test_a_build_without_the_launchers_refuses():
+    """without any launcher the filter's is the one missed; with the filter's alone (tests/hostemu_clip_denoise.cpp) the temporal pass's"""
+    refused_without_its_launcher(NO_LAUNCHER, "tptDenoiseClipDevice: this build has no frame-stack a-trous kernel")
+    refused_without_its_launcher(NO_LAUNCHER, "tptDenoiseClipDevice: this build has no temporal accumulation kernel",
+                                 "libtpt_hostemu_clip_atrous.so", ["hostemu_clip_denoise.cpp"])
 
 
 DATA_FLOW = r'''

@@ -1,11 +1,12 @@
 """tptDenoiseDevice without a GPU: the declaration, the binding and the export of the entry point; the binding's argument checks; the
 gfx950 code of the a-trous kernels in the shipped library; and every refusal of the ABI, driven through the host runtime compiled
-against tests/hostemu (a refused call returns before anything is enqueued, so no kernel is emulated)."""
+against tests/hostemu (a refused call returns before anything is enqueued, so no kernel is emulated), and the growth of the scratch
+plane between the calls of one sequence, for which tests/hostemu_denoise.cpp runs the filter and tests/denoise_checker.c says the image."""
 import re
 
 import pytest
 
-from isa_lib import code_object, count, exported_symbols, header, header_params, no_library, run_refusals  # noqa: F401  (code_object: a module fixture)
+from isa_lib import code_object, count, exported_symbols, header, header_params, no_library, refusal_messages, refused_without_its_launcher, run_refusals  # noqa: F401  (code_object: a module fixture)
 from kernel_manifest import DENOISE, family
 
 
@@ -147,8 +148,64 @@ tpt.synchronize()
 assert np.isnan(out).all(), "a refused call wrote deviceOut"
 assert (col == 0.5).all() and (alb == 0.25).all() and (nd == 3.0).all()
 tpt.ShutdownTest()
+# two rules broken at once: the one that is checked first is the one reported
+tpt.InitializeTest()
+def order(expect, **kw):
+    rc = call(**kw)
+    msg = lib.tptGetLastError().decode()
+    assert rc != 0 and msg == "tptDenoiseDevice: " + expect, (expect, kw, rc, msg)
+    print("order:", sorted(kw), "--", expect)
+order("w and h must lie in 1..8192", ww=0, c=None)
+order("deviceColour and deviceOut are required", o=None, a=out)
+order("deviceOut overlaps an input", o=col, it=0)
+order("iterations must lie in 1..8", it=9, sc=-1.0)
+order("every sigma must be 0 or lie in [1e-6, 1e6]", sd=float("nan"), n=None)
+order("sigmaNormal and sigmaDepth need deviceNormalDepth", n=None, fl=2)
+order("unknown flag bits", fl=3, a=None)
+assert launches() == 8
+# the scratch plane the iterations ping-pong through (Context::dDenoise) grows between the calls of one sequence: 8 x 8, 24 x 16, 8 x 8
+# again with no wait in between, the launcher now running the filter as stream work (tests/hostemu_denoise.cpp).  The growth itself
+# drains the context stream (under the lazy schedule nothing else runs the first call before its plane goes), and every image is
+# tests/denoise_checker.c's.  Four iterations: the scratch plane is written, read, written and read again.
+import tempfile
+sys.path.insert(0, sys.argv[1] + "/tests")
+from denoise_lib import DenoiseChecker, random_planes
+checker = DenoiseChecker(tempfile.mkdtemp(prefix="denoise_abi_"))
+emu = C.CDLL(tpt.library_path())
+emu.hostemuDenoiseRun(1)
+def stats():
+    st = (C.c_longlong * 2)(); emu.hostemu_stats(st); return st[0], st[1]
+rng = np.random.default_rng(11)
+planes = [random_planes(rng, hh, ww) for ww, hh in ((8, 8), (24, 16), (8, 8))]
+outs = [np.full(p[0].shape, np.nan, np.float32) for p in planes]
+def run(k):
+    c, a, n = planes[k]
+    assert call(ww=c.shape[1], hh=c.shape[0], c=c, a=a, n=n, o=outs[k], it=4) == 0, lib.tptGetLastError().decode()
+run(0)
+ran, frees = stats()
+run(1)
+assert stats()[1] == frees + 1, "the scratch plane did not grow"
+assert stats()[0] > ran, "the growth did not drain the context stream"
+run(2)
+assert stats()[1] == frees + 1, "the scratch plane was replaced again"
+tpt.synchronize()
+for k, (c, a, n) in enumerate(planes):
+    want = checker.run(c, a, n, iterations=4, sigma_colour=1.0, sigma_normal=0.2, sigma_depth=0.5, flags=1)
+    assert outs[k].tobytes() == want.tobytes(), ("growth", k)
+print("growth: the scratch plane grows between calls")
+tpt.ShutdownTest()
 print("ok")
 '''
+
+
+def test_a_build_without_the_launcher_refuses():
+    refused_without_its_launcher('''
+col, out = np.zeros((8, 16, 4), np.float32), np.full((8, 16, 4), np.nan, np.float32)
+lib.tptDenoiseDevice.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_uint]
+rc = lib.tptDenoiseDevice(16, 8, col.ctypes.data, None, None, out.ctypes.data, 3, 1.0, 0.0, 0.0, 0)
+tpt.synchronize()
+assert np.isnan(out).all()
+''', "tptDenoiseDevice: this build has no a-trous kernel")
 
 
 def test_refusals_through_the_host_runtime(tmp_path):
@@ -156,3 +213,15 @@ def test_refusals_through_the_host_runtime(tmp_path):
     out = run_refusals(REFUSALS, "libtpt_hostemu_denoise.so", ["hostemu_denoise.cpp"])
     assert out.count("refused:") == 1 + 5 + 2 + 3 + 2 + 3 + 27 + 3 + 4, out
     assert out.count("accepted:") == 8, out
+    assert out.count("order:") == 7 and "growth: the scratch plane grows between calls" in out, out
+    assert refusal_messages(out) == {
+        "tpt: not initialised (call tptInitialize / InitializeTest first)": 1,
+        "tptDenoiseDevice: w and h must lie in 1..8192": 5,
+        "tptDenoiseDevice: deviceColour and deviceOut are required": 2,
+        "tptDenoiseDevice: deviceOut overlaps an input": 5,
+        "tptDenoiseDevice: iterations must lie in 1..8": 3,
+        "tptDenoiseDevice: every sigma must be 0 or lie in [1e-6, 1e6]": 27,
+        "tptDenoiseDevice: sigmaNormal and sigmaDepth need deviceNormalDepth": 2,
+        "tptDenoiseDevice: TPT_DENOISE_DEMODULATE needs deviceAlbedo": 1,
+        "tptDenoiseDevice: unknown flag bits": 4,
+    }

@@ -11,7 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from isa_lib import code_object, count, exported_symbols, header, header_params, no_library, run_refusals  # noqa: F401  (code_object: a module fixture)
+from isa_lib import code_object, count, exported_symbols, header, header_params, no_library, refusal_messages, refused_without_its_launcher, run_refusals  # noqa: F401  (code_object: a module fixture)
 from kernel_manifest import FLOW, family
 from oracle_lib import ROOT
 
@@ -249,6 +249,15 @@ refused("out holds the third table's last entry", **dict(OBJECTS, out=b + 16, mo
 refused("out holds the prev albedo plane", **dict(CONTINUED, out=b, prev_albedo=b + 3 * plane_b - 4))
 refused("out holds the prev normal/depth plane", **dict(CONTINUED, out=b + plane_b - 4, prev_nd=b))
 refused("out holds the prev object plane", **dict(CONTINUED, **dict(OBJECTS, out=b + w * h * 4 - 4, prev_object=b)))
+# two rules broken at once: the one that is checked first is the one reported
+def order(expect, **kw):
+    rc = call(**kw)
+    assert rc != 0 and msg() == F + ": " + expect, (expect, sorted(kw), rc, msg())
+    print("order:", sorted(kw), "--", expect)
+order("deviceFrameObjectMotion needs deviceFrameObjects", motion=ins["motion"], no=-1)
+order("nObjects must lie in 0..65534", **dict(OBJECTS, no=65535, dt=-1.0))
+order("deviceFrameObjectMotion and nObjects must be given together", **dict(OBJECTS, no=0, dt=-1.0))
+order("every tolerance must be finite and at least 0", dt=-1.0, out=ins["albedo"])
 assert launches() == 0 and so.hostemuTemporalLaunches() == 0, "a refused call reached a launcher"
 o0 = ops()
 tpt.synchronize()
@@ -357,3 +366,37 @@ def test_refusals_and_the_launch_plan_through_the_host_runtime():
     overlaps = 6 + 3 + 3
     assert out.count("refused:") == head + prev_set + tables + scalars_and_cameras + overlaps, out
     assert out.count("accepted:") == 12 + 1 + 1 + 1, out
+    assert out.count("order:") == 4, out
+    F = "tptMotionVectorsDevice: "
+    assert refusal_messages(out) == {
+        "tpt: not initialised (call tptInitialize / InitializeTest first)": 1,
+        F + "args is required": 1,
+        F + "nFrames must lie in 1..4096": 3,
+        F + "w and h must lie in 1..8192": 5,
+        F + "flags must be 0": 3,
+        F + "cameras, deviceFrameAlbedo, deviceFrameNormalDepth and deviceFrameMotion are required": 4,
+        F + "devicePrevAlbedo, devicePrevNormalDepth and devicePrevObject need prevCamera": 6,
+        F + "prevCamera needs devicePrevAlbedo and devicePrevNormalDepth": 3,
+        F + "with prevCamera, devicePrevObject must be given exactly when deviceFrameObjects is": 2,
+        F + "deviceFrameObjectMotion needs deviceFrameObjects": 1,
+        F + "nObjects must lie in 0..65534": 3,
+        F + "deviceFrameObjectMotion and nObjects must be given together": 2,
+        F + "every tolerance must be finite and at least 0": 9,
+        F + "camera has a non-finite field, a degenerate frame or its frame behind its origin": 9,
+        F + "prevCamera has a non-finite field, a degenerate frame or its frame behind its origin": 2,
+        F + "deviceFrameMotion overlaps an input": 12,
+    }
+
+
+def test_a_build_without_the_launcher_refuses():
+    refused_without_its_launcher('''
+sys.path.insert(0, sys.argv[1] + "/tests")
+from temporal_lib import look_at_camera
+planes = [np.full((2, 8, 16, 4), 0.25, np.float32) for _ in range(2)] + [np.full((2, 8, 16, 4), np.nan, np.float32)]
+cams = np.stack([look_at_camera([0.02 * j, 2.0, 3.0], [0.0, 0.0, 0.0], 16, 8) for j in range(2)])
+A = tpt.MotionVectorsArgs(screenWidth=16, screenHeight=8, nFrames=2, cameras=cams.ctypes.data, deviceFrameAlbedo=planes[0].ctypes.data,
+                          deviceFrameNormalDepth=planes[1].ctypes.data, deviceFrameMotion=planes[2].ctypes.data, depthTolerance=0.1)
+rc = lib.tptMotionVectorsDevice(C.byref(A))
+tpt.synchronize()
+assert np.isnan(planes[2]).all()
+''', "tptMotionVectorsDevice: this build has no motion-vector kernel")

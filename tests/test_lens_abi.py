@@ -11,7 +11,7 @@ import sys
 import numpy as np
 import pytest
 
-from isa_lib import code_object, exported_symbols, header, header_params, no_library, run_refusals  # noqa: F401  (code_object: a fixture)
+from isa_lib import code_object, exported_symbols, header, header_params, no_library, refusal_messages, run_refusals  # noqa: F401  (code_object: a fixture)
 from kernel_manifest import TRACE, family
 from lens_lib import EQUIRECT, FISHEYE, ORTHO, PI, TWO_PI, Lens, LensChecker, make_lens
 from oracle_lib import ROOT
@@ -129,7 +129,7 @@ LENS_FAULTS = [
     dict(tile=None), dict(tile=-16), dict(tile=1.5), dict(tile="t"), dict(count=-1), dict(count=2.5), dict(count=True),
     dict(count=4096 + 8), dict(count=4096 + 16 * 16 * 8 - 1), dict(count=4096 - 7), dict(lens=None), dict(lens="equirect"),
     dict(lens=Lens()),
-] + [dict(lens_fault=f) for f in LENS_FAULTS], ids=lambda a: ",".join("%s=%.40r" % kv for kv in a.items()))
+] + [dict(lens_fault=f) for f in LENS_FAULTS], ids=lambda a: ",".join("%s=%.40r" % (k, "Lens()" if isinstance(v, Lens) else v) for k, v in a.items()))
 def test_binding_checks_arguments_before_the_library(monkeypatch, args):
     from toypathtracer_amd import api
     monkeypatch.setattr(api, "load_library", no_library)
@@ -345,12 +345,28 @@ if REFUSALS:
               ("equirect with a maxAngle", E(maxAngle=0.5)), ("ortho with a maxAngle", O(maxAngle=1e-9))]
     for what, lens in faults:
         refused("lens: " + what, lens=lens)
+    # two rules broken at once: the one that is checked first is the one reported
+    def order(expect, **kw):
+        refused("order", **kw)
+        assert msg() == "tptDrawDeviceLens: " + expect, (expect, kw, msg())
+        print("order:", sorted(kw), "--", expect)
+    order("screenWidth and screenHeight must lie in 1..8192", w=0, frame=-1)
+    order("frameCount must not be negative", frame=-1, flags=1)
+    order("flags must be 0 or TPT_FLAG_PROGRESSIVE", flags=1, tile=None)
+    order("deviceTile is required", tile=None, lens=E(kind=0))
+    order("deviceRayCount lies inside the tile", count=b, lens=E(kind=0))
+    order("unknown lens kind", lens=E(kind=0, sx=nan))
     # what a scene can do
     s, m = cloud_scene(3100, lights=3073)
     tpt.set_scene(s, m)
     tpt.UpdateTest(0.0, 0, W, H, 0)
     assert len(tpt.GetSceneDesc()[3]) == 3073
     refused("3073 emissive spheres")
+    order("a fisheye scale beyond 4", lens=F(sx=4.5))  # (the lens before the scene)
+    tpt.set_kernel_variant(2, 1, 1)
+    tpt.UpdateTest(0.0, 0, W, H, 0)
+    order("too many emissive spheres for the LDS light table (3072 at most)")  # (the lights before the LDS fit)
+    tpt.set_kernel_variant(0, 3, -1)
     s, m = cloud_scene(3000)
     tpt.set_scene(s, m)
     tpt.set_kernel_variant(2, 1, 1)  # flat, and staged in LDS whatever its size: 3000 x 68 B
@@ -383,6 +399,27 @@ if REFUSALS:
 tpt.InitializeTest()
 tpt.UpdateTest(0.0, 0, W, H, 0)
 s, m = tpt.GetSceneDesc()[:2]
+# the draw's colour plane (Context::dLensColour) grows between the draws of one sequence: 8 x 8, 24 x 16, 8 x 8 again with no wait in
+# between.  The growth itself drains the context stream (under the lazy schedule nothing else runs the first draw before its plane
+# goes), and every tile is the checker's.  In the forward fold, which has no bounce-stack spill: the plane is the only buffer that grows.
+def stats():
+    st = (C.c_longlong * 2)(); so.hostemu_stats(st); return st[0], st[1]
+tpt.set_samples_per_pixel(2)
+tpt.set_fold_mode(1)
+lens = make_lens(FISHEYE, max_angle=PI)
+tiles = [np.zeros((h, w, 4), np.float32) for w, h in ((8, 8), (24, 16), (8, 8))]
+tpt.draw_device_lens(0, 8, 8, ptr(tiles[0]), to_api(lens))
+ran, frees = stats()
+tpt.draw_device_lens(1, 24, 16, ptr(tiles[1]), to_api(lens))
+assert stats()[1] == frees + 1, "the colour plane did not grow"
+assert stats()[0] > ran, "the growth did not drain the context stream"
+tpt.draw_device_lens(2, 8, 8, ptr(tiles[2]), to_api(lens))
+assert stats()[1] == frees + 1, "the plane was replaced again"
+tpt.synchronize()
+tpt.set_fold_mode(0)
+for frame, tile in enumerate(tiles):
+    assert tile.tobytes() == checker.render(s, m, lens, tile.shape[1], tile.shape[0], 2, frame, fold=1)[1].tobytes(), ("growth", frame)
+print("accepted: the colour plane grows between draws")
 n_draws = 0
 for kind in sorted(KINDS):
     lens = make_lens(KINDS[kind])
@@ -452,6 +489,15 @@ print("ok")
 '''
 
 
+# (the script's order cases: the message each is held to, and how many of them)
+ORDER = {"tptDrawDeviceLens: screenWidth and screenHeight must lie in 1..8192": 1, "tptDrawDeviceLens: frameCount must not be negative": 1,
+         "tptDrawDeviceLens: flags must be 0 or TPT_FLAG_PROGRESSIVE": 1, "tptDrawDeviceLens: deviceTile is required": 1,
+         "tptDrawDeviceLens: deviceRayCount lies inside the tile": 1, "tptDrawDeviceLens: unknown lens kind": 1,
+         "tptDrawDeviceLens: a fisheye scale beyond 4": 1,
+         "tptDrawDeviceLens: too many emissive spheres for the LDS light table (3072 at most)": 1}
+ORDER_CASES = sum(ORDER.values())
+
+
 def run_script(mode, policy):
     from test_host_logic import build
     path = build("libtpt_hostemu_lens.so", [os.path.join(ROOT, "tests", "hostemu_lens.cpp")])
@@ -465,15 +511,40 @@ def run_script(mode, policy):
 
 def test_refusals_through_the_host_runtime():
     out = run_script("refusals", "lazy")
-    assert out.count("refused:") == 1 + 1 + 1 + 6 + 2 + 4 + 1 + 4 + 30 + 2, out
+    assert out.count("refused:") == 1 + 1 + 1 + 6 + 2 + 4 + 1 + 4 + 30 + 2 + ORDER_CASES, out
     assert "accepted: at the limits" in out
+    assert out.count("order:") == ORDER_CASES, out
+    messages = refusal_messages(out)
+    for message, cases in ORDER.items():  # (an order case is a refused case too, and is held to its message by the script)
+        messages[message] -= cases
+    assert messages == {
+        "tpt: not initialised (call tptInitialize / InitializeTest first)": 1,
+        "tptDrawDeviceLens: call tptUpdate first": 1,
+        "tptDrawDeviceLens: args is required": 1,
+        "tptDrawDeviceLens: screenWidth and screenHeight must lie in 1..8192": 6,
+        "tptDrawDeviceLens: frameCount must not be negative": 2,
+        "tptDrawDeviceLens: flags must be 0 or TPT_FLAG_PROGRESSIVE": 4,
+        "tptDrawDeviceLens: deviceTile is required": 1,
+        "tptDrawDeviceLens: deviceRayCount lies inside the tile": 4,
+        "tptDrawDeviceLens: unknown lens kind": 3,
+        "tptDrawDeviceLens: a non-finite lens field": 9,
+        "tptDrawDeviceLens: a basis vector is not of unit length (its squared length must lie in 0.99..1.01)": 3,
+        "tptDrawDeviceLens: two basis vectors are not orthogonal (their dot product must lie in -0.01..0.01)": 3,
+        "tptDrawDeviceLens: sx and sy must be positive": 3,
+        "tptDrawDeviceLens: an equirectangular span beyond 2 pi x pi": 2,
+        "tptDrawDeviceLens: a fisheye scale beyond 4": 2,
+        "tptDrawDeviceLens: a fisheye maxAngle outside (0, pi]": 3,
+        "tptDrawDeviceLens: maxAngle must be 0 for this lens kind": 2,
+        "tptDrawDeviceLens: too many emissive spheres for the LDS light table (3072 at most)": 1,
+        "tptDrawDeviceLens: scene too large for LDS staging; use tptSetKernelVariant(.., .., 0)": 1,
+    }
 
 
 @pytest.mark.parametrize("policy", ["eager", "lazy"])
 def test_accepted_draws_equal_the_checker(policy):
     out = run_script("accepted", policy)
     assert "accepted: 36 draws equal the checker" in out, out
-    for line in ("folds, variants, scenes", "row-serial context, back to back"):
+    for line in ("the colour plane grows between draws", "folds, variants, scenes", "row-serial context, back to back"):
         assert "accepted: " + line in out, out
 
 
@@ -485,13 +556,25 @@ import numpy as np
 sys.path.insert(0, sys.argv[1])
 from toypathtracer_amd import api as tpt
 lib = tpt.load_library()
+from toypathtracer_amd.scenes import cloud_scene
 tpt.InitializeTest()
-tpt.UpdateTest(0.0, 0, 16, 8, 0)
 tile = np.full((8, 16, 4), np.nan, np.float32)
 a = tpt.DrawLensArgs(screenWidth=16, screenHeight=8, frameCount=0, flags=0, lens=tpt.lens_equirect(), deviceTile=tile.ctypes.data, deviceRayCount=None)
+# the launcher is looked for last: a scene whose LDS does not fit is still refused as that
+s, m = cloud_scene(3000)
+tpt.set_scene(s, m)
+tpt.set_kernel_variant(2, 1, 1)
+tpt.UpdateTest(0.0, 0, 16, 8, 0)
+assert lib.tptDrawDeviceLens(C.byref(a)) != 0
+m = lib.tptGetLastError().decode()
+assert m == "tptDrawDeviceLens: scene too large for LDS staging; use tptSetKernelVariant(.., .., 0)", m
+tpt.set_kernel_variant(0, 3, -1)
+tpt.set_scene(None, None)
+tpt.UpdateTest(0.0, 0, 16, 8, 0)
 assert lib.tptDrawDeviceLens(C.byref(a)) != 0
 m = lib.tptGetLastError().decode()
 assert "tptDrawDeviceLens" in m and "launcher" in m, m
+assert m == "tptDrawDeviceLens: this build has no lens launcher", m
 tpt.synchronize()
 assert np.isnan(tile).all()
 tpt.ShutdownTest()

@@ -7,7 +7,7 @@ import re
 
 import pytest
 
-from isa_lib import code_object, count, exported_symbols, header, header_params, no_library, run_refusals  # noqa: F401  (code_object: a module fixture)
+from isa_lib import code_object, count, exported_symbols, header, header_params, no_library, refusal_messages, refused_without_its_launcher, run_refusals  # noqa: F401  (code_object: a module fixture)
 from kernel_manifest import AOV, MOMENTS, QUEUE, VARIANCE, family
 
 
@@ -199,6 +199,21 @@ for v in (-1.0, 1e-7, float("nan"), 2e6):
 refused("sigmaDepth without the plane", den, V, n=None, sn=0.0)
 refused("demodulate without albedo", den, V, a=None)
 refused("unknown flag", den, V, fl=2)
+# two rules broken at once: the one that is checked first is the one reported
+def order(expect, **kw):
+    rc = den(**kw)
+    msg = lib.tptGetLastError().decode()
+    assert rc != 0 and msg == V + ": " + expect, (expect, kw, rc, msg)
+    print("order:", sorted(kw), "--", expect)
+order("deviceColour and deviceOut are required", c=None, m=None)
+order("deviceMoments is required", m=None, o=tile)
+order("deviceOut overlaps an input", o=mo, it=0)
+order("iterations must lie in 1..8", it=0, s=0.0)
+order("samples must be finite and at least 1", s=float("nan"), sl=0.0)
+order("sigmaLuminance must lie in (0, 1e6]", sl=0.0, sn=float("nan"))
+order("sigmaNormal and sigmaDepth must be 0 or lie in [1e-6, 1e6]", sd=2e6, n=None)
+order("sigmaNormal and sigmaDepth need deviceNormalDepth", n=None, fl=2)
+order("unknown flag bits", fl=3, a=None)
 launches = C.CDLL(tpt.library_path()).hostemuVarianceLaunches
 assert launches() == 0, "a refused call reached the launcher"
 for kw in (dict(it=1), dict(it=8), dict(s=1.0), dict(s=3e38), dict(sl=1e6), dict(sl=1e-30), dict(a=None, fl=0),
@@ -218,3 +233,39 @@ def test_refusals_through_the_host_runtime(tmp_path):
     out = run_refusals(REFUSALS, "libtpt_hostemu_variance.so", ["hostemu_variance.cpp"])
     assert out.count("refused:") == 2 + 9 + 8 + 2 + 6 + 2 + 5 + 6 + 4 + 3, out
     assert out.count("accepted:") == 9, out
+    assert out.count("order:") == 9, out
+    assert refusal_messages(out) == {
+        "tpt: not initialised (call tptInitialize / InitializeTest first)": 2,
+        "tptDrawDeviceMoments: call tptUpdate (UpdateTest) at this size first": 2,
+        "tptDrawDeviceMoments: bad arguments (deviceTile, deviceMoments, size)": 2,
+        "tptDrawDeviceMoments: deviceMoments overlaps the tile or a plane": 4,
+        "tptDrawDeviceMoments: frames of at most 8192 x 8192": 1,
+        "tptDrawDeviceMoments: needs per-pixel seeds (tptSetSeedMode(1)); row-serial moments are not supported": 1,
+        "tptDrawDeviceMoments: needs the recursive fold (tptSetFoldMode(0))": 1,
+        "tptDrawDeviceMoments: needs the path-queue kernel (tptSetKernelVariant(0, 3, ..))": 2,
+        "tptDrawDeviceMoments: at most 2047 samples per pixel (the path-queue kernel)": 1,
+        "tptDrawDeviceMoments: not with row sharding or a communicator (sharded moments are not supported)": 2,
+        "tptDrawDeviceMoments: not with a tile mirror (tptSetTileMirror)": 1,
+        "tptDenoiseDeviceVariance: w and h must lie in 1..8192": 2,
+        "tptDenoiseDeviceVariance: deviceColour and deviceOut are required": 2,
+        "tptDenoiseDeviceVariance: deviceMoments is required": 1,
+        "tptDenoiseDeviceVariance: deviceOut overlaps an input": 3,
+        "tptDenoiseDeviceVariance: iterations must lie in 1..8": 2,
+        "tptDenoiseDeviceVariance: samples must be finite and at least 1": 5,
+        "tptDenoiseDeviceVariance: sigmaLuminance must lie in (0, 1e6]": 6,
+        "tptDenoiseDeviceVariance: sigmaNormal and sigmaDepth must be 0 or lie in [1e-6, 1e6]": 4,
+        "tptDenoiseDeviceVariance: sigmaNormal and sigmaDepth need deviceNormalDepth": 1,
+        "tptDenoiseDeviceVariance: TPT_DENOISE_DEMODULATE needs deviceAlbedo": 1,
+        "tptDenoiseDeviceVariance: unknown flag bits": 1,
+    }
+
+
+def test_a_build_without_the_variance_launcher_refuses():
+    refused_without_its_launcher('''
+planes = [np.zeros((8, 16, 4), np.float32) for _ in range(2)] + [np.full((8, 16, 4), np.nan, np.float32)]
+lib.tptDenoiseDeviceVariance.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int,
+                                         C.c_float, C.c_float, C.c_float, C.c_uint]
+rc = lib.tptDenoiseDeviceVariance(16, 8, planes[0].ctypes.data, None, None, planes[1].ctypes.data, 4.0, planes[2].ctypes.data, 3, 4.0, 0.0, 0.0, 0)
+tpt.synchronize()
+assert np.isnan(planes[2]).all()
+''', "tptDenoiseDeviceVariance: this build has no variance-guided a-trous kernel")

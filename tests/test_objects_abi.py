@@ -7,7 +7,7 @@ import re
 import numpy as np
 import pytest
 
-from isa_lib import code_object, count, exported_symbols, header_params, no_library, run_refusals  # noqa: F401  (code_object: a module fixture)
+from isa_lib import code_object, count, exported_symbols, header_params, no_library, refusal_messages, refused_without_its_launcher, run_refusals  # noqa: F401  (code_object: a module fixture)
 from kernel_manifest import OBJECT_PLANE as PLANE, REPROJECT, TEMPORAL, family
 
 TEMPORAL_PARAMS = [
@@ -350,6 +350,17 @@ refused("pass: the object plane's tail holds an output's head", call, T, o={2: b
 refused("pass: an output overlaps the previous object plane", call, T, o={3: big}, pob=big.ctypes.data + 64)
 refused("pass: an output holds the table", call, T, o={0: big}, m=big.ctypes.data + plane_b - 16, n=1)
 refused("pass: the table's last entry lies in an output", call, T, o={1: big.ctypes.data + 4 * 16}, m=big, n=5)
+# two rules broken at once: the one that is checked first is the one reported
+def order(expect, **kw):
+    rc = call(**kw)
+    assert rc != 0 and msg() == T + ": " + expect, (expect, sorted(kw), rc, msg())
+    print("order:", sorted(kw), "--", expect)
+order("two outputs overlap", o={0: outs[1]}, ob=None)  # (the plain pass's rules before its own)
+order("maxHistory must lie in 1..65536", mh=0.0, ob=None)
+order("deviceObject is required", ob=None, pob=None)
+order("devicePrevObject must be given exactly when prevCamera and the prev planes are", pob=None, n=-1)
+order("nObjects must lie in 0..65534", n=65535, m=None)
+order("deviceObjectMotion and nObjects must be given together", n=0, o={0: big}, ob=big.ctypes.data)
 assert so.hostemuObjectPassLaunches() == 0, "a refused call reached the launcher"
 so.hostemuObjectPassConsts.restype = C.POINTER(C.c_float * 34)
 accepted = (dict(), first, dict(m=None, n=0), dict(first, m=None, n=0), dict(n=1), dict(n=65534, m=np.zeros((65534, 4), np.float32)),
@@ -382,3 +393,54 @@ def test_refusals_and_the_motion_table_through_the_host_runtime():
     own = 3 + 3 + 2 + 6
     assert out.count("refused:") == table + plane + plain + own, out
     assert out.count("accepted: pass") == 11, out
+    assert out.count("order:") == 6, out
+    M, P, T = "tptObjectMotionTable: ", "tptObjectPlaneDevice: ", "tptTemporalAccumulateObjectsDevice: "
+    assert refusal_messages(out) == {
+        "tpt: not initialised (call tptInitialize / InitializeTest first)": 1,
+        M + "outTable is required": 1,
+        M + "capacity is smaller than the object count": 3,
+        P + "call tptUpdate first": 1,
+        P + "nFrames must lie in 1..4096": 3,
+        P + "w and h must lie in 1..8192": 5,
+        P + "deviceFrameObjects is required": 1,
+        P + "without cameras the size must be the last tptUpdate's": 2,
+        P + "a camera has a non-finite origin, lowerLeftCorner, horizontal or vertical": 4,
+        P + "unknown flag bits": 4,
+        T + "w and h must lie in 1..8192": 4,
+        T + "camera is required": 1,
+        T + "the four planes of this frame are required": 4,
+        T + "the four output planes are required": 4,
+        T + "prevCamera and the four prev planes must be all NULL or all given": 6,
+        T + "an output overlaps an input": 8,
+        T + "two outputs overlap": 1,
+        T + "maxHistory must lie in 1..65536": 4,
+        T + "every tolerance must be finite and at least 0": 9,
+        T + "camera has a non-finite field, a degenerate frame or its frame behind its origin": 2,
+        T + "prevCamera has a non-finite field, a degenerate frame or its frame behind its origin": 2,
+        T + "deviceObject is required": 1,
+        T + "devicePrevObject must be given exactly when prevCamera and the prev planes are": 2,
+        T + "nObjects must lie in 0..65534": 3,
+        T + "deviceObjectMotion and nObjects must be given together": 2,
+        T + "an output overlaps an object plane or the motion table": 6,
+    }
+
+
+def test_a_build_without_the_launchers_refuses():
+    refused_without_its_launcher('''
+tpt.UpdateTest(0.0, 0, 16, 8, 0)
+objects = np.full((8, 16), -7, np.int32)
+rc = lib.tptObjectPlaneDevice(1, None, None, 16, 8, objects.ctypes.data, 0)
+tpt.synchronize()
+assert (objects == -7).all()
+''', "tptObjectPlaneDevice: this build has no object plane kernel")
+    refused_without_its_launcher('''
+sys.path.insert(0, sys.argv[1] + "/tests")
+from temporal_lib import look_at_camera
+cam = look_at_camera([0.0, 2.0, 3.0], [0.0, 0.0, 0.0], 16, 8)
+ins, outs = [np.full((8, 16, 4), 0.25, np.float32) for _ in range(4)], [np.full((8, 16, 4), np.nan, np.float32) for _ in range(4)]
+objects = np.zeros((8, 16), np.int32)
+rc = lib.tptTemporalAccumulateObjectsDevice(16, 8, cam.ctypes.data, None, *[p.ctypes.data for p in ins], None, None, None, None,
+                                            *[p.ctypes.data for p in outs], 4.0, 0.1, 0.25, 0.0, objects.ctypes.data, None, None, 0)
+tpt.synchronize()
+assert all(np.isnan(p).all() for p in outs)
+''', "tptTemporalAccumulateObjectsDevice: this build has no object-following accumulation kernel")

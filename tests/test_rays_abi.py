@@ -10,7 +10,7 @@ import sys
 
 import pytest
 
-from isa_lib import code_object, exported_symbols, header, header_params, no_library, run_refusals  # noqa: F401  (code_object: a fixture)
+from isa_lib import code_object, exported_symbols, header, header_params, no_library, refusal_messages, run_refusals  # noqa: F401  (code_object: a fixture)
 from kernel_manifest import TRACE, family
 from oracle_lib import ROOT
 
@@ -161,12 +161,33 @@ if REFUSALS:
                      ("the counter in the radiance", dict(rad=b, count=b + 8)),
                      ("the counter in the hits", dict(hits=b, count=b + 32 * N - 8))):
         kept.append(refused("overlap: " + what, **kw))
+    # two rules broken at once: the one that is checked first is the one reported
+    def order(expect, **kw):
+        r, rad, hits = fresh()
+        a = dict(n=N, rays=r, rad=rad, hits=hits, count=count, flags=0)
+        a.update(kw)
+        rc = raw(a["n"], a["rays"], a["rad"], a["hits"], a["count"], a["flags"])
+        assert rc != 0 and msg() == "tptTraceRaysDevice: " + expect, (expect, kw, rc, msg())
+        print("order:", sorted(kw), "--", expect)
+        kept.append((rad, hits))
+    order("nRays must lie in 1..16777216", n=0, flags=1)
+    order("flags must be 0", flags=1, rays=None)
+    order("deviceRays is required", rays=None, rad=None, hits=None)
+    order("deviceRadiance or deviceHits is required", rad=None, hits=None, count=b)
+    order("an output overlaps deviceRays", rays=b, rad=b, hits=b + 8)
+    order("an output overlaps deviceRays", rays=b, rad=b + 32 * N, hits=b + 48 * N - 4, count=b + 8)  # (the counter is the last pair looked at)
+    order("two outputs overlap", rays=b, rad=b + 32 * N, hits=b + 48 * N - 4, count=b + 40 * N)
     # what a scene can do
     s, m = cloud_scene(3100, lights=3073)
     tpt.set_scene(s, m)
     tpt.UpdateTest(0.0, 0, W, H, 0)
     assert len(tpt.GetSceneDesc()[3]) == 3073
     kept.append(refused("3073 emissive spheres"))
+    order("two outputs overlap", rad=b, hits=b + 16 * N - 4)  # (the buffers before the scene)
+    tpt.set_kernel_variant(2, 1, 1)
+    tpt.UpdateTest(0.0, 0, W, H, 0)
+    order("too many emissive spheres for the LDS light table (3072 at most)")  # (the lights before the LDS fit)
+    tpt.set_kernel_variant(0, 3, -1)
     s, m = cloud_scene(3000)
     tpt.set_scene(s, m)
     tpt.set_kernel_variant(2, 1, 1)  # flat, and staged in LDS whatever its size: 3000 x 68 B
@@ -218,6 +239,27 @@ def check(out, want, what):
             bad = np.argwhere(got[1:-1].view(np.uint32) != w.view(np.uint32))
             raise AssertionError("%s: %s: %d words differ, first at %s: %r / %r" % (what, name, len(bad), bad[0], got[1:-1][bad[0][0]], w[bad[0][0]]))
     assert out["cnt"].tolist() == [5, 1000 + (total if out["counted"] else 0), 5], (what, out["cnt"], total)
+# the bounce-stack spill grows between the calls of one sequence: in the context's default mode -- the recursive fold (tptSetFoldMode(0))
+# with 6 of the 10 stack levels in LDS -- a launch has a spill column per thread (Context::dRayStack), so 64 rays need one workgroup's,
+# 4096 rays 64 workgroups'.  Small, large, small again with no wait in between: the growth itself drains the context stream (under the
+# lazy schedule nothing else runs the first call before its buffer goes), and every call's records are the checker's.
+def stats():
+    st = (C.c_longlong * 2)(); so.hostemu_stats(st); return st[0], st[1]
+tpt.UpdateTest(0.0, 0, W, H, 0)
+s, m = rays_lib.default_scene()
+grid = checker.camera_rays(Oracle.get().default_camera(64, 64), 64, 64)
+small, large = np.ascontiguousarray(grid[:64]), np.ascontiguousarray(grid[:4096])
+first = run(small, sync=False)
+ran, frees = stats()
+second = run(large, sync=False)
+assert stats()[1] == frees + 1, "the spill did not grow"
+assert stats()[0] > ran, "the growth did not drain the context stream"
+third = run(small, sync=False)
+assert stats()[1] == frees + 1, "the spill was replaced again"
+tpt.synchronize()
+for out, r, what in ((first, small, "before the growth"), (second, large, "the call that grows the spill"), (third, small, "after the growth")):
+    check(out, checker.trace(s, m, r), what)
+print("accepted: the spill grows between calls")
 n_calls = 0
 for scene in ("default", "grouped"):
     s, m = rays_lib.SCENES[scene]()
@@ -368,6 +410,20 @@ def test_refusals_through_the_host_runtime():
     out = finish(run_script("refusals", "lazy"))
     assert out.count("refused:") == 1 + 1 + 1 + 4 + 3 + 1 + 1 + 11 + 2, out
     assert "accepted: buffers that touch" in out
+    assert out.count("order:") == 7 + 2, out
+    assert refusal_messages(out) == {
+        "tpt: not initialised (call tptInitialize / InitializeTest first)": 1,
+        NAME + ": call tptUpdate first": 1,
+        NAME + ": args is required": 1,
+        NAME + ": nRays must lie in 1..16777216": 4,
+        NAME + ": flags must be 0": 3,
+        NAME + ": deviceRays is required": 1,
+        NAME + ": deviceRadiance or deviceHits is required": 1,
+        NAME + ": an output overlaps deviceRays": 7,
+        NAME + ": two outputs overlap": 4,
+        NAME + ": too many emissive spheres for the LDS light table (3072 at most)": 1,
+        NAME + ": scene too large for LDS staging; use tptSetKernelVariant(.., .., 0)": 1,
+    }
 
 
 @pytest.fixture(scope="module")
@@ -381,7 +437,7 @@ def schedules():
 def test_accepted_calls_equal_the_checker(schedules, policy):
     out = schedules[policy]
     assert "accepted: 56 calls equal the checker" in out, out
-    for line in ("the ray counts", "three calls back to back", "a scene set behind a running call", "non-finite and zero-direction records",
+    for line in ("the spill grows between calls", "the ray counts", "three calls back to back", "a scene set behind a running call", "non-finite and zero-direction records",
                  "frames traced ahead are kept", "a stream of frames is kept"):
         assert "accepted: " + line in out, out
 
@@ -394,13 +450,25 @@ import numpy as np
 sys.path.insert(0, sys.argv[1])
 from toypathtracer_amd import api as tpt
 lib = tpt.load_library()
+from toypathtracer_amd.scenes import cloud_scene
 tpt.InitializeTest()
-tpt.UpdateTest(0.0, 0, 16, 8, 0)
 rays, rad = np.ones((4, 8), np.float32), np.full((4, 4), np.nan, np.float32)
 a = tpt.TraceRaysArgs(nRays=4, flags=0, deviceRays=rays.ctypes.data, deviceRadiance=rad.ctypes.data, deviceHits=None, deviceRayCount=None)
+# the launcher is looked for last: a scene whose LDS does not fit is still refused as that
+s, m = cloud_scene(3000)
+tpt.set_scene(s, m)
+tpt.set_kernel_variant(2, 1, 1)
+tpt.UpdateTest(0.0, 0, 16, 8, 0)
+assert lib.tptTraceRaysDevice(C.byref(a)) != 0
+m = lib.tptGetLastError().decode()
+assert m == "tptTraceRaysDevice: scene too large for LDS staging; use tptSetKernelVariant(.., .., 0)", m
+tpt.set_kernel_variant(0, 3, -1)
+tpt.set_scene(None, None)
+tpt.UpdateTest(0.0, 0, 16, 8, 0)
 assert lib.tptTraceRaysDevice(C.byref(a)) != 0
 m = lib.tptGetLastError().decode()
 assert "tptTraceRaysDevice" in m and "launcher" in m, m
+assert m == "tptTraceRaysDevice: this build has no ray launcher", m
 tpt.synchronize()
 assert np.isnan(rad).all()
 tpt.ShutdownTest()

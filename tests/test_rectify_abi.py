@@ -8,7 +8,7 @@ import re
 
 import pytest
 
-from isa_lib import code_object, count, exported_symbols, header_params, no_library, run_refusals  # noqa: F401  (code_object: a module fixture)
+from isa_lib import code_object, count, exported_symbols, header_params, no_library, refusal_messages, run_refusals  # noqa: F401  (code_object: a module fixture)
 from kernel_manifest import RECTIFY, family
 from oracle_lib import ROOT
 
@@ -176,6 +176,17 @@ def test_refusals_through_the_host_runtime():
     out = run_refusals(REFUSALS, "libtpt_hostemu_rectify.so", ["hostemu_rectify.cpp"])
     assert out.count("refused:") == 1 + 5 + 4 + 3 + 4 + 5 + 10 + 8, out
     assert out.count("accepted:") == 8, out
+    F = "tptRectifyHistoryDevice: "
+    assert refusal_messages(out) == {
+        "tpt: not initialised (call tptInitialize / InitializeTest first)": 1,
+        F + "w and h must lie in 1..8192": 5,
+        F + "this frame's colour and moments planes and the accumulated ones are required": 4,
+        F + "the three output planes are required": 3,
+        F + "radius must lie in 1..3": 4,
+        F + "gamma must be finite and at least 0": 5,
+        F + "an output overlaps an input (other than in place)": 16,
+        F + "two outputs overlap": 2,
+    }
 
 
 NO_KERNEL = r'''
@@ -189,6 +200,7 @@ planes = [np.full((4, 8, 4), np.nan, np.float32) for _ in range(7)]
 rc = lib.tptRectifyHistoryDevice(8, 4, *[p.ctypes.data for p in planes], 2, 1.0)
 msg = lib.tptGetLastError().decode()
 assert rc != 0 and "tptRectifyHistoryDevice: this build has no" in msg and "kernel" in msg, (rc, msg)
+assert msg == "tptRectifyHistoryDevice: this build has no history rectification kernel", msg
 assert all(np.isnan(p).all() for p in planes)
 tpt.ShutdownTest()
 print("ok")

@@ -9,7 +9,7 @@ import re
 
 import pytest
 
-from isa_lib import code_object, count, exported_symbols, header_params, no_library, run_refusals  # noqa: F401  (code_object: a module fixture)
+from isa_lib import code_object, count, exported_symbols, header_params, no_library, refusal_messages, run_refusals  # noqa: F401  (code_object: a module fixture)
 from kernel_manifest import SPREAD, family
 from oracle_lib import ROOT
 
@@ -158,6 +158,16 @@ class Launch(C.Structure):
     _fields_ = [("planes", C.c_void_p * 3), ("width", C.c_int), ("height", C.c_int), ("frames", C.c_int), ("radius", C.c_int),
                 ("spp", C.c_float), ("ms", C.c_float), ("inn", C.c_float), ("idd", C.c_float), ("grid", C.c_uint * 3), ("stream", C.c_void_p)]
 so.hostemuSpreadLast.restype = C.POINTER(Launch)
+# two rules broken at once: the one that is checked first is the one reported
+def order(expect, **kw):
+    rc = call(**kw)
+    assert rc != 0 and msg() == F + ": " + expect, (expect, kw, rc, msg())
+    print("order:", sorted(kw), "--", expect)
+order("radius must lie in 1..3", radius=0, spp=0.0)
+order("samplesPerFrame must be finite and at least 1", spp=float("nan"), ms=0.0)
+order("minSamples must be at least 1 (+infinity: every pixel is estimated)", ms=0.5, sn=float("nan"))
+order("sigmaNormal and sigmaDepth must be 0 or lie in [1e-6, 1e6]", sd=2e6, g=None)
+order("sigmaNormal and sigmaDepth need deviceFrameNormalDepth", g=None, o=mo)
 launches = so.hostemuSpreadLaunches
 assert launches() == 0, "a refused call reached the launcher"
 f32 = np.float32
@@ -194,6 +204,20 @@ def test_refusals_through_the_host_runtime():
     out = run_refusals(REFUSALS, "libtpt_hostemu_spatial_variance.so", ["hostemu_spatial_variance.cpp"])
     assert out.count("refused:") == 1 + 5 + 4 + 2 + 4 + 5 + 4 + 5 + 2 + 6, out
     assert out.count("accepted:") == 12, out
+    assert out.count("order:") == 5, out
+    F = "tptSpatialVarianceDevice: "
+    assert refusal_messages(out) == {
+        "tpt: not initialised (call tptInitialize / InitializeTest first)": 1,
+        F + "screenWidth and screenHeight must lie in 1..8192": 5,
+        F + "nFrames must lie in 1..4096": 4,
+        F + "deviceFrameMoments and deviceFrameOutVariance are required": 2,
+        F + "radius must lie in 1..3": 4,
+        F + "samplesPerFrame must be finite and at least 1": 5,
+        F + "minSamples must be at least 1 (+infinity: every pixel is estimated)": 4,
+        F + "sigmaNormal and sigmaDepth must be 0 or lie in [1e-6, 1e6]": 5,
+        F + "sigmaNormal and sigmaDepth need deviceFrameNormalDepth": 2,
+        F + "deviceFrameOutVariance overlaps an input": 6,
+    }
 
 
 NO_KERNEL = r'''
@@ -207,6 +231,7 @@ planes = [np.full((4, 8, 4), np.nan, np.float32) for _ in range(3)]
 rc = lib.tptSpatialVarianceDevice(8, 4, 1, *[p.ctypes.data for p in planes], 1.0, 2.0, 1, 0.03, 0.5)
 msg = lib.tptGetLastError().decode()
 assert rc != 0 and "tptSpatialVarianceDevice: this build has no" in msg and "kernel" in msg, (rc, msg)
+assert msg == "tptSpatialVarianceDevice: this build has no spatial variance kernel", msg
 assert all(np.isnan(p).all() for p in planes)
 tpt.ShutdownTest()
 print("ok")

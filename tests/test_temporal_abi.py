@@ -7,7 +7,7 @@ import re
 import numpy as np
 import pytest
 
-from isa_lib import code_object, count, exported_symbols, header, header_params, no_library, run_refusals  # noqa: F401  (code_object: a module fixture)
+from isa_lib import code_object, count, exported_symbols, header, header_params, no_library, refusal_messages, refused_without_its_launcher, run_refusals  # noqa: F401  (code_object: a module fixture)
 from kernel_manifest import TEMPORAL
 
 
@@ -172,3 +172,31 @@ def test_refusals_through_the_host_runtime(tmp_path):
     out = run_refusals(REFUSALS, "libtpt_hostemu_temporal.so", ["hostemu_temporal.cpp"])
     assert out.count("refused:") == 1 + 4 + 1 + 8 + 1 + 4 + 1 + 8 + 4 + 6 + 12 + 2 * 7, out
     assert out.count("accepted:") == 8, out
+    F = "tptTemporalAccumulateDevice: "
+    assert refusal_messages(out) == {
+        "tpt: not initialised (call tptInitialize / InitializeTest first)": 1,
+        F + "w and h must lie in 1..8192": 4,
+        F + "camera is required": 1,
+        F + "the four planes of this frame are required": 4,
+        F + "the four output planes are required": 4,
+        F + "prevCamera and the four prev planes must be all NULL or all given": 6,
+        F + "an output overlaps an input": 10,
+        F + "two outputs overlap": 2,
+        F + "maxHistory must lie in 1..65536": 6,
+        F + "every tolerance must be finite and at least 0": 12,
+        F + "camera has a non-finite field, a degenerate frame or its frame behind its origin": 7,
+        F + "prevCamera has a non-finite field, a degenerate frame or its frame behind its origin": 7,
+    }
+
+
+def test_a_build_without_the_launcher_refuses():
+    refused_without_its_launcher('''
+sys.path.insert(0, sys.argv[1] + "/tests")
+from temporal_lib import look_at_camera
+cam = look_at_camera([0.0, 2.0, 3.0], [0.0, 0.0, 0.0], 16, 8)
+ins, outs = [np.full((8, 16, 4), 0.25, np.float32) for _ in range(4)], [np.full((8, 16, 4), np.nan, np.float32) for _ in range(4)]
+rc = lib.tptTemporalAccumulateDevice(16, 8, cam.ctypes.data, None, *[p.ctypes.data for p in ins], None, None, None, None,
+                                     *[p.ctypes.data for p in outs], 4.0, 0.1, 0.25, 0.0)
+tpt.synchronize()
+assert all(np.isnan(p).all() for p in outs)
+''', "tptTemporalAccumulateDevice: this build has no temporal accumulation kernel")

@@ -3,10 +3,13 @@
 //
 //   tpt_host.cpp           context, initialisation, scene staging, the setters, UpdateTest, the reference's C++ symbols
 //   tpt_host_pipeline.cpp  one frame: plan, buffers, trace launch, ordered blend; tail helpers; tptDrawDevice and its variants (Batch,
-//                          Views, Animation, AnimationMoments, Aov, Moments)
-//   tpt_host_draw.cpp      the queue of launches traced ahead of their call (LaunchQueue); DrawTest on a host backbuffer: banded
-//                          copies; display conversion; the denoiser's entry points (tptDenoiseDevice, tptDenoiseDeviceVariance,
-//                          tptTemporalAccumulateDevice)
+//                          Views, Animation, AnimationMoments, CameraClip, KeyframeClip, Aov, Moments, BatchMoments, Adaptive); the
+//                          blocking calls
+//   tpt_host_draw.cpp      the queue of launches traced ahead of their call (LaunchQueue, traceAhead); DrawTest on a host backbuffer
+//                          (tptDraw: look-ahead, row-serial batches, banded copies) and its three setters; the display conversion;
+//                          the entry points that run on the context stream outside the frame pipeline: the post-process passes (the
+//                          a-trous filters, temporal accumulation, rectification, spatial variance, the clip chain, motion vectors,
+//                          the adaptive plan), the object plane and motion table, the caller's rays, the lens draw
 //   tpt_host_shard.cpp     multi-GPU inside the library: RCCL (dlopen), tptDrawSharded, tptShardedFinish
 //   tpt_host_hooks.cpp     unit-test / profiling entry points (include/tpt_test_hooks.h; the second build only)
 // and, of the headers they share with the kernels (tpt_kernels.hip): tpt_device.h, the kernels' argument block and the launch functions;
@@ -479,7 +482,7 @@ struct AovPlanes {
 int enqueueTrace(int frameCount, int w, int h, unsigned testFlags, unsigned long long* frameRays, TraceTicket& T, int batch = 1, int rayStride = 0,
                  const BatchTable* table = nullptr, const AovPlanes* aov = nullptr);
 int enqueueResolve(const TraceTicket& T, float* deviceTile, const unsigned long long* frameRays);
-size_t laneRefillLds(KernelArgs& a, bool& ldsScene); // (the lane-refill kernel's plan: chooseKernel, tptTraceRaysDevice)
+size_t laneRefillLds(KernelArgs& a, bool& ldsScene); // (the lane-refill kernel's plan: chooseKernel, tptTraceRaysDevice, tptDrawDeviceLens)
 bool fitsCuLds(size_t lds);
 int laneRefillOccupancy(bool ldsScene, size_t lds);
 int syncAllStreams();

@@ -1,5 +1,7 @@
 // tpt_host_draw.cpp -- the launches traced ahead of their call (LaunchQueue); DrawTest on the caller's HOST backbuffer (Test.cpp:344-367,
-// synchronous): look-ahead, row-serial batches, banded copies; the display conversion
+// synchronous): look-ahead, row-serial batches, banded copies; the display conversion; and the entry points that run on the context
+// stream outside the frame pipeline -- the post-process passes, the object plane and motion table, the caller's rays, the lens draw --
+// with the checks, the buffer growth and the launch plan they share (Span .. checkObjectCount, laneRefillScene, laneRefillChunks)
 // (one of the host runtime's translation units: tpt_context.h lists them)
 #include "tpt_context.h"
 
@@ -91,6 +93,65 @@ int traceAhead(int frameCount, int w, int h, unsigned testFlags, unsigned long l
     return 0;
 }
 
+static_assert(sizeof(CameraPOD) == 22 * sizeof(float), "the reference's Camera: the callers' camera arrays are read as records of this size");
+
+// A caller's buffer at its full extent, and whether two of them share a byte (a null one shares none).
+struct Span {
+    const void* p;
+    uintptr_t bytes;
+};
+static bool overlaps(Span a, Span b)
+{
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a.p), y = reinterpret_cast<uintptr_t>(b.p);
+    return x && y && x < y + b.bytes && y < x + a.bytes;
+}
+// Does one of `outs` share a byte with one of `ins`?
+static bool anyOverlaps(std::initializer_list<Span> outs, std::initializer_list<Span> ins)
+{
+    for (const Span& o : outs)
+        for (const Span& i : ins)
+            if (overlaps(o, i)) return true;
+    return false;
+}
+// Do two of `spans` share a byte?
+static bool anyTwoOverlap(std::initializer_list<Span> spans)
+{
+    for (const Span* a = spans.begin(); a != spans.end(); ++a)
+        for (const Span* b = a + 1; b != spans.end(); ++b)
+            if (overlaps(*a, *b)) return true;
+    return false;
+}
+
+// A device buffer that only the context stream uses, grown to `need` bytes when it holds fewer (`held`; kept until tptShutdown).  The
+// stream is drained first: an earlier call's work may still be using the buffer that goes.  `zero`: the new buffer is cleared on the stream.
+template <class T>
+static int growStreamBuffer(T*& buffer, size_t& held, size_t need, bool zero = false)
+{
+    if (need <= held) return 0;
+    HIPCHK(hipStreamSynchronize(g.stream));
+    (void)hipFree(buffer);
+    buffer = nullptr;
+    held = 0;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&buffer), need));
+    held = need;
+    if (zero) HIPCHK(hipMemsetAsync(buffer, 0, need, g.stream));
+    return 0;
+}
+
+// The scalars' rules the passes share.  (NaN fails every comparison, +inf the upper one.)
+static bool finiteAtLeast(float v, float lo) { return v >= lo && v <= 3.40282347e38f; }
+static bool sigmaOk(float s) { return s == 0.0f || (s >= 1e-6f && s <= 1e6f); }
+static float inv2(float s) { return s > 0.0f ? 1.0f / (s * s) : 0.0f; } // (what the kernels take of a sigma; 0: the guide is off)
+
+// What the calls with a motion table refuse of it (f: the entry point; tableName: its parameter): the count's range, then that table
+// and count are given together.
+static int checkObjectCount(const std::string& f, const char* tableName, const void* table, int nObjects)
+{
+    if (nObjects < 0 || nObjects > 65534) return fail(f + ": nObjects must lie in 0..65534");
+    if ((table != nullptr) != (nObjects > 0)) return fail(f + ": " + tableName + " and nObjects must be given together");
+    return 0;
+}
+
 // What tptDenoiseDevice and tptDenoiseDeviceVariance refuse, in the order they check it (fn: the entry point).  The variance filter
 // (`variance`) also requires deviceMoments, an input like the others, and checks `samples` and its luminance sigma (`sigma0`) before the
 // guides' sigmas; the plain filter checks its colour sigma (`sigma0`) with them.
@@ -104,9 +165,8 @@ static int checkDenoise(const char* fn, bool variance, int w, int h, const float
     if (variance && !moments) return fail(f + ": deviceMoments is required");
     if (overlapsAny(out, {colour, albedo, normalDepth, moments}, (uintptr_t)w * (uintptr_t)h * 16u)) return fail(f + ": deviceOut overlaps an input");
     if (iterations < 1 || iterations > 8) return fail(f + ": iterations must lie in 1..8");
-    auto sigmaOk = [](float s) { return s == 0.0f || (s >= 1e-6f && s <= 1e6f); }; // (NaN fails both comparisons)
     if (variance) {
-        if (!(samples >= 1.0f && samples <= 3.40282347e38f)) return fail(f + ": samples must be finite and at least 1"); // (NaN and +inf fail)
+        if (!finiteAtLeast(samples, 1.0f)) return fail(f + ": samples must be finite and at least 1");
         if (!(sigma0 > 0.0f && sigma0 <= 1e6f)) return fail(f + ": sigmaLuminance must lie in (0, 1e6]");
         if (!sigmaOk(sigmaNormal) || !sigmaOk(sigmaDepth)) return fail(f + ": sigmaNormal and sigmaDepth must be 0 or lie in [1e-6, 1e6]");
     } else if (!sigmaOk(sigma0) || !sigmaOk(sigmaNormal) || !sigmaOk(sigmaDepth)) {
@@ -118,21 +178,6 @@ static int checkDenoise(const char* fn, bool variance, int w, int h, const float
     return 0;
 }
 
-// The context's scratch plane of both a-trous filters, grown to a w x h plane when a call needs more.
-static int ensureDenoisePlane(int w, int h)
-{
-    const uintptr_t bytes = (uintptr_t)w * (uintptr_t)h * 16u;
-    if (bytes <= g.denoiseBytes) return 0;
-    // (an earlier call's iterations may still be reading the plane being replaced; only the context stream uses it)
-    HIPCHK(hipStreamSynchronize(g.stream));
-    (void)hipFree(g.dDenoise);
-    g.dDenoise = nullptr;
-    g.denoiseBytes = 0;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dDenoise), bytes));
-    g.denoiseBytes = bytes;
-    return 0;
-}
-
 // What the temporal passes refuse of their scalars and of the two cameras (prevCamera may be null), in the order they check it, and
 // what the kernels need of the cameras, made here in the stated order (k): the second half of checkTemporal, which
 // tptDenoiseClipDevice runs on its own for every frame of its clip.
@@ -140,8 +185,7 @@ static int temporalConsts(const std::string& f, const void* camera, const void* 
                           float normalTolerance, float coverageTolerance, tptTemporalConsts& k)
 {
     if (!(maxHistory >= 1.0f && maxHistory <= 65536.0f)) return fail(f + ": maxHistory must lie in 1..65536"); // (NaN fails)
-    auto tolOk = [](float t) { return t >= 0.0f && t <= 3.40282347e38f; };
-    if (!tolOk(depthTolerance) || !tolOk(normalTolerance) || !tolOk(coverageTolerance))
+    if (!finiteAtLeast(depthTolerance, 0.0f) || !finiteAtLeast(normalTolerance, 0.0f) || !finiteAtLeast(coverageTolerance, 0.0f))
         return fail(f + ": every tolerance must be finite and at least 0");
     auto dot3 = [](const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
     // The reference's Camera is 22 consecutive floats: origin, lowerLeftCorner, horizontal, vertical, uu, vv, ww, lensRadius.  A camera
@@ -153,7 +197,6 @@ static int temporalConsts(const std::string& f, const void* camera, const void* 
         fc = -dot3(a, c + 18);
         return dot3(c + 6, c + 6) != 0.0f && dot3(c + 9, c + 9) != 0.0f && fc > 0.0f;
     };
-    static_assert(sizeof(CameraPOD) == 22 * sizeof(float), "the reference's Camera");
     float cam[22], prev[22], a[3], fc;
     k = {};
     memcpy(cam, camera, sizeof cam);
@@ -420,8 +463,7 @@ int tptDenoiseDevice(int w, int h, const float* deviceColour, const float* devic
                           sigmaColour, sigmaNormal, sigmaDepth, denoiseFlags);
     if (rc) return rc;
     if (!tptLaunchDenoise) return fail("tptDenoiseDevice: this build has no a-trous kernel");
-    if (iterations > 1 && (rc = ensureDenoisePlane(w, h))) return rc;
-    auto inv2 = [](float s) { return s > 0.0f ? 1.0f / (s * s) : 0.0f; };
+    if (iterations > 1 && (rc = growStreamBuffer(g.dDenoise, g.denoiseBytes, (size_t)w * (size_t)h * sizeof(f4)))) return rc;
     HIPCHK(tptLaunchDenoise(deviceColour, deviceAlbedo, deviceNormalDepth, deviceOut, reinterpret_cast<float*>(g.dDenoise), w, h,
                             iterations, inv2(sigmaColour), inv2(sigmaNormal), inv2(sigmaDepth), (denoiseFlags & TPT_DENOISE_DEMODULATE) != 0,
                             g.stream));
@@ -439,8 +481,7 @@ int tptDenoiseDeviceVariance(int w, int h, const float* deviceColour, const floa
                           iterations, samples, sigmaLuminance, sigmaNormal, sigmaDepth, denoiseFlags);
     if (rc) return rc;
     if (!tptLaunchDenoiseVariance) return fail("tptDenoiseDeviceVariance: this build has no variance-guided a-trous kernel");
-    if (iterations > 1 && (rc = ensureDenoisePlane(w, h))) return rc;
-    auto inv2 = [](float s) { return s > 0.0f ? 1.0f / (s * s) : 0.0f; };
+    if (iterations > 1 && (rc = growStreamBuffer(g.dDenoise, g.denoiseBytes, (size_t)w * (size_t)h * sizeof(f4)))) return rc;
     HIPCHK(tptLaunchDenoiseVariance(deviceColour, deviceAlbedo, deviceNormalDepth, deviceMoments, deviceOut,
                                     reinterpret_cast<float*>(g.dDenoise), w, h, iterations, samples, sigmaLuminance * sigmaLuminance,
                                     inv2(sigmaNormal), inv2(sigmaDepth), (denoiseFlags & TPT_DENOISE_DEMODULATE) != 0, g.stream));
@@ -484,7 +525,7 @@ int tptRectifyHistoryDevice(int w, int h, const float* deviceColour, const float
         return fail(f + ": this frame's colour and moments planes and the accumulated ones are required");
     if (!deviceOutColour || !deviceOutMoments || !deviceOutVariance) return fail(f + ": the three output planes are required");
     if (radius < 1 || radius > TPT_RECTIFY_MAX_RADIUS) return fail(f + ": radius must lie in 1..3");
-    if (!(gamma >= 0.0f && gamma <= 3.40282347e38f)) return fail(f + ": gamma must be finite and at least 0"); // (NaN fails both)
+    if (!finiteAtLeast(gamma, 0.0f)) return fail(f + ": gamma must be finite and at least 0");
     const uintptr_t bytes = (uintptr_t)w * (uintptr_t)h * 16u;
     const float* ins[4] = {deviceColour, deviceMoments, deviceAccColour, deviceAccMoments};
     const float* outs[3] = {deviceOutColour, deviceOutMoments, deviceOutVariance};
@@ -516,10 +557,8 @@ int tptSpatialVarianceDevice(int screenWidth, int screenHeight, int nFrames, con
     if (nFrames < 1 || nFrames > 4096) return fail(f + ": nFrames must lie in 1..4096");
     if (!deviceFrameMoments || !deviceFrameOutVariance) return fail(f + ": deviceFrameMoments and deviceFrameOutVariance are required");
     if (radius < 1 || radius > TPT_SPREAD_MAX_RADIUS) return fail(f + ": radius must lie in 1..3");
-    if (!(samplesPerFrame >= 1.0f && samplesPerFrame <= 3.40282347e38f))
-        return fail(f + ": samplesPerFrame must be finite and at least 1"); // (NaN and +inf fail)
+    if (!finiteAtLeast(samplesPerFrame, 1.0f)) return fail(f + ": samplesPerFrame must be finite and at least 1");
     if (!(minSamples >= 1.0f)) return fail(f + ": minSamples must be at least 1 (+infinity: every pixel is estimated)"); // (NaN fails)
-    auto sigmaOk = [](float s) { return s == 0.0f || (s >= 1e-6f && s <= 1e6f); }; // (NaN fails both comparisons)
     if (!sigmaOk(sigmaNormal) || !sigmaOk(sigmaDepth)) return fail(f + ": sigmaNormal and sigmaDepth must be 0 or lie in [1e-6, 1e6]");
     if ((sigmaNormal != 0.0f || sigmaDepth != 0.0f) && !deviceFrameNormalDepth)
         return fail(f + ": sigmaNormal and sigmaDepth need deviceFrameNormalDepth");
@@ -527,7 +566,6 @@ int tptSpatialVarianceDevice(int screenWidth, int screenHeight, int nFrames, con
     if (overlapsAny(deviceFrameOutVariance, {deviceFrameMoments, deviceFrameNormalDepth}, bytes))
         return fail(f + ": deviceFrameOutVariance overlaps an input");
     if (!tptLaunchSpread) return fail(f + ": this build has no spatial variance kernel");
-    auto inv2 = [](float s) { return s > 0.0f ? 1.0f / (s * s) : 0.0f; };
     HIPCHK(tptLaunchSpread(deviceFrameMoments, deviceFrameNormalDepth, deviceFrameOutVariance, w, h, nFrames, samplesPerFrame, minSamples,
                            radius, inv2(sigmaNormal), inv2(sigmaDepth), g.stream));
     return 0;
@@ -553,36 +591,16 @@ int tptTemporalAccumulateObjectsDevice(int w, int h, const void* camera, const v
     if (!deviceObject) return fail(f + ": deviceObject is required");
     if ((devicePrevObject != nullptr) != (prevCamera != nullptr))
         return fail(f + ": devicePrevObject must be given exactly when prevCamera and the prev planes are");
-    if (nObjects < 0 || nObjects > 65534) return fail(f + ": nObjects must lie in 0..65534");
-    if ((deviceObjectMotion != nullptr) != (nObjects > 0)) return fail(f + ": deviceObjectMotion and nObjects must be given together");
+    if ((rc = checkObjectCount(f, "deviceObjectMotion", deviceObjectMotion, nObjects))) return rc;
     // no output may share a byte with an object plane or the table, each at its full extent
-    const uintptr_t plane = (uintptr_t)w * (uintptr_t)h;
-    const struct { const void* p; uintptr_t bytes; } more[3] = {{deviceObject, plane * 4u}, {devicePrevObject, plane * 4u},
-                                                                {deviceObjectMotion, (uintptr_t)nObjects * 16u}};
-    const float* outs[4] = {deviceOutColour, deviceOutAlbedo, deviceOutMoments, deviceOutVariance};
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 3; ++j) {
-            const uintptr_t a = reinterpret_cast<uintptr_t>(outs[i]), b = reinterpret_cast<uintptr_t>(more[j].p);
-            if (b && a < b + more[j].bytes && b < a + plane * 16u) return fail(f + ": an output overlaps an object plane or the motion table");
-        }
+    const uintptr_t pixels = (uintptr_t)w * (uintptr_t)h, plane = pixels * 16u;
+    if (anyOverlaps({{deviceOutColour, plane}, {deviceOutAlbedo, plane}, {deviceOutMoments, plane}, {deviceOutVariance, plane}},
+                    {{deviceObject, pixels * 4u}, {devicePrevObject, pixels * 4u}, {deviceObjectMotion, (uintptr_t)nObjects * 16u}}))
+        return fail(f + ": an output overlaps an object plane or the motion table");
     if (!tptLaunchReprojectObjects) return fail(f + ": this build has no object-following accumulation kernel");
     HIPCHK(tptLaunchReprojectObjects(deviceColour, deviceAlbedo, deviceNormalDepth, deviceMoments, devicePrevColour, devicePrevAlbedo,
                                      devicePrevNormalDepth, devicePrevMoments, deviceOutColour, deviceOutAlbedo, deviceOutMoments,
                                      deviceOutVariance, deviceObject, devicePrevObject, deviceObjectMotion, nObjects, w, h, k, g.stream));
-    return 0;
-}
-
-// The context's staging of tptDenoiseClipDevice, grown to `bytes` when a call needs more.
-static int ensureClipStage(size_t bytes)
-{
-    if (bytes <= g.clipStageBytes) return 0;
-    // (an earlier call's launches may still be using the staging being replaced; only the context stream uses it)
-    HIPCHK(hipStreamSynchronize(g.stream));
-    (void)hipFree(g.dClipStage);
-    g.dClipStage = nullptr;
-    g.clipStageBytes = 0;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dClipStage), bytes));
-    g.clipStageBytes = bytes;
     return 0;
 }
 
@@ -621,10 +639,8 @@ int tptDenoiseClipDevice(const tptClipDenoiseArgs* args)
     int rc = checkDenoise(f.c_str(), true, w, h, A.deviceFrameImages, A.deviceFrameAlbedo, A.deviceFrameNormalDepth, A.deviceFrameMoments,
                           A.deviceFrameOut, A.iterations, A.samples, A.sigmaLuminance, A.sigmaNormal, A.sigmaDepth, A.denoiseFlags);
     if (rc) return rc;
-    if (A.nObjects < 0 || A.nObjects > 65534) return fail(f + ": nObjects must lie in 0..65534");
-    if ((A.deviceFrameObjectMotion != nullptr) != (A.nObjects > 0)) return fail(f + ": deviceFrameObjectMotion and nObjects must be given together");
+    if ((rc = checkObjectCount(f, "deviceFrameObjectMotion", A.deviceFrameObjectMotion, A.nObjects))) return rc;
     if (A.deviceFrameObjectMotion && !objects) return fail(f + ": deviceFrameObjectMotion needs deviceFrameObjects");
-    static_assert(sizeof(CameraPOD) == 22 * sizeof(float), "the reference's Camera");
     std::vector<tptTemporalConsts> consts(spatial ? 0 : (size_t)nFrames);
     for (int j = 0; !spatial && j < nFrames; ++j) {
         const char* cam = static_cast<const char*>(A.cameras) + sizeof(CameraPOD) * (size_t)j;
@@ -639,25 +655,21 @@ int tptDenoiseClipDevice(const tptClipDenoiseArgs* args)
     const int chunk = fit < 32 ? (int)fit : 32, held = chunk < nFrames ? chunk : nFrames;
     // no output may share a byte with an input or with the other output, each at its full extent
     const uintptr_t stack = (uintptr_t)planeBytes * (uintptr_t)nFrames;
-    const struct { const void* p; uintptr_t bytes; } outs[2] = {{A.deviceFrameOut, stack}, {A.deviceHistory, (uintptr_t)planeBytes * 3u}},
-        ins[8] = {{A.deviceFrameImages, stack}, {A.deviceFrameMoments, stack}, {A.deviceFrameAlbedo, stack}, {A.deviceFrameNormalDepth, stack},
-                  {A.deviceFrameObjects, (uintptr_t)pixels * 4u * (uintptr_t)nFrames},
-                  {A.deviceFrameObjectMotion, (uintptr_t)nFrames * (uintptr_t)A.nObjects * 16u}, {A.devicePrevNormalDepth, planeBytes},
-                  {A.devicePrevObject, (uintptr_t)pixels * 4u}};
-    auto overlap = [](const void* p, uintptr_t pn, const void* q, uintptr_t qn) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-        return a && b && a < b + qn && b < a + pn;
-    };
-    for (const auto& o : outs)
-        for (const auto& i : ins)
-            if (overlap(o.p, o.bytes, i.p, i.bytes)) return fail(f + ": deviceFrameOut or deviceHistory overlaps an input");
-    if (overlap(outs[0].p, outs[0].bytes, outs[1].p, outs[1].bytes)) return fail(f + ": deviceFrameOut overlaps deviceHistory");
+    const Span out = {A.deviceFrameOut, stack}, history = {A.deviceHistory, (uintptr_t)planeBytes * 3u};
+    if (anyOverlaps({out, history},
+                    {{A.deviceFrameImages, stack}, {A.deviceFrameMoments, stack}, {A.deviceFrameAlbedo, stack}, {A.deviceFrameNormalDepth, stack},
+                     {A.deviceFrameObjects, (uintptr_t)pixels * 4u * (uintptr_t)nFrames},
+                     {A.deviceFrameObjectMotion, (uintptr_t)nFrames * (uintptr_t)A.nObjects * 16u}, {A.devicePrevNormalDepth, planeBytes},
+                     {A.devicePrevObject, (uintptr_t)pixels * 4u}}))
+        return fail(f + ": deviceFrameOut or deviceHistory overlaps an input");
+    if (overlaps(out, history)) return fail(f + ": deviceFrameOut overlaps deviceHistory");
     if (!tptLaunchFramesAtrous) return fail(f + ": this build has no frame-stack a-trous kernel");
     if (!spatial && !(objects ? (bool)tptLaunchReprojectObjects : (bool)tptLaunchTemporal))
         return fail(f + ": this build has no temporal accumulation kernel");
-    if ((!spatial || A.iterations > 1) && (rc = ensureClipStage(planeBytes * (spatial ? (size_t)held : 4u * (size_t)held + 4u)))) return rc;
+    if ((!spatial || A.iterations > 1) &&
+        (rc = growStreamBuffer(g.dClipStage, g.clipStageBytes, planeBytes * (spatial ? (size_t)held : 4u * (size_t)held + 4u))))
+        return rc;
 
-    auto inv2 = [](float s) { return s > 0.0f ? 1.0f / (s * s) : 0.0f; };
     const float sl2 = A.sigmaLuminance * A.sigmaLuminance, in = inv2(A.sigmaNormal), id = inv2(A.sigmaDepth);
     const bool demod = (A.denoiseFlags & TPT_DENOISE_DEMODULATE) != 0;
     const size_t plane = pixels * 4u; // (floats)
@@ -784,9 +796,7 @@ int tptMotionVectorsDevice(const tptMotionVectorsArgs* args)
         return fail(f + ": devicePrevAlbedo, devicePrevNormalDepth and devicePrevObject need prevCamera");
     }
     if (A.deviceFrameObjectMotion && !objects) return fail(f + ": deviceFrameObjectMotion needs deviceFrameObjects");
-    if (A.nObjects < 0 || A.nObjects > 65534) return fail(f + ": nObjects must lie in 0..65534");
-    if ((A.deviceFrameObjectMotion != nullptr) != (A.nObjects > 0)) return fail(f + ": deviceFrameObjectMotion and nObjects must be given together");
-    static_assert(sizeof(CameraPOD) == 22 * sizeof(float), "the reference's Camera");
+    if (int rc = checkObjectCount(f, "deviceFrameObjectMotion", A.deviceFrameObjectMotion, A.nObjects)) return rc;
     std::vector<tptFlowConsts> consts((size_t)nFrames);
     for (int j = 0; j < nFrames; ++j) {
         const char* cam = static_cast<const char*>(A.cameras) + sizeof(CameraPOD) * (size_t)j;
@@ -802,14 +812,11 @@ int tptMotionVectorsDevice(const tptMotionVectorsArgs* args)
     // the output may not share a byte with an input, each at its full extent
     const size_t pixels = (size_t)w * (size_t)h, planeBytes = pixels * 16u;
     const uintptr_t stack = (uintptr_t)planeBytes * (uintptr_t)nFrames;
-    const struct { const void* p; uintptr_t bytes; } ins[7] = {{A.deviceFrameAlbedo, stack}, {A.deviceFrameNormalDepth, stack},
-        {A.deviceFrameObjects, (uintptr_t)pixels * 4u * (uintptr_t)nFrames},
-        {A.deviceFrameObjectMotion, (uintptr_t)nFrames * (uintptr_t)A.nObjects * 16u}, {A.devicePrevAlbedo, planeBytes},
-        {A.devicePrevNormalDepth, planeBytes}, {A.devicePrevObject, (uintptr_t)pixels * 4u}};
-    for (const auto& i : ins) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(A.deviceFrameMotion), b = reinterpret_cast<uintptr_t>(i.p);
-        if (b && a < b + i.bytes && b < a + stack) return fail(f + ": deviceFrameMotion overlaps an input");
-    }
+    if (anyOverlaps({{A.deviceFrameMotion, stack}},
+                    {{A.deviceFrameAlbedo, stack}, {A.deviceFrameNormalDepth, stack}, {A.deviceFrameObjects, (uintptr_t)pixels * 4u * (uintptr_t)nFrames},
+                     {A.deviceFrameObjectMotion, (uintptr_t)nFrames * (uintptr_t)A.nObjects * 16u}, {A.devicePrevAlbedo, planeBytes},
+                     {A.devicePrevNormalDepth, planeBytes}, {A.devicePrevObject, (uintptr_t)pixels * 4u}}))
+        return fail(f + ": deviceFrameMotion overlaps an input");
     if (!tptLaunchFlow) return fail(f + ": this build has no motion-vector kernel");
 
     const int first = A.prevCamera ? 0 : 1; // the first frame with a predecessor
@@ -853,7 +860,6 @@ int tptObjectPlaneDevice(int nFrames, const float* times, const void* cameras, i
     if (!deviceFrameObjects) return fail(f + ": deviceFrameObjects is required");
     if (!cameras && (w != g.updatedW || h != g.updatedH)) return fail(f + ": without cameras the size must be the last tptUpdate's");
     if (testFlags & ~(unsigned)(TPT_FLAG_ANIMATE | TPT_FLAG_PROGRESSIVE)) return fail(f + ": unknown flag bits");
-    static_assert(sizeof(CameraPOD) == 22 * sizeof(float), "the reference's Camera");
     for (int j = 0; cameras && j < nFrames; ++j) {
         float c[12];
         memcpy(c, static_cast<const char*>(cameras) + sizeof(CameraPOD) * (size_t)j, sizeof c);
@@ -886,6 +892,37 @@ int tptObjectPlaneDevice(int nFrames, const float* times, const void* cameras, i
     return 0;
 }
 
+// The plan of a lane-refill launch outside the frame pipeline (tptTraceRaysDevice, tptDrawDeviceLens), in two pieces; between them the
+// caller looks for its launcher and fills in its work items (a.numItems).  The first (f: the entry point): the scene set the context
+// last staged, and how the kernel takes it -- a.scene, whether it is staged in LDS, the launch's LDS bytes (laneRefillLds) -- refused
+// where chooseKernel refuses a frame.
+static int laneRefillScene(const std::string& f, KernelArgs& a, bool& ldsScene, size_t& lds)
+{
+    Context::SceneSet* S = activeSet();
+    if (!S || !S->dev || S->nSpheres < 1) return fail(f + ": no scene staged (call tptUpdate first)");
+    if (S->nLights > TPT_MAX_LIGHTS)
+        return fail(f + ": too many emissive spheres for the LDS light table (" + std::to_string(TPT_MAX_LIGHTS) + " at most)");
+    a.scene = deviceView();
+    lds = laneRefillLds(a, ldsScene);
+    if (!fitsCuLds(lds)) return fail(f + ": scene too large for LDS staging; use tptSetKernelVariant(.., .., 0)");
+    return 0;
+}
+
+// The second: sizeGrid's chunks for a.numItems work items -- 256 a chunk, 64 when that leaves a resident wave fewer than eight -- and the
+// grid, a workgroup per chunk up to what is resident at once.  Returns the workgroups.
+static int laneRefillChunks(KernelArgs& a, bool ldsScene, size_t lds)
+{
+    const int occ = laneRefillOccupancy(ldsScene, lds), resident = g.traceCUs * occ;
+    a.chunkSize = a.numItems / TPT_CHUNK_PIXELS < 8 * resident ? 64 : TPT_CHUNK_PIXELS;
+    a.chunkShift = a.chunkSize == 64 ? 6 : 8;
+    a.numChunks = (a.numItems + a.chunkSize - 1) / a.chunkSize;
+    a.chunksPerFrame = a.numChunks;
+    int blocks = a.numChunks < resident ? a.numChunks : resident;
+    if (blocks < 1) blocks = 1;
+    a.totalWaves = (unsigned)blocks;
+    return blocks;
+}
+
 // The buffers of a lane-refill launch outside the frame pipeline (tptTraceRaysDevice, tptDrawDeviceLens; tpt_context.h: dRayStack,
 // dRayWork): the bounce-stack spill for `blocks` workgroups, grown on demand, the counter block, and the word the rays are counted into
 // -- the caller's, or the block's own.
@@ -897,15 +934,7 @@ static int rayLaunchBuffers(KernelArgs& a, int blocks, unsigned long long* devic
     }
     const bool needStack = g.foldMode == FOLD_RECURSIVE && a.ldsStackLevels < TPT_MAX_DEPTH;
     const size_t stackBytes = needStack ? (size_t)blocks * TPT_BLOCK * (size_t)(TPT_MAX_DEPTH - a.ldsStackLevels) * sizeof(f4) : 0;
-    if (stackBytes > g.rayStackBytes) {
-        HIPCHK(hipStreamSynchronize(g.stream)); // (an earlier ray call may still spill into the buffer that goes)
-        (void)hipFree(g.dRayStack);
-        g.dRayStack = nullptr;
-        g.rayStackBytes = 0;
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dRayStack), stackBytes));
-        g.rayStackBytes = stackBytes;
-        HIPCHK(hipMemsetAsync(g.dRayStack, 0, stackBytes, g.stream));
-    }
+    if (int rc = growStreamBuffer(g.dRayStack, g.rayStackBytes, stackBytes, true)) return rc;
     a.stackBuf = needStack ? g.dRayStack : nullptr;
     a.stackStride = needStack ? blocks * TPT_BLOCK : 0;
     a.work = g.dRayWork;
@@ -934,23 +963,14 @@ int tptTraceRaysDevice(const tptTraceRaysArgs* args)
     if (!A.deviceRadiance && !A.deviceHits) return fail(f + ": deviceRadiance or deviceHits is required");
     // the input and the three outputs, each at its own extent: no output may share a byte with the input or with another output
     const uintptr_t n = (uintptr_t)A.nRays;
-    const struct { const void* p; uintptr_t bytes; } bufs[4] = {{A.deviceRays, n * 32u}, {A.deviceRadiance, n * 16u}, {A.deviceHits, n * 32u},
-                                                                {A.deviceRayCount, sizeof(unsigned long long)}};
-    for (int i = 0; i < 4; ++i)
-        for (int k = i + 1; k < 4; ++k) {
-            const uintptr_t a = reinterpret_cast<uintptr_t>(bufs[i].p), b = reinterpret_cast<uintptr_t>(bufs[k].p);
-            if (a && b && a < b + bufs[k].bytes && b < a + bufs[i].bytes)
-                return fail(f + (i == 0 ? ": an output overlaps deviceRays" : ": two outputs overlap"));
-        }
-    Context::SceneSet* S = activeSet();
-    if (!S || !S->dev || S->nSpheres < 1) return fail(f + ": no scene staged (call tptUpdate first)");
-    if (S->nLights > TPT_MAX_LIGHTS)
-        return fail(f + ": too many emissive spheres for the LDS light table (" + std::to_string(TPT_MAX_LIGHTS) + " at most)");
+    const Span radiance = {A.deviceRadiance, n * 16u}, hits = {A.deviceHits, n * 32u}, count = {A.deviceRayCount, sizeof(unsigned long long)};
+    if (anyOverlaps({radiance, hits, count}, {{A.deviceRays, n * 32u}})) return fail(f + ": an output overlaps deviceRays");
+    if (anyTwoOverlap({radiance, hits, count})) return fail(f + ": two outputs overlap");
     KernelArgs a = KernelArgs{};
-    a.scene = deviceView();
     bool ldsScene = false;
-    const size_t lds = laneRefillLds(a, ldsScene);
-    if (!fitsCuLds(lds)) return fail(f + ": scene too large for LDS staging; use tptSetKernelVariant(.., .., 0)");
+    size_t lds = 0;
+    int rc = laneRefillScene(f, a, ldsScene, lds);
+    if (rc) return rc;
     if (!tptLaunchTraceRays) return fail(f + ": this build has no ray launcher");
 
     memset(&a.fc, 0, sizeof a.fc); // (the camera plays no part)
@@ -963,18 +983,9 @@ int tptTraceRaysDevice(const tptTraceRaysArgs* args)
     a.numItems = A.nRays;
     a.batchFrames = 1;
     a.laneCap = 64;
-    // sizeGrid's chunks: 256 rays a chunk, 64 when that leaves a resident wave fewer than eight
-    const int occ = laneRefillOccupancy(ldsScene, lds), resident = g.traceCUs * occ;
-    a.chunkSize = a.numItems / TPT_CHUNK_PIXELS < 8 * resident ? 64 : TPT_CHUNK_PIXELS;
-    a.chunkShift = a.chunkSize == 64 ? 6 : 8;
-    a.numChunks = (a.numItems + a.chunkSize - 1) / a.chunkSize;
-    a.chunksPerFrame = a.numChunks;
-    int blocks = a.numChunks < resident ? a.numChunks : resident;
-    if (blocks < 1) blocks = 1;
-    a.totalWaves = (unsigned)blocks;
+    const int blocks = laneRefillChunks(a, ldsScene, lds); // (256 rays a chunk, or 64)
 
-    int rc = rayLaunchBuffers(a, blocks, A.deviceRayCount);
-    if (rc) return rc;
+    if ((rc = rayLaunchBuffers(a, blocks, A.deviceRayCount))) return rc;
     a.rays = reinterpret_cast<const f4*>(A.deviceRays);
     a.rayRadiance = reinterpret_cast<f4*>(A.deviceRadiance);
     a.rayHits = reinterpret_cast<f4*>(A.deviceHits);
@@ -1025,20 +1036,14 @@ int tptDrawDeviceLens(const tptDrawLensArgs* args)
     if (A.flags != 0 && A.flags != (unsigned)TPT_FLAG_PROGRESSIVE) return fail(f + ": flags must be 0 or TPT_FLAG_PROGRESSIVE");
     if (!A.deviceTile) return fail(f + ": deviceTile is required");
     const size_t nPixels = (size_t)w * (size_t)h;
-    {
-        const uintptr_t t = reinterpret_cast<uintptr_t>(A.deviceTile), c = reinterpret_cast<uintptr_t>(A.deviceRayCount);
-        if (c && c < t + nPixels * sizeof(f4) && t < c + sizeof(unsigned long long)) return fail(f + ": deviceRayCount lies inside the tile");
-    }
+    if (overlaps({A.deviceRayCount, sizeof(unsigned long long)}, {A.deviceTile, nPixels * sizeof(f4)}))
+        return fail(f + ": deviceRayCount lies inside the tile");
     if (const char* why = lensFault(A.lens)) return fail(f + ": " + why);
-    Context::SceneSet* S = activeSet();
-    if (!S || !S->dev || S->nSpheres < 1) return fail(f + ": no scene staged (call tptUpdate first)");
-    if (S->nLights > TPT_MAX_LIGHTS)
-        return fail(f + ": too many emissive spheres for the LDS light table (" + std::to_string(TPT_MAX_LIGHTS) + " at most)");
     KernelArgs a = KernelArgs{};
-    a.scene = deviceView();
     bool ldsScene = false;
-    const size_t lds = laneRefillLds(a, ldsScene);
-    if (!fitsCuLds(lds)) return fail(f + ": scene too large for LDS staging; use tptSetKernelVariant(.., .., 0)");
+    size_t lds = 0;
+    int rc = laneRefillScene(f, a, ldsScene, lds);
+    if (rc) return rc;
     if (!tptLaunchTraceLens) return fail(f + ": this build has no lens launcher");
 
     // (the camera plays no part; seeds per pixel, the flags' blend)
@@ -1051,27 +1056,10 @@ int tptDrawDeviceLens(const tptDrawLensArgs* args)
     a.batchFrames = 1;
     a.framePlane = h * w;
     a.laneCap = 64;
-    // sizeGrid's chunks: 256 pixels a chunk, single 8x8 tiles when that leaves a resident wave fewer than eight
-    const int occ = laneRefillOccupancy(ldsScene, lds), resident = g.traceCUs * occ;
-    a.chunkSize = a.numItems / TPT_CHUNK_PIXELS < 8 * resident ? 64 : TPT_CHUNK_PIXELS;
-    a.chunkShift = a.chunkSize == 64 ? 6 : 8;
-    a.numChunks = (a.numItems + a.chunkSize - 1) / a.chunkSize;
-    a.chunksPerFrame = a.numChunks;
-    int blocks = a.numChunks < resident ? a.numChunks : resident;
-    if (blocks < 1) blocks = 1;
-    a.totalWaves = (unsigned)blocks;
+    const int blocks = laneRefillChunks(a, ldsScene, lds); // (256 pixels a chunk, or single 8x8 tiles)
 
-    int rc = rayLaunchBuffers(a, blocks, A.deviceRayCount);
-    if (rc) return rc;
-    const size_t colourBytes = nPixels * sizeof(f4);
-    if (colourBytes > g.lensColourBytes) {
-        HIPCHK(hipStreamSynchronize(g.stream)); // (an earlier lens draw may still read the plane that goes)
-        (void)hipFree(g.dLensColour);
-        g.dLensColour = nullptr;
-        g.lensColourBytes = 0;
-        HIPCHK(hipMalloc(reinterpret_cast<void**>(&g.dLensColour), colourBytes));
-        g.lensColourBytes = colourBytes;
-    }
+    if ((rc = rayLaunchBuffers(a, blocks, A.deviceRayCount))) return rc;
+    if ((rc = growStreamBuffer(g.dLensColour, g.lensColourBytes, nPixels * sizeof(f4)))) return rc;
     a.frameColour = g.dLensColour;
     if ((rc = enqueueSceneUpload(g.stream))) return rc;
     HIPCHK(tptLaunchTraceLens(a, g.hs, g.foldMode, ldsScene, blocks, lds, g.stream));
@@ -1108,16 +1096,10 @@ int tptAdaptiveSamplesDevice(int w, int h, const float* deviceMoments, float tar
     if (!(targetError > 0.0f && targetError <= 1e6f)) return fail(f + ": targetError must lie in (0, 1e6]"); // (NaN fails)
     if (minSamples < 0 || maxSamples > 2047 || minSamples > maxSamples) return fail(f + ": 0 <= minSamples <= maxSamples <= 2047 expected");
     // the input and the three outputs, each at its own extent: no output may share a byte with the input or with another output
-    const struct { const void* p; uintptr_t bytes; } bufs[4] = {{deviceMoments, (uintptr_t)w * (uintptr_t)h * 16u},
-                                                                {deviceSampleCounts, (uintptr_t)w * (uintptr_t)h * 4u},
-                                                                {deviceOutVariance, (uintptr_t)w * (uintptr_t)h * 16u},
-                                                                {deviceTotalSamples, sizeof(int64_t)}};
-    for (int i = 0; i < 4; ++i)
-        for (int k = i + 1; k < 4; ++k) {
-            const uintptr_t a = reinterpret_cast<uintptr_t>(bufs[i].p), b = reinterpret_cast<uintptr_t>(bufs[k].p);
-            if (a && b && a < b + bufs[k].bytes && b < a + bufs[i].bytes)
-                return fail(f + (i == 0 ? ": an output overlaps deviceMoments" : ": two outputs overlap"));
-        }
+    const uintptr_t pixels = (uintptr_t)w * (uintptr_t)h;
+    const Span counts = {deviceSampleCounts, pixels * 4u}, variance = {deviceOutVariance, pixels * 16u}, total = {deviceTotalSamples, sizeof(int64_t)};
+    if (anyOverlaps({counts, variance, total}, {{deviceMoments, pixels * 16u}})) return fail(f + ": an output overlaps deviceMoments");
+    if (anyTwoOverlap({counts, variance, total})) return fail(f + ": two outputs overlap");
     if (!tptLaunchAdaptivePlan) return fail(f + ": this build has no adaptive plan kernel");
     HIPCHK(tptLaunchAdaptivePlan(deviceMoments, deviceSampleCounts, deviceOutVariance, deviceTotalSamples, w, h, targetError, minSamples,
                                  maxSamples, g.stream));
