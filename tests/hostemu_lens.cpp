@@ -3,16 +3,22 @@
 // (traceLaneRefill), this restates its lens mode with the product's own lane headers -- mapItem, laneBeginPixel, laneLens, hitSpheres,
 // lanePost, lanePixelColour -- pixel by pixel in chunk order, and does with the argument block what the kernel does: which pixel an item
 // is, where its colour goes, which word the rays are counted into, how the work counters are found and re-armed.  It refuses a launch
-// whose constants are not the lens mode's, and counts the launches, so a test can tell accepted calls from refused ones.
+// whose constants are not the lens mode's, and counts the launches, so a test can tell accepted calls from refused ones.  It keeps the
+// plan of the last launch it accepted (hostemuLensPlan: the work items, the chunks and the grid as KernelArgs and the launch hold them),
+// and on request (hostemuLensPlanOnly) records the plan and answers hipErrorNotReady without running anything, so that a test can
+// read the plan of an image it has no time to draw.
 #include "tpt_device.h"
 #include "tpt_queue_layout.h"
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 using namespace tpt;
 
 namespace {
 int gLaunches = 0;
+bool gPlanOnly = false;
+long long gPlan[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 struct LensJob {
     KernelArgs a;
     int hs, fold;
@@ -99,9 +105,15 @@ hipError_t tptLaunchTraceLens(const KernelArgs& a, int hs, int fold, bool ldsSce
         return hipErrorInvalidValue;
     if (blocks < 1 || blocks > a.numChunks || (unsigned)blocks != a.totalWaves || lds > 160 * 1024) return hipErrorInvalidValue;
     if (fold == FOLD_RECURSIVE && a.ldsStackLevels < TPT_MAX_DEPTH && (!a.stackBuf || a.stackStride != blocks * TPT_BLOCK)) return hipErrorInvalidValue;
+    gPlan[0] = a.numItems; gPlan[1] = a.chunkSize; gPlan[2] = a.chunkShift; gPlan[3] = a.numChunks;
+    gPlan[4] = blocks; gPlan[5] = (long long)lds; gPlan[6] = a.tilesX; gPlan[7] = a.chunksPerFrame;
+    if (gPlanOnly) return hipErrorNotReady;
     ++gLaunches;
     LensJob J; J.a = a; J.hs = hs; J.fold = fold; J.ldsScene = ldsScene;
     hostemuEnqueue(stream, runLens, &J, sizeof(J));
     return hipSuccess;
 }
 extern "C" __attribute__((visibility("default"))) int hostemuLensLaunches() { return gLaunches; }
+// {numItems, chunkSize, chunkShift, numChunks, workgroups, LDS bytes, tilesX, chunksPerFrame} of the last launch that passed the checks
+extern "C" __attribute__((visibility("default"))) void hostemuLensPlan(long long* out8) { memcpy(out8, gPlan, sizeof gPlan); }
+extern "C" __attribute__((visibility("default"))) void hostemuLensPlanOnly(int on) { gPlanOnly = on != 0; }

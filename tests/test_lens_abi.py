@@ -1,7 +1,9 @@
 """tptDrawDeviceLens without a GPU: the declaration, binding and export; the binding's argument checks; the structs' layout; lensGetRay of
 csrc/tpt_trace.h compiled for the host against tests/lens_checker.c bit for bit; the code object's kernel set (no kernel of its own);
 and, through the host runtime compiled against tests/hostemu with tests/hostemu_lens.cpp as the launcher, every refusal (no operation
-run, no byte written) and the accepted draws held byte for byte against the checker."""
+run, no byte written) and the accepted draws held byte for byte against the checker; the binding's and the library's statements of the
+basis rules held together a step either side of every bound; and the launch's plan -- chunk size, shift and count, the grid -- on both
+sides of the seam between 8 x 8 tiles and chunks of 256 pixels and at 8192 x 8192 (tests/lens_kinds_lib.py has the records and sizes)."""
 import ctypes as C
 import os
 import re
@@ -289,6 +291,71 @@ def raw(w, h, frame, flags, lens, tile, count):
     a = tpt.DrawLensArgs(screenWidth=w, screenHeight=h, frameCount=frame, flags=flags, lens=to_api(lens), deviceTile=ptr(tile), deviceRayCount=ptr(count))
     return lib.tptDrawDeviceLens(C.byref(a))
 W, H = 16, 8
+if sys.argv[2] == "bounds":
+    # every bound of the basis rules, a step inside and a step outside, through the C call and the binding's own statement of the
+    # rules with the same records: both accept, or both refuse -- the C call with the message, nothing enqueued and nothing written
+    import lens_kinds_lib
+    tpt.InitializeTest()
+    tpt.UpdateTest(0.0, 0, W, H, 0)
+    tpt.synchronize()
+    s, m = tpt.GetSceneDesc()[:2]
+    tpt.set_samples_per_pixel(1)
+    for name, lens, inside, message in lens_kinds_lib.bound_records():
+        tile, tile2 = (np.full((H, W, 4), 7.0, np.float32) for _ in range(2))  # (finite: a plain draw adds 0 * what was there)
+        tpt.synchronize()
+        ops0 = ops()
+        rc = raw(W, H, 0, 0, lens, tile, None)
+        said = msg()
+        try:
+            tpt.draw_device_lens(0, W, H, ptr(tile2), to_api(lens))
+            binding = True
+        except ValueError as e:
+            binding = False
+            assert ("unit length" in str(e)) == ("unit length" in message) and ("orthogonal" in str(e)) == ("orthogonal" in message), (name, e)
+        assert (rc == 0) == binding == inside, (name, rc, binding, inside, said)
+        tpt.synchronize()
+        if inside:
+            want = checker.render(s, m, lens, W, H, 1, backbuffer=np.full((H, W, 4), 7.0, np.float32))[1].tobytes()
+            assert tile.tobytes() == want and tile2.tobytes() == want and (tile[..., :3] != 7).any(), name
+        else:
+            assert said == "tptDrawDeviceLens: " + message, (name, said)
+            assert ops() == ops0 and (tile == 7).all() and (tile2 == 7).all(), (name, "a refused call enqueued or wrote")
+        print("bound: %s: %s" % (name, "accepted by both" if inside else "refused by both -- " + said))
+    tpt.ShutdownTest()
+    print("ok")
+    sys.exit(0)
+if sys.argv[2] == "plans":
+    # what laneRefillChunks makes of an image on either side of the seam between 8 x 8 tiles and chunks of 256 pixels, and of the
+    # largest image: KernelArgs and the grid as the launcher gets them (hostemuLensPlan), on a device whose CUs HOSTEMU_CUS names
+    import lens_kinds_lib
+    tpt.InitializeTest()
+    tpt.UpdateTest(0.0, 0, W, H, 0)
+    plan = (C.c_longlong * 8)()
+    small = np.zeros((8, 8, 4), np.float32)
+    tpt.set_samples_per_pixel(4)
+    tpt.draw_device_lens(0, 8, 8, ptr(small), to_api(make_lens(EQUIRECT)))
+    tpt.synchronize()
+    so.hostemuLensPlan(plan)
+    assert list(plan)[:5] == [64, 64, 6, 1, 1] and plan[6] == 1, list(plan)
+    resident = lens_kinds_lib.emulated_resident(int(os.environ["HOSTEMU_CUS"]), plan[5])
+    above, under = lens_kinds_lib.seam_sizes(resident)
+    so.hostemuLensPlanOnly(1)  # the launcher records the plan and runs nothing: the call fails after its planning, the tile is not touched
+    for (w, h), chunk in ((under, 64), (above, 256), ((8192, 8192), 256), ((8192, 8), 256 if 1024 * 64 >= 2048 * resident else 64)):
+        assert raw(w, h, 0, 0, make_lens(FISHEYE), small, None) != 0 and "tptLaunchTraceLens" in msg(), msg()
+        so.hostemuLensPlan(plan)
+        items = lens_kinds_lib.items_of(w, h)
+        chunks = (items + chunk - 1) // chunk
+        want = [items, chunk, {64: 6, 256: 8}[chunk], chunks, min(chunks, resident), plan[5], (w + 7) // 8, chunks]
+        assert list(plan) == want, ((w, h), list(plan), want)
+        print("plan: %d x %d: %d items in %d chunks of %d (shift %d), %d workgroups of %d resident" % (w, h, items, chunks, chunk, plan[2], plan[4], resident))
+    so.hostemuLensPlanOnly(0)
+    assert lens_kinds_lib.items_of(*under) < 2048 * resident <= lens_kinds_lib.items_of(*above)
+    tpt.draw_device_lens(0, 8, 8, ptr(small), to_api(make_lens(EQUIRECT)))  # and the context draws on
+    tpt.synchronize()
+    assert small.tobytes() == checker.render(tpt.GetSceneDesc()[0], tpt.GetSceneDesc()[1], make_lens(EQUIRECT), 8, 8, 4)[1].tobytes()
+    tpt.ShutdownTest()
+    print("ok")
+    sys.exit(0)
 if REFUSALS:
     count = np.full(4, 7, np.uint64)
     tile = np.full((H * W + 4, 4), np.nan, np.float32)
@@ -498,11 +565,13 @@ ORDER = {"tptDrawDeviceLens: screenWidth and screenHeight must lie in 1..8192": 
 ORDER_CASES = sum(ORDER.values())
 
 
-def run_script(mode, policy):
+def run_script(mode, policy, cus=None):
     from test_host_logic import build
     path = build("libtpt_hostemu_lens.so", [os.path.join(ROOT, "tests", "hostemu_lens.cpp")])
     env = dict(os.environ, TPT_LIB=path, HOSTEMU_POLICY=policy)
     env.pop("TPT_LIB_DIR", None)
+    if cus:
+        env["HOSTEMU_CUS"] = str(cus)
     p = subprocess.run([sys.executable, "-c", SCRIPT, ROOT, mode], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
     out = p.stdout.decode()
     assert p.returncode == 0 and out.rstrip().endswith("ok"), out[-4000:]
@@ -538,6 +607,32 @@ def test_refusals_through_the_host_runtime():
         "tptDrawDeviceLens: too many emissive spheres for the LDS light table (3072 at most)": 1,
         "tptDrawDeviceLens: scene too large for LDS staging; use tptSetKernelVariant(.., .., 0)": 1,
     }
+
+
+def test_the_binding_and_the_library_agree_at_every_bound_of_the_basis_rules():
+    """the Python binding states the basis rules a second time (api._check_lens): records a clear 1e-6 inside and outside each bound --
+    the squared length of each vector at 0.99 and 1.01, each dot product at -0.01 and 0.01 -- get the same verdict from both, the
+    library's with its message"""
+    import lens_kinds_lib
+    records = lens_kinds_lib.bound_records()
+    out = run_script("bounds", "lazy")
+    assert out.count("bound:") == len(records) == 24, out
+    assert out.count(": accepted by both") == 12, out
+    assert out.count(": refused by both -- tptDrawDeviceLens: " + lens_kinds_lib.UNIT_MESSAGE) == 6, out
+    assert out.count(": refused by both -- tptDrawDeviceLens: " + lens_kinds_lib.ORTHOGONAL_MESSAGE) == 6, out
+    for name, _, inside, _ in records:
+        assert "bound: %s: %s" % (name, "accepted" if inside else "refused") in out, name
+
+
+@pytest.mark.parametrize("cus", [2, 256])
+def test_the_plan_on_both_sides_of_the_seam_and_at_the_largest_image(cus):
+    """chunkSize, chunkShift, numChunks and the grid as the launcher gets them, where the resident workgroups are known exactly: a
+    device of two CUs (the seam at 361 x 177) and one of 256 (the seam at 4089 x 2041, 8192 x 8 still in tiles)"""
+    out = run_script("plans", "eager", cus)
+    plans = [ln for ln in out.splitlines() if ln.startswith("plan:")]
+    assert len(plans) == 4 and "chunks of 64 (shift 6)" in plans[0] and "chunks of 256 (shift 8)" in plans[1], plans
+    assert plans[2].startswith("plan: 8192 x 8192: 67108864 items in 262144 chunks of 256 (shift 8), %d workgroups" % (cus * 16)), plans
+    assert ("chunks of 256 (shift 8)" if cus == 2 else "chunks of 64 (shift 6)") in plans[3], plans
 
 
 @pytest.mark.parametrize("policy", ["eager", "lazy"])
