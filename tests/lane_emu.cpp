@@ -474,6 +474,62 @@ void emu_hit_spheres(const void* spheres, const void* mats, int count, int hs, c
     }
 }
 
+// HitSpheres as the moved-sphere kernels run it for a frame that is not the launch's last (tests/test_motion_kinds.py): the filter data
+// of the STAGED scene, the launch-uniform mask of the moved spheres (sphere i at bit 63 - i) and the frame's table of centres (one f4
+// per moved sphere in ascending index; keyed == 0: the two centres of spheres 1 and 8, the mask is TPT_MOVED_CANDIDATES' and ignored)
+// against the exact loop over the frame's OWN spheres.  outId / outT: hitSpheresTwoPhase<true, KEYS>; outMatrixId / outMatrixT:
+// hitSpheresCandidates<true, KEYS> behind phase1MatrixHRef where the staged scene has a table (untouched otherwise); wantId / wantT:
+// hitSpheresSimple over packScene(own).  Returns the number of hits at which qNormal<true, KEYS> over the staged scene differs in a
+// bit from qNormal over the frame's own; info[0] = the staged scene's mxR1, info[1] = the own scene's (< 0: no table).
+long long emu_hit_spheres_moved(const void* stagedSpheres, const void* ownSpheres, const void* mats, int count, int keyed, unsigned long long mask,
+                                const float* table, const float* rays, int n, int* outId, float* outT, int* outMatrixId, float* outMatrixT,
+                                int* wantId, float* wantT, int* info)
+{
+    std::vector<SpherePOD> S((const SpherePOD*)stagedSpheres, (const SpherePOD*)stagedSpheres + count);
+    std::vector<SpherePOD> O((const SpherePOD*)ownSpheres, (const SpherePOD*)ownSpheres + count);
+    std::vector<MaterialPOD> M((const MaterialPOD*)mats, (const MaterialPOD*)mats + count);
+    PackedScene staged, own;
+    packScene(S, M, staged);
+    packScene(O, M, own);
+    const SceneView sv = viewOf(staged), exact = viewOf(own);
+    info[0] = staged.mxR1;
+    info[1] = own.mxR1;
+    f4 centres[8];
+    for (int k = 0; k < 8; ++k) centres[k] = f4{table[k * 4], table[k * 4 + 1], table[k * 4 + 2], table[k * 4 + 3]};
+    long long badNormals = 0;
+    for (int i = 0; i < n; ++i) {
+        const f3 o = mk3(rays[i * 6], rays[i * 6 + 1], rays[i * 6 + 2]), d = mk3(rays[i * 6 + 3], rays[i * 6 + 4], rays[i * 6 + 5]);
+        float t = 0;
+        wantId[i] = hitSpheresSimple(exact, o, d, TPT_MIN_T, TPT_MAX_T, t);
+        wantT[i] = t;
+        outId[i] = keyed ? hitSpheresTwoPhase<true, true>(sv, o, d, TPT_MIN_T, TPT_MAX_T, t, centres, mask)
+                         : hitSpheresTwoPhase<true, false>(sv, o, d, TPT_MIN_T, TPT_MAX_T, t, centres, 0);
+        outT[i] = t;
+        if (sv.mxR1 >= 0) {
+            const uint64_t cand = phase1MatrixHRef(sv.amatH, sv.mxR1, sv.nSpheres, o, d);
+            outMatrixId[i] = keyed ? hitSpheresCandidates<true, true>(sv, cand, o, d, TPT_MIN_T, TPT_MAX_T, t, centres, mask)
+                                   : hitSpheresCandidates<true, false>(sv, cand, o, d, TPT_MIN_T, TPT_MAX_T, t, centres, 0);
+            outMatrixT[i] = t;
+        }
+        if (wantId[i] >= 0) {
+            const f3 p = o + d * wantT[i];
+            const f3 n0 = qNormal(exact, wantId[i], p);
+            const f3 n1 = keyed ? qNormal<true, true>(sv, wantId[i], p, centres, mask) : qNormal<true, false>(sv, wantId[i], p, centres, 0);
+            badNormals += f2u(n0.x) != f2u(n1.x) || f2u(n0.y) != f2u(n1.y) || f2u(n0.z) != f2u(n1.z);
+        }
+    }
+    return badNormals;
+}
+// the mxR1 packScene gives this scene (< 0: no matrix table)
+int emu_matrix_r1(const void* spheres, const void* mats, int count)
+{
+    std::vector<SpherePOD> S((const SpherePOD*)spheres, (const SpherePOD*)spheres + count);
+    std::vector<MaterialPOD> M((const MaterialPOD*)mats, (const MaterialPOD*)mats + count);
+    PackedScene P;
+    packScene(S, M, P);
+    return P.mxR1;
+}
+
 // Candidate masks of the matrix-core filter's host restatement (phase1MatrixHRef: same table, same ray slots, f32
 // accumulation in slot order) and, per (ray, sphere), the EXACT slot sum and the sum of the slot products' magnitudes in
 // binary64 (outSum / outAbs, [n][nSpheres], optional): the GPU test holds the device's sign bits against them within the

@@ -184,6 +184,8 @@ TPT_HD void testSphere(f4 s, int i, f3 o, f3 d, float tMin, float& hitT, int& id
 // move; spheres 1 and 8 are made candidates of every ray (TPT_MOVED_CANDIDATES), so phase 1 can drop nothing a frame's exact test
 // accepts, whatever the motion: every filter bit depends on its own sphere only, and phase 2 gives the same nearest hit for any
 // superset of the spheres the exact test accepts (index order, strict t < hitT -- what the reference's loop over all spheres does).
+// tests/test_motion_kinds.py holds this on the host for motion that takes the staged scene and a frame's own apart (across the matrix
+// table's limit, ties, up to 3e38); tests/test_gpu_motion_kinds.py holds the kernels to it byte for byte.
 // (`moved` is an LDS address explicitly: with a generic pointer LLVM merges the two loads into one FLAT load from either address)
 #if defined(__HIP_DEVICE_COMPILE__)
 typedef const f4 __attribute__((address_space(3))) * LdsMovedPtr;
